@@ -16,6 +16,11 @@ torch.distributed.run (WORLD_SIZE unset); under the launcher it reads RANK / LOC
 WORLD_SIZE / MASTER_*.  torch.distributed (gloo) carries the control plane only: the rendezvous of
 the RCCL unique id, the barriers around the timed region and the max over ranks.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds everything else the
+line used to carry: the roofline, BASELINE config 3 at its size, device post-processing, the PCIe-inclusive rate, the
+CPU baselines (the reference binary with its BED check) and the four side workloads.  `--dump-outputs DIR` writes the
+records of the last timed step as DIR/<name>.npy (float64), for comparing two builds output for output.
 """
 import argparse
 import ctypes as C
@@ -30,8 +35,10 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+HBM_PEAK_GBS = 8000.0  # MI355X: HBM3E 8 TB/s spec
 N_SLOTS = 4            # distinct resident batches per rank that take turns
+DUMP_BYTES = 48 << 20  # --dump-outputs: the sample of read ids is sized to this (hard cap 64 MB in all)
+DUMP_SEED = 20240607   # --dump-outputs: the seed of that sample (fixed: the same pairs in every run and build)
 
 
 def log(*a):
@@ -208,10 +215,11 @@ def sub_steps(pairs):
     return [s] * (n - 1) + [pairs - s * (n - 1)]
 
 
-def timed_run(g, args, rank, world, dist, seed0, exchange):
+def timed_run(g, args, rank, world, dist, seed0, exchange, on_last=None):
     """parks the distinct batches, then warm-up + K timed steps; returns (dt of this rank, stage sums, Stats, mapped).
     A step maps args.pairs pairs: one resident batch (N_SLOTS distinct ones take turns), or -- more than SUB_STEP_MAX pairs,
-    --strong at few GPUs -- every one of its sub-steps' batches in turn, all of them distinct and resident"""
+    --strong at few GPUs -- every one of its sub-steps' batches in turn, all of them distinct and resident.
+    The batch mapped last stays resident until the timer has stopped: on_last(g, records, pairs) then reads its records"""
     import torch
     from chromap_amd import Stats
     subs = sub_steps(args.pairs)
@@ -219,17 +227,23 @@ def timed_run(g, args, rank, world, dist, seed0, exchange):
     for b in range(n_slots):
         gen(g, args, seed0 + rank * 64 + b, subs[b % len(subs)])
         g.swap_resident(b)
+    last = {}
 
-    def step(i, stats):
+    def step(i, stats, keep=False):
         k, tms = 0, {}
-        for sl in ([i % n_slots] if len(subs) == 1 else range(n_slots)):
+        sls = [i % n_slots] if len(subs) == 1 else list(range(n_slots))
+        for sl in sls:
             g.swap_resident(sl)
-            k += g.map_resident(stats)
+            kk = g.map_resident(stats)
+            k += kk
             MAPPED["pairs"] += subs[sl % len(subs)]
             if exchange:
                 g.exchange_step()
             for name, ms in g.timings():
                 tms[name] = tms.get(name, 0.0) + ms
+            if keep and sl == sls[-1]:  # parked by the caller once the timer has stopped
+                last.update(slot=sl, records=kk, pairs=subs[sl % len(subs)])
+                break
             g.swap_resident(sl)
         return k, list(tms.items())
 
@@ -251,7 +265,7 @@ def timed_run(g, args, rank, world, dist, seed0, exchange):
     t0 = time.perf_counter()
     mapped = 0
     for i in range(args.steps):
-        k, tm = step(args.warmup + i, st)
+        k, tm = step(args.warmup + i, st, keep=i == args.steps - 1)
         mapped += k
         for name, ms in tm:
             stage_ms[name] = stage_ms.get(name, 0.0) + ms
@@ -259,7 +273,38 @@ def timed_run(g, args, rank, world, dist, seed0, exchange):
     if dist is not None:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if last:
+        if on_last is not None:
+            on_last(g, last["records"], last["pairs"])
+        g.swap_resident(last["slot"])
     return dt, stage_ms, st, mapped
+
+
+def dump_outputs(out_dir, g, n_records, n_pairs):
+    """--dump-outputs: the records of the batch mapped last (what cmgpu_download_records / cmgpu_download_sam hand a caller),
+    one DIR/records_<field>.npy per field in float64 (every field is an integer of at most 32 bits: exact).  Where all pairs'
+    records would not fit DUMP_BYTES, only the records of a fixed sample of read ids (DUMP_SEED) are written, in pair order"""
+    import numpy as np
+    from chromap_amd import _capi
+    if g.params.output_format == _capi.FORMAT_SAM:
+        rec, _, _, _, n_slots = g.download_sam()
+        a = np.frombuffer(rec, dtype=np.dtype(_capi.SamRecord), count=n_slots)
+        a = a[a["valid"] != 0]
+    else:
+        rec, k = g.download_records(n_records)
+        # --preset hic (split alignment): the 24-byte slots hold pairs records
+        a = np.frombuffer(rec, dtype=np.dtype(_capi.PairsRecord if g.params.split_alignment else _capi.Record), count=k)
+    fields = [f for f in a.dtype.names if f != "valid"]
+    ids = min(n_pairs, DUMP_BYTES // (8 * len(fields)))
+    if ids < n_pairs:
+        keep = np.random.default_rng(DUMP_SEED).choice(n_pairs, ids, replace=False)
+        a = a[np.isin(a["read_id"], keep)]
+    a = a[:(64 << 20) // (8 * (len(fields) + 1))]  # (several records per read: -n > 1)
+    os.makedirs(out_dir, exist_ok=True)
+    for f in fields:
+        np.save(os.path.join(out_dir, "records_%s.npy" % f), a[f].astype(np.float64))
+    np.save(os.path.join(out_dir, "records_total.npy"), np.array([n_records], np.float64))
+    log("[bench] --dump-outputs: %d of %d records (%d pairs) in %s" % (len(a), n_records, n_pairs, out_dir))
 
 
 GRADED_LOOKUPS_MIN = 100_000_000  # SURVEY 8(d): the graded launch of the probe kernel has at least 10^8 lookups
@@ -439,7 +484,7 @@ def main():
                          "(SINE-like families of ~19 000 copies, LINE-like of ~830) ('' = skip it)")
     ap.add_argument("--headline-repeats", default="", help="plant repeats in the headline workload's genome too (not the default)")
     ap.add_argument("--skip-cpu", action="store_true")
-    ap.add_argument("--skip-extras", action="store_true", help="timed region and roofline only")
+    ap.add_argument("--skip-extras", action="store_true", help="with --full: timed region and roofline only")
     ap.add_argument("--cpu-baseline", choices=["auto", "reference", "port"], default="auto",
                     help="reference: oracle/_ref/chromap itself; port: the oracle restatement with OpenMP; auto: reference if its binary is here")
     ap.add_argument("--probe-repeat", type=int, default=10)
@@ -461,7 +506,15 @@ def main():
     ap.add_argument("--config3-pairs", type=int, default=100_000_000,
                     help="extra (N = 1): one timed pass over this many DISTINCT resident pairs, BASELINE config 3's size (0 = skip it)")
     ap.add_argument("--option", action="append", default=[], help="name=value for cmgpu_set_option (measurement knobs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: roofline, config 3 at its size, device post-processing, PCIe-inclusive rate, CPU "
+                         "baselines and the side workloads (a plain run sets up, warms up, times the K steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records of the last timed step (rank 0; --strong: its last sub-step) as DIR/records_<field>.npy, "
+                         "float64; a fixed, seeded sample of read ids when all of them would exceed the size budget")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        raise SystemExit("--dump-outputs needs at least one timed step")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -530,7 +583,11 @@ def main():
         if dist is not None:
             dist.broadcast_object_list(uid, src=0)
         g.exchange_init(uid[0], rank, world)
-    dt, stage_ms, st, mapped = timed_run(g, args, rank, world, dist, 1000, exchange)
+    on_last = None
+    if args.dump_outputs and rank == 0:
+        def on_last(g_, n_records, n_pairs):
+            dump_outputs(args.dump_outputs, g_, n_records, n_pairs)
+    dt, stage_ms, st, mapped = timed_run(g, args, rank, world, dist, 1000, exchange, on_last)
     info = {"rank": rank, "mapped_pairs": int(mapped), "dt_s": dt}
     if exchange:
         info.update(g.exchange_info())
@@ -555,13 +612,14 @@ def main():
     total_pairs = args.pairs * args.steps * world
     value = total_pairs / dt / 1e6
     s = st.as_dict()
-    # the kernel-only probe measurement wants one batch's minimizers resident in one piece
-    g.set_option("lanes", 1)
-    roof = roofline(g, args, steps)
-    g.set_option("lanes", args.lanes)
-    post = pcie = cpu = rep_out = harsh_out = harsh2_out = hic_out = cfg3 = None
+    roof = post = pcie = cpu = rep_out = harsh_out = harsh2_out = hic_out = cfg3 = None
+    if args.full:
+        # the kernel-only probe measurement wants one batch's minimizers resident in one piece
+        g.set_option("lanes", 1)
+        roof = roofline(g, args, steps)
+        g.set_option("lanes", args.lanes)
     # (on the headline genome only: a repeat-rich genome's candidate arrays for 25 M-pair sub-steps do not fit three lanes' worth of HBM)
-    if not args.skip_extras and world == 1 and args.config3_pairs and not args.strong and not args.headline_repeats:
+    if args.full and not args.skip_extras and world == 1 and args.config3_pairs and not args.strong and not args.headline_repeats:
         # BASELINE config 3 at its stated size on this one GPU: 100 M DISTINCT pairs, generated on the device and resident, mapped
         # once inside one timed step as sub-steps of <= SUB_STEP_MAX pairs (what --strong 100000000 --gpus 1 runs)
         try:
@@ -577,7 +635,7 @@ def main():
                 g.swap_resident(b)
         except Exception as e:
             cfg3 = {"error": repr(e)}
-    if not args.skip_extras:
+    if args.full and not args.skip_extras:
         # device-side post-processing, outside the timed region: the records of the four resident
         # batches go to the record store; one call sorts, de-duplicates, filters and renders the BED text in HBM
         try:
@@ -729,14 +787,17 @@ def main():
                    "pairs_per_gpu_per_step": args.pairs, "lanes": args.exchange_lanes if exchange else args.lanes,
                    "parallelism": ("read-shard x%d, records to chromosome owners by device partition + RCCL all-to-all on the library's "
                                    "mapping stream inside every step" % world) if exchange else "single GPU"},
-        "roofline": roof, "cpu_baseline": cpu, "repeat_workload": rep_out, "harsh_repeat_workload": harsh_out, "harsh2_repeat_workload": harsh2_out, "hic_workload": hic_out, "config3_full_size_pass": cfg3, "postprocess_on_device": post, "pcie_inclusive": pcie,
         "stage_ms_per_step": {k: round(v / steps, 3) for k, v in stage_ms.items()},
         "stage_ms_note": "HIP events of the calling thread's lane (1 / %d of the batch when lanes > 1; the lanes overlap)" % args.lanes,
         "counters_per_step": {k: v // steps for k, v in s.items()},
         "mapped_pairs_per_step": mapped // steps, "index_build_s": round(t_index, 1),
-        "pairs_mapped_in_process": MAPPED["pairs"], "s3b_label": args.headline_repeats or "headline",
-        "host": host_info(),
     }
+    if args.full:
+        out.update({
+            "roofline": roof, "cpu_baseline": cpu, "repeat_workload": rep_out, "harsh_repeat_workload": harsh_out, "harsh2_repeat_workload": harsh2_out, "hic_workload": hic_out, "config3_full_size_pass": cfg3, "postprocess_on_device": post, "pcie_inclusive": pcie,
+            "pairs_mapped_in_process": MAPPED["pairs"], "s3b_label": args.headline_repeats or "headline",
+            "host": host_info(),
+        })
     if exchange:
         out["exchange"] = {"ranks": world, "transport": "RCCL (ncclAllGather of counts + grouped ncclSend/ncclRecv) on the mapping stream",
                            "per_rank": [{k: x[k] for k in ("rank", "mapped_pairs", "records_sent", "records_owned")} for x in infos]}

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out/$TAG
 mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python $R/bench.py --skip-extras --graded-probe-only --steps 6 --warmup 2 "$@" > $O/bench.json 2> $O/stats.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python $R/bench.py --full --skip-extras --graded-probe-only --steps 6 --warmup 2 "$@" > $O/bench.json 2> $O/stats.log
 cp $O/stats/bench_kernel_stats.csv $R/gpurun_out/${TAG}_kernel_stats.csv
 find $O -name "*kernel_trace.csv" -delete
 python - <<PY
