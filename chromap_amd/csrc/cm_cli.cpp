@@ -490,7 +490,7 @@ struct ReadFormat {
     }
     return out;
   }
-  // SequenceEffectiveRange::Replace for the host parser (pairs / SAM output)
+  // SequenceEffectiveRange::Replace for the host parser (SAM output, --host-ingest)
   void apply(std::string &seq, std::string &qual) const {
     if (identity()) return;
     std::string ns, nq;
@@ -775,7 +775,7 @@ int main(int argc, char **argv) {
 
   cmgpu_stats st;
   memset(&st, 0, sizeof(st));
-  std::vector<std::string> read_names;  // pairs output needs read-1 names by read_id
+  std::vector<std::string> read_names;  // pairs output needs read-1 names by read_id (host parser only: the device ingest keeps them in HBM)
   uint64_t num_reads = 0;
   uint32_t next_read_id = 0, bc_len = 0;
 
@@ -791,7 +791,12 @@ int main(int argc, char **argv) {
   if (exchange) {  // records travel to the contexts that own their chromosomes (RCCL over xGMI, issued by the library)
     if (cmgpu_exchange_init_all(ctxs.data(), a.gpus) != CMGPU_OK) die(cmgpu_last_error(ctxs[0]));
   }
-  const bool device_ingest = !a.out_pairs && !a.out_sam && !a.host_ingest;  // pairs / SAM output need read names (and qualities): host parser
+  // Pairs output (--preset hic, --pairs) goes through the device ingest like BED: stream 0 keeps the read names in HBM and the final
+  // step renders the text from them (cmgpu_store_format_pairs_resident).  --SAM stays on the host parser: its text is written on the
+  // host from host strings (names, bases, qualities of both mates), and moving it is a separate change.  --gpus N > 1 with pairs
+  // output stays refused above.  --host-ingest forces the kseq-style parser (the fallback the CMGPU_EFORMAT message names).
+  const bool device_ingest = !a.out_sam && !a.host_ingest;
+  if (device_ingest && a.out_pairs && cmgpu_fastq_keep_names(ctx, 0, 1) != CMGPU_OK) die(cmgpu_last_error(ctx));
   // --SAM: everything the final sort needs, over all batches
   std::vector<cmgpu_sam_record> sam_rec;
   std::vector<uint32_t> sam_cigar;
@@ -864,6 +869,7 @@ int main(int argc, char **argv) {
     for (cmgpu_stats &x : wst) memset(&x, 0, sizeof(x));
     size_t turn = 0;
     bool store_sized = false;
+    uint64_t names_seen = 0, name_bytes_seen = 0;
     const bool overlap1 = NG == 1 && !exchange && !getenv("CM_CLI_NO_OVERLAP");  // (the variable: the serial order, for measurements)
     auto finish_round = [&]() {
       for (size_t gi = 0; gi < NG; ++gi) if (busy[gi]) { workers[gi].join(); busy[gi] = 0; }
@@ -992,6 +998,12 @@ int main(int argc, char **argv) {
         t_parse += now_s() - t0 - (tj1 - tj0);
         t_map += tj1 - tj0;
         if (dbg_times) fprintf(stderr, "[times] scan %.4f take %.4f wait for the batch before %.4f\n", ts1 - ts0, tj0 - ts1, tj1 - tj0);
+        if (dbg_times && a.out_pairs) {  // names of this batch: what the commit added to the name store
+          uint64_t nn = 0, nb = 0;
+          ckx(cmgpu_names_info(cx, &nn, &nb, nullptr));
+          fprintf(stderr, "[times] names %llu %llu\n", (unsigned long long)(nn - names_seen), (unsigned long long)(nb - name_bytes_seen));
+          names_seen = nn; name_bytes_seen = nb;
+        }
         t0 = now_s();
         {
           const size_t gi = turn;
@@ -1190,13 +1202,17 @@ int main(int argc, char **argv) {
                             paired ? sam_b2.data() : nullptr, paired ? sam_q2.data() : nullptr, paired ? sam_o2.data() : nullptr,
                             a.out_path.c_str());
   } else if (a.out_pairs) {
-    // sort + MAPQ filter + text on the device; the read names go up once as a blob
-    std::string blob;
-    std::vector<uint64_t> roff(read_names.size() + 1, 0);
-    for (size_t i = 0; i < read_names.size(); ++i) { blob += read_names[i]; roff[i + 1] = blob.size(); }
+    // sort + MAPQ filter + text on the device; the read names are in HBM already (device ingest) or go up once as a blob (host parser)
     uint64_t nl = 0, nbytes = 0;
-    if (cmgpu_store_format_pairs(ctx, out_names.data(), ref.n_sequences, &a.p, blob.data(), roff.data(), (uint32_t)read_names.size(), 0, &nl, &nbytes) != CMGPU_OK)
-      die(cmgpu_last_error(ctx));
+    if (device_ingest) {
+      if (cmgpu_store_format_pairs_resident(ctx, out_names.data(), ref.n_sequences, &a.p, &nl, &nbytes) != CMGPU_OK) die(cmgpu_last_error(ctx));
+    } else {
+      std::string blob;
+      std::vector<uint64_t> roff(read_names.size() + 1, 0);
+      for (size_t i = 0; i < read_names.size(); ++i) { blob += read_names[i]; roff[i + 1] = blob.size(); }
+      if (cmgpu_store_format_pairs(ctx, out_names.data(), ref.n_sequences, &a.p, blob.data(), roff.data(), (uint32_t)read_names.size(), 0, &nl, &nbytes) != CMGPU_OK)
+        die(cmgpu_last_error(ctx));
+    }
     if (cmgpu_write_pairs_header(out_names.data(), out_lengths.data(), ref.n_sequences, pairs_rank.empty() ? nullptr : pairs_rank.data(), a.out_path.c_str()) != CMGPU_OK)
       die("Cannot write " + a.out_path);
     if (cmgpu_store_write_text(ctx, a.out_path.c_str(), 1) != CMGPU_OK) die(cmgpu_last_error(ctx));

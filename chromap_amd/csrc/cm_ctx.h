@@ -40,6 +40,11 @@ struct CmFqStream {
   int n_ranges = 0;
   int rng_start[4] = {0, 0, 0, 0}, rng_end[4] = {-1, -1, -1, -1};
   bool minus = false;
+  // read names (cmgpu_fastq_keep_names): the taken records' names back to back in the STAGING blob st_nm, nm_off their n + 1 offsets;
+  // cmgpu_fastq_commit appends them to the context's run-wide name store
+  bool keep_names = false;
+  DevBuf nm_len, nm_off, st_nm;
+  uint32_t taken_name_bytes = 0;
 };
 
 // multi-GPU record exchange (cm_exchange.hip): this context's place in a group of `world` contexts, one per GPU
@@ -122,6 +127,12 @@ struct cmgpu_ctx {
   uint64_t store_n = 0, store_cap = 0, text_bytes = 0, text_lines = 0;
   bool store_has_bc = false;
   CmFqStream fq[3];  // read 1, read 2, barcode
+  // run-wide read-name store (cm_ingest.hip): the names of reads nm_base .. nm_base + nm_n - 1 back to back in nm_blob, nm_offs their
+  // nm_n + 1 64-bit offsets; fed by cmgpu_fastq_commit from the one stream that keeps names, read where it lies by
+  // cmgpu_store_format_pairs_resident
+  DevBuf nm_blob, nm_offs;
+  uint64_t nm_n = 0, nm_bytes = 0, nm_cap_n = 0;
+  uint32_t nm_base = 0;
   // --SAM outputs of the last batch (cm_stages.h: cm_ref_start_end_sam)
   DevBuf sam_rec, sam_cigar, sam_md, sam_z;
   DevBuf pairs_rank;
@@ -205,8 +216,8 @@ struct cmgpu_ctx {
 
   std::vector<DevBuf *> all_bufs() {
     std::vector<DevBuf *> v = core_bufs();
-    for (CmFqStream &f : fq) for (DevBuf *b : {&f.text, &f.cnt, &f.off, &f.nl, &f.keep, &f.pos, &f.recidx, &f.len, &f.bad, &f.text2, &f.comp, &f.btab, &f.toks, &f.ntok, &f.scan_tmp, &f.red_tmp}) v.push_back(b);
-    for (DevBuf *b : {&st_rb0, &st_rb1, &st_ro0, &st_ro1, &st_bcb, &st_bcq, &st_bco}) v.push_back(b);
+    for (CmFqStream &f : fq) for (DevBuf *b : {&f.text, &f.cnt, &f.off, &f.nl, &f.keep, &f.pos, &f.recidx, &f.len, &f.bad, &f.text2, &f.comp, &f.btab, &f.toks, &f.ntok, &f.scan_tmp, &f.red_tmp, &f.nm_len, &f.nm_off, &f.st_nm}) v.push_back(b);
+    for (DevBuf *b : {&st_rb0, &st_rb1, &st_ro0, &st_ro1, &st_bcb, &st_bcq, &st_bco, &nm_blob, &nm_offs}) v.push_back(b);
     for (CmBatchSlot &sl : slots) for (DevBuf *b : {&sl.rb0, &sl.rb1, &sl.ro0, &sl.ro1}) v.push_back(b);
     return v;
   }

@@ -9,6 +9,9 @@
 //          records with an empty sequence line are dropped from the stream
 //   take:  the first n records' sequence (and quality) lines are gathered into the resident
 //          batch arrays of that mate; bytes_consumed tells the host where the next chunk starts
+//   names: a stream told to keep them (cmgpu_fastq_keep_names) also gathers the taken records' names -- kseq's name.s: the header
+//          line after '@' up to the first isspace() byte, ks_getuntil(ks, 0, &seq->name, &c), kseq.h:188 -- into a staging blob;
+//          the commit appends them to the context's run-wide name store, which the pairs text is rendered from where it lies
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <cstring>
@@ -150,6 +153,67 @@ __global__ __launch_bounds__(FQ_BLOCK) void k_fq_gather(const uint8_t *__restric
       if (quals) quals[dst] = text[qs + (uint32_t)p];
     }
   }
+}
+
+// ---- read names ------------------------------------------------------------------------------------------------------------------
+// bit 7 of every byte of w for which C's isspace() holds (' ', \t \n \v \f \r); exact per byte: the sums stay below 256, so nothing
+// carries from one byte into the next
+__device__ __forceinline__ uint64_t fq_space_mask(uint64_t w) {
+  const uint64_t L = 0x0101010101010101ull, H = 0x8080808080808080ull;
+  const uint64_t x = w & ~H;
+  const uint64_t ctl = ~(x + (0x80 - 14) * L) & (x + (0x80 - 9) * L) & ~w;  // 9 <= byte < 14
+  const uint64_t y = w ^ (0x20 * L);
+  const uint64_t sp = ~(((y & ~H) + ~H) | y);                                // byte == ' '
+  return (ctl | sp) & H;
+}
+// first byte of the name of taken record j: behind the '@' of its header line
+__device__ __forceinline__ uint32_t fq_name_start(const uint32_t *__restrict__ nl, uint32_t raw) {
+  return (raw == 0 ? 0u : nl[4 * raw - 1] + 1u) + 1u;
+}
+// name length of every taken record: the header is read in aligned 16-byte pieces from the piece that holds its first byte on (a
+// thread per record: a header is a few tens of bytes, two or three loads).  The line's own '\n' ends the search at the latest; the text
+// buffers have 32 bytes of room behind n_bytes, so the last piece stays inside the allocation.
+__global__ __launch_bounds__(FQ_BLOCK) void k_fq_name_len(const uint8_t *__restrict__ text, uint64_t n_bytes, const uint32_t *__restrict__ nl,
+                                                            const uint32_t *__restrict__ recidx, uint32_t n, uint32_t *__restrict__ len) {
+  const uint32_t j = blockIdx.x * FQ_BLOCK + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t s = fq_name_start(nl, recidx[j]);
+  uint32_t a = s & ~15u, skip = s - a, end = (uint32_t)n_bytes;
+  while (a < n_bytes) {
+    const uint4 v = *reinterpret_cast<const uint4 *>(text + a);
+    uint64_t m0 = fq_space_mask((uint64_t)v.x | ((uint64_t)v.y << 32)), m1 = fq_space_mask((uint64_t)v.z | ((uint64_t)v.w << 32));
+    if (skip >= 8) { m0 = 0; m1 &= ~0ull << (8 * (skip - 8)); }  // (bytes of the piece in front of the name)
+    else if (skip) m0 &= ~0ull << (8 * skip);
+    skip = 0;
+    if (m0) { end = a + (uint32_t)(__ffsll((unsigned long long)m0) - 1) / 8u; break; }
+    if (m1) { end = a + 8u + (uint32_t)(__ffsll((unsigned long long)m1) - 1) / 8u; break; }
+    a += 16u;
+  }
+  len[j] = end > s ? end - s : 0u;
+}
+// the names back to back: single bytes up to the destination's next 4-byte boundary, then whole words (the source is read at whatever
+// alignment it has), then the last bytes
+__global__ __launch_bounds__(FQ_BLOCK) void k_fq_name_gather(const uint8_t *__restrict__ text, const uint32_t *__restrict__ nl,
+                                                               const uint32_t *__restrict__ recidx, const uint32_t *__restrict__ off, uint32_t n,
+                                                               uint8_t *__restrict__ blob) {
+  const uint32_t j = blockIdx.x * FQ_BLOCK + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t o = off[j], len = off[j + 1] - o;
+  const uint8_t *src = text + fq_name_start(nl, recidx[j]);
+  uint8_t *dst = blob + o;
+  uint32_t i = 0;
+  for (; i < len && ((o + i) & 3u); ++i) dst[i] = src[i];
+  for (; i + 4 <= len; i += 4) {
+    uint32_t w;
+    __builtin_memcpy(&w, src + i, 4);
+    *reinterpret_cast<uint32_t *>(dst + i) = w;
+  }
+  for (; i < len; ++i) dst[i] = src[i];
+}
+// commit: the batch's n + 1 staging offsets, moved behind the bytes the store already holds, become the store's offsets nm_n .. nm_n + n
+__global__ __launch_bounds__(FQ_BLOCK) void k_fq_name_append(const uint32_t *__restrict__ off, uint32_t n, uint64_t base, uint64_t *__restrict__ out) {
+  const uint32_t j = blockIdx.x * FQ_BLOCK + threadIdx.x;
+  if (j <= n) out[j] = base + off[j];
 }
 
 struct FqMaxOp {
@@ -453,6 +517,7 @@ extern "C" int cmgpu_fastq_take(cmgpu_ctx *c, int stream, uint32_t n, uint64_t *
   f.taken = n;
   f.taken_bases = 0;
   f.taken_max_len = 0;
+  f.taken_name_bytes = 0;
   // where the host resumes: the end of the last raw record used; trailing empty records and,
   // at the end of the file, blank lines go with it
   uint32_t last_raw = 0;
@@ -478,7 +543,8 @@ extern "C" int cmgpu_fastq_take(cmgpu_ctx *c, int stream, uint32_t n, uint64_t *
     FQCHECK(c, cm_stream_sync(s));
     return f.dev_mode ? fq_retain_rest(c, f, consumed, f.final_chunk && n == f.n_rec, bytes_consumed) : CMGPU_OK;
   }
-  if (f.len.ensure(((size_t)n + 1) * 4) || f.scan_tmp.ensure(cm_scan_tmp_words(n) * 4) || f.bad.ensure(4)) {
+  if (f.len.ensure(((size_t)n + 1) * 4) || f.scan_tmp.ensure(cm_scan_tmp_words(n) * 4) || f.bad.ensure(4) ||
+      (f.keep_names && (f.nm_len.ensure(((size_t)n + 1) * 4) || f.nm_off.ensure(((size_t)n + 1) * 4)))) {
     cm_set_error(c, "out of device memory (FASTQ lengths)"); return CMGPU_ENOMEM;
   }
   const dim3 g((n + FQ_BLOCK - 1) / FQ_BLOCK), b(FQ_BLOCK);
@@ -492,18 +558,80 @@ extern "C" int cmgpu_fastq_take(cmgpu_ctx *c, int stream, uint32_t n, uint64_t *
   (void)rocprim::reduce(nullptr, tb, (const uint32_t *)f.len.p, (uint32_t *)f.bad.p, 0u, (size_t)n, FqMaxOp(), s);
   if (f.red_tmp.ensure(tb + 256)) { cm_set_error(c, "out of device memory (reduce)"); return CMGPU_ENOMEM; }
   hipError_t e = rocprim::reduce(f.red_tmp.p, tb, (const uint32_t *)f.len.p, (uint32_t *)f.bad.p, 0u, (size_t)n, FqMaxOp(), s);
-  uint32_t total = 0, mx = 0;
+  uint32_t total = 0, mx = 0, name_total = 0;
+  if (f.keep_names) {  // (lengths and offsets of the names in the same wait as the bases')
+    hipLaunchKernelGGL(k_fq_name_len, g, b, 0, s, (const uint8_t *)f.text.p, f.n_bytes, (const uint32_t *)f.nl.p, (const uint32_t *)f.recidx.p, n,
+                       (uint32_t *)f.nm_len.p);
+    cm_scan_u32((const uint32_t *)f.nm_len.p, (uint32_t *)f.nm_off.p, n, (uint32_t *)f.scan_tmp.p, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&name_total, (uint32_t *)f.nm_off.p + n, 4, hipMemcpyDeviceToHost, s);
+  }
   if (e == hipSuccess) e = hipMemcpyAsync(&total, (uint32_t *)offs.p + n, 4, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipMemcpyAsync(&mx, f.bad.p, 4, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = cm_stream_sync(s);
   if (e != hipSuccess) { cm_set_error(c, std::string("FASTQ take: ") + hipGetErrorString(e)); return CMGPU_EHIP; }
   if (bases.ensure((size_t)total + 16) || (stream == 2 && c->st_bcq.ensure((size_t)total + 16))) { cm_set_error(c, "out of device memory (reads)"); return CMGPU_ENOMEM; }
+  if (f.keep_names && f.st_nm.ensure((size_t)name_total + 16)) { cm_set_error(c, "out of device memory (read names)"); return CMGPU_ENOMEM; }
   hipLaunchKernelGGL(k_fq_gather, g, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, (const uint32_t *)f.recidx.p,
                      (const uint32_t *)offs.p, n, fmt, (uint8_t *)bases.p, stream == 2 ? (uint8_t *)c->st_bcq.p : (uint8_t *)nullptr);
+  if (f.keep_names)
+    hipLaunchKernelGGL(k_fq_name_gather, g, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, (const uint32_t *)f.recidx.p,
+                       (const uint32_t *)f.nm_off.p, n, (uint8_t *)f.st_nm.p);
   FQCHECK(c, cm_stream_sync(s));
   f.taken_bases = total;
   f.taken_max_len = mx;
+  f.taken_name_bytes = name_total;
   if (f.dev_mode) return fq_retain_rest(c, f, consumed, f.final_chunk && n == f.n_rec, bytes_consumed);
+  return CMGPU_OK;
+}
+
+// ---- the run-wide name store: blob + 64-bit offsets indexed by read_id - nm_base, doubling like the record store (cm_post.hip) ----
+static int fq_names_reserve(cmgpu_ctx *c, CmFqStream &f, uint64_t need_n, uint64_t need_bytes) {
+  hipStream_t s = fq_hs(c, f);
+  if (need_n > c->nm_cap_n || !c->nm_offs.p) {
+    uint64_t cap = c->nm_cap_n ? c->nm_cap_n * 2 : 1u << 20;
+    if (cap < need_n) cap = need_n;
+    DevBuf nb;
+    if (nb.ensure((cap + 1) * 8)) { cm_set_error(c, "out of device memory (read-name store: offsets of " + std::to_string((unsigned long long)cap) + " names)"); return CMGPU_ENOMEM; }
+    hipError_t e = c->nm_offs.p ? hipMemcpyAsync(nb.p, c->nm_offs.p, (c->nm_n + 1) * 8, hipMemcpyDeviceToDevice, s) : hipMemsetAsync(nb.p, 0, 8, s);
+    if (e == hipSuccess) e = cm_stream_sync(s);
+    if (e != hipSuccess) { nb.release(); FQCHECK(c, e); }
+    c->nm_offs.release();
+    c->nm_offs = nb;
+    c->nm_cap_n = cap;
+  }
+  if (need_bytes + 16 > c->nm_blob.cap) {
+    uint64_t cap = c->nm_blob.cap ? c->nm_blob.cap * 2 : 32u << 20;
+    if (cap < need_bytes + 16) cap = need_bytes + 16;
+    DevBuf nb;
+    // (ensure() asks for a quarter more than it is told and falls back to the bare size)
+    if (nb.ensure(cap)) { cm_set_error(c, "out of device memory (read-name store: " + std::to_string((unsigned long long)cap) + " bytes of names)"); return CMGPU_ENOMEM; }
+    hipError_t e = c->nm_bytes ? hipMemcpyAsync(nb.p, c->nm_blob.p, c->nm_bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
+    if (e == hipSuccess) e = cm_stream_sync(s);
+    if (e != hipSuccess) { nb.release(); FQCHECK(c, e); }
+    c->nm_blob.release();
+    c->nm_blob = nb;
+  }
+  return CMGPU_OK;
+}
+// the n names last taken from f (staging) behind the store's; they must continue it: first_read_id == nm_base + nm_n
+static int fq_names_append(cmgpu_ctx *c, CmFqStream &f, uint32_t n, uint32_t first_read_id) {
+  if (c->nm_n == 0) c->nm_base = first_read_id;
+  else if ((uint64_t)first_read_id != (uint64_t)c->nm_base + c->nm_n) {
+    cm_set_error(c, "read names are kept for consecutive read ids: the store ends at read " + std::to_string((unsigned long long)c->nm_base + c->nm_n) +
+                        ", the batch starts at " + std::to_string(first_read_id) + " (cmgpu_names_clear starts a new run)");
+    return CMGPU_EINVAL;
+  }
+  if (n == 0) return CMGPU_OK;
+  const int rc = fq_names_reserve(c, f, c->nm_n + n, c->nm_bytes + f.taken_name_bytes);
+  if (rc) return rc;
+  hipStream_t s = fq_hs(c, f);
+  hipLaunchKernelGGL(k_fq_name_append, dim3(n / FQ_BLOCK + 1), dim3(FQ_BLOCK), 0, s, (const uint32_t *)f.nm_off.p, n, c->nm_bytes,
+                     (uint64_t *)c->nm_offs.p + c->nm_n);
+  if (f.taken_name_bytes)
+    FQCHECK(c, hipMemcpyAsync((uint8_t *)c->nm_blob.p + c->nm_bytes, f.st_nm.p, f.taken_name_bytes, hipMemcpyDeviceToDevice, s));
+  FQCHECK(c, cm_stream_sync(s));
+  c->nm_n += n;
+  c->nm_bytes += f.taken_name_bytes;
   return CMGPU_OK;
 }
 
@@ -518,6 +646,13 @@ extern "C" int cmgpu_fastq_commit(cmgpu_ctx *c, uint32_t n, uint32_t first_read_
   if (n > 0x3fffffffu) { cm_set_error(c, "batch too large"); return CMGPU_EINVAL; }
   if (!paired && c->p.split) { cm_set_error(c, "single-end split alignment is not supported"); return CMGPU_EINVAL; }
   if (barcoded && c->wl_size != 0 && c->wl_num_sample == 0) { cm_set_error(c, "barcode abundance not computed"); return CMGPU_EINVAL; }
+  // the batch's names join the run-wide store first: a commit that cannot keep them (a gap in the read ids, no memory) changes nothing
+  for (int m = 0; m < 2; ++m)
+    if (c->fq[m].keep_names) {
+      if (m == 1 && !paired) { cm_set_error(c, "the names of read 2 are kept, but the batch is single-end"); return CMGPU_EINVAL; }
+      const int nrc = fq_names_append(c, c->fq[m], n, first_read_id);
+      if (nrc) return nrc;
+    }
   // the taken batch becomes the resident one: the staging buffers and the resident batch's swap (the old batch's buffers take the next
   // take).  The caller has no cmgpu_map_* call of this context running here.
   std::swap(c->rb0, c->st_rb0); std::swap(c->ro0, c->st_ro0);
@@ -536,6 +671,39 @@ extern "C" int cmgpu_fastq_commit(cmgpu_ctx *c, uint32_t n, uint32_t first_read_
     if (c->ro1.ensure(((size_t)n + 1) * 4) || c->rb1.ensure(16)) { cm_set_error(c, "out of device memory (reads)"); return CMGPU_ENOMEM; }
     FQCHECK(c, hipMemset(c->ro1.p, 0, ((size_t)n + 1) * 4));
   }
+  return CMGPU_OK;
+}
+
+// Replaces kseq's name.s for the device ingest (kseq.h:188, read into SequenceBatch by LoadOneSequenceAndSaveAt, sequence_batch.cc:36):
+// the stream's takes also gather the records' names.  One stream per context: the store is indexed by read id.
+extern "C" int cmgpu_fastq_keep_names(cmgpu_ctx *c, int stream, int on) {
+  if (!c || stream < 0 || stream > 1) return CMGPU_EINVAL;
+  if (on && c->fq[1 - stream].keep_names) { cm_set_error(c, "the names of one stream are kept per context (those of the other mate are already on)"); return CMGPU_EINVAL; }
+  c->fq[stream].keep_names = on != 0;
+  c->fq[stream].taken_name_bytes = 0;
+  return CMGPU_OK;
+}
+extern "C" int cmgpu_names_clear(cmgpu_ctx *c) {
+  if (!c) return CMGPU_EINVAL;
+  c->nm_n = 0;
+  c->nm_bytes = 0;
+  c->nm_base = 0;
+  return CMGPU_OK;
+}
+extern "C" int cmgpu_names_info(const cmgpu_ctx *c, uint64_t *n_names, uint64_t *n_bytes, uint32_t *read_id_base) {
+  if (!c) return CMGPU_EINVAL;
+  if (n_names) *n_names = c->nm_n;
+  if (n_bytes) *n_bytes = c->nm_bytes;
+  if (read_id_base) *read_id_base = c->nm_base;
+  return CMGPU_OK;
+}
+extern "C" int cmgpu_download_names(cmgpu_ctx *c, char *blob, uint64_t blob_capacity, uint64_t *offsets) {
+  if (!c || !offsets || (!blob && c->nm_bytes)) return CMGPU_EINVAL;
+  if (blob_capacity < c->nm_bytes) { cm_set_error(c, "name buffer too small"); return CMGPU_ECAPACITY; }
+  FQCHECK(c, cm_enter(c));
+  offsets[0] = 0;
+  if (c->nm_n) FQCHECK(c, hipMemcpy(offsets, c->nm_offs.p, (c->nm_n + 1) * 8, hipMemcpyDeviceToHost));
+  if (c->nm_bytes) FQCHECK(c, hipMemcpy(blob, c->nm_blob.p, c->nm_bytes, hipMemcpyDeviceToHost));
   return CMGPU_OK;
 }
 

@@ -808,10 +808,11 @@ __global__ __launch_bounds__(PP_BLOCK) void k_pp_pairs_format(const uint8_t *__r
   *p++ = '\n';
 }
 
-extern "C" int cmgpu_store_format_pairs(cmgpu_ctx *c, const char *const *names, uint32_t n_sequences, const cmgpu_params *p,
-                                        const char *read_names, const uint64_t *read_name_offsets, uint32_t n_read_names,
-                                        uint32_t read_id_base, uint64_t *n_lines, uint64_t *n_bytes) {
-  if (!c || !names || !p || !n_lines || !n_bytes || (!read_names && n_read_names) || (!read_name_offsets && n_read_names)) return CMGPU_EINVAL;
+// the body of cmgpu_store_format_pairs and cmgpu_store_format_pairs_resident.  resident: the read names are the context's name store
+// (cm_ingest.hip), read by the kernels above where they lie; otherwise the caller's host blob and offsets are uploaded first.
+static int pp_format_pairs(cmgpu_ctx *c, const char *const *names, uint32_t n_sequences, const cmgpu_params *p, bool resident,
+                           const char *read_names, const uint64_t *read_name_offsets, uint32_t n_read_names,
+                           uint32_t read_id_base, uint64_t *n_lines, uint64_t *n_bytes) {
   if (!cm_pairs_records(c)) { cm_set_error(c, "pairs text needs pairs records (split alignment, or output_format = CMGPU_FORMAT_PAIRS)"); return CMGPU_EINVAL; }
   // (cell barcodes: they decided which pairs were mapped -- CorrectBarcodeAt, chromap.h:896-906 -- and go no further: a PairsMapping's barcode is
   //  neither printed nor part of its order or equality, pairs_mapping.h:40-50, GetBarcode() == 0; the store's key array is left alone)
@@ -827,20 +828,25 @@ extern "C" int cmgpu_store_format_pairs(cmgpu_ctx *c, const char *const *names, 
   std::vector<uint32_t> noff(n_sequences + 1, 0);
   std::string blob;
   for (uint32_t i = 0; i < n_sequences; ++i) { blob += names[i]; noff[i + 1] = (uint32_t)blob.size(); }
-  const uint64_t rn_bytes = n_read_names ? read_name_offsets[n_read_names] : 0;
+  const uint64_t rn_bytes = !resident && n_read_names ? read_name_offsets[n_read_names] : 0;
   DevBuf d_names, d_noff, d_rn, d_rnoff, k0, k1, v0, v1, tmp, llen, loff;
   auto fail = [&](int rc) { d_names.release(); d_noff.release(); d_rn.release(); d_rnoff.release(); k0.release(); k1.release(); v0.release();
                             v1.release(); tmp.release(); llen.release(); loff.release(); return rc; };
-  if (d_names.ensure(blob.size() + 16) || d_noff.ensure(noff.size() * 4) || d_rn.ensure(rn_bytes + 16) || d_rnoff.ensure(((size_t)n_read_names + 1) * 8) ||
+  if (d_names.ensure(blob.size() + 16) || d_noff.ensure(noff.size() * 4) || d_rn.ensure(rn_bytes + 16) ||
+      d_rnoff.ensure(resident ? 8 : ((size_t)n_read_names + 1) * 8) ||
       k0.ensure((size_t)n * 8) || k1.ensure((size_t)n * 8) || v0.ensure((size_t)n * 4) || v1.ensure((size_t)n * 4) || llen.ensure(((size_t)n + 1) * 8) ||
       loff.ensure(((size_t)n + 1) * 8)) { cm_set_error(c, "out of device memory (post-processing)"); return fail(CMGPU_ENOMEM); }
   const uint64_t zero = 0;
   if (hipMemcpyAsync(d_names.p, blob.data(), blob.size(), hipMemcpyHostToDevice, s) != hipSuccess ||
       hipMemcpyAsync(d_noff.p, noff.data(), noff.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
       (rn_bytes && hipMemcpyAsync(d_rn.p, read_names, rn_bytes, hipMemcpyHostToDevice, s) != hipSuccess) ||
-      hipMemcpyAsync(d_rnoff.p, n_read_names ? (const void *)read_name_offsets : (const void *)&zero, ((size_t)n_read_names + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess) {
+      hipMemcpyAsync(d_rnoff.p, !resident && n_read_names ? (const void *)read_name_offsets : (const void *)&zero,
+                     resident ? 8 : ((size_t)n_read_names + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess) {
     cm_set_error(c, "name upload failed"); return fail(CMGPU_EHIP);
   }
+  // (no names at all: the one zero offset uploaded above stands for an empty table)
+  const uint8_t *rn = resident && n_read_names ? (const uint8_t *)c->nm_blob.p : (const uint8_t *)d_rn.p;
+  const uint64_t *rn_off = resident && n_read_names ? (const uint64_t *)c->nm_offs.p : (const uint64_t *)d_rnoff.p;
   const dim3 g((n + PP_BLOCK - 1) / PP_BLOCK), b(PP_BLOCK);
   const uint8_t *store = (const uint8_t *)c->store.p;
   uint64_t *ka = (uint64_t *)k0.p, *kb = (uint64_t *)k1.p;
@@ -859,7 +865,7 @@ extern "C" int cmgpu_store_format_pairs(cmgpu_ctx *c, const char *const *names, 
   if ((rc = pp_sort_pass(c, tmp, ka, kb, va, vb, n, 2 * rid_bits))) return fail(rc);
   std::swap(va, vb);
   hipLaunchKernelGGL(k_pp_pairs_len, g, b, 0, s, store, (const uint32_t *)va, n, p->mapq_threshold, n_sequences, (const uint32_t *)d_noff.p,
-                     (const uint64_t *)d_rnoff.p, read_id_base, n_read_names, (uint64_t *)llen.p,
+                     rn_off, read_id_base, n_read_names, (uint64_t *)llen.p,
                      p->remove_pcr_duplicates ? (p->low_memory_mode ? 1 : 2) : 0);
   if (hipMemsetAsync((uint64_t *)llen.p + n, 0, 8, s) != hipSuccess) { cm_set_error(c, "memset failed"); return fail(CMGPU_EHIP); }
   size_t tb = 0, tb2 = 0;
@@ -878,8 +884,7 @@ extern "C" int cmgpu_store_format_pairs(cmgpu_ctx *c, const char *const *names, 
   if (e != hipSuccess) { cm_set_error(c, std::string("post-processing scan: ") + hipGetErrorString(e)); return fail(CMGPU_EHIP); }
   if (c->text.ensure(total + 64)) { cm_set_error(c, "out of device memory (text)"); return fail(CMGPU_ENOMEM); }
   hipLaunchKernelGGL(k_pp_pairs_format, g, b, 0, s, store, (const uint32_t *)va, n, (const uint64_t *)llen.p, (const uint64_t *)loff.p,
-                     (const uint8_t *)d_names.p, (const uint32_t *)d_noff.p, (const uint8_t *)d_rn.p, (const uint64_t *)d_rnoff.p, read_id_base,
-                     (uint8_t *)c->text.p);
+                     (const uint8_t *)d_names.p, (const uint32_t *)d_noff.p, rn, rn_off, read_id_base, (uint8_t *)c->text.p);
   e = cm_stream_sync(s);
   if (e != hipSuccess) { cm_set_error(c, std::string("text formatting: ") + hipGetErrorString(e)); return fail(CMGPU_EHIP); }
   c->text_bytes = total;
@@ -887,6 +892,20 @@ extern "C" int cmgpu_store_format_pairs(cmgpu_ctx *c, const char *const *names, 
   *n_lines = lines;
   *n_bytes = total;
   return fail(CMGPU_OK);
+}
+
+extern "C" int cmgpu_store_format_pairs(cmgpu_ctx *c, const char *const *names, uint32_t n_sequences, const cmgpu_params *p,
+                                        const char *read_names, const uint64_t *read_name_offsets, uint32_t n_read_names,
+                                        uint32_t read_id_base, uint64_t *n_lines, uint64_t *n_bytes) {
+  if (!c || !names || !p || !n_lines || !n_bytes || (!read_names && n_read_names) || (!read_name_offsets && n_read_names)) return CMGPU_EINVAL;
+  return pp_format_pairs(c, names, n_sequences, p, false, read_names, read_name_offsets, n_read_names, read_id_base, n_lines, n_bytes);
+}
+// the same with the read names the device ingest kept (cmgpu_fastq_keep_names): nothing is uploaded or copied
+extern "C" int cmgpu_store_format_pairs_resident(cmgpu_ctx *c, const char *const *names, uint32_t n_sequences, const cmgpu_params *p,
+                                                 uint64_t *n_lines, uint64_t *n_bytes) {
+  if (!c || !names || !p || !n_lines || !n_bytes) return CMGPU_EINVAL;
+  if (c->nm_n > 0xffffffffull) { cm_set_error(c, "more than 2^32 read names"); return CMGPU_ECAPACITY; }
+  return pp_format_pairs(c, names, n_sequences, p, true, nullptr, nullptr, (uint32_t)c->nm_n, c->nm_base, n_lines, n_bytes);
 }
 
 extern "C" int cmgpu_store_text(cmgpu_ctx *c, char *out, uint64_t capacity) {

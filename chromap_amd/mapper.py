@@ -492,6 +492,28 @@ class ChromapGPU:
         self._check(self.L.cmgpu_fastq_commit(self.ctx, n, first_read_id, int(paired), int(barcoded)), self.ctx)
         self._n_resident = n
 
+    def fastq_keep_names(self, stream=0, on=True):
+        """the stream's takes also gather the read names (kseq's name.s); commits append them to the context's name store"""
+        self._check(self.L.cmgpu_fastq_keep_names(self.ctx, stream, int(on)), self.ctx)
+
+    def names_clear(self):
+        self._check(self.L.cmgpu_names_clear(self.ctx), self.ctx)
+
+    def names_info(self):
+        """(names, bytes, read id of the first name) of the name store"""
+        n, nb, base = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        self._check(self.L.cmgpu_names_info(self.ctx, C.byref(n), C.byref(nb), C.byref(base)), self.ctx)
+        return int(n.value), int(nb.value), int(base.value)
+
+    def download_names(self):
+        """the name store as a list of bytes, entry i: the name of read read_id_base + i"""
+        n, nb, _ = self.names_info()
+        blob = C.create_string_buffer(max(1, nb))
+        off = np.zeros(n + 1, np.uint64)
+        self._check(self.L.cmgpu_download_names(self.ctx, blob, nb, off.ctypes.data), self.ctx)
+        raw = blob.raw
+        return [raw[int(off[i]):int(off[i + 1])] for i in range(n)]
+
     def download_batch(self, n):
         """resident batch back on the host: (b1, o1, b2, o2)"""
         o1 = np.zeros(n + 1, np.uint32)
@@ -571,6 +593,14 @@ class ChromapGPU:
         nl, nb = C.c_uint64(0), C.c_uint64(0)
         self._check(self.L.cmgpu_store_format_pairs(self.ctx, names, len(self.names), C.byref(p), blob, off.ctypes.data, len(read_names),
                                                     read_id_base, C.byref(nl), C.byref(nb)), self.ctx)
+        return int(nl.value), int(nb.value)
+
+    def store_format_pairs_resident(self, params=None):
+        """store_format_pairs with the read names the device ingest kept (fastq_keep_names) instead of a host list"""
+        p = params if params is not None else self.params
+        names = (C.c_char_p * len(self.names))(*self.names)
+        nl, nb = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.cmgpu_store_format_pairs_resident(self.ctx, names, len(self.names), C.byref(p), C.byref(nl), C.byref(nb)), self.ctx)
         return int(nl.value), int(nb.value)
 
     def write_pairs_header(self, path):

@@ -482,6 +482,11 @@ int cmgpu_store_format(cmgpu_ctx *ctx, int kind, const char *const *names, uint3
 int cmgpu_store_format_pairs(cmgpu_ctx *ctx, const char *const *names, uint32_t n_sequences, const cmgpu_params *params,
                              const char *read_names, const uint64_t *read_name_offsets, uint32_t n_read_names, uint32_t read_id_base,
                              uint64_t *n_lines, uint64_t *n_bytes);
+/* cmgpu_store_format_pairs with the read names taken from the context's name store (cmgpu_fastq_keep_names) instead of a host
+ * blob: MappingWriter<PairsMapping>::AppendMapping's read_name column (src/mapping_writer.cc:400-423) comes from HBM, where the
+ * device ingest left it -- no upload, no copy.  Same order, filter and bytes. */
+int cmgpu_store_format_pairs_resident(cmgpu_ctx *ctx, const char *const *names, uint32_t n_sequences, const cmgpu_params *params,
+                                      uint64_t *n_lines, uint64_t *n_bytes);
 int cmgpu_write_pairs_header(const char *const *names, const uint32_t *lengths, uint32_t n_sequences, const uint32_t *pairs_rank,
                              const char *out_path);
 int cmgpu_store_text(cmgpu_ctx *ctx, char *out, uint64_t capacity);
@@ -507,7 +512,10 @@ int cmgpu_store_info(const cmgpu_ctx *ctx, uint64_t *n_records, uint64_t *text_b
  * Overlap: scans and takes touch only the streams' own buffers, HIP streams and the staging buffers, so ONE thread may
  * scan and take the next batch while ANOTHER is inside cmgpu_map_resident / cmgpu_store_append_resident with the
  * committed one (chromap-amd does; tests/test_gpu_ingest.py::test_next_batch_taken_while_the_last_is_mapped).
- * cmgpu_fastq_commit itself must not run beside a mapping call of the same context. */
+ * cmgpu_fastq_commit itself must not run beside a mapping call of the same context.
+ * Read names: cmgpu_fastq_keep_names makes a stream's takes gather the records' names as well (staging, like the bases); the
+ * commit appends them to a run-wide name store in HBM (cmgpu_names_info / cmgpu_download_names / cmgpu_names_clear), from which
+ * cmgpu_store_format_pairs_resident renders the pairs text -- so --preset hic / --pairs runs use this ingest too. */
 /* --read-format for one stream (SequenceEffectiveRange, src/sequence_effective_range.h, src/chromap.cc:825-866):
  * up to four [start, end] base ranges (0-based, inclusive, end -1 = last base) are concatenated, then the result is
  * reverse-complemented (bases) / reversed (qualities) when strand is '-'.  Applies to the following cmgpu_fastq_take calls. */
@@ -523,6 +531,21 @@ int cmgpu_fastq_scan(cmgpu_ctx *ctx, int stream, const char *text, uint64_t n_by
 int cmgpu_fastq_scan_bgzf(cmgpu_ctx *ctx, int stream, const void *blocks, uint64_t n_bytes, int final_chunk, uint32_t *n_records);
 int cmgpu_fastq_take(cmgpu_ctx *ctx, int stream, uint32_t n, uint64_t *bytes_consumed);
 int cmgpu_fastq_commit(cmgpu_ctx *ctx, uint32_t n, uint32_t first_read_id, int paired, int barcoded);
+/* Replaces kseq's name.s (ks_getuntil(ks, 0, &seq->name, &c), kseq.h:188, kept per read by SequenceBatch::LoadOneSequenceAndSaveAt,
+ * src/sequence_batch.cc:36) for the device ingest: with on != 0 every following cmgpu_fastq_take of the stream (0 = read 1 or
+ * 1 = read 2; one of them per context) also gathers, for the records it takes, the bytes of the header line after the '@' up to, not
+ * including, the first isspace() byte -- the comment is dropped, an empty name has length 0, records with an empty sequence have no
+ * name as they have no record; --read-format does not touch names.  cmgpu_fastq_commit then appends the batch's names to the
+ * context's name store, indexed by read_id - read_id_base: batches must be committed with consecutive read ids (a gap:
+ * CMGPU_EINVAL, nothing is committed); no room in HBM: CMGPU_ENOMEM.  Call it before the first scan of a run; on = 0 (the default)
+ * costs nothing. */
+int cmgpu_fastq_keep_names(cmgpu_ctx *ctx, int stream, int on);
+/* empties the name store (a new run; the next commit sets read_id_base) */
+int cmgpu_names_clear(cmgpu_ctx *ctx);
+int cmgpu_names_info(const cmgpu_ctx *ctx, uint64_t *n_names, uint64_t *n_bytes, uint32_t *read_id_base);
+/* the name store on the host: the names back to back in blob (capacity >= n_bytes), offsets[n_names + 1] into it -- what the host
+ * parser keeps in SequenceBatch::GetSequenceNameAt (src/sequence_batch.h); for tests and host-side writers */
+int cmgpu_download_names(cmgpu_ctx *ctx, char *blob, uint64_t blob_capacity, uint64_t *offsets);
 /* cmgpu_compute_barcode_abundance over the barcodes last taken from stream 2; feed the barcode
  * file in whole reference batches and stop when *done is set (20 M sampled, src/chromap.h:211). */
 int cmgpu_barcode_abundance_resident(cmgpu_ctx *ctx, uint64_t *num_sample_barcodes, int *done);
@@ -536,7 +559,8 @@ int64_t cmgpu_write_bed_pe(const char *const *names, uint32_t n_sequences, const
 
 /* pairs output of --preset hic (src/mapping_writer.cc:381-420): sort by PairsMapping::operator<
  * (src/pairs_mapping.h:40-43), MAPQ filter, header + one line per record.  read_names[read_id -
- * read_id_base] is the name of read 1 of the pair (names never go to the device). */
+ * read_id_base] is the name of read 1 of the pair (host strings; cmgpu_store_format_pairs_resident renders the same lines from the
+ * names the device ingest kept). */
 int64_t cmgpu_write_pairs(const char *const *names, const uint32_t *lengths, uint32_t n_sequences,
                           const cmgpu_params *params, cmgpu_pairs_record *records, uint64_t n_records,
                           const char *const *read_names, uint32_t read_id_base, const char *out_path);

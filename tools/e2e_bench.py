@@ -2,6 +2,9 @@
 """End-to-end run of the CLI on the GPU box (SURVEY.md 8(d) "Mapped all reads" analogue):
 synthetic genome + index built on the device and written to disk in the reference's formats,
 synthetic read pairs written as FASTQ, then `chromap-amd --preset atac` from files to BED.
+`--preset hic`: 2 x 150 Hi-C shaped pairs with ligation junctions (the generator of bench.py's hic workload), `chromap-amd --preset hic`
+from files to a pairs file, through the device ingest (read names kept in HBM) and through the host parser (`--host-ingest`, the route
+every pairs run took before), plain FASTQ and -- with --gz -- BGZF, `--reps` runs each; the pairs files must be identical.
 Prints one JSON object; everything is written under --dir (default /tmp/chromap_amd_e2e)."""
 import argparse
 import ctypes as C
@@ -35,15 +38,20 @@ def main():
     ap.add_argument("--genome", type=int, default=200_000_000)
     ap.add_argument("--nseq", type=int, default=8)
     ap.add_argument("--pairs", type=int, default=8_000_000)
-    ap.add_argument("--readlen", type=int, default=50)
+    ap.add_argument("--preset", default="atac", choices=("atac", "hic"))
+    ap.add_argument("--readlen", type=int, default=0, help="default: 50 (atac), 150 (hic)")
     ap.add_argument("--dir", default="/tmp/chromap_amd_e2e")
     ap.add_argument("--gz", action="store_true", help="also time gzip-compressed input (inflated on the host, one thread per file) and BGZF input (on the device)")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--baseline-cli", default="", help="--preset hic: also time this other chromap-amd binary (a build of an earlier commit) on the same files")
     ap.add_argument("--skip-host-ingest", action="store_true", help="a long job: leave the host parser's run out")
     args = ap.parse_args()
     os.makedirs(args.dir, exist_ok=True)
+    hic = args.preset == "hic"
+    if not args.readlen:
+        args.readlen = 150 if hic else 50
     from chromap_amd import ChromapGPU
-    g = ChromapGPU(synthetic=(args.genome, args.nseq, 4242), preset="atac")
+    g = ChromapGPU(synthetic=(args.genome, args.nseq, 4242), preset=args.preset)
     idx = os.path.join(args.dir, "g.index")
     fa = os.path.join(args.dir, "g.fa")
     g.save_index(idx)
@@ -58,21 +66,26 @@ def main():
             f.write(b">chr%d\n" % (i + 1))
             f.write(buf.raw[:lens[i]])
             f.write(b"\n")
-    g.generate_resident(args.pairs, read_length=args.readlen, frag_min=30, frag_max=600, sub_rate=0.01, seed=99)
+    if hic:  # mates from independent loci, 35 % of the reads with a ligation junction, 0.1 % indels: bench.py's hic workload
+        g.generate_resident(args.pairs, read_length=args.readlen, sub_rate=0.01, seed=99, indel_rate=0.001, hic=0.35)
+    else:
+        g.generate_resident(args.pairs, read_length=args.readlen, frag_min=30, frag_max=600, sub_rate=0.01, seed=99)
     b1, o1, b2, o2 = g.download_batch(args.pairs)
     r1 = os.path.join(args.dir, "r1.fq")
     r2 = os.path.join(args.dir, "r2.fq")
     write_fastq(r1, b1, args.pairs, args.readlen)
     write_fastq(r2, b2, args.pairs, args.readlen)
     g.close()
-    out = os.path.join(args.dir, "out.bed")
+    out = os.path.join(args.dir, "out.pairs" if hic else "out.bed")
     cli = os.path.join(ROOT, "chromap_amd", "chromap-amd")
     res = {}
 
-    def run(label, f1, f2, extra=(), reps=args.reps):
+    def run(label, f1, f2, extra=(), reps=args.reps, cli=cli):
         """the CLI `reps` times; the run with the shortest 'Mapped all reads' time is the one reported"""
         best = None
         times = []
+        walls = []
+        md5s_run = []
         for _ in range(reps):
             # every run starts from the same file-system state: no output file to truncate, no dirty pages of the run before
             # (the 246 MB a run writes are throttled by the write-back of the 246 MB the one before wrote)
@@ -80,20 +93,57 @@ def main():
                 os.remove(out)
             os.sync()
             t0 = time.time()
-            p = subprocess.run([cli, "--preset", "atac", "-x", idx, "-r", fa, "-1", f1, "-2", f2, "-o", out] + list(extra), stderr=subprocess.PIPE, check=True)
+            p = subprocess.run([cli, "--preset", args.preset, "-x", idx, "-r", fa, "-1", f1, "-2", f2, "-o", out] + list(extra), stderr=subprocess.PIPE, check=True)
             dt = time.time() - t0
             tail = [ln for ln in p.stderr.decode().splitlines() if ln.startswith("Mapped all reads") or ln.startswith("Sorted,")]
             mapped = [float(ln.split("in ")[1].split("s")[0]) for ln in tail if ln.startswith("Mapped all reads")]
             mapped = mapped[0] if mapped else None
             times.append(mapped)
-            if best is None or (mapped is not None and mapped < best["mapped_all_reads_s"]):
+            walls.append(round(dt, 3))
+            md5s_run.append(subprocess.check_output(["md5sum", out]).split()[0].decode())
+            # (the host parser's run prints no "Mapped all reads" line: its runs are ranked by wall time)
+            if best is None or (mapped is not None and mapped < best["mapped_all_reads_s"]) or (mapped is None and dt < best["wall_s"]):
                 best = {"wall_s": round(dt, 2), "M_pairs_per_s_wall": round(args.pairs / dt / 1e6, 2), "mapped_all_reads_s": mapped,
                         "M_pairs_per_s_mapped_all_reads": round(args.pairs / mapped / 1e6, 2) if mapped else None, "cli": tail,
                         "bed_md5": subprocess.check_output(["md5sum", out]).split()[0].decode(), "bed_bytes": os.path.getsize(out)}
         best["mapped_all_reads_s_runs"] = times
+        best["wall_s_runs"] = walls
+        best["md5_runs"] = md5s_run
         res[label] = best
 
     run("device_ingest", r1, r2)
+    if hic:
+        # the two routes of a pairs run, whole-process wall time: the requirement is slowest(device) < fastest(host) for each input kind
+        run("host_ingest", r1, r2, ["--host-ingest"])
+        if args.baseline_cli:
+            run("baseline_cli", r1, r2, cli=args.baseline_cli)
+        kinds = [("", "fastq")]
+        if args.gz:
+            sys.path.insert(0, os.path.join(ROOT, "tools"))
+            import bgzf
+            for f in (r1, r2):
+                bgzf.compress_file(f, f + ".bgz")
+            run("device_ingest_bgzf", r1 + ".bgz", r2 + ".bgz")
+            run("host_ingest_bgzf", r1 + ".bgz", r2 + ".bgz", ["--host-ingest"])
+            if args.baseline_cli:
+                run("baseline_cli_bgzf", r1 + ".bgz", r2 + ".bgz", cli=args.baseline_cli)
+            res["device_ingest_bgzf"]["bgzf_bytes"] = os.path.getsize(r1 + ".bgz") + os.path.getsize(r2 + ".bgz")
+            kinds.append(("_bgzf", "bgzf"))
+        md5s = set(m for k in res for m in res[k]["md5_runs"])  # every run of every route
+        verdict = {}
+        for sfx, kind in kinds:
+            d, h = res["device_ingest" + sfx]["wall_s_runs"], res["host_ingest" + sfx]["wall_s_runs"]
+            if args.baseline_cli:  # the baseline's fastest run: whichever of the two is faster
+                h = h + res["baseline_cli" + sfx]["wall_s_runs"]
+            verdict[kind] = {"device_slowest_s": max(d), "host_fastest_s": min(h), "device_beats_host": max(d) < min(h),
+                             "speedup_fastest_over_fastest": round(min(h) / min(d), 2)}
+        res["same_output"] = len(md5s) == 1
+        res["hic_routes"] = verdict
+        res["config"] = {"preset": "hic", "pairs": args.pairs, "readlen": args.readlen, "genome": args.genome, "reps": args.reps,
+                         "fastq_bytes": os.path.getsize(r1) + os.path.getsize(r2), "index_bytes": os.path.getsize(idx),
+                         "hardware_threads": os.cpu_count(), "cpu_budget": cpu_budget()}
+        print(json.dumps(res))
+        return
     if not args.skip_host_ingest:
         run("host_ingest", r1, r2, ["--host-ingest"], reps=1)
     if args.gz:
