@@ -121,6 +121,9 @@ extern "C" int cmgpu_set_option(cmgpu_ctx *c, const char *name, int64_t value) {
     return cm_build_fast_table(c, (int)value);
   } else if (n == "long_read_fused") {  // 0: reads longer than 69 bases take the two-pass minimizer kernels (count, scan, fill)
     c->opt_long_fused = value ? 1 : 0;
+  } else if (n == "sam_format_group") {  // lanes that render one SAM line (cm_sam_post.hip: k_sp_format)
+    if (value != 8 && value != 16 && value != 64) { cm_set_error(c, "sam_format_group: 8, 16 or 64"); return CMGPU_EINVAL; }
+    c->opt_sam_group = (int)value;
   } else if (n == "verify_planes") {  // 0: k_s5b_verify aligns on the reference / read bytes (the round-2 form) instead of their bit planes
     c->opt_planes = value ? 1 : 0;  // (the planes stay where they are: contexts made by cmgpu_create_shared may hold views of them)
   } else if (n == "speculative_sizes") {  // 0: every batch waits for the total of its candidate lists before sizing their arrays
@@ -296,6 +299,7 @@ int cm_ctx_init_common(cmgpu_ctx *c, const cmgpu_params *params, int kmer, int w
 // Every translation unit's device code, loaded now (the runtime defers it to the first launch: round 6 found 13 ms of a job's first FASTQ
 // scan inside the first prefix sum -- cm_kernels' code object being loaded -- and as much again in the first mapping and post-processing calls)
 void cm_touch_post(hipStream_t s);
+void cm_touch_sam_post(hipStream_t s);
 void cm_touch_ingest(hipStream_t s);
 void cm_touch_exchange(hipStream_t s);
 void cm_touch_synth(hipStream_t s);
@@ -306,7 +310,7 @@ static void cm_load_device_code(hipStream_t s) {
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
   std::call_once(once[dev], [s]() {
     hipLaunchKernelGGL(k_touch_api, dim3(1), dim3(1), 0, s);
-    cm_touch_post(s); cm_touch_ingest(s); cm_touch_exchange(s); cm_touch_synth(s);
+    cm_touch_post(s); cm_touch_sam_post(s); cm_touch_ingest(s); cm_touch_exchange(s); cm_touch_synth(s);
     // (cm_kernels.hip, the largest: through one of its launchers -- a prefix sum of four numbers -- the file itself stays as the
     //  committed profiles' source hash has it)
     DevBuf tiny;

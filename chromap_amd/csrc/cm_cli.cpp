@@ -731,7 +731,7 @@ int main(int argc, char **argv) {
   // one context (index + reference resident, own streams) per GPU; ctx = the first one, which also runs every single-GPU path
   const bool exchange = a.gpus > 1 || a.force_exchange;
   if (exchange && (a.out_pairs || a.out_sam || a.host_ingest))
-    die("--gpus > 1 needs BED / TagAlign output and device-side FASTQ ingest (pairs and SAM records are post-processed on the host)");
+    die("--gpus > 1 needs BED / TagAlign output and device-side FASTQ ingest (pairs and SAM text is rendered by one context from its own stores)");
   std::vector<cmgpu_ctx *> ctxs((size_t)a.gpus, nullptr);
   warm.join();
   if (!out_opened) die("cannot write " + a.out_path);
@@ -792,12 +792,16 @@ int main(int argc, char **argv) {
     if (cmgpu_exchange_init_all(ctxs.data(), a.gpus) != CMGPU_OK) die(cmgpu_last_error(ctxs[0]));
   }
   // Pairs output (--preset hic, --pairs) goes through the device ingest like BED: stream 0 keeps the read names in HBM and the final
-  // step renders the text from them (cmgpu_store_format_pairs_resident).  --SAM stays on the host parser: its text is written on the
-  // host from host strings (names, bases, qualities of both mates), and moving it is a separate change.  --gpus N > 1 with pairs
-  // output stays refused above.  --host-ingest forces the kseq-style parser (the fallback the CMGPU_EFORMAT message names).
-  const bool device_ingest = !a.out_sam && !a.host_ingest;
+  // step renders the text from them (cmgpu_store_format_pairs_resident).  --SAM does too: the streams of read 1 and read 2 keep whole
+  // reads (names, bases, qualities) in HBM, every batch's alignment records join the SAM record store, and the final step sorts,
+  // de-duplicates and renders the lines there (cmgpu_store_format_sam).  --barcode-translate with --SAM stays on the host parser and
+  // writer: its CB value needs the table.  --gpus N > 1 with pairs or SAM output stays refused above.  --host-ingest forces the
+  // kseq-style parser (the fallback the CMGPU_EFORMAT message names).
+  const bool device_ingest = !a.host_ingest && !(a.out_sam && !a.translate_path.empty());
+  const bool sam_device = a.out_sam && device_ingest;
   if (device_ingest && a.out_pairs && cmgpu_fastq_keep_names(ctx, 0, 1) != CMGPU_OK) die(cmgpu_last_error(ctx));
-  // --SAM: everything the final sort needs, over all batches
+  if (sam_device && cmgpu_fastq_keep_reads(ctx, 1) != CMGPU_OK) die(cmgpu_last_error(ctx));
+  // --SAM on the host route: everything the final sort needs, over all batches
   std::vector<cmgpu_sam_record> sam_rec;
   std::vector<uint32_t> sam_cigar;
   std::vector<std::vector<char>> sam_md_batches;
@@ -869,7 +873,7 @@ int main(int argc, char **argv) {
     for (cmgpu_stats &x : wst) memset(&x, 0, sizeof(x));
     size_t turn = 0;
     bool store_sized = false;
-    uint64_t names_seen = 0, name_bytes_seen = 0;
+    uint64_t names_seen = 0, name_bytes_seen = 0, reads_seen[2] = {0, 0};
     const bool overlap1 = NG == 1 && !exchange && !getenv("CM_CLI_NO_OVERLAP");  // (the variable: the serial order, for measurements)
     auto finish_round = [&]() {
       for (size_t gi = 0; gi < NG; ++gi) if (busy[gi]) { workers[gi].join(); busy[gi] = 0; }
@@ -982,7 +986,7 @@ int main(int argc, char **argv) {
           if (wrc[0] != CMGPU_OK) die(cmgpu_last_error(ctxs[0]));
         }
         const double tj1 = now_s();
-        if (!store_sized && overlap1 && a.p.max_num_best_mappings == 1) {
+        if (!store_sized && overlap1 && a.p.max_num_best_mappings == 1 && !a.out_sam) {
           // the record store sized once from what the first piece says about the files (records scanned / share of the file they came
           // from, over all input files): grown on demand it doubles each time with an allocation, a copy and a synchronous free
           store_sized = true;
@@ -1004,6 +1008,14 @@ int main(int argc, char **argv) {
           fprintf(stderr, "[times] names %llu %llu\n", (unsigned long long)(nn - names_seen), (unsigned long long)(nb - name_bytes_seen));
           names_seen = nn; name_bytes_seen = nb;
         }
+        if (dbg_times && sam_device) {  // reads of this batch: what the commit added to the read store, per mate
+          uint64_t nr = 0;
+          for (int m = 0; m < (paired ? 2 : 1); ++m) {
+            ckx(cmgpu_reads_info(cx, m, &nr, nullptr, nullptr, nullptr));
+            fprintf(stderr, "[times] reads %d %llu\n", m + 1, (unsigned long long)(nr - reads_seen[m]));
+            reads_seen[m] = nr;
+          }
+        }
         t0 = now_s();
         {
           const size_t gi = turn;
@@ -1012,7 +1024,7 @@ int main(int argc, char **argv) {
             const double tm0 = now_s();
             int rc = cmgpu_map_resident(cx, &k, &wst[gi]);
             const double tm1 = now_s();
-            if (rc == CMGPU_OK && !exchange) rc = cmgpu_store_append_resident(cx, nullptr);
+            if (rc == CMGPU_OK && !exchange) rc = a.out_sam ? cmgpu_sam_store_append_resident(cx, nullptr) : cmgpu_store_append_resident(cx, nullptr);
             if (getenv("CM_CLI_TIMES")) fprintf(stderr, "[times] map %.4f store_append %.4f\n", tm1 - tm0, now_s() - tm1);
             wrc[gi] = rc;
           });
@@ -1166,7 +1178,13 @@ int main(int argc, char **argv) {
             (unsigned long long)st.num_barcode_in_whitelist, (unsigned long long)st.num_corrected_barcode);
   int64_t lines;
   uint64_t nl = 0, nbytes = 0;
-  if (a.out_sam) {
+  if (sam_device) {
+    // sort + duplicate removal + MAPQ filter + SAM lines on the device, from the reads and records in HBM
+    if (cmgpu_store_format_sam(ctx, out_names.data(), out_lengths.data(), ref.n_sequences, &a.p, barcoded ? bc_len : 0, &nl, &nbytes) != CMGPU_OK) die(cmgpu_last_error(ctx));
+    if (cmgpu_write_sam_header(out_names.data(), out_lengths.data(), ref.n_sequences, a.out_path.c_str()) != CMGPU_OK) die("Cannot write " + a.out_path);
+    if (cmgpu_store_write_text(ctx, a.out_path.c_str(), 1) != CMGPU_OK) die(cmgpu_last_error(ctx));
+    lines = (long long)nl;
+  } else if (a.out_sam) {
     uint32_t cap = 1;
     for (uint32_t c : sam_md_caps) cap = c > cap ? c : cap;
     std::vector<char> md(sam_rec.size() * (size_t)cap + 1);

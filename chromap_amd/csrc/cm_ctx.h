@@ -45,6 +45,26 @@ struct CmFqStream {
   bool keep_names = false;
   DevBuf nm_len, nm_off, st_nm;
   uint32_t taken_name_bytes = 0;
+  // whole reads (cmgpu_fastq_keep_reads, streams 0 and 1): the takes gather names (as above) and quality lines (st_q, at the bases' offsets)
+  // too; cmgpu_fastq_commit appends names, bases and qualities to the context's run-wide read store
+  bool keep_reads = false;
+  DevBuf st_q;
+};
+
+// run-wide read store of one mate (cm_ingest.hip): names, bases and qualities of reads base .. base + n - 1 of the context's CmReadStore,
+// back to back, with n + 1 64-bit offsets each (bases and qualities share theirs)
+struct CmReadMate {
+  DevBuf names, name_offs, bases, quals, offs;
+  uint64_t name_bytes = 0, base_bytes = 0;
+};
+// run-wide SAM record store (cm_sam_post.hip): the valid slots of every batch, compacted.  rec: 40-byte cmgpu_sam_record entries whose
+// `valid` byte holds 1 + mate; var: per record its CIGAR words followed by its MD bytes (padded to a word), var_offs its n + 1 64-bit
+// byte offsets; bc: the pair's barcode key per record (barcoded runs)
+struct CmSamStore {
+  DevBuf rec, var, var_offs, bc;
+  DevBuf vlen, voff, scan_tmp, flags;  // scratch of an append (sizes, their scan, its work area, the overflow flag): kept, a hipFree per batch would wait for the whole device
+  uint64_t n = 0, var_bytes = 0;
+  bool has_bc = false, paired = false;
 };
 
 // multi-GPU record exchange (cm_exchange.hip): this context's place in a group of `world` contexts, one per GPU
@@ -133,6 +153,14 @@ struct cmgpu_ctx {
   DevBuf nm_blob, nm_offs;
   uint64_t nm_n = 0, nm_bytes = 0, nm_cap_n = 0;
   uint32_t nm_base = 0;
+  // run-wide read store (cmgpu_fastq_keep_reads; fed by cmgpu_fastq_commit, read where it lies by cmgpu_store_format_sam) and the SAM
+  // record store (cmgpu_sam_store_append_resident)
+  CmReadMate rd[2];
+  uint64_t rd_n = 0;
+  uint32_t rd_base = 0;
+  bool rd_paired = false;
+  CmSamStore ss;
+  int opt_sam_group = 8;   // lanes that render one SAM line (k_sp_format: 8, 16 or 64; 11.8 / 15.7 / 33.4 ms for 4.8 GB of text in profiles/r08a_sam_kernel_stats.csv)
   // --SAM outputs of the last batch (cm_stages.h: cm_ref_start_end_sam)
   DevBuf sam_rec, sam_cigar, sam_md, sam_z;
   DevBuf pairs_rank;
@@ -216,7 +244,9 @@ struct cmgpu_ctx {
 
   std::vector<DevBuf *> all_bufs() {
     std::vector<DevBuf *> v = core_bufs();
-    for (CmFqStream &f : fq) for (DevBuf *b : {&f.text, &f.cnt, &f.off, &f.nl, &f.keep, &f.pos, &f.recidx, &f.len, &f.bad, &f.text2, &f.comp, &f.btab, &f.toks, &f.ntok, &f.scan_tmp, &f.red_tmp, &f.nm_len, &f.nm_off, &f.st_nm}) v.push_back(b);
+    for (CmFqStream &f : fq) for (DevBuf *b : {&f.text, &f.cnt, &f.off, &f.nl, &f.keep, &f.pos, &f.recidx, &f.len, &f.bad, &f.text2, &f.comp, &f.btab, &f.toks, &f.ntok, &f.scan_tmp, &f.red_tmp, &f.nm_len, &f.nm_off, &f.st_nm, &f.st_q}) v.push_back(b);
+    for (CmReadMate &m : rd) for (DevBuf *b : {&m.names, &m.name_offs, &m.bases, &m.quals, &m.offs}) v.push_back(b);
+    for (DevBuf *b : {&ss.rec, &ss.var, &ss.var_offs, &ss.bc, &ss.vlen, &ss.voff, &ss.scan_tmp, &ss.flags}) v.push_back(b);
     for (DevBuf *b : {&st_rb0, &st_rb1, &st_ro0, &st_ro1, &st_bcb, &st_bcq, &st_bco, &nm_blob, &nm_offs}) v.push_back(b);
     for (CmBatchSlot &sl : slots) for (DevBuf *b : {&sl.rb0, &sl.rb1, &sl.ro0, &sl.ro1}) v.push_back(b);
     return v;
@@ -262,6 +292,9 @@ static inline uint64_t cm_rec_slots(const cmgpu_ctx *c) { return (uint64_t)c->n_
 int cm_ensure_slot_scratch(cmgpu_ctx *c, uint64_t slots);
 // cm_post.hip: n 32-byte {record, barcode} entries -> the store's record / barcode arrays at position store_n
 void cm_store_split_bc(cmgpu_ctx *c, const void *in32, uint64_t n, hipStream_t s);
+// cm_ingest.hip: b with room for `need` bytes, its first `used` bytes preserved (geometric growth from `first` bytes; the copy runs on s and
+// is waited for).  what: the store's name for the CMGPU_ENOMEM message
+int cm_grow_buf(cmgpu_ctx *c, DevBuf &b, uint64_t used, uint64_t need, uint64_t first, hipStream_t s, const char *what);
 // cm_exchange.hip
 void cm_exchange_release(cmgpu_ctx *c);
 // waits for an exchange payload still in flight (it lands in the record store): before anything reads or moves the store

@@ -12,6 +12,9 @@
 //   names: a stream told to keep them (cmgpu_fastq_keep_names) also gathers the taken records' names -- kseq's name.s: the header
 //          line after '@' up to the first isspace() byte, ks_getuntil(ks, 0, &seq->name, &c), kseq.h:188 -- into a staging blob;
 //          the commit appends them to the context's run-wide name store, which the pairs text is rendered from where it lies
+//   reads: with cmgpu_fastq_keep_reads the takes of read 1 and read 2 gather names AND quality lines (at the bases' offsets, --read-format
+//          applied as to the bases, reversed for '-'); the commit appends names, bases and qualities to the run-wide read store (per mate,
+//          64-bit offsets), which the SAM text is rendered from (cm_sam_post.hip)
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <cstring>
@@ -73,6 +76,8 @@ __device__ __forceinline__ void fq_line(const uint8_t *__restrict__ text, const 
 // per raw record: marker check, sequence length, keep flag (non-empty sequence)
 __global__ __launch_bounds__(FQ_BLOCK) void k_fq_records(const uint8_t *__restrict__ text, const uint32_t *__restrict__ nl, uint32_t n_raw,
                                                            int want_qual, uint32_t *__restrict__ keep, uint32_t *__restrict__ bad) {
+  // (bad[0]: first record with a missing marker or -- want_qual -- a quality line of another length than its sequence; bad[1]: first
+  //  record whose markers are fine and whose quality line alone is wrong, kseq's "truncated quality")
   const uint32_t r = blockIdx.x * FQ_BLOCK + threadIdx.x;
   if (r >= n_raw) return;
   uint32_t s0, e0, s1, e1, s2, e2, s3, e3;
@@ -81,7 +86,7 @@ __global__ __launch_bounds__(FQ_BLOCK) void k_fq_records(const uint8_t *__restri
   fq_line(text, nl, 4 * r + 2, &s2, &e2);
   fq_line(text, nl, 4 * r + 3, &s3, &e3);
   bool ok = e0 > s0 && text[s0] == '@' && e2 > s2 && text[s2] == '+';
-  if (want_qual && (e3 - s3) != (e1 - s1)) ok = false;  // kseq: quality and sequence lengths must agree
+  if (want_qual && (e3 - s3) != (e1 - s1)) { if (ok) atomicMin(bad + 1, r); ok = false; }  // kseq: quality and sequence lengths must agree
   // a GROUP of four blank lines (spaces and tabs at most) is no record and no damage either -- a file may end in any number of blank
   // lines.  Narrower than kseq, which skips ANY junk up to the next '@': one to three blank lines between two records shift the
   // four-line frame of every record after them here, the scan then fails with EFORMAT and the CLI says "rerun with --host-ingest"
@@ -271,19 +276,26 @@ static int fq_scan_resident(cmgpu_ctx *c, int stream, uint64_t n_bytes, int fina
   const uint32_t n_raw = n_nl / 4;
   f.n_raw = n_raw;
   if (n_raw == 0) return CMGPU_OK;
-  if (f.keep.ensure(((size_t)n_raw + 1) * 4) || f.pos.ensure(((size_t)n_raw + 1) * 4) || f.recidx.ensure((size_t)n_raw * 4) || f.bad.ensure(4) ||
+  if (f.keep.ensure(((size_t)n_raw + 1) * 4) || f.pos.ensure(((size_t)n_raw + 1) * 4) || f.recidx.ensure((size_t)n_raw * 4) || f.bad.ensure(8) ||
       f.scan_tmp.ensure(cm_scan_tmp_words(n_raw) * 4)) { cm_set_error(c, "out of device memory (FASTQ records)"); return CMGPU_ENOMEM; }
   const uint32_t none = 0xffffffffu;
-  FQCHECK(c, hipMemcpyAsync(f.bad.p, &none, 4, hipMemcpyHostToDevice, s));
+  FQCHECK(c, hipMemsetAsync(f.bad.p, 0xff, 8, s));
   const dim3 gr((n_raw + FQ_BLOCK - 1) / FQ_BLOCK);
-  hipLaunchKernelGGL(k_fq_records, gr, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, n_raw, stream == 2 ? 1 : 0,
+  hipLaunchKernelGGL(k_fq_records, gr, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, n_raw, stream == 2 || f.keep_reads ? 1 : 0,
                      (uint32_t *)f.keep.p, (uint32_t *)f.bad.p);
   cm_scan_u32((const uint32_t *)f.keep.p, (uint32_t *)f.pos.p, n_raw, (uint32_t *)f.scan_tmp.p, s);
   hipLaunchKernelGGL(k_fq_compact, gr, b, 0, s, (const uint32_t *)f.keep.p, (const uint32_t *)f.pos.p, n_raw, (uint32_t *)f.recidx.p);
-  uint32_t bad = 0, n_rec = 0;
+  uint32_t bad = 0, bad_q = 0, n_rec = 0;
   FQCHECK(c, hipMemcpyAsync(&bad, f.bad.p, 4, hipMemcpyDeviceToHost, s));
+  FQCHECK(c, hipMemcpyAsync(&bad_q, (uint32_t *)f.bad.p + 1, 4, hipMemcpyDeviceToHost, s));
   FQCHECK(c, hipMemcpyAsync(&n_rec, (uint32_t *)f.pos.p + n_raw, 4, hipMemcpyDeviceToHost, s));
   FQCHECK(c, cm_stream_sync(s));
+  if (bad != none && bad == bad_q && stream != 2) {  // (only seen with keep_reads on: the qualities of reads are not looked at otherwise)
+    cm_set_error(c, "truncated quality: the quality line is not as long as the sequence at record " + std::to_string(bad) +
+                        " of the chunk (whole reads are kept for SAM output, cmgpu_fastq_keep_reads)");
+    f.n_raw = 0;
+    return CMGPU_EFORMAT;
+  }
   if (bad != none) {
     cm_set_error(c, "not a 4-line FASTQ record (missing '@' / '+' marker or quality length) at record " + std::to_string(bad) + " of the chunk");
     f.n_raw = 0;
@@ -518,6 +530,7 @@ extern "C" int cmgpu_fastq_take(cmgpu_ctx *c, int stream, uint32_t n, uint64_t *
   f.taken_bases = 0;
   f.taken_max_len = 0;
   f.taken_name_bytes = 0;
+  const bool names = f.keep_names || f.keep_reads, reads = f.keep_reads && stream < 2;
   // where the host resumes: the end of the last raw record used; trailing empty records and,
   // at the end of the file, blank lines go with it
   uint32_t last_raw = 0;
@@ -544,7 +557,7 @@ extern "C" int cmgpu_fastq_take(cmgpu_ctx *c, int stream, uint32_t n, uint64_t *
     return f.dev_mode ? fq_retain_rest(c, f, consumed, f.final_chunk && n == f.n_rec, bytes_consumed) : CMGPU_OK;
   }
   if (f.len.ensure(((size_t)n + 1) * 4) || f.scan_tmp.ensure(cm_scan_tmp_words(n) * 4) || f.bad.ensure(4) ||
-      (f.keep_names && (f.nm_len.ensure(((size_t)n + 1) * 4) || f.nm_off.ensure(((size_t)n + 1) * 4)))) {
+      (names && (f.nm_len.ensure(((size_t)n + 1) * 4) || f.nm_off.ensure(((size_t)n + 1) * 4)))) {
     cm_set_error(c, "out of device memory (FASTQ lengths)"); return CMGPU_ENOMEM;
   }
   const dim3 g((n + FQ_BLOCK - 1) / FQ_BLOCK), b(FQ_BLOCK);
@@ -559,7 +572,7 @@ extern "C" int cmgpu_fastq_take(cmgpu_ctx *c, int stream, uint32_t n, uint64_t *
   if (f.red_tmp.ensure(tb + 256)) { cm_set_error(c, "out of device memory (reduce)"); return CMGPU_ENOMEM; }
   hipError_t e = rocprim::reduce(f.red_tmp.p, tb, (const uint32_t *)f.len.p, (uint32_t *)f.bad.p, 0u, (size_t)n, FqMaxOp(), s);
   uint32_t total = 0, mx = 0, name_total = 0;
-  if (f.keep_names) {  // (lengths and offsets of the names in the same wait as the bases')
+  if (names) {  // (lengths and offsets of the names in the same wait as the bases')
     hipLaunchKernelGGL(k_fq_name_len, g, b, 0, s, (const uint8_t *)f.text.p, f.n_bytes, (const uint32_t *)f.nl.p, (const uint32_t *)f.recidx.p, n,
                        (uint32_t *)f.nm_len.p);
     cm_scan_u32((const uint32_t *)f.nm_len.p, (uint32_t *)f.nm_off.p, n, (uint32_t *)f.scan_tmp.p, s);
@@ -570,10 +583,11 @@ extern "C" int cmgpu_fastq_take(cmgpu_ctx *c, int stream, uint32_t n, uint64_t *
   if (e == hipSuccess) e = cm_stream_sync(s);
   if (e != hipSuccess) { cm_set_error(c, std::string("FASTQ take: ") + hipGetErrorString(e)); return CMGPU_EHIP; }
   if (bases.ensure((size_t)total + 16) || (stream == 2 && c->st_bcq.ensure((size_t)total + 16))) { cm_set_error(c, "out of device memory (reads)"); return CMGPU_ENOMEM; }
-  if (f.keep_names && f.st_nm.ensure((size_t)name_total + 16)) { cm_set_error(c, "out of device memory (read names)"); return CMGPU_ENOMEM; }
+  if (names && f.st_nm.ensure((size_t)name_total + 16)) { cm_set_error(c, "out of device memory (read names)"); return CMGPU_ENOMEM; }
+  if (reads && f.st_q.ensure((size_t)total + 16)) { cm_set_error(c, "out of device memory (read qualities)"); return CMGPU_ENOMEM; }
   hipLaunchKernelGGL(k_fq_gather, g, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, (const uint32_t *)f.recidx.p,
-                     (const uint32_t *)offs.p, n, fmt, (uint8_t *)bases.p, stream == 2 ? (uint8_t *)c->st_bcq.p : (uint8_t *)nullptr);
-  if (f.keep_names)
+                     (const uint32_t *)offs.p, n, fmt, (uint8_t *)bases.p, stream == 2 ? (uint8_t *)c->st_bcq.p : reads ? (uint8_t *)f.st_q.p : (uint8_t *)nullptr);
+  if (names)
     hipLaunchKernelGGL(k_fq_name_gather, g, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, (const uint32_t *)f.recidx.p,
                        (const uint32_t *)f.nm_off.p, n, (uint8_t *)f.st_nm.p);
   FQCHECK(c, cm_stream_sync(s));
@@ -635,6 +649,67 @@ static int fq_names_append(cmgpu_ctx *c, CmFqStream &f, uint32_t n, uint32_t fir
   return CMGPU_OK;
 }
 
+// ---- the run-wide read store (cmgpu_fastq_keep_reads): per mate names / bases / qualities with 64-bit offsets, indexed by read_id - rd_base ----
+int cm_grow_buf(cmgpu_ctx *c, DevBuf &b, uint64_t used, uint64_t need, uint64_t first, hipStream_t s, const char *what) {
+  if (need <= b.cap && b.p) return CMGPU_OK;
+  uint64_t cap = b.cap ? (uint64_t)b.cap * 2 : first;
+  if (cap < need) cap = need;
+  DevBuf nb;
+  if (nb.ensure(cap)) { cm_set_error(c, std::string("out of device memory (") + what + ": " + std::to_string((unsigned long long)cap) + " bytes)"); return CMGPU_ENOMEM; }
+  hipError_t e = used && b.p ? hipMemcpyAsync(nb.p, b.p, used, hipMemcpyDeviceToDevice, s) : hipSuccess;
+  if (e == hipSuccess) e = cm_stream_sync(s);
+  if (e != hipSuccess) { nb.release(); FQCHECK(c, e); }
+  b.release();
+  b = nb;
+  return CMGPU_OK;
+}
+// room for the batch last taken (n records per mate) behind the store's reads; changes no count
+static int fq_reads_reserve(cmgpu_ctx *c, int mates, uint32_t n) {
+  for (int m = 0; m < mates; ++m) {
+    CmFqStream &f = c->fq[m];
+    CmReadMate &r = c->rd[m];
+    hipStream_t s = fq_hs(c, f);
+    const uint64_t have = c->rd_n ? (c->rd_n + 1) * 8 : 0, want = (c->rd_n + n + 1) * 8;
+    int rc = cm_grow_buf(c, r.name_offs, have, want, 8u << 20, s, "read store: name offsets");
+    if (!rc) rc = cm_grow_buf(c, r.offs, have, want, 8u << 20, s, "read store: base offsets");
+    if (!rc) rc = cm_grow_buf(c, r.names, r.name_bytes, r.name_bytes + f.taken_name_bytes + 16, 32u << 20, s, "read store: names");
+    if (!rc) rc = cm_grow_buf(c, r.bases, r.base_bytes, r.base_bytes + f.taken_bases + 16, 128u << 20, s, "read store: bases");
+    if (!rc) rc = cm_grow_buf(c, r.quals, r.base_bytes, r.base_bytes + f.taken_bases + 16, 128u << 20, s, "read store: qualities");
+    if (rc) return rc;
+  }
+  return CMGPU_OK;
+}
+// the batch last taken (staging buffers: the commit has not swapped them yet) behind the store's reads; first_read_id == rd_base + rd_n
+static int fq_reads_append(cmgpu_ctx *c, int mates, uint32_t n, uint32_t first_read_id) {
+  if (c->rd_n && ((uint64_t)first_read_id != (uint64_t)c->rd_base + c->rd_n || c->rd_paired != (mates == 2))) {
+    cm_set_error(c, "reads are kept for consecutive read ids of one kind of batch: the store ends at read " + std::to_string((unsigned long long)c->rd_base + c->rd_n) +
+                        ", the batch starts at " + std::to_string(first_read_id) + " (cmgpu_reads_clear starts a new run)");
+    return CMGPU_EINVAL;
+  }
+  if (n == 0) return CMGPU_OK;
+  const int rc = fq_reads_reserve(c, mates, n);
+  if (rc) return rc;
+  for (int m = 0; m < mates; ++m) {
+    CmFqStream &f = c->fq[m];
+    CmReadMate &r = c->rd[m];
+    hipStream_t s = fq_hs(c, f);
+    const DevBuf &sb = m == 0 ? c->st_rb0 : c->st_rb1, &so = m == 0 ? c->st_ro0 : c->st_ro1;
+    const dim3 g(n / FQ_BLOCK + 1), b(FQ_BLOCK);
+    hipLaunchKernelGGL(k_fq_name_append, g, b, 0, s, (const uint32_t *)f.nm_off.p, n, r.name_bytes, (uint64_t *)r.name_offs.p + c->rd_n);
+    hipLaunchKernelGGL(k_fq_name_append, g, b, 0, s, (const uint32_t *)so.p, n, r.base_bytes, (uint64_t *)r.offs.p + c->rd_n);
+    if (f.taken_name_bytes) FQCHECK(c, hipMemcpyAsync((uint8_t *)r.names.p + r.name_bytes, f.st_nm.p, f.taken_name_bytes, hipMemcpyDeviceToDevice, s));
+    if (f.taken_bases) {
+      FQCHECK(c, hipMemcpyAsync((uint8_t *)r.bases.p + r.base_bytes, sb.p, f.taken_bases, hipMemcpyDeviceToDevice, s));
+      FQCHECK(c, hipMemcpyAsync((uint8_t *)r.quals.p + r.base_bytes, f.st_q.p, f.taken_bases, hipMemcpyDeviceToDevice, s));
+    }
+  }
+  for (int m = 0; m < mates; ++m) FQCHECK(c, cm_stream_sync(fq_hs(c, c->fq[m])));
+  if (c->rd_n == 0) { c->rd_base = first_read_id; c->rd_paired = mates == 2; }
+  for (int m = 0; m < mates; ++m) { c->rd[m].name_bytes += c->fq[m].taken_name_bytes; c->rd[m].base_bytes += c->fq[m].taken_bases; }
+  c->rd_n += n;
+  return CMGPU_OK;
+}
+
 // declares the records taken from the streams the resident batch (what cmgpu_upload_batch does
 // for host SoA buffers); cmgpu_map_resident maps it
 extern "C" int cmgpu_fastq_commit(cmgpu_ctx *c, uint32_t n, uint32_t first_read_id, int paired, int barcoded) {
@@ -653,6 +728,10 @@ extern "C" int cmgpu_fastq_commit(cmgpu_ctx *c, uint32_t n, uint32_t first_read_
       const int nrc = fq_names_append(c, c->fq[m], n, first_read_id);
       if (nrc) return nrc;
     }
+  if (c->fq[0].keep_reads) {  // (likewise the whole reads; names and reads exclude each other, so at most one store is written)
+    const int rrc = fq_reads_append(c, paired ? 2 : 1, n, first_read_id);
+    if (rrc) return rrc;
+  }
   // the taken batch becomes the resident one: the staging buffers and the resident batch's swap (the old batch's buffers take the next
   // take).  The caller has no cmgpu_map_* call of this context running here.
   std::swap(c->rb0, c->st_rb0); std::swap(c->ro0, c->st_ro0);
@@ -678,6 +757,7 @@ extern "C" int cmgpu_fastq_commit(cmgpu_ctx *c, uint32_t n, uint32_t first_read_
 // the stream's takes also gather the records' names.  One stream per context: the store is indexed by read id.
 extern "C" int cmgpu_fastq_keep_names(cmgpu_ctx *c, int stream, int on) {
   if (!c || stream < 0 || stream > 1) return CMGPU_EINVAL;
+  if (on && c->fq[0].keep_reads) { cm_set_error(c, "whole reads are kept already (cmgpu_fastq_keep_reads): their names are among them"); return CMGPU_EINVAL; }
   if (on && c->fq[1 - stream].keep_names) { cm_set_error(c, "the names of one stream are kept per context (those of the other mate are already on)"); return CMGPU_EINVAL; }
   c->fq[stream].keep_names = on != 0;
   c->fq[stream].taken_name_bytes = 0;
@@ -704,6 +784,53 @@ extern "C" int cmgpu_download_names(cmgpu_ctx *c, char *blob, uint64_t blob_capa
   offsets[0] = 0;
   if (c->nm_n) FQCHECK(c, hipMemcpy(offsets, c->nm_offs.p, (c->nm_n + 1) * 8, hipMemcpyDeviceToHost));
   if (c->nm_bytes) FQCHECK(c, hipMemcpy(blob, c->nm_blob.p, c->nm_bytes, hipMemcpyDeviceToHost));
+  return CMGPU_OK;
+}
+
+// Replaces, for the device ingest, what SequenceBatch::LoadOneSequenceAndSaveAt keeps of a record for SAM output (sequence_batch.cc:22-62: name,
+// sequence, quality): the takes of read 1 and read 2 gather all three, the commit appends them to the read store.
+extern "C" int cmgpu_fastq_keep_reads(cmgpu_ctx *c, int on) {
+  if (!c) return CMGPU_EINVAL;
+  if (on && (c->fq[0].keep_names || c->fq[1].keep_names)) { cm_set_error(c, "read names are kept already (cmgpu_fastq_keep_names): keep either names or whole reads"); return CMGPU_EINVAL; }
+  for (int m = 0; m < 2; ++m) { c->fq[m].keep_reads = on != 0; c->fq[m].taken_name_bytes = 0; }
+  return CMGPU_OK;
+}
+extern "C" int cmgpu_reads_clear(cmgpu_ctx *c) {
+  if (!c) return CMGPU_EINVAL;
+  c->rd_n = 0;
+  c->rd_base = 0;
+  c->rd_paired = false;
+  for (CmReadMate &r : c->rd) { r.name_bytes = 0; r.base_bytes = 0; }
+  return CMGPU_OK;
+}
+extern "C" int cmgpu_reads_info(const cmgpu_ctx *c, int mate, uint64_t *n_reads, uint64_t *name_bytes, uint64_t *base_bytes, uint32_t *read_id_base) {
+  if (!c || mate < 0 || mate > 1) return CMGPU_EINVAL;
+  const bool has = mate == 0 || c->rd_paired;
+  if (n_reads) *n_reads = has ? c->rd_n : 0;
+  if (name_bytes) *name_bytes = c->rd[mate].name_bytes;
+  if (base_bytes) *base_bytes = c->rd[mate].base_bytes;
+  if (read_id_base) *read_id_base = c->rd_base;
+  return CMGPU_OK;
+}
+extern "C" int cmgpu_download_reads(cmgpu_ctx *c, int mate, char *names, uint64_t names_capacity, uint64_t *name_offsets, char *bases, char *quals,
+                                    uint64_t bases_capacity, uint64_t *offsets) {
+  if (!c || mate < 0 || mate > 1 || !name_offsets || !offsets) return CMGPU_EINVAL;
+  const CmReadMate &r = c->rd[mate];
+  const uint64_t n = mate == 0 || c->rd_paired ? c->rd_n : 0;
+  if ((!names && r.name_bytes) || ((!bases || !quals) && r.base_bytes)) return CMGPU_EINVAL;
+  if (names_capacity < r.name_bytes || bases_capacity < r.base_bytes) { cm_set_error(c, "read buffer too small"); return CMGPU_ECAPACITY; }
+  FQCHECK(c, cm_enter(c));
+  name_offsets[0] = 0;
+  offsets[0] = 0;
+  if (n) {
+    FQCHECK(c, hipMemcpy(name_offsets, r.name_offs.p, (n + 1) * 8, hipMemcpyDeviceToHost));
+    FQCHECK(c, hipMemcpy(offsets, r.offs.p, (n + 1) * 8, hipMemcpyDeviceToHost));
+  }
+  if (r.name_bytes) FQCHECK(c, hipMemcpy(names, r.names.p, r.name_bytes, hipMemcpyDeviceToHost));
+  if (r.base_bytes) {
+    FQCHECK(c, hipMemcpy(bases, r.bases.p, r.base_bytes, hipMemcpyDeviceToHost));
+    FQCHECK(c, hipMemcpy(quals, r.quals.p, r.base_bytes, hipMemcpyDeviceToHost));
+  }
   return CMGPU_OK;
 }
 

@@ -514,6 +514,64 @@ class ChromapGPU:
         raw = blob.raw
         return [raw[int(off[i]):int(off[i + 1])] for i in range(n)]
 
+    def fastq_keep_reads(self, on=True):
+        """the takes of read 1 / read 2 also gather names and qualities; commits append whole reads to the context's read store"""
+        self._check(self.L.cmgpu_fastq_keep_reads(self.ctx, int(on)), self.ctx)
+
+    def reads_clear(self):
+        self._check(self.L.cmgpu_reads_clear(self.ctx), self.ctx)
+
+    def reads_info(self, mate=0):
+        """(reads, name bytes, base bytes, read id of the first read) of one mate of the read store"""
+        n, nn, nb, base = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        self._check(self.L.cmgpu_reads_info(self.ctx, mate, C.byref(n), C.byref(nn), C.byref(nb), C.byref(base)), self.ctx)
+        return int(n.value), int(nn.value), int(nb.value), int(base.value)
+
+    def download_reads(self, mate=0):
+        """one mate of the read store: (names, bases, quals, offsets) -- names a list of bytes, bases / quals uint8 arrays that
+        share the n + 1 uint64 offsets; entry i belongs to read read_id_base + i"""
+        n, nn, nb, _ = self.reads_info(mate)
+        blob = C.create_string_buffer(max(1, nn))
+        noff = np.zeros(n + 1, np.uint64)
+        off = np.zeros(n + 1, np.uint64)
+        bases = np.zeros(max(1, nb), np.uint8)
+        quals = np.zeros(max(1, nb), np.uint8)
+        self._check(self.L.cmgpu_download_reads(self.ctx, mate, C.cast(blob, C.c_void_p), nn, noff.ctypes.data, bases.ctypes.data,
+                                                quals.ctypes.data, nb, off.ctypes.data), self.ctx)
+        raw = blob.raw
+        return [raw[int(noff[i]):int(noff[i + 1])] for i in range(n)], bases[:nb], quals[:nb], off
+
+    # ---- --SAM on the device: record store -> sorted / deduplicated SAM text in HBM (reads from the read store)
+    def sam_store_append_resident(self):
+        """appends the valid SAM records of the last map_resident call; returns the store size"""
+        n = C.c_uint64(0)
+        self._check(self.L.cmgpu_sam_store_append_resident(self.ctx, C.byref(n)), self.ctx)
+        return int(n.value)
+
+    def sam_store_clear(self):
+        self._check(self.L.cmgpu_sam_store_clear(self.ctx), self.ctx)
+
+    def sam_store_info(self):
+        """(records, bytes of HBM they take)"""
+        n, nb = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.cmgpu_sam_store_info(self.ctx, C.byref(n), C.byref(nb)), self.ctx)
+        return int(n.value), int(nb.value)
+
+    def store_format_sam(self, params=None, barcode_length=0):
+        """sort + duplicate removal + MAPQ filter + SAM lines of the SAM record store, all in HBM; returns (lines, bytes); the
+        text is fetched with store_text() / store_write_text(); the @SQ lines: write_sam_header()"""
+        p = params if params is not None else self.params
+        names = (C.c_char_p * len(self.names))(*self.names)
+        nl, nb = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.cmgpu_store_format_sam(self.ctx, names, C.cast(self.reference_lengths(), C.c_void_p), len(self.names), C.byref(p),
+                                                  int(barcode_length), C.byref(nl), C.byref(nb)), self.ctx)
+        return int(nl.value), int(nb.value)
+
+    def write_sam_header(self, path):
+        names = (C.c_char_p * len(self.names))(*self.names)
+        if self.L.cmgpu_write_sam_header(names, C.cast(self.reference_lengths(), C.c_void_p), len(self.names), path.encode()) != 0:
+            raise ChromapError("cannot write %s" % path)
+
     def download_batch(self, n):
         """resident batch back on the host: (b1, o1, b2, o2)"""
         o1 = np.zeros(n + 1, np.uint32)

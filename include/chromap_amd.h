@@ -447,6 +447,28 @@ int64_t cmgpu_write_sam_barcoded_translated(const char *const *ref_names, const 
                                             const char *quals2, const uint32_t *offsets2, const uint64_t *barcode_keys, uint32_t barcode_length,
                                             const char *translate_table, uint64_t translate_table_bytes, const char *out_path);
 
+/* ---- SAM output on the device -------------------------------------------------------------
+ * Replaces the host writers above for runs that go through the device ingest: the SAMMapping objects the reference keeps per
+ * mapped read (src/sam_mapping.h:151-212) stay in HBM, and MappingWriter<SAMMapping>::AppendMapping's text
+ * (src/mapping_writer.cc:312-356) is rendered there from the read store (cmgpu_fastq_keep_reads).
+ *   cmgpu_sam_store_append_resident  after a cmgpu_map_resident of a CMGPU_FORMAT_SAM context: the batch's valid slots -- record,
+ *                                    mate, CIGAR words, MD bytes and, for barcoded batches, the pair's barcode key -- join a run-wide
+ *                                    store, compacted (the fixed CIGAR / MD slots stay per batch); n_total = records in the store
+ *   cmgpu_store_format_sam           sorts the store by SAMMapping::operator< (rid, pos, barcode, mrid, mpos, flag & 64, mapq,
+ *                                    read_id), removes duplicates on operator== (low_memory_mode: the first record with the run's
+ *                                    largest MAPQ; otherwise the last of the run), applies the MAPQ filter and renders one line per
+ *                                    record into the context's text store: cmgpu_store_text / cmgpu_store_write_text /
+ *                                    cmgpu_store_info then work as for BED and pairs.  The bytes equal cmgpu_write_sam* without
+ *                                    the header; offsets are 64-bit (the text of a realistic run passes 4 GiB)
+ *   cmgpu_write_sam_header           the @SQ lines, on the host; the text follows with cmgpu_store_write_text(path, 1) */
+int cmgpu_sam_store_append_resident(cmgpu_ctx *ctx, uint64_t *n_total);
+int cmgpu_sam_store_clear(cmgpu_ctx *ctx);
+/* n_bytes: HBM the stored records take (records, offsets, CIGAR + MD, barcode keys) */
+int cmgpu_sam_store_info(const cmgpu_ctx *ctx, uint64_t *n_records, uint64_t *n_bytes);
+int cmgpu_store_format_sam(cmgpu_ctx *ctx, const char *const *ref_names, const uint32_t *ref_lengths, uint32_t n_sequences,
+                           const cmgpu_params *params, uint32_t barcode_length, uint64_t *n_lines, uint64_t *n_bytes);
+int cmgpu_write_sam_header(const char *const *ref_names, const uint32_t *ref_lengths, uint32_t n_sequences, const char *out_path);
+
 /* ---- device-side post-processing -------------------------------------
  * Replaces, for BED output: MappingProcessor::SortOutputMappings / RemovePCRDuplicate
  * (src/mapping_processor.h:100-202), the low-memory merge's duplicate handling
@@ -546,6 +568,24 @@ int cmgpu_names_info(const cmgpu_ctx *ctx, uint64_t *n_names, uint64_t *n_bytes,
 /* the name store on the host: the names back to back in blob (capacity >= n_bytes), offsets[n_names + 1] into it -- what the host
  * parser keeps in SequenceBatch::GetSequenceNameAt (src/sequence_batch.h); for tests and host-side writers */
 int cmgpu_download_names(cmgpu_ctx *ctx, char *blob, uint64_t blob_capacity, uint64_t *offsets);
+/* Whole reads for SAM output.  Replaces what SequenceBatch::LoadOneSequenceAndSaveAt keeps of every record (src/sequence_batch.cc:22-62:
+ * name, sequence, quality) for the device ingest: with on != 0 every following cmgpu_fastq_take of read 1 (and, for paired batches,
+ * read 2) also gathers the taken records' names (kseq's rule, as cmgpu_fastq_keep_names) and quality lines -- at the bases' offsets,
+ * --read-format applied as to the bases, reversed for '-'.  cmgpu_fastq_commit appends names, bases and qualities to a run-wide read
+ * store in HBM: per mate, indexed by read_id - read_id_base, 64-bit offsets, geometric growth.  Batches must be committed with
+ * consecutive read ids (a gap: CMGPU_EINVAL, nothing is committed); no room in HBM: CMGPU_ENOMEM (the message names the store and its
+ * size).  With it on, a record whose quality line is not as long as its sequence (kseq's "truncated quality") makes the scan return
+ * CMGPU_EFORMAT; with it off the qualities of reads are not looked at.  Call it before the first scan of a run.  It and
+ * cmgpu_fastq_keep_names exclude each other (CMGPU_EINVAL).  Cost: name + 2 x length bytes + 16 bytes of offsets per read. */
+int cmgpu_fastq_keep_reads(cmgpu_ctx *ctx, int on);
+/* empties the read store (a new run; the next commit sets read_id_base) */
+int cmgpu_reads_clear(cmgpu_ctx *ctx);
+/* mate: 0 = read 1, 1 = read 2 (n_reads 0 for single-end runs) */
+int cmgpu_reads_info(const cmgpu_ctx *ctx, int mate, uint64_t *n_reads, uint64_t *name_bytes, uint64_t *base_bytes, uint32_t *read_id_base);
+/* one mate of the read store on the host: names back to back with name_offsets[n_reads + 1], bases and quals (base_bytes each) with
+ * offsets[n_reads + 1] -- what the host parser keeps in SequenceBatch (src/sequence_batch.h); for tests and host-side writers */
+int cmgpu_download_reads(cmgpu_ctx *ctx, int mate, char *names, uint64_t names_capacity, uint64_t *name_offsets, char *bases, char *quals,
+                         uint64_t bases_capacity, uint64_t *offsets);
 /* cmgpu_compute_barcode_abundance over the barcodes last taken from stream 2; feed the barcode
  * file in whole reference batches and stop when *done is set (20 M sampled, src/chromap.h:211). */
 int cmgpu_barcode_abundance_resident(cmgpu_ctx *ctx, uint64_t *num_sample_barcodes, int *done);

@@ -5,6 +5,8 @@ synthetic read pairs written as FASTQ, then `chromap-amd --preset atac` from fil
 `--preset hic`: 2 x 150 Hi-C shaped pairs with ligation junctions (the generator of bench.py's hic workload), `chromap-amd --preset hic`
 from files to a pairs file, through the device ingest (read names kept in HBM) and through the host parser (`--host-ingest`, the route
 every pairs run took before), plain FASTQ and -- with --gz -- BGZF, `--reps` runs each; the pairs files must be identical.
+`--sam`: 2 x 150 ordinary pairs, `chromap-amd --preset chip --SAM` from files to a SAM file through the device ingest (whole reads and
+alignment records kept in HBM, text rendered there) and through the host parser and writer (`--host-ingest`), timed like the hic routes.
 Prints one JSON object; everything is written under --dir (default /tmp/chromap_amd_e2e)."""
 import argparse
 import ctypes as C
@@ -44,14 +46,18 @@ def main():
     ap.add_argument("--gz", action="store_true", help="also time gzip-compressed input (inflated on the host, one thread per file) and BGZF input (on the device)")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--baseline-cli", default="", help="--preset hic: also time this other chromap-amd binary (a build of an earlier commit) on the same files")
+    ap.add_argument("--sam", action="store_true", help="time --preset chip --SAM through the device route and the host route (and --baseline-cli)")
     ap.add_argument("--skip-host-ingest", action="store_true", help="a long job: leave the host parser's run out")
     args = ap.parse_args()
     os.makedirs(args.dir, exist_ok=True)
+    if args.sam:
+        args.preset = "chip"
     hic = args.preset == "hic"
+    two_routes = hic or args.sam  # the same files through the device route and the host route, whole-process wall time
     if not args.readlen:
-        args.readlen = 150 if hic else 50
+        args.readlen = 150 if two_routes else 50
     from chromap_amd import ChromapGPU
-    g = ChromapGPU(synthetic=(args.genome, args.nseq, 4242), preset=args.preset)
+    g = ChromapGPU(synthetic=(args.genome, args.nseq, 4242), preset="atac" if args.sam else args.preset)
     idx = os.path.join(args.dir, "g.index")
     fa = os.path.join(args.dir, "g.fa")
     g.save_index(idx)
@@ -76,7 +82,8 @@ def main():
     write_fastq(r1, b1, args.pairs, args.readlen)
     write_fastq(r2, b2, args.pairs, args.readlen)
     g.close()
-    out = os.path.join(args.dir, "out.pairs" if hic else "out.bed")
+    out = os.path.join(args.dir, "out.sam" if args.sam else "out.pairs" if hic else "out.bed")
+    fmt = ["--SAM"] if args.sam else []
     cli = os.path.join(ROOT, "chromap_amd", "chromap-amd")
     res = {}
 
@@ -93,7 +100,7 @@ def main():
                 os.remove(out)
             os.sync()
             t0 = time.time()
-            p = subprocess.run([cli, "--preset", args.preset, "-x", idx, "-r", fa, "-1", f1, "-2", f2, "-o", out] + list(extra), stderr=subprocess.PIPE, check=True)
+            p = subprocess.run([cli, "--preset", args.preset, "-x", idx, "-r", fa, "-1", f1, "-2", f2, "-o", out] + fmt + list(extra), stderr=subprocess.PIPE, check=True)
             dt = time.time() - t0
             tail = [ln for ln in p.stderr.decode().splitlines() if ln.startswith("Mapped all reads") or ln.startswith("Sorted,")]
             mapped = [float(ln.split("in ")[1].split("s")[0]) for ln in tail if ln.startswith("Mapped all reads")]
@@ -112,9 +119,12 @@ def main():
         res[label] = best
 
     run("device_ingest", r1, r2)
-    if hic:
-        # the two routes of a pairs run, whole-process wall time: the requirement is slowest(device) < fastest(host) for each input kind
-        run("host_ingest", r1, r2, ["--host-ingest"])
+    if two_routes:
+        # the two routes of a pairs / SAM run, whole-process wall time: the requirement is slowest(device) < fastest(host) for each input kind
+        # (--skip-host-ingest with --baseline-cli: the baseline build stands for the host route, the only one it has)
+        host = not (args.skip_host_ingest and args.baseline_cli)
+        if host:
+            run("host_ingest", r1, r2, ["--host-ingest"])
         if args.baseline_cli:
             run("baseline_cli", r1, r2, cli=args.baseline_cli)
         kinds = [("", "fastq")]
@@ -124,7 +134,8 @@ def main():
             for f in (r1, r2):
                 bgzf.compress_file(f, f + ".bgz")
             run("device_ingest_bgzf", r1 + ".bgz", r2 + ".bgz")
-            run("host_ingest_bgzf", r1 + ".bgz", r2 + ".bgz", ["--host-ingest"])
+            if host:
+                run("host_ingest_bgzf", r1 + ".bgz", r2 + ".bgz", ["--host-ingest"])
             if args.baseline_cli:
                 run("baseline_cli_bgzf", r1 + ".bgz", r2 + ".bgz", cli=args.baseline_cli)
             res["device_ingest_bgzf"]["bgzf_bytes"] = os.path.getsize(r1 + ".bgz") + os.path.getsize(r2 + ".bgz")
@@ -132,14 +143,14 @@ def main():
         md5s = set(m for k in res for m in res[k]["md5_runs"])  # every run of every route
         verdict = {}
         for sfx, kind in kinds:
-            d, h = res["device_ingest" + sfx]["wall_s_runs"], res["host_ingest" + sfx]["wall_s_runs"]
+            d, h = res["device_ingest" + sfx]["wall_s_runs"], res["host_ingest" + sfx]["wall_s_runs"] if host else []
             if args.baseline_cli:  # the baseline's fastest run: whichever of the two is faster
                 h = h + res["baseline_cli" + sfx]["wall_s_runs"]
             verdict[kind] = {"device_slowest_s": max(d), "host_fastest_s": min(h), "device_beats_host": max(d) < min(h),
                              "speedup_fastest_over_fastest": round(min(h) / min(d), 2)}
         res["same_output"] = len(md5s) == 1
-        res["hic_routes"] = verdict
-        res["config"] = {"preset": "hic", "pairs": args.pairs, "readlen": args.readlen, "genome": args.genome, "reps": args.reps,
+        res["sam_routes" if args.sam else "hic_routes"] = verdict
+        res["config"] = {"preset": args.preset, "sam": args.sam, "pairs": args.pairs, "readlen": args.readlen, "genome": args.genome, "reps": args.reps,
                          "fastq_bytes": os.path.getsize(r1) + os.path.getsize(r2), "index_bytes": os.path.getsize(idx),
                          "hardware_threads": os.cpu_count(), "cpu_budget": cpu_budget()}
         print(json.dumps(res))
