@@ -620,7 +620,7 @@ static Args parse(int argc, char **argv) {
     else if (o == "--device") a.device = atoi(need("--device"));
     else if (o == "--gpus") a.gpus = atoi(need("--gpus"));           // one context + host thread per GPU, records exchanged to chromosome owners
     else if (o == "--force-exchange") a.force_exchange = true;      // the multi-GPU code path with one GPU
-    else if (o == "--host-ingest") a.host_ingest = true;   // kseq-style host parser (FASTA / multi-line records)
+    else if (o == "--host-ingest") a.host_ingest = true;   // kseq-style host parser (the fallback for text the device ingest refuses)
     else if (o == "--ingest-chunk-mb") { a.chunk_bytes = (size_t)atol(need("--ingest-chunk-mb")) << 20; a.chunk_given = true; }
     else if (o == "--batch-pairs") a.batch_pairs = (uint32_t)atol(need("--batch-pairs"));
     else if (o == "-v" || o == "--version") { printf("chromap-amd 0.1 (hot path of chromap 0.3.3-r521 on gfx950)\n"); exit(0); }
@@ -799,6 +799,12 @@ int main(int argc, char **argv) {
   // kseq-style parser (the fallback the CMGPU_EFORMAT message names).
   const bool device_ingest = !a.host_ingest && !(a.out_sam && !a.translate_path.empty());
   const bool sam_device = a.out_sam && device_ingest;
+  // every stream of every context reads what kseq reads -- wrapped lines, FASTA, stray blank lines (CMGPU_FASTX_FREE; plain four-line
+  // text stays on the four-line path, cm_ingest.hip)
+  if (device_ingest)
+    for (cmgpu_ctx *cx : ctxs)
+      for (int m = 0; m < 3; ++m)
+        if (cmgpu_fastq_set_layout(cx, m, CMGPU_FASTX_FREE) != CMGPU_OK) die(cmgpu_last_error(cx));
   if (device_ingest && a.out_pairs && cmgpu_fastq_keep_names(ctx, 0, 1) != CMGPU_OK) die(cmgpu_last_error(ctx));
   if (sam_device && cmgpu_fastq_keep_reads(ctx, 1) != CMGPU_OK) die(cmgpu_last_error(ctx));
   // --SAM on the host route: everything the final sort needs, over all batches
@@ -847,7 +853,13 @@ int main(int argc, char **argv) {
           free(keys);
         }
         uint32_t cnt = 0;
-        ck(cmgpu_fastq_scan(ctx, 2, br.text(), br.len, br.eof, &cnt));
+        {
+          const int brc = cmgpu_fastq_scan(ctx, 2, br.text(), br.len, br.eof, &cnt);
+          if (brc == CMGPU_EFORMAT && strstr(cmgpu_last_error(ctx), "truncated quality"))
+            die(std::string("Didn't reach the end of sequence file, which might be corrupted! (") + cmgpu_last_error(ctx) + ")");
+          if (brc == CMGPU_EFORMAT) die(std::string(cmgpu_last_error(ctx)) + " -- rerun with --host-ingest");
+          ck(brc);
+        }
         uint32_t n = cnt;
         if (!br.eof) n -= n % 500000;
         if (n == 0 && !br.eof) { target *= 2; continue; }
@@ -948,10 +960,18 @@ int main(int argc, char **argv) {
           const int rc = src[m];
           if (rc == CMGPU_EFORMAT && dev && strstr(serr[m].c_str(), "BGZF"))
             die(std::string("Didn't reach the end of sequence file, which might be corrupted! (") + serr[m] + ")");
+          if (rc == CMGPU_EFORMAT && strstr(serr[m].c_str(), "truncated quality"))  // (kseq's -2: what the reference says about it)
+            die(std::string("Didn't reach the end of sequence file, which might be corrupted! (") + serr[m] + ")");
           if (rc == CMGPU_EFORMAT) die(serr[m] + " -- rerun with --host-ingest");
           if (rc != CMGPU_OK) die(serr[m]);
         }
         const double ts1 = now_s();
+        if (dbg_times)  // which path each scan took: the four-line one, or the general one of layout CMGPU_FASTX_FREE
+          for (int m = 0; m < ns_streams; ++m) {
+            int general = 0;
+            ckx(cmgpu_fastq_scan_info(cx, sid[m], &general, nullptr));
+            fprintf(stderr, "[times] layout %d %s\n", sid[m], general ? "free" : "strict");
+          }
         uint32_t n = cnt[0];
         for (int m = 1; m < ns_streams; ++m) n = cnt[m] < n ? cnt[m] : n;
         if (n > a.batch_pairs) n = a.batch_pairs;

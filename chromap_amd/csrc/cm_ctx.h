@@ -49,6 +49,13 @@ struct CmFqStream {
   // too; cmgpu_fastq_commit appends names, bases and qualities to the context's run-wide read store
   bool keep_reads = false;
   DevBuf st_q;
+  // record layout (cmgpu_fastq_set_layout): CMGPU_FASTX_FREE reads what kseq reads (cm_fastx.h).  general: the last scan left the
+  // 4-line path -- recidx then holds HEADER LINES, and fx_nxt / fx_send / fx_sl describe the record that starts at a line
+  int layout = 0;
+  bool general = false;
+  uint32_t fx_seen = 0;  // CM_FX_SEEN_*: kinds of records the file has shown so far (cleared when a final chunk is taken whole)
+  uint32_t fx_lines = 0, fx_stop = 0;  // lines of the chunk; the line where the countable records end (seek state: the next chunk starts there)
+  DevBuf fx_li, fx_nxt, fx_send, fx_sl, fx_exit, fx_entry, fx_res;
 };
 
 // run-wide read store of one mate (cm_ingest.hip): names, bases and qualities of reads base .. base + n - 1 of the context's CmReadStore,
@@ -244,7 +251,7 @@ struct cmgpu_ctx {
 
   std::vector<DevBuf *> all_bufs() {
     std::vector<DevBuf *> v = core_bufs();
-    for (CmFqStream &f : fq) for (DevBuf *b : {&f.text, &f.cnt, &f.off, &f.nl, &f.keep, &f.pos, &f.recidx, &f.len, &f.bad, &f.text2, &f.comp, &f.btab, &f.toks, &f.ntok, &f.scan_tmp, &f.red_tmp, &f.nm_len, &f.nm_off, &f.st_nm, &f.st_q}) v.push_back(b);
+    for (CmFqStream &f : fq) for (DevBuf *b : {&f.text, &f.cnt, &f.off, &f.nl, &f.keep, &f.pos, &f.recidx, &f.len, &f.bad, &f.text2, &f.comp, &f.btab, &f.toks, &f.ntok, &f.scan_tmp, &f.red_tmp, &f.nm_len, &f.nm_off, &f.st_nm, &f.st_q, &f.fx_li, &f.fx_nxt, &f.fx_send, &f.fx_sl, &f.fx_exit, &f.fx_entry, &f.fx_res}) v.push_back(b);
     for (CmReadMate &m : rd) for (DevBuf *b : {&m.names, &m.name_offs, &m.bases, &m.quals, &m.offs}) v.push_back(b);
     for (DevBuf *b : {&ss.rec, &ss.var, &ss.var_offs, &ss.bc, &ss.vlen, &ss.voff, &ss.scan_tmp, &ss.flags}) v.push_back(b);
     for (DevBuf *b : {&st_rb0, &st_rb1, &st_ro0, &st_ro1, &st_bcb, &st_bcq, &st_bco, &nm_blob, &nm_offs}) v.push_back(b);

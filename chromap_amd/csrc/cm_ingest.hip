@@ -1,5 +1,5 @@
 // cm_ingest.hip -- FASTQ text -> SoA read batch on the device.
-// Replaces, for 4-line FASTQ, kseq_read + SequenceBatch::LoadOneSequenceAndSaveAt
+// Replaces kseq_read + SequenceBatch::LoadOneSequenceAndSaveAt
 // (sequence_batch.cc:22-62, kseq.h): the host only moves (inflated) file bytes; line splitting,
 // record validation, the skip of empty sequences (sequence_batch.cc:27-30) and the packing of
 // bases / qualities / offsets run as scans and gathers in HBM.
@@ -7,6 +7,9 @@
 //   scan:  16 bytes per thread -> newline counts -> exclusive scan -> newline positions;
 //          records = complete groups of four lines; '@' / '+' markers are checked;
 //          records with an empty sequence line are dropped from the stream
+//   free:  a stream in layout CMGPU_FASTX_FREE whose text fails the four-line check -- wrapped sequence / quality lines, FASTA, stray
+//          blank lines -- resolves kseq's record chain over the same line index instead (cm_fastx.h; k_fx_* below): records are then
+//          described by their header line, and the take concatenates a record's sequence and quality lines
 //   take:  the first n records' sequence (and quality) lines are gathered into the resident
 //          batch arrays of that mate; bytes_consumed tells the host where the next chunk starts
 //   names: a stream told to keep them (cmgpu_fastq_keep_names) also gathers the taken records' names -- kseq's name.s: the header
@@ -24,6 +27,7 @@
 #include "cm_ctx.h"
 #include "cm_kernels.h"
 #include "cm_inflate.h"
+#include "cm_fastx.h"
 
 #define FQ_BLOCK 256
 #define FQCHECK(ctx, call)                                                                   \
@@ -75,9 +79,12 @@ __device__ __forceinline__ void fq_line(const uint8_t *__restrict__ text, const 
 
 // per raw record: marker check, sequence length, keep flag (non-empty sequence)
 __global__ __launch_bounds__(FQ_BLOCK) void k_fq_records(const uint8_t *__restrict__ text, const uint32_t *__restrict__ nl, uint32_t n_raw,
-                                                           int want_qual, uint32_t *__restrict__ keep, uint32_t *__restrict__ bad) {
+                                                           int flags, uint32_t *__restrict__ keep, uint32_t *__restrict__ bad) {
   // (bad[0]: first record with a missing marker or -- want_qual -- a quality line of another length than its sequence; bad[1]: first
   //  record whose markers are fine and whose quality line alone is wrong, kseq's "truncated quality")
+  // flags: 1 = the quality's length is checked; 2 = layout CMGPU_FASTX_FREE: a sequence line that starts with '@', '+' or '>' is flagged
+  // too -- kseq reads such a line as a marker, and the general path (k_fx_*) decides what the text is
+  const int want_qual = flags & 1;
   const uint32_t r = blockIdx.x * FQ_BLOCK + threadIdx.x;
   if (r >= n_raw) return;
   uint32_t s0, e0, s1, e1, s2, e2, s3, e3;
@@ -86,11 +93,13 @@ __global__ __launch_bounds__(FQ_BLOCK) void k_fq_records(const uint8_t *__restri
   fq_line(text, nl, 4 * r + 2, &s2, &e2);
   fq_line(text, nl, 4 * r + 3, &s3, &e3);
   bool ok = e0 > s0 && text[s0] == '@' && e2 > s2 && text[s2] == '+';
+  if ((flags & 2) && e1 > s1) { const uint8_t c1 = text[s1]; if (c1 == '@' || c1 == '+' || c1 == '>') ok = false; }
+  // (... and a sequence or quality line that is a lone '\r': kseq keeps that byte, kseq.h:141; fq_line has dropped it, the line's '\n' tells)
+  if ((flags & 2) && ((e1 == s1 && nl[4 * r + 1] > s1) || (e3 == s3 && nl[4 * r + 3] > s3))) ok = false;
   if (want_qual && (e3 - s3) != (e1 - s1)) { if (ok) atomicMin(bad + 1, r); ok = false; }  // kseq: quality and sequence lengths must agree
   // a GROUP of four blank lines (spaces and tabs at most) is no record and no damage either -- a file may end in any number of blank
-  // lines.  Narrower than kseq, which skips ANY junk up to the next '@': one to three blank lines between two records shift the
-  // four-line frame of every record after them here, the scan then fails with EFORMAT and the CLI says "rerun with --host-ingest"
-  // (the host parser is kseq's twin).  Tolerated on the device path: blank lines in groups of four only.
+  // lines.  One to three blank lines between two records shift the four-line frame of every record after them: the record is flagged.
+  // In layout CMGPU_FASTX_STRICT4 the scan then fails with EFORMAT; in CMGPU_FASTX_FREE the general path reads the chunk as kseq does.
   bool blank = true;
   for (uint32_t i = s0; blank && i < e3; ++i) { const uint8_t ch = text[i]; blank = ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r'; }
   if (!ok && !blank) atomicMin(bad, r);
@@ -171,18 +180,22 @@ __device__ __forceinline__ uint64_t fq_space_mask(uint64_t w) {
   const uint64_t sp = ~(((y & ~H) + ~H) | y);                                // byte == ' '
   return (ctl | sp) & H;
 }
-// first byte of the name of taken record j: behind the '@' of its header line
+// first byte of the name of taken record j: behind the '@' of its header line.  FREE: the record is known by its header line (general path
+// of layout CMGPU_FASTX_FREE), not by its place among the groups of four
+template <bool FREE>
 __device__ __forceinline__ uint32_t fq_name_start(const uint32_t *__restrict__ nl, uint32_t raw) {
-  return (raw == 0 ? 0u : nl[4 * raw - 1] + 1u) + 1u;
+  const uint32_t line = FREE ? raw : 4 * raw;
+  return (line == 0 ? 0u : nl[line - 1] + 1u) + 1u;
 }
 // name length of every taken record: the header is read in aligned 16-byte pieces from the piece that holds its first byte on (a
 // thread per record: a header is a few tens of bytes, two or three loads).  The line's own '\n' ends the search at the latest; the text
 // buffers have 32 bytes of room behind n_bytes, so the last piece stays inside the allocation.
+template <bool FREE>
 __global__ __launch_bounds__(FQ_BLOCK) void k_fq_name_len(const uint8_t *__restrict__ text, uint64_t n_bytes, const uint32_t *__restrict__ nl,
                                                             const uint32_t *__restrict__ recidx, uint32_t n, uint32_t *__restrict__ len) {
   const uint32_t j = blockIdx.x * FQ_BLOCK + threadIdx.x;
   if (j >= n) return;
-  const uint32_t s = fq_name_start(nl, recidx[j]);
+  const uint32_t s = fq_name_start<FREE>(nl, recidx[j]);
   uint32_t a = s & ~15u, skip = s - a, end = (uint32_t)n_bytes;
   while (a < n_bytes) {
     const uint4 v = *reinterpret_cast<const uint4 *>(text + a);
@@ -198,13 +211,14 @@ __global__ __launch_bounds__(FQ_BLOCK) void k_fq_name_len(const uint8_t *__restr
 }
 // the names back to back: single bytes up to the destination's next 4-byte boundary, then whole words (the source is read at whatever
 // alignment it has), then the last bytes
+template <bool FREE>
 __global__ __launch_bounds__(FQ_BLOCK) void k_fq_name_gather(const uint8_t *__restrict__ text, const uint32_t *__restrict__ nl,
                                                                const uint32_t *__restrict__ recidx, const uint32_t *__restrict__ off, uint32_t n,
                                                                uint8_t *__restrict__ blob) {
   const uint32_t j = blockIdx.x * FQ_BLOCK + threadIdx.x;
   if (j >= n) return;
   const uint32_t o = off[j], len = off[j + 1] - o;
-  const uint8_t *src = text + fq_name_start(nl, recidx[j]);
+  const uint8_t *src = text + fq_name_start<FREE>(nl, recidx[j]);
   uint8_t *dst = blob + o;
   uint32_t i = 0;
   for (; i < len && ((o + i) & 3u); ++i) dst[i] = src[i];
@@ -219,6 +233,75 @@ __global__ __launch_bounds__(FQ_BLOCK) void k_fq_name_gather(const uint8_t *__re
 __global__ __launch_bounds__(FQ_BLOCK) void k_fq_name_append(const uint32_t *__restrict__ off, uint32_t n, uint64_t base, uint64_t *__restrict__ out) {
   const uint32_t j = blockIdx.x * FQ_BLOCK + threadIdx.x;
   if (j <= n) out[j] = base + off[j];
+}
+
+// ---- layout CMGPU_FASTX_FREE, general path: kseq's record chain over the line index (cm_fastx.h) -----------------------------------------
+__global__ __launch_bounds__(FQ_BLOCK) void k_fx_lines(const uint8_t *__restrict__ text, const uint32_t *__restrict__ nl, uint32_t n_lines,
+                                                         uint32_t *__restrict__ li) {
+  const uint32_t i = blockIdx.x * FQ_BLOCK + threadIdx.x;
+  if (i < n_lines) li[i] = cm_fx_line_info(text, nl, i);
+}
+// a lane per line; only header candidates walk further than their own line, and then the lines of one record
+__global__ __launch_bounds__(FQ_BLOCK) void k_fx_walk(const uint32_t *__restrict__ li, uint32_t n_lines, int final_chunk, int unterminated,
+                                                        uint32_t *__restrict__ nxt, uint32_t *__restrict__ send, uint32_t *__restrict__ sl) {
+  const uint32_t i = blockIdx.x * FQ_BLOCK + threadIdx.x;
+  if (i >= n_lines) return;
+  uint32_t a, b, c;
+  cm_fx_walk(li, n_lines, i, final_chunk != 0, unterminated != 0, &a, &b, &c);
+  nxt[i] = a; send[i] = b; sl[i] = c;
+}
+// a block per tile of CM_FX_TILE lines: every line's first chain element behind the tile, by pointer doubling in LDS
+__global__ __launch_bounds__(FQ_BLOCK) void k_fx_tile(const uint32_t *__restrict__ nxt, uint32_t n_lines, uint32_t *__restrict__ exit_) {
+  __shared__ uint32_t e[CM_FX_TILE];
+  const uint32_t t0 = blockIdx.x * CM_FX_TILE, t1 = t0 + CM_FX_TILE < n_lines ? t0 + CM_FX_TILE : n_lines, cnt = t1 - t0;
+  for (uint32_t k = threadIdx.x; k < cnt; k += FQ_BLOCK) e[k] = nxt[t0 + k];
+  __syncthreads();
+  for (int r = 0; r < CM_FX_TILE_ROUNDS; ++r) {
+    for (uint32_t k = threadIdx.x; k < cnt; k += FQ_BLOCK) cm_fx_tile_jump(e, t0, t1, k);
+    __syncthreads();
+  }
+  for (uint32_t k = threadIdx.x; k < cnt; k += FQ_BLOCK) exit_[t0 + k] = e[k];
+}
+// one lane: a step per tile the chain touches (entry: 0xff-filled before)
+__global__ void k_fx_entries(const uint32_t *__restrict__ exit_, uint32_t n_lines, uint32_t *__restrict__ entry) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) cm_fx_tile_entries(exit_, n_lines, entry);
+}
+// a lane per tile walks the tile's members: complete records with a sequence are kept (keep: zeroed before), the one member that ends the
+// chain early goes to res[0] (line) / res[1] (status), the first record without quality of a stream that needs qualities to res[2], the
+// kinds of records kept (CM_FX_SEEN_*) to res[3]
+__global__ __launch_bounds__(64) void k_fx_mark(const uint32_t *__restrict__ nxt, const uint32_t *__restrict__ sl, const uint32_t *__restrict__ entry,
+                                                uint32_t n_tiles, uint32_t n_lines, int want_qual, uint32_t *__restrict__ keep, uint32_t *__restrict__ res) {
+  const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= n_tiles) return;
+  const uint32_t first = entry[t];
+  if (first == CM_FX_NONE) return;
+  const uint32_t t1 = (t + 1) * CM_FX_TILE < n_lines ? (t + 1) * CM_FX_TILE : n_lines;
+  uint32_t seen = 0;
+  cm_fx_tile_members(nxt, first, t1, [&](uint32_t i) {
+    const uint32_t st = sl[i] >> 28, len = sl[i] & CM_FX_LEN_MASK;
+    if (st <= CM_FX_FASTA) {
+      if (len == 0) return;  // (no record and no name: sequence_batch.cc:27-30)
+      if (st == CM_FX_FASTA && want_qual) atomicMin(res + 2, i);
+      else { keep[i] = 1u; seen |= st == CM_FX_FASTA ? CM_FX_SEEN_FASTA : CM_FX_SEEN_FASTQ; }
+    } else if (st != CM_FX_SKIP) { res[0] = i; res[1] = st; }
+  });
+  if (seen) atomicOr(res + 3, seen);
+}
+// the take's kernels for records known by their header line h = recidx[j]: sequence lines (h, send[h]), quality lines (send[h], nxt[h])
+__global__ __launch_bounds__(FQ_BLOCK) void k_fx_len(const uint32_t *__restrict__ sl, const uint32_t *__restrict__ recidx, uint32_t n, FqFormat fmt,
+                                                       uint32_t *__restrict__ len) {
+  const uint32_t j = blockIdx.x * FQ_BLOCK + threadIdx.x;
+  if (j < n) len[j] = fq_eff_len(fmt, sl[recidx[j]] & CM_FX_LEN_MASK);
+}
+__global__ __launch_bounds__(FQ_BLOCK) void k_fx_gather(const uint8_t *__restrict__ text, const uint32_t *__restrict__ nl, const uint32_t *__restrict__ nxt,
+                                                          const uint32_t *__restrict__ send, const uint32_t *__restrict__ sl,
+                                                          const uint32_t *__restrict__ recidx, const uint32_t *__restrict__ off, uint32_t n,
+                                                          FqFormat fmt, uint8_t *__restrict__ bases, uint8_t *__restrict__ quals) {
+  const uint32_t j = blockIdx.x * FQ_BLOCK + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t h = recidx[j], raw = sl[h] & CM_FX_LEN_MASK, se = send[h], o = off[j], l = off[j + 1] - o;
+  cm_fx_copy(text, nl, h + 1, se, raw, fmt.n_ranges, fmt.start, fmt.end, fmt.minus, fmt.minus != 0, o, l, bases);
+  if (quals) cm_fx_copy(text, nl, se + 1, nxt[h], raw, fmt.n_ranges, fmt.start, fmt.end, fmt.minus, false, o, l, quals);
 }
 
 struct FqMaxOp {
@@ -244,15 +327,76 @@ extern "C" int cmgpu_fastq_scan(cmgpu_ctx *c, int stream, const char *text, uint
   *n_records = 0;
   f.dev_mode = false; f.dev_len = 0;
   f.n_bytes = n_bytes; f.n_nl = 0; f.n_raw = 0; f.n_rec = 0; f.final_chunk = final_chunk != 0;
+  f.general = false; f.fx_lines = 0; f.fx_stop = 0;
   if (n_bytes == 0) return CMGPU_OK;
   if (f.text.ensure(n_bytes + 32)) { cm_set_error(c, "out of device memory (FASTQ text)"); return CMGPU_ENOMEM; }
   FQCHECK(c, hipMemcpyAsync(f.text.p, text, n_bytes, hipMemcpyHostToDevice, fq_hs(c, f)));
   return fq_scan_resident(c, stream, n_bytes, final_chunk, text[n_bytes - 1], n_records);
 }
 
+// layout CMGPU_FASTX_FREE, the chunk is not plain four-line text: the records of its n_lines lines (f.nl) as kseq reads them
+static int fq_scan_general(cmgpu_ctx *c, int stream, uint32_t n_lines, bool final_chunk, bool unterminated, uint32_t *n_records) {
+  CmFqStream &f = c->fq[stream];
+  hipStream_t s = fq_hs(c, f);
+  f.general = true;
+  f.fx_lines = n_lines; f.fx_stop = 0;
+  f.n_raw = 0; f.n_rec = 0;
+  *n_records = 0;
+  if (n_lines == 0) return CMGPU_OK;
+  const uint32_t n_tiles = (n_lines + CM_FX_TILE - 1) / CM_FX_TILE;
+  const size_t per_line = ((size_t)n_lines + 1) * 4;
+  if (f.fx_li.ensure(per_line) || f.fx_nxt.ensure(per_line) || f.fx_send.ensure(per_line) || f.fx_sl.ensure(per_line) || f.fx_exit.ensure(per_line) ||
+      f.fx_entry.ensure((size_t)n_tiles * 4) || f.fx_res.ensure(16) || f.keep.ensure(per_line) || f.pos.ensure(per_line) || f.recidx.ensure(per_line) ||
+      f.scan_tmp.ensure(cm_scan_tmp_words(n_lines) * 4)) { cm_set_error(c, "out of device memory (FASTQ records)"); return CMGPU_ENOMEM; }
+  const uint32_t none = 0xffffffffu;
+  const uint32_t res0[4] = {none, 0u, none, 0u};
+  FQCHECK(c, hipMemcpyAsync(f.fx_res.p, res0, 16, hipMemcpyHostToDevice, s));
+  FQCHECK(c, hipMemsetAsync(f.fx_entry.p, 0xff, (size_t)n_tiles * 4, s));
+  FQCHECK(c, hipMemsetAsync(f.keep.p, 0, per_line, s));
+  const dim3 gl((n_lines + FQ_BLOCK - 1) / FQ_BLOCK), b(FQ_BLOCK);
+  const int want_qual = stream == 2 || f.keep_reads ? 1 : 0;
+  hipLaunchKernelGGL(k_fx_lines, gl, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, n_lines, (uint32_t *)f.fx_li.p);
+  hipLaunchKernelGGL(k_fx_walk, gl, b, 0, s, (const uint32_t *)f.fx_li.p, n_lines, final_chunk ? 1 : 0, unterminated ? 1 : 0, (uint32_t *)f.fx_nxt.p,
+                     (uint32_t *)f.fx_send.p, (uint32_t *)f.fx_sl.p);
+  hipLaunchKernelGGL(k_fx_tile, dim3(n_tiles), b, 0, s, (const uint32_t *)f.fx_nxt.p, n_lines, (uint32_t *)f.fx_exit.p);
+  hipLaunchKernelGGL(k_fx_entries, dim3(1), dim3(1), 0, s, (const uint32_t *)f.fx_exit.p, n_lines, (uint32_t *)f.fx_entry.p);
+  hipLaunchKernelGGL(k_fx_mark, dim3((n_tiles + 63) / 64), dim3(64), 0, s, (const uint32_t *)f.fx_nxt.p, (const uint32_t *)f.fx_sl.p,
+                     (const uint32_t *)f.fx_entry.p, n_tiles, n_lines, want_qual, (uint32_t *)f.keep.p, (uint32_t *)f.fx_res.p);
+  cm_scan_u32((const uint32_t *)f.keep.p, (uint32_t *)f.pos.p, n_lines, (uint32_t *)f.scan_tmp.p, s);
+  hipLaunchKernelGGL(k_fq_compact, gl, b, 0, s, (const uint32_t *)f.keep.p, (const uint32_t *)f.pos.p, n_lines, (uint32_t *)f.recidx.p);
+  uint32_t res[4] = {none, 0, none, 0}, n_rec = 0;
+  FQCHECK(c, hipMemcpyAsync(res, f.fx_res.p, 16, hipMemcpyDeviceToHost, s));
+  FQCHECK(c, hipMemcpyAsync(&n_rec, (uint32_t *)f.pos.p + n_lines, 4, hipMemcpyDeviceToHost, s));
+  FQCHECK(c, cm_stream_sync(s));
+  const bool early = res[0] != none, refused = early && res[1] != CM_FX_INCOMPLETE;
+  if (res[2] != none && !(refused && res[0] < res[2])) {
+    cm_set_error(c, "record without quality (FASTA) at line " + std::to_string(res[2]) + " of the chunk, and " +
+                        (stream == 2 ? std::string("the barcode stream needs qualities")
+                                     : std::string("whole reads are kept for SAM output (cmgpu_fastq_keep_reads): the reference cannot write SAM for FASTA reads either")));
+    return CMGPU_EFORMAT;
+  }
+  if (refused) {
+    const std::string at = " (line " + std::to_string(res[0]) + " of the chunk)";
+    if (res[1] == CM_FX_TRUNC) cm_set_error(c, "truncated quality: the quality is not as long as the sequence of the record" + at);
+    else if (res[1] == CM_FX_KEPT_CR) cm_set_error(c, "a line that holds only a carriage return starts the sequence or the quality of the record" + at);
+    else cm_set_error(c, "neither blank nor a '@' / '>' header where a record is looked for, or a line of 256 MiB and more" + at);
+    return CMGPU_EFORMAT;
+  }
+  f.fx_seen |= res[3];
+  if (f.fx_seen == (CM_FX_SEEN_FASTQ | CM_FX_SEEN_FASTA)) {
+    cm_set_error(c, "records with quality and records without in one stream: FASTA and FASTQ mixed, or a FASTQ file cut short inside a record (corrupted?)");
+    return CMGPU_EFORMAT;
+  }
+  f.fx_stop = early ? res[0] : n_lines;
+  f.n_rec = n_rec;
+  *n_records = n_rec;
+  return CMGPU_OK;
+}
+
 static int fq_scan_resident(cmgpu_ctx *c, int stream, uint64_t n_bytes, int final_chunk, char last_char, uint32_t *n_records) {
   CmFqStream &f = c->fq[stream];
   hipStream_t s = fq_hs(c, f);
+  const bool free_layout = f.layout == CMGPU_FASTX_FREE;
   const uint32_t n_thr = (uint32_t)((n_bytes + 15) / 16);
   if (f.cnt.ensure(((size_t)n_thr + 1) * 4) || f.off.ensure(((size_t)n_thr + 1) * 4) ||
       f.scan_tmp.ensure(cm_scan_tmp_words(n_thr) * 4)) { cm_set_error(c, "out of device memory (FASTQ text)"); return CMGPU_ENOMEM; }
@@ -266,6 +410,8 @@ static int fq_scan_resident(cmgpu_ctx *c, int stream, uint64_t n_bytes, int fina
   hipLaunchKernelGGL(k_fq_fill, g, b, 0, s, (const uint8_t *)f.text.p, n_bytes, n_thr, (const uint32_t *)f.off.p, (uint32_t *)f.nl.p);
   // a final chunk whose last line has no terminator: the end of the text closes it
   // (also an empty, unterminated quality line of the very last record: three lines seen)
+  const bool unterminated = final_chunk && last_char != '\n';
+  const uint32_t n_lines = n_nl + (unterminated ? 1u : 0u);  // (the lines of the text; the four-line path below may count an empty one more)
   if (final_chunk && (last_char != '\n' || n_nl % 4 == 3)) {
     const uint32_t endpos = (uint32_t)n_bytes;
     FQCHECK(c, hipMemcpyAsync((uint32_t *)f.nl.p + n_nl, &endpos, 4, hipMemcpyHostToDevice, s));
@@ -273,6 +419,8 @@ static int fq_scan_resident(cmgpu_ctx *c, int stream, uint64_t n_bytes, int fina
     ++n_nl;
   }
   f.n_nl = n_nl;
+  // (layout FREE: lines behind the last group of four at the end of the text are records or blank lines for the general path to tell)
+  if (free_layout && final_chunk && n_lines % 4 != 0) return fq_scan_general(c, stream, n_lines, true, unterminated, n_records);
   const uint32_t n_raw = n_nl / 4;
   f.n_raw = n_raw;
   if (n_raw == 0) return CMGPU_OK;
@@ -281,7 +429,8 @@ static int fq_scan_resident(cmgpu_ctx *c, int stream, uint64_t n_bytes, int fina
   const uint32_t none = 0xffffffffu;
   FQCHECK(c, hipMemsetAsync(f.bad.p, 0xff, 8, s));
   const dim3 gr((n_raw + FQ_BLOCK - 1) / FQ_BLOCK);
-  hipLaunchKernelGGL(k_fq_records, gr, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, n_raw, stream == 2 || f.keep_reads ? 1 : 0,
+  hipLaunchKernelGGL(k_fq_records, gr, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, n_raw,
+                     free_layout ? 3 : stream == 2 || f.keep_reads ? 1 : 0,  // (FREE: a quality of another length is kseq's -2 for every stream)
                      (uint32_t *)f.keep.p, (uint32_t *)f.bad.p);
   cm_scan_u32((const uint32_t *)f.keep.p, (uint32_t *)f.pos.p, n_raw, (uint32_t *)f.scan_tmp.p, s);
   hipLaunchKernelGGL(k_fq_compact, gr, b, 0, s, (const uint32_t *)f.keep.p, (const uint32_t *)f.pos.p, n_raw, (uint32_t *)f.recidx.p);
@@ -290,6 +439,7 @@ static int fq_scan_resident(cmgpu_ctx *c, int stream, uint64_t n_bytes, int fina
   FQCHECK(c, hipMemcpyAsync(&bad_q, (uint32_t *)f.bad.p + 1, 4, hipMemcpyDeviceToHost, s));
   FQCHECK(c, hipMemcpyAsync(&n_rec, (uint32_t *)f.pos.p + n_raw, 4, hipMemcpyDeviceToHost, s));
   FQCHECK(c, cm_stream_sync(s));
+  if (bad != none && free_layout) return fq_scan_general(c, stream, n_lines, final_chunk != 0, unterminated, n_records);
   if (bad != none && bad == bad_q && stream != 2) {  // (only seen with keep_reads on: the qualities of reads are not looked at otherwise)
     cm_set_error(c, "truncated quality: the quality line is not as long as the sequence at record " + std::to_string(bad) +
                         " of the chunk (whole reads are kept for SAM output, cmgpu_fastq_keep_reads)");
@@ -300,6 +450,14 @@ static int fq_scan_resident(cmgpu_ctx *c, int stream, uint64_t n_bytes, int fina
     cm_set_error(c, "not a 4-line FASTQ record (missing '@' / '+' marker or quality length) at record " + std::to_string(bad) + " of the chunk");
     f.n_raw = 0;
     return CMGPU_EFORMAT;
+  }
+  if (free_layout && n_rec) {  // (four-line records have their quality)
+    f.fx_seen |= CM_FX_SEEN_FASTQ;
+    if (f.fx_seen == (CM_FX_SEEN_FASTQ | CM_FX_SEEN_FASTA)) {
+      cm_set_error(c, "records with quality and records without in one stream: FASTA and FASTQ mixed, or a FASTQ file cut short inside a record (corrupted?)");
+      f.n_raw = 0;
+      return CMGPU_EFORMAT;
+    }
   }
   f.n_rec = n_rec;
   *n_records = n_rec;
@@ -508,6 +666,7 @@ extern "C" int cmgpu_fastq_scan_bgzf(cmgpu_ctx *c, int stream, const void *block
   }
   f.dev_len = out;
   f.n_bytes = out; f.n_nl = 0; f.n_raw = 0; f.n_rec = 0; f.final_chunk = final_chunk != 0;
+  f.general = false; f.fx_lines = 0; f.fx_stop = 0;
   if (out == 0) return CMGPU_OK;
   char last_char = 0;
   FQCHECK(c, hipMemcpyAsync(&last_char, (const uint8_t *)f.text.p + out - 1, 1, hipMemcpyDeviceToHost, s));
@@ -526,6 +685,7 @@ extern "C" int cmgpu_fastq_take(cmgpu_ctx *c, int stream, uint32_t n, uint64_t *
   if (n > f.n_rec) { cm_set_error(c, "more records requested than the chunk holds"); return CMGPU_EINVAL; }
   DevBuf &bases = stream == 0 ? c->st_rb0 : stream == 1 ? c->st_rb1 : c->st_bcb;
   DevBuf &offs = stream == 0 ? c->st_ro0 : stream == 1 ? c->st_ro1 : c->st_bco;
+  if (f.final_chunk && n == f.n_rec) f.fx_seen = 0;  // (the file ends with this take: the next one may hold the other kind of records)
   f.taken = n;
   f.taken_bases = 0;
   f.taken_max_len = 0;
@@ -535,13 +695,31 @@ extern "C" int cmgpu_fastq_take(cmgpu_ctx *c, int stream, uint32_t n, uint64_t *
   // at the end of the file, blank lines go with it
   uint32_t last_raw = 0;
   bool have_last = false;
-  if (n == f.n_rec) { if (f.n_raw) { last_raw = f.n_raw - 1; have_last = true; } }
+  if (f.general) {}
+  else if (n == f.n_rec) { if (f.n_raw) { last_raw = f.n_raw - 1; have_last = true; } }
   else if (n > 0) {
     FQCHECK(c, hipMemcpyAsync(&last_raw, (uint32_t *)f.recidx.p + (n - 1), 4, hipMemcpyDeviceToHost, s));
     FQCHECK(c, cm_stream_sync(s));
     have_last = true;
   }
   uint64_t consumed = 0;
+  if (f.general) {
+    // the line where seek state stands behind the taken records: where the countable records end, or the line after the last one taken
+    uint32_t line = f.fx_stop;
+    if (n < f.n_rec && n > 0) {
+      FQCHECK(c, hipMemcpyAsync(&last_raw, (uint32_t *)f.recidx.p + (n - 1), 4, hipMemcpyDeviceToHost, s));
+      FQCHECK(c, cm_stream_sync(s));
+      FQCHECK(c, hipMemcpyAsync(&line, (uint32_t *)f.fx_nxt.p + last_raw, 4, hipMemcpyDeviceToHost, s));
+      FQCHECK(c, cm_stream_sync(s));
+    } else if (n < f.n_rec) line = 0;
+    if (line > 0) {
+      uint32_t endnl = 0;
+      FQCHECK(c, hipMemcpyAsync(&endnl, (uint32_t *)f.nl.p + (line - 1), 4, hipMemcpyDeviceToHost, s));
+      FQCHECK(c, cm_stream_sync(s));
+      consumed = (uint64_t)endnl + 1;
+      if (consumed > f.n_bytes) consumed = f.n_bytes;
+    }
+  }
   if (have_last) {
     uint32_t endnl = 0;
     FQCHECK(c, hipMemcpyAsync(&endnl, (uint32_t *)f.nl.p + (4 * (size_t)last_raw + 3), 4, hipMemcpyDeviceToHost, s));
@@ -565,7 +743,8 @@ extern "C" int cmgpu_fastq_take(cmgpu_ctx *c, int stream, uint32_t n, uint64_t *
   fmt.n_ranges = f.n_ranges;
   for (int k = 0; k < 4; ++k) { fmt.start[k] = f.rng_start[k]; fmt.end[k] = f.rng_end[k]; }
   fmt.minus = f.minus ? 1 : 0;
-  hipLaunchKernelGGL(k_fq_len, g, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, (const uint32_t *)f.recidx.p, n, fmt, (uint32_t *)f.len.p);
+  if (f.general) hipLaunchKernelGGL(k_fx_len, g, b, 0, s, (const uint32_t *)f.fx_sl.p, (const uint32_t *)f.recidx.p, n, fmt, (uint32_t *)f.len.p);
+  else hipLaunchKernelGGL(k_fq_len, g, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, (const uint32_t *)f.recidx.p, n, fmt, (uint32_t *)f.len.p);
   cm_scan_u32((const uint32_t *)f.len.p, (uint32_t *)offs.p, n, (uint32_t *)f.scan_tmp.p, s);
   size_t tb = 0;
   (void)rocprim::reduce(nullptr, tb, (const uint32_t *)f.len.p, (uint32_t *)f.bad.p, 0u, (size_t)n, FqMaxOp(), s);
@@ -573,8 +752,10 @@ extern "C" int cmgpu_fastq_take(cmgpu_ctx *c, int stream, uint32_t n, uint64_t *
   hipError_t e = rocprim::reduce(f.red_tmp.p, tb, (const uint32_t *)f.len.p, (uint32_t *)f.bad.p, 0u, (size_t)n, FqMaxOp(), s);
   uint32_t total = 0, mx = 0, name_total = 0;
   if (names) {  // (lengths and offsets of the names in the same wait as the bases')
-    hipLaunchKernelGGL(k_fq_name_len, g, b, 0, s, (const uint8_t *)f.text.p, f.n_bytes, (const uint32_t *)f.nl.p, (const uint32_t *)f.recidx.p, n,
-                       (uint32_t *)f.nm_len.p);
+    if (f.general) hipLaunchKernelGGL(k_fq_name_len<true>, g, b, 0, s, (const uint8_t *)f.text.p, f.n_bytes, (const uint32_t *)f.nl.p, (const uint32_t *)f.recidx.p, n,
+                                      (uint32_t *)f.nm_len.p);
+    else hipLaunchKernelGGL(k_fq_name_len<false>, g, b, 0, s, (const uint8_t *)f.text.p, f.n_bytes, (const uint32_t *)f.nl.p, (const uint32_t *)f.recidx.p, n,
+                            (uint32_t *)f.nm_len.p);
     cm_scan_u32((const uint32_t *)f.nm_len.p, (uint32_t *)f.nm_off.p, n, (uint32_t *)f.scan_tmp.p, s);
     if (e == hipSuccess) e = hipMemcpyAsync(&name_total, (uint32_t *)f.nm_off.p + n, 4, hipMemcpyDeviceToHost, s);
   }
@@ -585,10 +766,18 @@ extern "C" int cmgpu_fastq_take(cmgpu_ctx *c, int stream, uint32_t n, uint64_t *
   if (bases.ensure((size_t)total + 16) || (stream == 2 && c->st_bcq.ensure((size_t)total + 16))) { cm_set_error(c, "out of device memory (reads)"); return CMGPU_ENOMEM; }
   if (names && f.st_nm.ensure((size_t)name_total + 16)) { cm_set_error(c, "out of device memory (read names)"); return CMGPU_ENOMEM; }
   if (reads && f.st_q.ensure((size_t)total + 16)) { cm_set_error(c, "out of device memory (read qualities)"); return CMGPU_ENOMEM; }
-  hipLaunchKernelGGL(k_fq_gather, g, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, (const uint32_t *)f.recidx.p,
-                     (const uint32_t *)offs.p, n, fmt, (uint8_t *)bases.p, stream == 2 ? (uint8_t *)c->st_bcq.p : reads ? (uint8_t *)f.st_q.p : (uint8_t *)nullptr);
-  if (names)
-    hipLaunchKernelGGL(k_fq_name_gather, g, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, (const uint32_t *)f.recidx.p,
+  uint8_t *quals = stream == 2 ? (uint8_t *)c->st_bcq.p : reads ? (uint8_t *)f.st_q.p : (uint8_t *)nullptr;
+  if (f.general)
+    hipLaunchKernelGGL(k_fx_gather, g, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, (const uint32_t *)f.fx_nxt.p, (const uint32_t *)f.fx_send.p,
+                       (const uint32_t *)f.fx_sl.p, (const uint32_t *)f.recidx.p, (const uint32_t *)offs.p, n, fmt, (uint8_t *)bases.p, quals);
+  else
+    hipLaunchKernelGGL(k_fq_gather, g, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, (const uint32_t *)f.recidx.p,
+                       (const uint32_t *)offs.p, n, fmt, (uint8_t *)bases.p, quals);
+  if (names && f.general)
+    hipLaunchKernelGGL(k_fq_name_gather<true>, g, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, (const uint32_t *)f.recidx.p,
+                       (const uint32_t *)f.nm_off.p, n, (uint8_t *)f.st_nm.p);
+  else if (names)
+    hipLaunchKernelGGL(k_fq_name_gather<false>, g, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, (const uint32_t *)f.recidx.p,
                        (const uint32_t *)f.nm_off.p, n, (uint8_t *)f.st_nm.p);
   FQCHECK(c, cm_stream_sync(s));
   f.taken_bases = total;
@@ -843,6 +1032,27 @@ extern "C" int cmgpu_fastq_set_format(cmgpu_ctx *c, int stream, int n_ranges, co
   f.minus = strand == '-';
   // the full range on the + strand is the identity (IsFullRangeAndPositiveStrand)
   if (n_ranges >= 1 && !f.minus && starts[0] == 0 && ends[0] == -1) f.n_ranges = 0;
+  return CMGPU_OK;
+}
+
+// Record layout of one stream (cm_fastx.h): CMGPU_FASTX_FREE reads what kseq_read reads (kseq.h:177-218); the default stays four-line FASTQ
+extern "C" int cmgpu_fastq_set_layout(cmgpu_ctx *c, int stream, int layout) {
+  if (!c || stream < 0 || stream > 2) return CMGPU_EINVAL;
+  if (layout != CMGPU_FASTX_STRICT4 && layout != CMGPU_FASTX_FREE) { cm_set_error(c, "unknown FASTQ record layout " + std::to_string(layout)); return CMGPU_EINVAL; }
+  CmFqStream &f = c->fq[stream];
+  if (layout != f.layout && f.dev_mode && f.dev_len) {
+    cm_set_error(c, "the record layout cannot change while text of the stream is kept on the device (cmgpu_fastq_scan_bgzf)");
+    return CMGPU_EINVAL;
+  }
+  f.layout = layout;
+  f.fx_seen = 0;
+  return CMGPU_OK;
+}
+extern "C" int cmgpu_fastq_scan_info(const cmgpu_ctx *c, int stream, int *general_path, uint32_t *n_lines) {
+  if (!c || stream < 0 || stream > 2) return CMGPU_EINVAL;
+  const CmFqStream &f = c->fq[stream];
+  if (general_path) *general_path = f.general ? 1 : 0;
+  if (n_lines) *n_lines = f.general ? f.fx_lines : f.n_nl;
   return CMGPU_OK;
 }
 

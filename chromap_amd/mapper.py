@@ -492,6 +492,17 @@ class ChromapGPU:
         self._check(self.L.cmgpu_fastq_commit(self.ctx, n, first_read_id, int(paired), int(barcoded)), self.ctx)
         self._n_resident = n
 
+    def fastq_set_layout(self, stream, layout):
+        """record layout of the stream's following scans: FASTX_STRICT4 (four lines per record, the default) or FASTX_FREE (what kseq
+        reads: wrapped sequence / quality lines, FASTA, blank lines between records)"""
+        self._check(self.L.cmgpu_fastq_set_layout(self.ctx, stream, int(layout)), self.ctx)
+
+    def fastq_scan_info(self, stream):
+        """(general_path, n_lines) of the stream's last scan: whether it had to leave the four-line path, and the chunk's lines"""
+        g, n = C.c_int(0), C.c_uint32(0)
+        self._check(self.L.cmgpu_fastq_scan_info(self.ctx, stream, C.byref(g), C.byref(n)), self.ctx)
+        return g.value, n.value
+
     def fastq_keep_names(self, stream=0, on=True):
         """the stream's takes also gather the read names (kseq's name.s); commits append them to the context's name store"""
         self._check(self.L.cmgpu_fastq_keep_names(self.ctx, stream, int(on)), self.ctx)

@@ -522,7 +522,7 @@ int cmgpu_store_info(const cmgpu_ctx *ctx, uint64_t *n_records, uint64_t *text_b
  * stream: 0 = read 1, 1 = read 2, 2 = cell barcodes (bases + qualities).
  *   cmgpu_fastq_scan   uploads one chunk (< 4 GiB) and counts its complete, non-empty records;
  *                      final_chunk != 0: the text ends the file (a missing last newline is fine).
- *                      CMGPU_EFORMAT: not 4-line FASTQ (multi-line records need a host parser).
+ *                      CMGPU_EFORMAT: not 4-line FASTQ (other layouts: cmgpu_fastq_set_layout, CMGPU_FASTX_FREE).
  *                      Scans (this call and cmgpu_fastq_scan_bgzf) of DIFFERENT streams of one context may be
  *                      made from different host threads at the same time: each stream has a HIP stream and
  *                      scratch of its own; every other call on a context is one thread at a time.
@@ -552,6 +552,31 @@ int cmgpu_fastq_scan(cmgpu_ctx *ctx, int stream, const char *text, uint64_t n_by
  * 4-line FASTQ.  A call of cmgpu_fastq_scan on the stream returns it to host-resubmitted text. */
 int cmgpu_fastq_scan_bgzf(cmgpu_ctx *ctx, int stream, const void *blocks, uint64_t n_bytes, int final_chunk, uint32_t *n_records);
 int cmgpu_fastq_take(cmgpu_ctx *ctx, int stream, uint32_t n, uint64_t *bytes_consumed);
+/* Record layout of a stream (0 = read 1, 1 = read 2, 2 = barcodes); applies to the following cmgpu_fastq_scan / _scan_bgzf calls.
+ * CMGPU_FASTX_STRICT4 (default): four lines per record, as described above, with its messages.
+ * CMGPU_FASTX_FREE: what kseq_read reads (src/kseq.h:177-218) -- sequence and quality wrapped over any number of lines, FASTA records,
+ * blank lines between records, CRLF, no final newline.  Over the lines of the text (split at '\n') kseq is this automaton on a line's
+ * first byte: SEEK skips lines up to one that starts with '@' or '>' (kseq.h:183), the header, whose name ends at the first isspace() byte
+ * (kseq.h:188).  SEQUENCE: a '+' line starts the quality; an '@' / '>' line ends the record without quality and is the next header
+ * (kseq.h:194-199); empty lines are skipped; other lines are appended without their '\r' (kseq.h:141); the end of the final chunk ends the
+ * record.  QUALITY: the rest of the '+' line is ignored (kseq.h:211); lines -- at least one, whatever their first byte -- are appended
+ * until the quality is as long as the sequence (kseq.h:213); another length, or the end of the text first, is kseq's -2 (kseq.h:212,216):
+ * CMGPU_EFORMAT "truncated quality", for every stream.  Records with an empty sequence give no record and no name
+ * (src/sequence_batch.cc:27-30).  Refused with CMGPU_EFORMAT, never read differently from kseq: a skipped line in SEEK state that is
+ * not blank; a line holding only '\r' where the sequence or the quality is still empty (kseq keeps that '\r'); a record without quality
+ * on a stream that needs qualities (cmgpu_fastq_keep_reads, the barcode stream -- the reference cannot write SAM for FASTA reads either);
+ * records with quality and records without in one stream (kseq reads such a mix, and with it half a record behind a FASTQ file's last
+ * whole one; a file of either kind alone is read, whatever its markers); lines or sequences of 256 MiB and more.  Records do not depend on how the text is cut into chunks: a non-final scan counts a record
+ * only when the chunk proves it complete (FASTQ: the quality reached the sequence's length; FASTA: the next header line is whole), and
+ * cmgpu_fastq_take's bytes_consumed ends behind the last taken record as before.
+ * The scan tries the four-line path first: text that passes it costs what it costs in CMGPU_FASTX_STRICT4, except that the quality's
+ * length is checked for every stream.  Only a chunk that fails it is resolved by the general path (cm_fastx.h), on the same resident
+ * text and line index.  cmgpu_fastq_scan_info: whether the stream's last scan took the general path, and the chunk's number of lines.
+ * An unknown layout, or a change while inflated text of the stream is kept on the device (BGZF mode), is CMGPU_EINVAL. */
+#define CMGPU_FASTX_STRICT4 0
+#define CMGPU_FASTX_FREE 1
+int cmgpu_fastq_set_layout(cmgpu_ctx *ctx, int stream, int layout);
+int cmgpu_fastq_scan_info(const cmgpu_ctx *ctx, int stream, int *general_path, uint32_t *n_lines);
 int cmgpu_fastq_commit(cmgpu_ctx *ctx, uint32_t n, uint32_t first_read_id, int paired, int barcoded);
 /* Replaces kseq's name.s (ks_getuntil(ks, 0, &seq->name, &c), kseq.h:188, kept per read by SequenceBatch::LoadOneSequenceAndSaveAt,
  * src/sequence_batch.cc:36) for the device ingest: with on != 0 every following cmgpu_fastq_take of the stream (0 = read 1 or
