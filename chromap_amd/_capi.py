@@ -86,6 +86,16 @@ class Stats(C.Structure):
         return {n: int(getattr(self, n)) for n in STAT_FIELDS}
 
 
+class SummaryEntry(C.Structure):
+    _fields_ = [("key", C.c_uint64), ("first_read_id", C.c_uint64), ("total", C.c_uint32), ("dup", C.c_uint32),
+                ("lowmapq", C.c_uint32), ("mapped", C.c_uint32)]
+
+
+class SummaryTable(C.Structure):
+    _fields_ = [("entries", C.POINTER(SummaryEntry)), ("n_entries", C.c_uint64), ("nonwhitelist_total", C.c_uint64)]
+
+
+assert C.sizeof(SummaryEntry) == 32
 assert C.sizeof(Record) == 24 == C.sizeof(PairsRecord)
 assert C.sizeof(RecordBc) == 32
 
@@ -104,6 +114,7 @@ SYMBOLS = ("cmgpu_default_params", "cmgpu_apply_preset", "cmgpu_create", "cmgpu_
            "cmgpu_fastq_keep_names", "cmgpu_names_clear", "cmgpu_names_info", "cmgpu_download_names", "cmgpu_store_format_pairs_resident",
            "cmgpu_fastq_set_layout", "cmgpu_fastq_scan_info", "cmgpu_fastq_keep_reads", "cmgpu_reads_clear", "cmgpu_reads_info", "cmgpu_download_reads", "cmgpu_sam_store_append_resident",
            "cmgpu_sam_store_clear", "cmgpu_sam_store_info", "cmgpu_store_format_sam", "cmgpu_write_sam_header",
+           "cmgpu_summary_enable", "cmgpu_summary_clear", "cmgpu_summary_info", "cmgpu_summary_download", "cmgpu_write_summary", "cmgpu_host_summary_begin", "cmgpu_host_summary_end",
            "cmgpu_load_index_file", "cmgpu_free_host_index", "cmgpu_load_reference_fasta", "cmgpu_free_host_ref",
            "cmgpu_create_synthetic_repeats", "cmgpu_create_synthetic_profile", "cmgpu_generate_resident_batch_indels", "cmgpu_generate_resident_batch_hic", "cmgpu_probe_bench_variant", "cmgpu_gather_sweep", "cmgpu_set_option", "cmgpu_get_option", "cmgpu_swap_resident_batch",
            "cmgpu_exchange_unique_id", "cmgpu_exchange_init", "cmgpu_exchange_init_all", "cmgpu_exchange_init_external",
@@ -217,6 +228,13 @@ def declare(L):
     sig("cmgpu_sam_store_info", C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint64)])
     sig("cmgpu_store_format_sam", C.c_int, [C.c_void_p, P(C.c_char_p), C.c_void_p, C.c_uint32, P(Params), C.c_uint32, P(C.c_uint64), P(C.c_uint64)])
     sig("cmgpu_write_sam_header", C.c_int, [P(C.c_char_p), C.c_void_p, C.c_uint32, C.c_char_p])
+    sig("cmgpu_summary_enable", C.c_int, [C.c_void_p, C.c_int])
+    sig("cmgpu_summary_clear", C.c_int, [C.c_void_p])
+    sig("cmgpu_summary_info", C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint64)])
+    sig("cmgpu_summary_download", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, P(C.c_uint64), P(C.c_uint64)])
+    sig("cmgpu_host_summary_begin", C.c_int, [])
+    sig("cmgpu_host_summary_end", C.c_int, [C.c_void_p, C.c_uint64, P(C.c_uint64)])
+    sig("cmgpu_write_summary", C.c_int, [P(SummaryTable), C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_char_p])
     sig("cmgpu_write_bed_se", C.c_int64, [P(C.c_char_p), C.c_uint32, P(Params), C.c_void_p, C.c_uint64, C.c_char_p])
     sig("cmgpu_load_whitelist_file", C.c_int, [C.c_char_p, C.c_uint32, P(C.c_void_p), P(C.c_uint32)])
     sig("cmgpu_set_whitelist", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32])
@@ -293,6 +311,25 @@ def default_params(preset=None, **overrides):
             raise KeyError(k)
         setattr(p, k, v)
     return p
+
+
+def write_summary(tables, path, barcode_length=0, nonwhitelist_row=False, halve_pairs=False, num_cache_slots_column=True):
+    """cmgpu_write_summary: the --summary CSV from one table per context.  A table is (entries, nonwhitelist_total) with entries an
+    iterable of (key, first_read_id, total, dup, lowmapq, mapped) -- what ChromapGPU.summary_table() returns."""
+    arrays, ts = [], (SummaryTable * max(1, len(tables)))()
+    for t, (entries, nonwl) in enumerate(tables):
+        entries = list(entries)
+        arr = (SummaryEntry * max(1, len(entries)))()
+        for i, e in enumerate(entries):
+            arr[i] = SummaryEntry(*[int(x) for x in e])
+        arrays.append(arr)
+        ts[t].entries = C.cast(arr, C.POINTER(SummaryEntry))
+        ts[t].n_entries = len(entries)
+        ts[t].nonwhitelist_total = int(nonwl)
+    rc = lib().cmgpu_write_summary(ts, len(tables), int(barcode_length), int(bool(nonwhitelist_row)), int(bool(halve_pairs)),
+                                   int(bool(num_cache_slots_column)), os.fsencode(path))
+    if rc != 0:
+        raise RuntimeError("cmgpu_write_summary(%s) failed: %d" % (path, rc))
 
 
 # record layouts of the device FASTQ ingest (include/chromap_amd.h: cmgpu_fastq_set_layout)

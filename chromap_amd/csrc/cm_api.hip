@@ -13,6 +13,7 @@
 #include "../../include/chromap_amd.h"
 #include "cm_ctx.h"
 #include "cm_kernels.h"
+#include "cm_summary.h"
 #include "cm_coop.h"
 #include <chrono>
 #include <mutex>
@@ -1356,6 +1357,7 @@ extern "C" int cmgpu_map_resident(cmgpu_ctx *c, uint64_t *n_out, cmgpu_stats *st
   }
   c->n_records = k;
   if (n_out) *n_out = k;
+  if (c->sm.on) return cm_summary_total(c);  // --summary: the batch's reads per (corrected) barcode
   return CMGPU_OK;
 }
 

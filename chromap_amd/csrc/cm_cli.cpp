@@ -511,7 +511,8 @@ struct ReadFormat {
 };
 
 struct Args {
-  std::string index_path, ref_path, out_path, preset, whitelist, chr_order_path, pairs_order_path, translate_path;
+  std::string index_path, ref_path, out_path, preset, whitelist, chr_order_path, pairs_order_path, translate_path, summary_path;
+  bool summary_cache_slots = true;  // --turn-off-num-uniq-cache-slots clears it
   std::vector<std::string> r1, r2, bc;
   cmgpu_params p;
   bool build_index = false, out_bed = true, out_pairs = false, cell_level_dedup = false, host_ingest = false, out_sam = false, out_tagalign = false, skip_bc_check = false;
@@ -595,6 +596,26 @@ static Args parse(int argc, char **argv) {
     else if (o == "-t" || o == "--num-threads") need("-t");  // host threads are irrelevant here
     else if (o == "--skip-barcode-check") a.skip_bc_check = true;
     else if (o == "--barcode-translate") a.translate_path = need("--barcode-translate");
+    else if (o == "--summary") { a.summary_path = need("--summary"); if (a.summary_path.empty()) die("missing value for --summary"); }
+    else if (o == "--turn-off-num-uniq-cache-slots") a.summary_cache_slots = false;
+    else if (o == "--frip-est-params") {
+      // five coefficients separated by ';' (chromap.h:706-727).  They weigh fric, which needs the minimizer cache's hit counts: this build
+      // does not model the cache, fric is 0 and estfrip with it, so the values are checked and go no further
+      const std::string f = need("--frip-est-params");
+      size_t cnt = 0, p0 = 0;
+      while (p0 <= f.size() && !f.empty()) {
+        size_t p1 = f.find(';', p0);
+        if (p1 == std::string::npos) p1 = f.size();
+        const std::string tok = f.substr(p0, p1 - p0);
+        char *end = nullptr;
+        (void)strtod(tok.c_str(), &end);
+        if (tok.empty() || end == tok.c_str()) die("--frip-est-params: '" + tok + "' is not a number (five coefficients separated by ';')");
+        ++cnt;
+        p0 = p1 + 1;
+        if (p1 == f.size()) break;
+      }
+      if (cnt != 5) die("--frip-est-params: invalid number of parameters, expecting 5 parameters but found " + std::to_string(cnt) + " parameters");
+    }
     else if (o == "--read-format") {
       const std::string f = need("--read-format");
       size_t i = 0;
@@ -627,10 +648,13 @@ static Args parse(int argc, char **argv) {
     else if (o == "-h" || o == "--help") {
       printf("Usage: chromap-amd -i -r ref.fa -o index | chromap-amd [--preset atac|chip|hic] -x index -r ref.fa -1 r1.fq[.gz] [-2 r2.fq[.gz]]\n"
              "       [-b barcode.fq --barcode-whitelist wl.txt] -o out [-e -s -f -l -q --min-read-length --trim-adapters\n"
-             "       --remove-pcr-duplicates --Tn5-shift --low-mem --BED|--pairs --bc-error-threshold ...]\n");
+             "       --remove-pcr-duplicates --Tn5-shift --low-mem --BED|--TagAlign|--pairs|--SAM --bc-error-threshold ...]\n"
+             "       [--summary FILE [--turn-off-num-uniq-cache-slots] [--frip-est-params a;b;c;d;e]]\n"
+             "  --summary FILE  per-barcode CSV (one row for bulk data): barcode,total,duplicate,unmapped,lowmapq counted on the device;\n"
+             "                  cachehit, fric, estfrip and numcacheslots are written as 0 (the minimizer cache is not modelled)\n");
       exit(0);
     }
-    else die("unsupported option " + o + " (PAF and summary outputs are outside this build)");
+    else die("unsupported option " + o + " (PAF output is outside this build)");
   }
   if (a.p.max_num_best_mappings > a.p.drop_repetitive_reads) {  // chromap_driver.cc:630-641
     fprintf(stderr, "WARNING: you want to drop mapped reads with more than %d mappings. But you want to output top %d best mappings. "
@@ -643,6 +667,8 @@ static Args parse(int argc, char **argv) {
   // reference batches of 500 000 pairs, so that the multi-mappers' sampling is the reference's); beyond 8192 one reference batch has more
   // than 2^32 slots
   if (a.p.max_num_best_mappings > 8192) die("-n above 8192 is outside this build (a 500000-pair batch then needs more than 2^32 record slots)");
+  // (the reference counts MAPPED per mapping there and prints total - mapped as an unsigned number that wraps: nothing to reproduce)
+  if (!a.summary_path.empty() && a.p.max_num_best_mappings > 1) die("--summary with -n > 1 is outside this build");
   if (a.out_sam) {
     if (a.p.max_num_best_mappings > 1) die("--SAM with -n > 1 is outside this build");
     a.p.output_format = CMGPU_FORMAT_SAM;
@@ -799,6 +825,14 @@ int main(int argc, char **argv) {
   // kseq-style parser (the fallback the CMGPU_EFORMAT message names).
   const bool device_ingest = !a.host_ingest && !(a.out_sam && !a.translate_path.empty());
   const bool sam_device = a.out_sam && device_ingest;
+  // --summary: the reads are counted per barcode as each batch is mapped and the duplicate runs where the device resolves them.  SAM
+  // text written by the host writer (--host-ingest, --barcode-translate) has its duplicates resolved on the host: the writer counts
+  // those runs (cmgpu_host_summary_begin / _end)
+  auto enable_summary = [&]() {  // (after the whitelist is in place: it sizes the table)
+    if (a.summary_path.empty()) return;
+    for (cmgpu_ctx *cx : ctxs) if (cmgpu_summary_enable(cx, 1) != CMGPU_OK) die(cmgpu_last_error(cx));
+    fprintf(stderr, "Summary: cachehit, fric, estfrip and numcacheslots are not computed (written as 0).\n");
+  };
   // every stream of every context reads what kseq reads -- wrapped lines, FASTA, stray blank lines (CMGPU_FASTX_FREE; plain four-line
   // text stays on the four-line path, cm_ingest.hip)
   if (device_ingest)
@@ -874,6 +908,7 @@ int main(int argc, char **argv) {
       fprintf(stderr, "Loaded %u barcodes.\nCompute barcode abundance using %llu.\n", nk, (unsigned long long)ns);
       for (size_t gi = 1; gi < ctxs.size(); ++gi) ck(cmgpu_copy_whitelist(ctxs[gi], ctx));
     }
+    enable_summary();
     // Batches are dealt to the contexts in turn; a context maps its batch on its own host thread while the next
     // batch is read and parsed for the next context.  With more than one context a round ends with the record
     // exchange (collective: every context takes part, with an empty batch when the input ran out).
@@ -1096,6 +1131,7 @@ int main(int argc, char **argv) {
       }
       fprintf(stderr, "Loaded %u barcodes.\nCompute barcode abundance using %llu.\n", nk, (unsigned long long)ns);
     }
+    enable_summary();
 
     for (size_t fi = 0; fi < a.r1.size(); ++fi) {
       FastxReader f1, f2, fb;
@@ -1205,6 +1241,7 @@ int main(int argc, char **argv) {
     if (cmgpu_store_write_text(ctx, a.out_path.c_str(), 1) != CMGPU_OK) die(cmgpu_last_error(ctx));
     lines = (long long)nl;
   } else if (a.out_sam) {
+    if (!a.summary_path.empty()) cmgpu_host_summary_begin();
     uint32_t cap = 1;
     for (uint32_t c : sam_md_caps) cap = c > cap ? c : cap;
     std::vector<char> md(sam_rec.size() * (size_t)cap + 1);
@@ -1340,6 +1377,33 @@ int main(int argc, char **argv) {
   }
   if (lines < 0) die("cannot write " + a.out_path);
   fprintf(stderr, "Number of output mappings (passed filters): %lld\n", (long long)lines);
+  if (!a.summary_path.empty()) {
+    // the contexts' tables (a multi-GPU run: reads were counted where they were mapped, runs where their chromosome is owned) as one CSV
+    std::vector<std::vector<cmgpu_summary_entry>> ent(ctxs.size() + 1);
+    std::vector<cmgpu_summary_table> tabs(ctxs.size());
+    for (size_t gi = 0; gi < ctxs.size(); ++gi) {
+      uint64_t nk = 0, got = 0;
+      if (cmgpu_summary_info(ctxs[gi], &nk, nullptr) != CMGPU_OK) die(cmgpu_last_error(ctxs[gi]));
+      ent[gi].resize(nk + 1);
+      if (cmgpu_summary_download(ctxs[gi], ent[gi].data(), nk, &got, &tabs[gi].nonwhitelist_total) != CMGPU_OK) die(cmgpu_last_error(ctxs[gi]));
+      tabs[gi].entries = ent[gi].data();
+      tabs[gi].n_entries = got;
+    }
+    if (a.out_sam && !sam_device) {  // the runs the host SAM writer resolved
+      uint64_t nk = 0;
+      int src = cmgpu_host_summary_end(nullptr, 0, &nk);  // (no room: the number of entries; an empty collector is closed by this call)
+      ent.back().resize(nk + 1);
+      if (src == CMGPU_ECAPACITY) src = cmgpu_host_summary_end(ent.back().data(), nk, &nk);
+      if (src != CMGPU_OK) die("summary: the host writer's counts are missing");
+      cmgpu_summary_table t;
+      t.entries = ent.back().data(); t.n_entries = nk; t.nonwhitelist_total = 0;
+      tabs.push_back(t);
+    }
+    // (single-end runs always have the last column: MapSingleEndReads calls OutputSummaryMetadata with its defaults, chromap.h:630)
+    if (cmgpu_write_summary(tabs.data(), (uint32_t)tabs.size(), barcoded ? bc_len : 0, !a.whitelist.empty() && !a.p.output_mappings_not_in_whitelist,
+                            a.out_sam && paired, a.summary_cache_slots || !paired, a.summary_path.c_str()) != CMGPU_OK)
+      die("cannot write " + a.summary_path);
+  }
   if (device_ingest)
     fprintf(stderr, "Mapped all reads in %.2fs (file read + inflate %.2fs, H2D + device FASTQ parse %.2fs, mapping %.2fs, post-processing + write %.2fs).\n",
             now_s() - t_begin, t_read, t_parse, t_map, t_post);

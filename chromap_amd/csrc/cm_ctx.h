@@ -74,6 +74,15 @@ struct CmSamStore {
   bool has_bc = false, paired = false;
 };
 
+// --summary (cm_summary.hip, cm_summary.h): per-barcode TOTAL / DUP / LOWMAPQ / MAPPED in an open-addressing table of `cap` slots
+struct CmSummary {
+  bool on = false;
+  DevBuf keys, first, cnt, meta;
+  uint32_t cap = 0;
+  uint64_t key_bound = 0;  // the table holds at most this many keys: kept on the host, so that a launch needs no look at the device's count
+  uint32_t slot0 = ~0u;    // slot of key 0 once it was found (~0u: not yet)
+};
+
 // multi-GPU record exchange (cm_exchange.hip): this context's place in a group of `world` contexts, one per GPU
 struct CmExchange {
   int transport = 0;        // 0: none, 1: RCCL (library-owned communicator on the mapping stream), 2: caller-provided callbacks
@@ -187,6 +196,7 @@ struct cmgpu_ctx {
   uint64_t rs_pool_want = 0;   // entries the previous range asked of the pool
   DevBuf coop_slab, hv_cnt, hv_list, perm_reads, perm_pairs, hv_tmp, srt_cnt, srt_list, rs_list, rs_cnt;
   bool use_perm = false;  // the current range has enough heavy reads to process them apart (cm_build_heavy_last)  // reads with long hit lists by size class (k_s3a_count -> k_s3b_heavy)
+  CmSummary sm;
   CmExchange ex;
   bool batch_exchanged = false;  // the resident batch's records have been through cmgpu_exchange_step
   CmBatchSlot slots[CM_BATCH_SLOTS];
@@ -254,6 +264,7 @@ struct cmgpu_ctx {
     for (CmFqStream &f : fq) for (DevBuf *b : {&f.text, &f.cnt, &f.off, &f.nl, &f.keep, &f.pos, &f.recidx, &f.len, &f.bad, &f.text2, &f.comp, &f.btab, &f.toks, &f.ntok, &f.scan_tmp, &f.red_tmp, &f.nm_len, &f.nm_off, &f.st_nm, &f.st_q, &f.fx_li, &f.fx_nxt, &f.fx_send, &f.fx_sl, &f.fx_exit, &f.fx_entry, &f.fx_res}) v.push_back(b);
     for (CmReadMate &m : rd) for (DevBuf *b : {&m.names, &m.name_offs, &m.bases, &m.quals, &m.offs}) v.push_back(b);
     for (DevBuf *b : {&ss.rec, &ss.var, &ss.var_offs, &ss.bc, &ss.vlen, &ss.voff, &ss.scan_tmp, &ss.flags}) v.push_back(b);
+    for (DevBuf *b : {&sm.keys, &sm.first, &sm.cnt, &sm.meta}) v.push_back(b);
     for (DevBuf *b : {&st_rb0, &st_rb1, &st_ro0, &st_ro1, &st_bcb, &st_bcq, &st_bco, &nm_blob, &nm_offs}) v.push_back(b);
     for (CmBatchSlot &sl : slots) for (DevBuf *b : {&sl.rb0, &sl.rb1, &sl.ro0, &sl.ro1}) v.push_back(b);
     return v;

@@ -500,6 +500,25 @@ static int parse_barcode_table(const char *text, uint64_t bytes, CmBarcodeTable 
   return t->from_len ? CMGPU_OK : CMGPU_EINVAL;
 }
 
+// --summary for SAM text written on the host: between cmgpu_host_summary_begin and _end the SAM writers called by this thread credit
+// every run of duplicates they resolve to its barcode (mapping_writer.h:281-301, 420-432), as the device does for its own text
+static thread_local std::unordered_map<uint64_t, cmgpu_summary_entry> *g_host_summary = nullptr;
+extern "C" int cmgpu_host_summary_begin(void) {
+  delete g_host_summary;
+  g_host_summary = new std::unordered_map<uint64_t, cmgpu_summary_entry>();
+  return CMGPU_OK;
+}
+extern "C" int cmgpu_host_summary_end(cmgpu_summary_entry *out, uint64_t capacity, uint64_t *n_out) {
+  if (!g_host_summary || !n_out || (!out && capacity)) return CMGPU_EINVAL;
+  *n_out = g_host_summary->size();
+  if (*n_out > capacity) return CMGPU_ECAPACITY;  // (the collector stays open: call again with room for *n_out entries)
+  uint64_t k = 0;
+  for (const auto &kv : *g_host_summary) out[k++] = kv.second;
+  delete g_host_summary;
+  g_host_summary = nullptr;
+  return CMGPU_OK;
+}
+
 static int64_t write_sam_impl(const char *const *ref_names, const uint32_t *ref_lengths, uint32_t n_sequences, const cmgpu_params *p,
                               const cmgpu_sam_record *rec, uint64_t n_slots, int paired, const uint32_t *cigar_pool,
                               const char *md_pool, uint32_t md_cap, const char *const *names1, const char *const *names2,
@@ -545,6 +564,14 @@ static int64_t write_sam_impl(const char *const *ref_names, const uint32_t *ref_
       }
     }
     const cmgpu_sam_record &r = rec[last];
+    if (g_host_summary && r.rid < n_sequences) {
+      uint32_t d = (uint32_t)(j - i);
+      if (inmem && d > 255) d = 255;  // (num_dups_ is a byte there)
+      cmgpu_summary_entry &e = (*g_host_summary)[bc_of(last)];
+      if (e.mapped == 0 && e.lowmapq == 0) { e.key = bc_of(last); e.first_read_id = ~0ull; e.total = 0; e.dup = 0; }
+      if ((int)r.mapq >= p->mapq_threshold) e.dup += d - 1; else e.lowmapq += d;
+      e.mapped += d;
+    }
     if ((int)r.mapq >= p->mapq_threshold && r.rid < n_sequences) {
       const uint64_t item = paired ? last / 2 : last;
       const bool mate2 = paired && (last & 1);
@@ -650,4 +677,105 @@ extern "C" int64_t cmgpu_write_sam_barcoded_translated(const char *const *ref_na
   if (rc) return rc;
   return write_sam_impl(ref_names, ref_lengths, n_sequences, p, rec, n_slots, paired, cigar_pool, md_pool, md_cap, names1, names2, bases1, quals1,
                         offsets1, bases2, quals2, offsets2, barcode_keys, barcode_length, out_path, &tr);
+}
+
+// ---------------------------------------------------------------------------------------
+// --summary: the CSV of SummaryMetadata::Output (summary_metadata.h:51-128)
+// ---------------------------------------------------------------------------------------
+// The rows come out in the bucket order of the reference's khash map of 64-bit keys (KHASH_MAP_INIT_INT64, summary_metadata.h:35), which
+// met the keys in read order.  This is that map's growth restated for a map that only ever inserts: 4 buckets at the first insertion,
+// doubled whenever the occupied buckets reach 77 % before an insertion; a key goes to the first free bucket of its probe sequence
+// (hash & mask, then +1, +2, +3, ...); a doubling re-inserts bucket by bucket IN PLACE -- a key that lands on a bucket whose old
+// occupant has not moved yet takes the bucket and sends that occupant on (khash.h:246-308).
+namespace {
+struct SmOrder {
+  std::vector<uint64_t> keys;
+  std::vector<uint8_t> used;
+  uint32_t n_buckets = 0, size = 0, upper = 0;
+  static uint32_t hash(uint64_t k) { return (uint32_t)(k >> 33 ^ k ^ k << 11); }
+  void grow() {
+    const uint32_t nb = n_buckets < 4 ? 4 : n_buckets * 2;
+    std::vector<uint8_t> moved_in(nb, 0);  // the new table's "occupied" marks
+    keys.resize(nb);
+    std::vector<uint8_t> waiting(used);    // old occupants that have not moved yet
+    waiting.resize(nb, 0);
+    const uint32_t mask = nb - 1;
+    for (uint32_t j = 0; j < n_buckets; ++j) {
+      if (!waiting[j]) continue;
+      uint64_t key = keys[j];
+      waiting[j] = 0;
+      for (;;) {
+        uint32_t i = hash(key) & mask, step = 0;
+        while (moved_in[i]) i = (i + (++step)) & mask;
+        moved_in[i] = 1;
+        if (i < n_buckets && waiting[i]) { std::swap(keys[i], key); waiting[i] = 0; }
+        else { keys[i] = key; break; }
+      }
+    }
+    used.swap(moved_in);
+    n_buckets = nb;
+    upper = (uint32_t)(nb * 0.77 + 0.5);
+  }
+  void put(uint64_t key) {
+    if (size >= upper) grow();
+    const uint32_t mask = n_buckets - 1;
+    uint32_t i = hash(key) & mask, step = 0;
+    while (used[i]) {
+      if (keys[i] == key) return;
+      i = (i + (++step)) & mask;
+    }
+    keys[i] = key;
+    used[i] = 1;
+    ++size;
+  }
+};
+}  // namespace
+
+extern "C" int cmgpu_write_summary(const cmgpu_summary_table *tables, uint32_t n_tables, uint32_t barcode_length, int nonwhitelist_row,
+                                   int halve_pairs, int num_cache_slots_column, const char *out_path) {
+  if ((!tables && n_tables) || !out_path || barcode_length > 32) return CMGPU_EINVAL;
+  // the contexts' tables as one: counters of equal keys added, the smallest first read id stands
+  std::unordered_map<uint64_t, size_t> at;
+  std::vector<cmgpu_summary_entry> all;
+  uint64_t nonwl = 0;
+  for (uint32_t t = 0; t < n_tables; ++t) {
+    if (!tables[t].entries && tables[t].n_entries) return CMGPU_EINVAL;
+    nonwl += tables[t].nonwhitelist_total;
+    for (uint64_t e = 0; e < tables[t].n_entries; ++e) {
+      const cmgpu_summary_entry &x = tables[t].entries[e];
+      auto it = at.find(x.key);
+      if (it == at.end()) { at.emplace(x.key, all.size()); all.push_back(x); continue; }
+      cmgpu_summary_entry &y = all[it->second];
+      y.total += x.total; y.dup += x.dup; y.lowmapq += x.lowmapq; y.mapped += x.mapped;
+      if (x.first_read_id < y.first_read_id) y.first_read_id = x.first_read_id;
+    }
+  }
+  std::vector<size_t> order(all.size());
+  for (size_t i = 0; i < order.size(); ++i) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+    return std::tie(all[a].first_read_id, all[a].key) < std::tie(all[b].first_read_id, all[b].key);
+  });
+  SmOrder map;
+  for (size_t i : order) map.put(all[i].key);
+  FILE *f = fopen(out_path, "w");
+  if (!f) return CMGPU_EIO;
+  bool ok = fputs(num_cache_slots_column ? "barcode,total,duplicate,unmapped,lowmapq,cachehit,fric,estfrip,numcacheslots\n"
+                                         : "barcode,total,duplicate,unmapped,lowmapq,cachehit,fric,estfrip\n", f) >= 0;
+  // (the reference's counters are ints read into size_t and printed with %ld: total - mapped below zero prints as a negative number)
+  auto row = [&](const char *barcode, long total, long dup, long mapped, long lowmapq) {
+    ok = fprintf(f, "%s,%ld,%ld,%ld,%ld,%ld,%.5lf,%.5lf", barcode, total, dup, total - mapped, lowmapq, 0l, 0.0, 0.0) > 0 && ok;
+    ok = fputs(num_cache_slots_column ? ",0\n" : "\n", f) >= 0 && ok;
+  };
+  char bc[33];
+  for (uint32_t b = 0; b < map.n_buckets; ++b) {
+    if (!map.used[b]) continue;
+    const cmgpu_summary_entry &x = all[at[map.keys[b]]];
+    for (uint32_t i = 0; i < barcode_length; ++i) bc[i] = "ACGT"[(x.key >> ((barcode_length - 1 - i) * 2)) & 3];  // Seed2Sequence
+    bc[barcode_length] = 0;
+    const int div = halve_pairs ? 2 : 1;
+    row(bc, (long)x.total, (long)((int)x.dup / div), (long)((int)x.mapped / div), (long)((int)x.lowmapq / div));
+  }
+  if (nonwhitelist_row) row("non-whitelist", (long)nonwl, 0, 0, 0);
+  ok = fclose(f) == 0 && ok;
+  return ok ? CMGPU_OK : CMGPU_EIO;
 }

@@ -28,6 +28,7 @@
 
 #include "cm_ctx.h"
 #include "cm_kernels.h"
+#include "cm_summary.h"
 
 #define PP_RUN_SERIAL 128u  // records of a duplicate run its head walks alone (k_pp_select); longer runs: k_pp_select_long
 #define PP_BLOCK 256
@@ -145,6 +146,13 @@ __device__ __forceinline__ uint32_t pp_abundance(const PpCfg &cfg, uint64_t key)
   }
 }
 
+// --summary: a resolved run of `dups` records whose survivor (barcode bcv) has MAPQ `mapq` (mapping_writer.h:281-301; the in-memory
+// writer counts the survivor's num_dups_, capped at 255, :420-432)
+__device__ __forceinline__ void pp_sm_run(const CmSmDev &sm, const PpCfg &cfg, uint64_t bcv, uint32_t dups, uint32_t mapq) {
+  if (cfg.inmem && dups > 255) dups = 255;
+  cm_sm_credit(sm, !pp_has_bc(cfg.kind), bcv, dups, (int)mapq >= cfg.mapq_thr);
+}
+
 // the survivor of sorted position j: MAPQ filter, Tn5 shift, line length; win / dups / line_len of the position
 __device__ __forceinline__ void pp_finish(uint32_t j, PpRec r, uint32_t wi, uint32_t dups, bool bulk_done, const PpCfg &cfg,
                                           const uint32_t *__restrict__ name_off, uint32_t *__restrict__ win,
@@ -176,7 +184,7 @@ __global__ __launch_bounds__(PP_BLOCK) void k_pp_select(const uint8_t *__restric
                                                           const uint32_t *__restrict__ idx, uint32_t n, PpCfg cfg,
                                                           const uint32_t *__restrict__ name_off, uint32_t *__restrict__ win,
                                                           uint32_t *__restrict__ dups_out, uint64_t *__restrict__ line_len,
-                                                          uint32_t *__restrict__ long_list, uint32_t *__restrict__ long_cnt) {
+                                                          uint32_t *__restrict__ long_list, uint32_t *__restrict__ long_cnt, CmSmDev sm) {
   const uint32_t j = blockIdx.x * PP_BLOCK + threadIdx.x;
   if (j >= n) return;
   uint32_t wi = idx[j];
@@ -231,6 +239,14 @@ __global__ __launch_bounds__(PP_BLOCK) void k_pp_select(const uint8_t *__restric
     r = pp_load(store, wi);
     // the very last run of the output is filtered on the run's maximal MAPQ (mapping_writer.h:331-337)
     const uint32_t filter_mapq = t == n && cfg.last_section ? maxq_mapq : (uint32_t)r.mapq;
+    // (the output's last run is tested before the best barcode group is chosen, mapping_writer.h:323-350: when it fails, the counts go
+    //  to the record the merge held then -- the first one of the run's largest MAPQ)
+    if (sm.keys && r.rid < cfg.n_seq) {
+      uint32_t ci = wi;
+      if ((int)filter_mapq < cfg.mapq_thr && t == n && cfg.last_section)
+        for (uint32_t u = j; u < t; ++u) { ci = idx[u]; if (pp_load(store, ci).mapq == maxq_mapq) break; }
+      pp_sm_run(sm, cfg, bc[ci], dups, filter_mapq);
+    }
     if ((int)filter_mapq < cfg.mapq_thr) { line_len[j] = 0; return; }
     bulk_done = true;
   } else
@@ -257,6 +273,7 @@ __global__ __launch_bounds__(PP_BLOCK) void k_pp_select(const uint8_t *__restric
       return;
     }
   }
+  if (sm.keys && !bulk_done && r.rid < cfg.n_seq) pp_sm_run(sm, cfg, pp_has_bc(cfg.kind) ? bc[wi] : 0, dups, r.mapq);
   pp_finish(j, r, wi, dups, bulk_done, cfg, name_off, win, dups_out, line_len);
 }
 
@@ -268,7 +285,7 @@ __global__ __launch_bounds__(64) void k_pp_select_long(const uint8_t *__restrict
                                                        const uint32_t *__restrict__ idx, uint32_t n, PpCfg cfg,
                                                        const uint32_t *__restrict__ name_off, uint32_t *__restrict__ win,
                                                        uint32_t *__restrict__ dups_out, uint64_t *__restrict__ line_len,
-                                                       const uint32_t *__restrict__ long_list, const uint32_t *__restrict__ long_cnt) {
+                                                       const uint32_t *__restrict__ long_list, const uint32_t *__restrict__ long_cnt, CmSmDev sm) {
   const uint32_t lane = threadIdx.x, cnt = *long_cnt;
   for (uint32_t e = blockIdx.x; e < cnt; e += gridDim.x) {
     const uint32_t j = long_list[e];
@@ -341,6 +358,12 @@ __global__ __launch_bounds__(64) void k_pp_select_long(const uint8_t *__restrict
         const uint32_t wi = idx[best_pos];
         const PpRec r = pp_load(store, wi);
         const uint32_t filter_mapq = run_end == n && cfg.last_section ? maxq : (uint32_t)r.mapq;
+        if (sm.keys && r.rid < cfg.n_seq) {
+          uint32_t ci = wi;
+          if ((int)filter_mapq < cfg.mapq_thr && run_end == n && cfg.last_section)  // (k_pp_select: the first record of the run's largest MAPQ)
+            for (uint32_t t = j; t < run_end; ++t) { ci = idx[t]; if (pp_load(store, ci).mapq == maxq) break; }
+          pp_sm_run(sm, cfg, bc[ci], run_end - j, filter_mapq);
+        }
         if ((int)filter_mapq < cfg.mapq_thr) line_len[j] = 0;
         else pp_finish(j, r, wi, run_end - j, true, cfg, name_off, win, dups_out, line_len);
       }
@@ -378,6 +401,7 @@ __global__ __launch_bounds__(64) void k_pp_select_long(const uint8_t *__restrict
       uint32_t wi = wi0;
       if (cfg.inmem) { wi = idx[run_end - 1]; r = pp_load(store, wi); }
       else if (my_mapq > (int)r0.mapq) { wi = idx[my_pos]; r = pp_load(store, wi); }
+      if (sm.keys && r.rid < cfg.n_seq) pp_sm_run(sm, cfg, pp_has_bc(cfg.kind) ? bc[wi] : 0, run_end - j, r.mapq);
       pp_finish(j, r, wi, run_end - j, false, cfg, name_off, win, dups_out, line_len);
     }
   }
@@ -689,10 +713,15 @@ extern "C" int cmgpu_store_format(cmgpu_ctx *c, int kind, const char *const *nam
   if (longs.ensure(((size_t)n / PP_RUN_SERIAL + 2) * 4)) { cm_set_error(c, "out of device memory (post-processing)"); return fail(CMGPU_ENOMEM); }
   uint32_t *long_cnt = (uint32_t *)longs.p, *long_list = long_cnt + 1;
   if (hipMemsetAsync(long_cnt, 0, 4, s) != hipSuccess) { cm_set_error(c, "memset failed"); return fail(CMGPU_EHIP); }
+  // --summary: the selection credits every run to its survivor's barcode.  The keys are in the table since their reads were counted;
+  // a store filled by the multi-GPU exchange also holds records of reads another context counted
+  CmSmDev sm;
+  if ((rc = cm_summary_dev(c, c->ex.transport ? n : 0, pp_has_bc(kind) && c->wl_size && !p->output_mappings_not_in_whitelist ? c->wl_size : 0,
+                           !pp_has_bc(kind), &sm))) return fail(rc);
   hipLaunchKernelGGL(k_pp_select, g, b, 0, s, store, bc, (const uint32_t *)va, n, cfg, (const uint32_t *)d_noff.p, (uint32_t *)win.p,
-                     (uint32_t *)dups.p, (uint64_t *)llen.p, long_list, long_cnt);
+                     (uint32_t *)dups.p, (uint64_t *)llen.p, long_list, long_cnt, sm);
   hipLaunchKernelGGL(k_pp_select_long, dim3(1024), dim3(64), 0, s, store, bc, (const uint32_t *)va, n, cfg, (const uint32_t *)d_noff.p,
-                     (uint32_t *)win.p, (uint32_t *)dups.p, (uint64_t *)llen.p, (const uint32_t *)long_list, (const uint32_t *)long_cnt);
+                     (uint32_t *)win.p, (uint32_t *)dups.p, (uint64_t *)llen.p, (const uint32_t *)long_list, (const uint32_t *)long_cnt, sm);
   if (hipMemsetAsync((uint64_t *)llen.p + n, 0, 8, s) != hipSuccess) { cm_set_error(c, "memset failed"); return fail(CMGPU_EHIP); }
   size_t tb = 0, tb2 = 0;
   (void)rocprim::exclusive_scan(nullptr, tb, (const uint64_t *)llen.p, (uint64_t *)loff.p, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s);
@@ -708,6 +737,7 @@ extern "C" int cmgpu_store_format(cmgpu_ctx *c, int kind, const char *const *nam
   if (e == hipSuccess) e = cm_stream_sync(s);
   d_count.release();
   if (e != hipSuccess) { cm_set_error(c, std::string("post-processing scan: ") + hipGetErrorString(e)); return fail(CMGPU_EHIP); }
+  if ((rc = cm_summary_check(c))) return fail(rc);
   if (c->text.ensure(total + 64)) { cm_set_error(c, "out of device memory (text)"); return fail(CMGPU_ENOMEM); }
   // ---- format
   hipLaunchKernelGGL(k_pp_format, g, b, 0, s, store, bc, (const uint32_t *)win.p, (const uint32_t *)dups.p, (const uint64_t *)llen.p,
@@ -749,11 +779,26 @@ __global__ __launch_bounds__(PP_BLOCK) void k_pp_pairs_key(const uint8_t *__rest
 }
 __global__ __launch_bounds__(PP_BLOCK) void k_pp_pairs_len(const uint8_t *__restrict__ store, const uint32_t *__restrict__ idx, uint32_t n, int mapq_thr,
                                                              uint32_t n_seq, const uint32_t *__restrict__ name_off, const uint64_t *__restrict__ rn_off,
-                                                             uint32_t rn_base, uint32_t rn_count, uint64_t *__restrict__ line_len, int dedup) {
+                                                             uint32_t rn_base, uint32_t rn_count, uint64_t *__restrict__ line_len, int dedup, CmSmDev sm) {
   const uint32_t j = blockIdx.x * PP_BLOCK + threadIdx.x;
   if (j >= n) return;
   const PpPairs r = pp_load_pairs(store, idx[j]);
   const uint32_t q = r.read_id - rn_base;
+  if (sm.keys && r.rid1 < n_seq && r.rid2 < n_seq && q < rn_count) {
+    // --summary: the first record of a run (every record without duplicate removal) counts the run; its last record has the run's largest
+    // MAPQ, which is the survivor's under either rule.  A PairsMapping has no barcode (GetBarcode() == 0): everything counts under key 0
+    auto same_run = [&](const PpPairs &x) { return x.rid1 == r.rid1 && x.pos1 == r.pos1 && x.rid2 == r.rid2 && x.pos2 == r.pos2; };
+    if (!dedup || j == 0 || !same_run(pp_load_pairs(store, idx[j - 1]))) {
+      uint32_t d = 1, mq = r.mapq;
+      for (uint32_t t = j + 1; dedup && t < n; ++t, ++d) {
+        const PpPairs nx = pp_load_pairs(store, idx[t]);
+        if (!same_run(nx)) break;
+        mq = nx.mapq;
+      }
+      if (dedup == 2 && d > 255) d = 255;
+      cm_sm_credit(sm, true, 0, d, (int)mq >= mapq_thr);
+    }
+  }
   if ((int)r.mapq < mapq_thr || r.rid1 >= n_seq || r.rid2 >= n_seq || q >= rn_count) { line_len[j] = 0; return; }
   // --remove-pcr-duplicates: one record per run of PairsMapping::operator== (rid1, pos1, rid2, pos2; pairs_mapping.h:45-50).  The records
   // stand in operator< order, i.e. inside a run by (mapq, read_id).  dedup == 1, the low-memory merge (mapping_writer.h:244-270): the
@@ -864,9 +909,11 @@ static int pp_format_pairs(cmgpu_ctx *c, const char *const *names, uint32_t n_se
   hipLaunchKernelGGL(k_pp_pairs_key, g, b, 0, s, store, (const uint32_t *)va, n, 2, rid_bits, ka, (uint32_t *)nullptr);
   if ((rc = pp_sort_pass(c, tmp, ka, kb, va, vb, n, 2 * rid_bits))) return fail(rc);
   std::swap(va, vb);
+  CmSmDev sm;
+  if ((rc = cm_summary_dev(c, 0, 0, true, &sm))) return fail(rc);
   hipLaunchKernelGGL(k_pp_pairs_len, g, b, 0, s, store, (const uint32_t *)va, n, p->mapq_threshold, n_sequences, (const uint32_t *)d_noff.p,
                      rn_off, read_id_base, n_read_names, (uint64_t *)llen.p,
-                     p->remove_pcr_duplicates ? (p->low_memory_mode ? 1 : 2) : 0);
+                     p->remove_pcr_duplicates ? (p->low_memory_mode ? 1 : 2) : 0, sm);
   if (hipMemsetAsync((uint64_t *)llen.p + n, 0, 8, s) != hipSuccess) { cm_set_error(c, "memset failed"); return fail(CMGPU_EHIP); }
   size_t tb = 0, tb2 = 0;
   auto lines_in = rocprim::make_transform_iterator((const uint64_t *)llen.p, PpLinesOp());
@@ -882,6 +929,7 @@ static int pp_format_pairs(cmgpu_ctx *c, const char *const *names, uint32_t n_se
   if (e == hipSuccess) e = cm_stream_sync(s);
   d_count.release();
   if (e != hipSuccess) { cm_set_error(c, std::string("post-processing scan: ") + hipGetErrorString(e)); return fail(CMGPU_EHIP); }
+  if ((rc = cm_summary_check(c))) return fail(rc);
   if (c->text.ensure(total + 64)) { cm_set_error(c, "out of device memory (text)"); return fail(CMGPU_ENOMEM); }
   hipLaunchKernelGGL(k_pp_pairs_format, g, b, 0, s, store, (const uint32_t *)va, n, (const uint64_t *)llen.p, (const uint64_t *)loff.p,
                      (const uint8_t *)d_names.p, (const uint32_t *)d_noff.p, rn, rn_off, read_id_base, (uint8_t *)c->text.p);

@@ -21,6 +21,7 @@
 
 #include "cm_ctx.h"
 #include "cm_kernels.h"
+#include "cm_summary.h"
 
 #define SP_BLOCK 256
 #define SPCHECK(ctx, call)                                                                   \
@@ -226,7 +227,7 @@ __device__ __forceinline__ uint32_t sp_seq_len(const SpRec &r, const uint32_t *_
 __global__ __launch_bounds__(SP_BLOCK) void k_sp_len(const uint8_t *__restrict__ rec, const uint64_t *__restrict__ bc, const uint8_t *__restrict__ var,
                                                        const uint64_t *__restrict__ var_offs, const uint32_t *__restrict__ idx, uint32_t n, SpCfg cfg,
                                                        SpReads rs, const uint32_t *__restrict__ name_off, uint64_t *__restrict__ line_len,
-                                                       unsigned long long *__restrict__ n_foreign) {
+                                                       unsigned long long *__restrict__ n_foreign, CmSmDev sm) {
   const uint32_t j = blockIdx.x * SP_BLOCK + threadIdx.x;
   if (j >= n) return;
   const uint32_t i = idx[j];
@@ -235,6 +236,25 @@ __global__ __launch_bounds__(SP_BLOCK) void k_sp_len(const uint8_t *__restrict__
   // a record whose read is not in the read store, or whose mate lies on a sequence the reference does not have: the stores are not of one
   // run -- counted, and the call fails (no line is written for it: the kernels never index past a store)
   if (q >= cfg.n_reads || (r.mrid >= 0 && (uint32_t)r.mrid >= cfg.n_seq)) { atomicAdd(n_foreign, 1ull); line_len[j] = 0; return; }
+  if (sm.keys && r.rid < cfg.n_seq) {
+    // --summary (mapping_writer.h:281-301, 420-432): the first record of an operator== run (every record without duplicate removal) counts
+    // the run under its barcode; the run's last record has its largest MAPQ, the survivor's under either rule.  Both mates of a pair are
+    // records here: the writer halves these counts for paired-end data (SummaryMetadata::AdjustPairedEndOverCount)
+    const uint64_t b = bc ? bc[i] : 0;
+    bool head = !cfg.dedup || j == 0;
+    if (!head) { const uint32_t i0 = idx[j - 1]; head = !sp_same_run(sp_load(rec, i0), bc ? bc[i0] : 0, r, b); }
+    if (head) {
+      uint32_t d = 1, mq = r.mapq;
+      for (uint32_t t = j + 1; cfg.dedup && t < n; ++t, ++d) {
+        const uint32_t i2 = idx[t];
+        const SpRec nx = sp_load(rec, i2);
+        if (!sp_same_run(nx, bc ? bc[i2] : 0, r, b)) break;
+        mq = nx.mapq;
+      }
+      if (cfg.dedup == 2 && d > 255) d = 255;
+      cm_sm_credit(sm, bc == nullptr, b, d, (int)mq >= cfg.mapq_thr);
+    }
+  }
   if ((int)r.mapq < cfg.mapq_thr || r.rid >= cfg.n_seq) { line_len[j] = 0; return; }
   // --remove-pcr-duplicates: one survivor per run of operator==; the records stand in operator< order, inside a run by (mapq, read_id).
   // The filter above is the survivor's: it has the run's largest MAPQ under either rule, and rid / mrid are the run's.
@@ -441,8 +461,10 @@ extern "C" int cmgpu_store_format_sam(cmgpu_ctx *c, const char *const *ref_names
     rs.name_offs[m] = (const uint64_t *)r.name_offs.p; rs.offs[m] = (const uint64_t *)r.offs.p;
   }
   if (hipMemsetAsync(d_count.p, 0, 16, s) != hipSuccess) { cm_set_error(c, "memset failed"); return fail(CMGPU_EHIP); }
+  CmSmDev sm;  // --summary: the length kernel credits every run to its barcode (the keys are in the table since their reads were counted)
+  { const int rc = cm_summary_dev(c, 0, 0, !st.has_bc, &sm); if (rc) return fail(rc); }
   hipLaunchKernelGGL(k_sp_len, g, b, 0, s, rec, bc, (const uint8_t *)st.var.p, (const uint64_t *)st.var_offs.p, (const uint32_t *)va, n, cfg, rs,
-                     (const uint32_t *)d_noff.p, (uint64_t *)llen.p, (unsigned long long *)d_count.p + 1);
+                     (const uint32_t *)d_noff.p, (uint64_t *)llen.p, (unsigned long long *)d_count.p + 1, sm);
   if (hipMemsetAsync((uint64_t *)llen.p + n, 0, 8, s) != hipSuccess) { cm_set_error(c, "memset failed"); return fail(CMGPU_EHIP); }
   size_t tb = 0, tb2 = 0;
   auto lines_in = rocprim::make_transform_iterator((const uint64_t *)llen.p, SpLinesOp());
@@ -457,6 +479,7 @@ extern "C" int cmgpu_store_format_sam(cmgpu_ctx *c, const char *const *ref_names
   if (e == hipSuccess) e = hipMemcpyAsync(&foreign, (uint64_t *)d_count.p + 1, 8, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = cm_stream_sync(s);
   if (e != hipSuccess) { cm_set_error(c, std::string("post-processing scan: ") + hipGetErrorString(e)); return fail(CMGPU_EHIP); }
+  { const int rc = cm_summary_check(c); if (rc) return fail(rc); }
   if (foreign) {
     cm_set_error(c, std::to_string((unsigned long long)foreign) + " SAM records belong to no read of the read store (reads " + std::to_string(c->rd_base) + " .. " +
                         std::to_string((unsigned long long)c->rd_base + c->rd_n) + ") or to a mate sequence the reference does not have: the record store and the read store are not of one run");

@@ -630,6 +630,34 @@ class ChromapGPU:
     def store_write_text(self, path, append=False):
         self._check(self.L.cmgpu_store_write_text(self.ctx, path.encode(), int(append)), self.ctx)
 
+    # ---- --summary: per-barcode TOTAL / DUP / LOWMAPQ / MAPPED counted on the device (include/chromap_amd.h)
+    def summary_enable(self, on=True):
+        """from now on every map_* call counts its reads per barcode and every store_format* call credits the duplicate runs;
+        call it after set_whitelist_file"""
+        self._check(self.L.cmgpu_summary_enable(self.ctx, int(on)), self.ctx)
+
+    def summary_clear(self):
+        self._check(self.L.cmgpu_summary_clear(self.ctx), self.ctx)
+
+    def summary_info(self):
+        """(keys in the table, slots of the table)"""
+        n, s = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.cmgpu_summary_info(self.ctx, C.byref(n), C.byref(s)), self.ctx)
+        return n.value, s.value
+
+    def summary_table(self):
+        """([(key, first_read_id, total, dup, lowmapq, mapped), ...] in no particular order, TOTAL of the non-whitelist row)"""
+        n, _ = self.summary_info()
+        arr = (_capi.SummaryEntry * max(1, n))()
+        k, nonwl = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.cmgpu_summary_download(self.ctx, arr, n, C.byref(k), C.byref(nonwl)), self.ctx)
+        return [(e.key, e.first_read_id, e.total, e.dup, e.lowmapq, e.mapped) for e in arr[:k.value]], nonwl.value
+
+    def write_summary(self, path, barcode_length=0, nonwhitelist_row=False, halve_pairs=False, num_cache_slots_column=True, others=()):
+        """the --summary CSV of this context's table (and those of `others`, the further contexts of a multi-GPU run)"""
+        tables = [self.summary_table()] + [g.summary_table() for g in others]
+        _capi.write_summary(tables, path, barcode_length, nonwhitelist_row, halve_pairs, num_cache_slots_column)
+
     def write_bed(self, rec, n, path, params=None):
         p = params if params is not None else self.params
         names = (C.c_char_p * len(self.names))(*self.names)

@@ -615,6 +615,54 @@ int cmgpu_download_reads(cmgpu_ctx *ctx, int mate, char *names, uint64_t names_c
  * file in whole reference batches and stop when *done is set (20 M sampled, src/chromap.h:211). */
 int cmgpu_barcode_abundance_resident(cmgpu_ctx *ctx, uint64_t *num_sample_barcodes, int *done);
 
+/* ---- --summary: per-barcode mapping statistics ------------------------------------------------
+ * Replaces SummaryMetadata (src/summary_metadata.h) and the places that feed it: TOTAL per read batch (src/chromap.h:495-515,
+ * 1190-1230) and DUP / LOWMAPQ / MAPPED where duplicates are resolved (src/mapping_writer.h:281-350, 405-437).  The counters live in
+ * an open-addressing table in HBM, keyed by the 2-bit packed (corrected) barcode; bulk data counts under key 0.
+ *   cmgpu_summary_enable    on != 0: from now on every cmgpu_map_resident (and so every cmgpu_map_* call) counts the batch's reads under
+ *                           their barcodes after correction -- a read whose barcode is not on the whitelist goes to the non-whitelist
+ *                           counter instead, unless output_mappings_not_in_whitelist -- and cmgpu_store_format / _format_pairs* /
+ *                           _format_sam credit every run of duplicates to its survivor's barcode: a run of d records whose survivor has
+ *                           MAPQ >= mapq_threshold adds d - 1 to dup, otherwise d to lowmapq; d to mapped either way.  d is the run
+ *                           length in low_memory_mode, min(255, run length) otherwise (num_dups_); without remove_pcr_duplicates every
+ *                           record is a run.  Each format call adds its store's runs once more: format once per run, or clear.
+ *                           Call it after cmgpu_set_whitelist / cmgpu_copy_whitelist (the table is sized from the whitelist; it
+ *                           grows by rehash when there is none).  Barcodes of 32 bases: CMGPU_EINVAL at the first batch.  A context
+ *                           without it launches exactly the kernels it launched before.
+ *   cmgpu_summary_clear     all counters and keys back to empty (a new run)
+ *   cmgpu_summary_download  the table's entries in no particular order; first_read_id = the smallest read id counted under the key
+ *                           (first_read_id of the batch + index; all ones: the key got records only, from another context of a
+ *                           multi-GPU run).  capacity < entries: CMGPU_ECAPACITY with *n_out = the number needed
+ *   cmgpu_write_summary     host: the CSV of SummaryMetadata::Output (src/summary_metadata.h:98-128) from the tables of one or more
+ *                           contexts (a multi-GPU run: counters of equal keys are added, the smallest first_read_id stands).  Rows come
+ *                           in the iteration order of the reference's khash map, which received the keys in first_read_id order;
+ *                           halve_pairs != 0 (paired-end --SAM): dup, lowmapq and mapped are halved per barcode
+ *                           (AdjustPairedEndOverCount); nonwhitelist_row != 0 (a whitelist was given and unlisted reads are not
+ *                           mapped): the "non-whitelist" row ends the file; num_cache_slots_column == 0:
+ *                           --turn-off-num-uniq-cache-slots.  barcode_length 0: bulk data, the barcode column is empty.  The
+ *                           reference's minimizer cache is not modelled: cachehit and numcacheslots are 0, fric and estfrip 0.00000. */
+typedef struct cmgpu_summary_entry {
+  uint64_t key;
+  uint64_t first_read_id;
+  uint32_t total, dup, lowmapq, mapped;
+} cmgpu_summary_entry;
+typedef struct cmgpu_summary_table {
+  const cmgpu_summary_entry *entries;
+  uint64_t n_entries;
+  uint64_t nonwhitelist_total;
+} cmgpu_summary_table;
+int cmgpu_summary_enable(cmgpu_ctx *ctx, int on);
+int cmgpu_summary_clear(cmgpu_ctx *ctx);
+int cmgpu_summary_info(cmgpu_ctx *ctx, uint64_t *n_keys, uint64_t *n_slots);
+int cmgpu_summary_download(cmgpu_ctx *ctx, cmgpu_summary_entry *out, uint64_t capacity, uint64_t *n_out, uint64_t *nonwhitelist_total);
+/* SAM text written on the host (cmgpu_write_sam*): between _begin and _end the writers called by this thread credit the runs they resolve;
+ * _end hands the entries over (total 0, first_read_id all ones) as one more table for cmgpu_write_summary, next to the context's, which
+ * holds the reads' TOTAL.  capacity too small: CMGPU_ECAPACITY with *n_out = the number needed, and the collector stays open. */
+int cmgpu_host_summary_begin(void);
+int cmgpu_host_summary_end(cmgpu_summary_entry *out, uint64_t capacity, uint64_t *n_out);
+int cmgpu_write_summary(const cmgpu_summary_table *tables, uint32_t n_tables, uint32_t barcode_length, int nonwhitelist_row,
+                        int halve_pairs, int num_cache_slots_column, const char *out_path);
+
 /* Host post-processing that defines the final BED bytes: sort by (rid, operator<),
  * PCR-duplicate removal as in the low-memory merge, MAPQ filter, Tn5 shift, text
  * formatting (src/mapping_writer.h:166-376, src/mapping_writer.cc:72-83). Sorts `records`

@@ -7,6 +7,9 @@ from files to a pairs file, through the device ingest (read names kept in HBM) a
 every pairs run took before), plain FASTQ and -- with --gz -- BGZF, `--reps` runs each; the pairs files must be identical.
 `--sam`: 2 x 150 ordinary pairs, `chromap-amd --preset chip --SAM` from files to a SAM file through the device ingest (whole reads and
 alignment records kept in HBM, text rendered there) and through the host parser and writer (`--host-ingest`), timed like the hic routes.
+`--barcodes N`: a single-cell job -- a whitelist of N random 16-mers, every pair draws one, 10 % of them with one substitution (the
+generator of tools/ref_baseline.py); `--summary` then times the same job without and with `--summary FILE`, `--reps` runs each, and
+`--baseline-cli` the build of an earlier commit on the same files (without `--summary`).
 Prints one JSON object; everything is written under --dir (default /tmp/chromap_amd_e2e)."""
 import argparse
 import ctypes as C
@@ -35,6 +38,31 @@ def write_fastq(path, bases, n, L):
     rec.tofile(path)
 
 
+def write_barcodes(d, n_all, n_wl, seed=1000):
+    """whitelist.txt and bc.fq under d; returns the CLI's arguments for them"""
+    rng = np.random.default_rng(seed)
+    wl = np.unique(rng.integers(0, 1 << 32, size=n_wl, dtype=np.uint64))  # 16-mers as 32-bit codes
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    shifts = (2 * np.arange(15, -1, -1)).astype(np.uint64)
+
+    def letters(codes):
+        return acgt[((codes[:, None] >> shifts[None, :]) & np.uint64(3)).astype(np.int64)]
+    wl_path, bc_path = os.path.join(d, "whitelist.txt"), os.path.join(d, "bc.fq")
+    with open(wl_path, "wb") as f:
+        f.write(b"\n".join(bytes(x) for x in letters(wl)) + b"\n")
+    seq = letters(wl[rng.integers(0, len(wl), size=n_all)])
+    rows = np.nonzero(rng.random(n_all) < 0.10)[0]
+    seq[rows, rng.integers(0, 16, size=len(rows))] = acgt[rng.integers(0, 4, size=len(rows))]
+    rec = np.empty((n_all, 39), np.uint8)  # "@b\n" + 16 + "\n+\n" + 16 x 'I' + "\n"
+    rec[:, 0:3] = np.frombuffer(b"@b\n", np.uint8)
+    rec[:, 3:19] = seq
+    rec[:, 19:22] = np.frombuffer(b"\n+\n", np.uint8)
+    rec[:, 22:38] = ord("I")
+    rec[:, 38] = ord("\n")
+    rec.tofile(bc_path)
+    return ["-b", bc_path, "--barcode-whitelist", wl_path]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--genome", type=int, default=200_000_000)
@@ -47,6 +75,8 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--baseline-cli", default="", help="--preset hic: also time this other chromap-amd binary (a build of an earlier commit) on the same files")
     ap.add_argument("--sam", action="store_true", help="time --preset chip --SAM through the device route and the host route (and --baseline-cli)")
+    ap.add_argument("--barcodes", type=int, default=0, help="--preset atac: a single-cell job with a whitelist of this many 16-mers (scATAC: 737280)")
+    ap.add_argument("--summary", action="store_true", help="--preset atac: also time the job with --summary FILE (and --baseline-cli without it)")
     ap.add_argument("--skip-host-ingest", action="store_true", help="a long job: leave the host parser's run out")
     args = ap.parse_args()
     os.makedirs(args.dir, exist_ok=True)
@@ -86,6 +116,7 @@ def main():
     fmt = ["--SAM"] if args.sam else []
     cli = os.path.join(ROOT, "chromap_amd", "chromap-amd")
     res = {}
+    job = write_barcodes(args.dir, args.pairs, args.barcodes) if args.barcodes else []
 
     def run(label, f1, f2, extra=(), reps=args.reps, cli=cli):
         """the CLI `reps` times; the run with the shortest 'Mapped all reads' time is the one reported"""
@@ -100,7 +131,7 @@ def main():
                 os.remove(out)
             os.sync()
             t0 = time.time()
-            p = subprocess.run([cli, "--preset", args.preset, "-x", idx, "-r", fa, "-1", f1, "-2", f2, "-o", out] + fmt + list(extra), stderr=subprocess.PIPE, check=True)
+            p = subprocess.run([cli, "--preset", args.preset, "-x", idx, "-r", fa, "-1", f1, "-2", f2, "-o", out] + fmt + job + list(extra), stderr=subprocess.PIPE, check=True)
             dt = time.time() - t0
             tail = [ln for ln in p.stderr.decode().splitlines() if ln.startswith("Mapped all reads") or ln.startswith("Sorted,")]
             mapped = [float(ln.split("in ")[1].split("s")[0]) for ln in tail if ln.startswith("Mapped all reads")]
@@ -119,6 +150,14 @@ def main():
         res[label] = best
 
     run("device_ingest", r1, r2)
+    if args.summary and not two_routes:
+        sm = os.path.join(args.dir, "out.summary.csv")
+        run("device_ingest_summary", r1, r2, ["--summary", sm])
+        res["device_ingest_summary"]["summary_rows"] = sum(1 for _ in open(sm)) - 1
+        res["summary_leaves_bed_unchanged"] = res["device_ingest_summary"]["bed_md5"] == res["device_ingest"]["bed_md5"]
+    if args.baseline_cli and not two_routes:
+        run("baseline_cli", r1, r2, cli=args.baseline_cli)
+        res["baseline_same_output"] = res["baseline_cli"]["bed_md5"] == res["device_ingest"]["bed_md5"]
     if two_routes:
         # the two routes of a pairs / SAM run, whole-process wall time: the requirement is slowest(device) < fastest(host) for each input kind
         # (--skip-host-ingest with --baseline-cli: the baseline build stands for the host route, the only one it has)
@@ -172,7 +211,7 @@ def main():
         run("device_ingest_bgzf_256MB_pieces", r1 + ".bgz", r2 + ".bgz", ["--ingest-chunk-mb", "256"])
         res["bgzf_same_output"] = res["device_ingest_bgzf"]["bed_md5"] == res["device_ingest"]["bed_md5"]
     res["same_output"] = res["device_ingest"]["bed_md5"] == res["host_ingest"]["bed_md5"] if "host_ingest" in res else None
-    res["config"] = {"pairs": args.pairs, "readlen": args.readlen, "genome": args.genome,
+    res["config"] = {"pairs": args.pairs, "readlen": args.readlen, "genome": args.genome, "barcodes": args.barcodes, "reps": args.reps,
                      "fastq_bytes": os.path.getsize(r1) + os.path.getsize(r2), "index_bytes": os.path.getsize(idx),
                      "hardware_threads": os.cpu_count(), "cpu_budget": cpu_budget()}
     print(json.dumps(res))

@@ -39,6 +39,8 @@ def main():
     ap.add_argument("--barcodes", type=int, default=0, help="single-cell run: a whitelist of this many random 16-mers, every pair draws one, "
                                                             "10 %% of them with one substitution (BASELINE config 4: 737280)")
     ap.add_argument("--bgzf-check", action="store_true", help="also run chromap-amd on BGZF-compressed copies of the read files: same output")
+    ap.add_argument("--summary", action="store_true", help="both runs also write --summary: barcodes, row order and the first five columns are compared "
+                                                            "(the four cache columns are the reference's cache's, which chromap-amd does not model)")
     ap.add_argument("--hic", type=float, default=-1.0, help="Hi-C shaped pairs with this fraction of chimeric reads (default: fragments)")
     args = ap.parse_args()
     if args.threads <= 0:
@@ -127,10 +129,15 @@ def main():
     n_pairs = args.pairs * args.batches
     res = {"setup_s": round(t_setup, 1), "pairs": n_pairs, "threads": args.threads,
            "index_bytes": os.path.getsize(idx), "fastq_bytes": os.path.getsize(r1) + os.path.getsize(r2)}
+    sum_ref, sum_gpu = os.path.join(args.dir, "ref.summary.csv"), os.path.join(args.dir, "gpu.summary.csv")
     # ---- the reference
+    if args.summary:
+        extra_ref, extra_gpu = extra + ["--summary", sum_ref], extra + ["--summary", sum_gpu]
+    else:
+        extra_ref = extra_gpu = extra
     out_ref = os.path.join(args.dir, "ref.out")
     t0 = time.time()
-    p = subprocess.run([ref_bin, "--preset", args.preset, "-x", idx, "-r", fa, "-1", r1, "-2", r2, "-o", out_ref, "-t", str(args.threads)] + extra,
+    p = subprocess.run([ref_bin, "--preset", args.preset, "-x", idx, "-r", fa, "-1", r1, "-2", r2, "-o", out_ref, "-t", str(args.threads)] + extra_ref,
                        stderr=subprocess.PIPE)
     wall = time.time() - t0
     log = p.stderr.decode(errors="replace")
@@ -149,7 +156,7 @@ def main():
     out_gpu = os.path.join(args.dir, "gpu.out")
     cli = os.path.join(ROOT, "chromap_amd", "chromap-amd")
     t0 = time.time()
-    p = subprocess.run([cli, "--preset", args.preset, "-x", idx, "-r", fa, "-1", r1, "-2", r2, "-o", out_gpu] + extra, stderr=subprocess.PIPE)
+    p = subprocess.run([cli, "--preset", args.preset, "-x", idx, "-r", fa, "-1", r1, "-2", r2, "-o", out_gpu] + extra_gpu, stderr=subprocess.PIPE)
     wall = time.time() - t0
     log = p.stderr.decode(errors="replace")
     if p.returncode != 0:
@@ -160,6 +167,16 @@ def main():
                               "bed_md5": subprocess.check_output(["md5sum", out_gpu]).split()[0].decode()}
     if "bed_md5" in res.get("reference", {}) and "bed_md5" in res.get("chromap_amd", {}):
         res["bed_identical_to_reference"] = res["reference"]["bed_md5"] == res["chromap_amd"]["bed_md5"]
+    if args.summary and os.path.exists(sum_ref) and os.path.exists(sum_gpu):
+        a = open(sum_ref).read().splitlines()
+        b = open(sum_gpu).read().splitlines()
+        ra, rb = [x.split(",") for x in a[1:]], [x.split(",") for x in b[1:]]
+        res["summary"] = {"header_identical": a[:1] == b[:1], "rows_reference": len(ra), "rows_chromap_amd": len(rb),
+                          "same_barcodes_same_order": [x[0] for x in ra] == [x[0] for x in rb],
+                          "rows_differing_in_first_five_columns": sum(1 for x, y in zip(ra, rb) if x[:5] != y[:5]) + abs(len(ra) - len(rb)),
+                          "reference_rows_with_cachehit": sum(1 for x in ra if x[5] != "0"),
+                          "reference_cachehit_total": sum(int(x[5]) for x in ra),
+                          "totals_reference": [sum(int(x[c]) for x in ra) for c in range(1, 5)]}
     if args.bgzf_check and "bed_md5" in res.get("chromap_amd", {}):
         # the same reads as BGZF (block-parallel inflate in the CLI's reader): the output must not change
         sys.path.insert(0, os.path.join(ROOT, "tools"))
