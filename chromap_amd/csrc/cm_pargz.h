@@ -436,7 +436,7 @@ struct ParGunzip {
             memcpy(&va, pa + x, 8);
             memcpy(&vb, pb + x, 8);
             if (va == vb) memcpy(o + x, &va, 8);
-            else for (size_t k = x; k < x + 8; ++k) o[k] = fill(p, k);
+            else for (size_t y = x; y < x + 8; ++y) o[y] = fill(p, y);
           }
           for (; x < it.x1; ++x) o[x] = fill(p, x);
         } else if (p.b) for (size_t x = it.x0; x < it.x1; ++x) o[x] = fill(p, x);

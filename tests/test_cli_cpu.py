@@ -22,14 +22,15 @@ def test_version_and_help():
     assert r.returncode == 0 and b"Usage" in r.stdout
 
 
-def test_unknown_option_and_mismatched_inputs_are_errors():
+def test_unknown_option_and_mismatched_inputs_are_errors(tmp_path):
+    o = str(tmp_path / "o")
     r = _run("--PAF")
     assert r.returncode != 0 and b"unsupported option" in r.stderr
     fa, _, _ = datasets.case_inputs("toy_atac")
     idx = datasets.case_index("toy_atac")
-    r = _run("-x", idx, "-r", fa, "-1", "a.fq,b.fq", "-2", "c.fq", "-o", "o")
+    r = _run("-x", idx, "-r", fa, "-1", "a.fq,b.fq", "-2", "c.fq", "-o", o)
     assert r.returncode != 0 and b"don't match" in r.stderr, r.stderr
-    r = _run("-x", idx, "-r", fa, "-1", "a.fq,b.fq", "-2", "c.fq,d.fq", "-b", "e.fq", "-o", "o")
+    r = _run("-x", idx, "-r", fa, "-1", "a.fq,b.fq", "-2", "c.fq,d.fq", "-b", "e.fq", "-o", o)
     assert r.returncode != 0 and b"don't match" in r.stderr, r.stderr
 
 
@@ -49,22 +50,51 @@ def test_mapping_refuses_to_run_without_a_gpu(tmp_path):
     assert b"HIP" in r.stderr or b"device" in r.stderr or b"GPU" in r.stderr, r.stderr[-500:]
 
 
-def test_flag_combinations_without_a_record_type_are_refused():
+def test_flag_combinations_without_a_record_type_are_refused(tmp_path):
     """argument checks happen before any device work: the refusals are testable without a GPU.  (--pairs on the ordinary pairing,
     pairs with cell barcodes and -n up to 8192 were refused in rounds 1-5; they are accepted now: tests/test_gpu_cli_golden.py)"""
-    r = _run("--gpus", "0", "-x", "x", "-r", "y", "-1", "a", "-o", "o")
+    o = str(tmp_path / "o")
+    r = _run("--gpus", "0", "-x", "x", "-r", "y", "-1", "a", "-o", o)
     assert r.returncode != 0 and b"--gpus" in r.stderr
     # -n: BED / TagAlign / pairs carry up to n records per read; one SAM slot per read on the device
-    r = _run("--SAM", "-n", "2", "-x", "x", "-r", "y", "-1", "a", "-o", "o")
+    r = _run("--SAM", "-n", "2", "-x", "x", "-r", "y", "-1", "a", "-o", o)
     assert r.returncode != 0 and b"--SAM with -n > 1" in r.stderr
-    r = _run("-n", "8193", "-x", "x", "-r", "y", "-1", "a", "-o", "o")
+    r = _run("-n", "8193", "-x", "x", "-r", "y", "-1", "a", "-o", o)
     assert r.returncode != 0 and b"-n above 8192" in r.stderr
-    r = _run("-n", "0", "-x", "x", "-r", "y", "-1", "a", "-o", "o")
+    r = _run("-n", "0", "-x", "x", "-r", "y", "-1", "a", "-o", o)
     assert r.returncode != 0 and b"at least 1" in r.stderr
     # what used to be refused gets past the argument checks (and then fails on the missing files, not on the flags)
     for flags in (["--pairs"], ["--preset", "hic", "-b", "c"], ["-n", "100"]):
-        r = _run(*flags, "-x", "x", "-r", "y", "-1", "a", "-2", "b", "-o", "o")
+        r = _run(*flags, "-x", "x", "-r", "y", "-1", "a", "-2", "b", "-o", o)
         assert r.returncode != 0 and b"outside this build" not in r.stderr, (flags, r.stderr)
+
+
+def _refused_invocations(out):
+    """invocations that validate() refuses from their arguments alone, with the real toy reference and index"""
+    fa, _, _ = datasets.case_inputs("toy_atac")
+    idx = datasets.case_index("toy_atac")
+    return ((["-x", idx, "-r", fa, "-1", "a.fq,b.fq", "-2", "c.fq", "-o", out], b"don't match"),
+            (["--gpus", "2", "--SAM", "-x", idx, "-r", fa, "-1", "a.fq", "-2", "c.fq", "-o", out], b"--gpus > 1 needs"),
+            (["--gpus", "2", "--host-ingest", "-x", idx, "-r", fa, "-1", "a.fq", "-2", "c.fq", "-o", out], b"--gpus > 1 needs"))  # (BED: the kind of output that is emptied early)
+
+
+def test_refused_invocation_leaves_an_existing_output_alone(tmp_path):
+    """the arguments are checked before the output file is opened and emptied"""
+    out = tmp_path / "kept.bed"
+    for args, msg in _refused_invocations(str(out)):
+        out.write_bytes(b"chr1\t1\t2\tlast run's output\n")
+        r = _run(*args)
+        assert r.returncode != 0 and msg in r.stderr, r.stderr
+        assert out.read_bytes() == b"chr1\t1\t2\tlast run's output\n"
+
+
+def test_refused_invocation_creates_no_output(tmp_path):
+    out = tmp_path / "new.bed"
+    for args, msg in _refused_invocations(str(out)):
+        r = _run(*args)
+        assert r.returncode != 0 and msg in r.stderr, r.stderr
+        assert not out.exists()
+    assert os.listdir(tmp_path) == []
 
 
 def test_ingest_reader_inflates_bgzf_gzip_and_plain_text(tmp_path):

@@ -9,7 +9,7 @@ every pairs run took before), plain FASTQ and -- with --gz -- BGZF, `--reps` run
 alignment records kept in HBM, text rendered there) and through the host parser and writer (`--host-ingest`), timed like the hic routes.
 `--barcodes N`: a single-cell job -- a whitelist of N random 16-mers, every pair draws one, 10 % of them with one substitution (the
 generator of tools/ref_baseline.py); `--summary` then times the same job without and with `--summary FILE`, `--reps` runs each, and
-`--baseline-cli` the build of an earlier commit on the same files (without `--summary`).
+`--baseline-cli` the build of an earlier commit on the same files (without `--summary`; with `--gz` on the BGZF files too).
 Prints one JSON object; everything is written under --dir (default /tmp/chromap_amd_e2e)."""
 import argparse
 import ctypes as C
@@ -210,6 +210,9 @@ def main():
         res["device_ingest_bgzf"]["bgzf_bytes"] = os.path.getsize(r1 + ".bgz") + os.path.getsize(r2 + ".bgz")
         run("device_ingest_bgzf_256MB_pieces", r1 + ".bgz", r2 + ".bgz", ["--ingest-chunk-mb", "256"])
         res["bgzf_same_output"] = res["device_ingest_bgzf"]["bed_md5"] == res["device_ingest"]["bed_md5"]
+        if args.baseline_cli:
+            run("baseline_cli_bgzf", r1 + ".bgz", r2 + ".bgz", cli=args.baseline_cli)
+            res["baseline_same_output"] = res["baseline_same_output"] and res["baseline_cli_bgzf"]["bed_md5"] == res["device_ingest_bgzf"]["bed_md5"]
     res["same_output"] = res["device_ingest"]["bed_md5"] == res["host_ingest"]["bed_md5"] if "host_ingest" in res else None
     res["config"] = {"pairs": args.pairs, "readlen": args.readlen, "genome": args.genome, "barcodes": args.barcodes, "reps": args.reps,
                      "fastq_bytes": os.path.getsize(r1) + os.path.getsize(r2), "index_bytes": os.path.getsize(idx),
