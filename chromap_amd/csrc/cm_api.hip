@@ -13,6 +13,7 @@
 #include "../../include/chromap_amd.h"
 #include "cm_ctx.h"
 #include "cm_kernels.h"
+#include "cm_classes.h"
 #include "cm_summary.h"
 #include "cm_coop.h"
 #include <chrono>
@@ -70,8 +71,6 @@ void DevBuf::release() {
   cap = 0;
 }
 
-// tuning knobs for measurements (defaults are what the measurements chose)
-static int build_fast_table(cmgpu_ctx *c, int shift);
 // the arrays indexed through m_off (merged / filtered candidates, draft mappings, alignment results): room for n_m entries
 static int cm_ensure_candidate_arrays(cmgpu_ctx *c, uint64_t n_m) {
   return c->mbuf.ensure((size_t)n_m * 8 + 8) || c->mcnt.ensure((size_t)n_m + 4) || c->fbuf.ensure((size_t)n_m * 8 + 8) ||
@@ -83,52 +82,52 @@ extern "C" int cmgpu_set_option(cmgpu_ctx *c, const char *name, int64_t value) {
   const std::string n(name);
   if (n == "probe_lookups_per_lane") {
     if (value != 1 && value != 2 && value != 4 && value != 8) { cm_set_error(c, "probe_lookups_per_lane: 1, 2, 4 or 8"); return CMGPU_EINVAL; }
-    c->opt_probe_variant = (int)value | (c->opt_probe_variant & 16);
+    c->opt.probe_variant = (int)value | (c->opt.probe_variant & 16);
   } else if (n == "probe_pair_prefetch") {
-    c->opt_probe_variant = (c->opt_probe_variant & 15) | (value ? 16 : 0);
+    c->opt.probe_variant = (c->opt.probe_variant & 15) | (value ? 16 : 0);
   } else if (n == "h2d_copy_blocks") {  // 0: hipMemcpyAsync; else blocks of the copy kernel that reads page-locked host memory
     if (value < 0 || value > 4096) { cm_set_error(c, "h2d_copy_blocks: 0..4096"); return CMGPU_EINVAL; }
-    c->opt_h2d_kernel = (int)value;
+    c->opt.h2d_kernel = (int)value;
   } else if (n == "d2h_copy_blocks") {  // the record download the same way (0: hipMemcpyAsync)
     if (value < 0 || value > 4096) { cm_set_error(c, "d2h_copy_blocks: 0..4096"); return CMGPU_EINVAL; }
-    c->opt_d2h_kernel = (int)value;
+    c->opt.d2h_kernel = (int)value;
   } else if (n == "mm_chunks") {
     if (value < 1 || value > CM_MM_CHUNKS) { cm_set_error(c, "mm_chunks: 1.." + std::to_string(CM_MM_CHUNKS)); return CMGPU_EINVAL; }
-    c->opt_mm_chunks = (int)value;
+    c->opt.mm_chunks = (int)value;
   } else if (n == "prep_kernel") {
-    c->opt_prep_kernel = (int)value;
+    c->opt.prep_kernel = (int)value;
   } else if (n == "prep_tile_reads") {
     if (value < 8 || value > 128) { cm_set_error(c, "prep_tile_reads: 8..128"); return CMGPU_EINVAL; }
-    c->opt_prep_tile_reads = (int)value;
+    c->opt.prep_tile_reads = (int)value;
   } else if (n == "heavy_wave_max" || n == "heavy_block_max" || n == "heavy_big_max") {  // tests: force the size classes
-    c->opt_heavy_max[n == "heavy_wave_max" ? 0 : n == "heavy_block_max" ? 1 : 2] = (int)value;
+    c->opt.heavy_max[n == "heavy_wave_max" ? 0 : n == "heavy_block_max" ? 1 : 2] = (int)value;
   } else if (n == "s3b_lane_cap") {  // hits a lane clusters in its own LDS slots; longer lists go to a wave / block each
     if (value < 0 || value > 64) { cm_set_error(c, "s3b_lane_cap: 0 (by read length) or 1..64"); return CMGPU_EINVAL; }
-    c->opt_s3b_cap = (int)value;
+    c->opt.s3b_cap = (int)value;
   } else if (n == "exchange_overlap") {
-    c->opt_exchange_overlap = value ? 1 : 0;
+    c->opt.exchange_overlap = value ? 1 : 0;
   } else if (n == "lanes") {
     if (value < 1 || value > 8) { cm_set_error(c, "lanes: 1..8"); return CMGPU_EINVAL; }
-    c->opt_lanes = (int)value;
+    c->opt.lanes = (int)value;
   } else if (n == "first_read_id") {  // read id of the resident batch's first pair (device-generated batches start at 0)
     if (value < 0 || value > 0xffffffffll) { cm_set_error(c, "first_read_id: 0..2^32-1"); return CMGPU_EINVAL; }
     c->first_read_id = (uint32_t)value;
   } else if (n == "heavy_mid_max") {  // longest hit list a group of 16 lanes takes (default 64; -1: no such class)
-    c->opt_heavy_mid = (int)value;
+    c->opt.heavy_mid = (int)value;
   } else if (n == "heavy_last") {
-    c->opt_heavy_last = (int)value;
+    c->opt.heavy_last = (int)value;
   } else if (n == "probe_table_shift") {  // 0: probe the file's table; 1 / 2: a device copy with 2 / 4 times the buckets
     if (value < 0 || value > 4) { cm_set_error(c, "probe_table_shift: 0..4"); return CMGPU_EINVAL; }
     return cm_build_fast_table(c, (int)value);
   } else if (n == "long_read_fused") {  // 0: reads longer than 69 bases take the two-pass minimizer kernels (count, scan, fill)
-    c->opt_long_fused = value ? 1 : 0;
+    c->opt.long_fused = value ? 1 : 0;
   } else if (n == "sam_format_group") {  // lanes that render one SAM line (cm_sam_post.hip: k_sp_format)
     if (value != 8 && value != 16 && value != 64) { cm_set_error(c, "sam_format_group: 8, 16 or 64"); return CMGPU_EINVAL; }
-    c->opt_sam_group = (int)value;
+    c->opt.sam_group = (int)value;
   } else if (n == "verify_planes") {  // 0: k_s5b_verify aligns on the reference / read bytes (the round-2 form) instead of their bit planes
-    c->opt_planes = value ? 1 : 0;  // (the planes stay where they are: contexts made by cmgpu_create_shared may hold views of them)
+    c->opt.planes = value ? 1 : 0;  // (the planes stay where they are: contexts made by cmgpu_create_shared may hold views of them)
   } else if (n == "speculative_sizes") {  // 0: every batch waits for the total of its candidate lists before sizing their arrays
-    c->opt_spec = value ? 1 : 0;
+    c->opt.spec = value ? 1 : 0;
     if (value < 0) { c->cls_seen = 0; memset(c->cls_age, 0, sizeof(c->cls_age)); }  // tests: an empty speculative launch set -- the next range finds classes with items and is mapped again
   } else if (n == "debug_candidate_capacity") {  // tests: pretend the previous batch left this much room (forces the re-run path)
     // (the arrays are made to hold what is claimed: the device-side check trusts m_cap)
@@ -137,11 +136,11 @@ extern "C" int cmgpu_set_option(cmgpu_ctx *c, const char *name, int64_t value) {
   } else if (n == "coop_profile") {  // measurement aid: per-phase cycle sums of k_s3b_coop (cmgpu_get_option coop_profile_0 .. _15)
     if (value) { if (c->coop_prof.ensure(64 * 8)) return CMGPU_ENOMEM; HIPCHECK(c, hipMemset(c->coop_prof.p, 0, 64 * 8)); } else c->coop_prof.release();
   } else if (n == "coop_run_table") {  // tests: a small table makes the cooperative sorters decline reads (their fallback paths)
-    c->opt_coop_rb = (int)value;
+    c->opt.coop_rb = (int)value;
   } else if (n == "coop") {  // bit mask of the stages whose long lists go to groups of lanes (cm_coop.h)
-    c->opt_coop = (int)value;
+    c->opt.coop = (int)value;
   } else if (n == "item_limit") {  // forces the sub-batch path (tests): largest dense intermediate the pipeline may allocate
-    c->opt_item_limit = value > 0 ? (uint64_t)value : 0xfffffff0ull;
+    c->opt.item_limit = value > 0 ? (uint64_t)value : 0xfffffff0ull;
   } else {
     cm_set_error(c, "unknown option " + n);
     return CMGPU_EINVAL;
@@ -152,16 +151,16 @@ extern "C" int cmgpu_set_option(cmgpu_ctx *c, const char *name, int64_t value) {
 extern "C" int cmgpu_get_option(const cmgpu_ctx *c, const char *name, int64_t *value) {
   if (!c || !name || !value) return CMGPU_EINVAL;
   const std::string n(name);
-  if (n == "probe_lookups_per_lane") *value = c->opt_probe_variant & 15;
-  else if (n == "probe_pair_prefetch") *value = (c->opt_probe_variant & 16) ? 1 : 0;
-  else if (n == "mm_chunks") *value = c->opt_mm_chunks;
-  else if (n == "h2d_copy_blocks") *value = c->opt_h2d_kernel;
-  else if (n == "d2h_copy_blocks") *value = c->opt_d2h_kernel;
-  else if (n == "prep_kernel") *value = c->opt_prep_kernel;
-  else if (n == "prep_tile_reads") *value = c->opt_prep_tile_reads;
-  else if (n == "item_limit") *value = (int64_t)c->opt_item_limit;
-  else if (n == "lanes") *value = c->opt_lanes;
-  else if (n == "coop") *value = c->opt_coop;
+  if (n == "probe_lookups_per_lane") *value = c->opt.probe_variant & 15;
+  else if (n == "probe_pair_prefetch") *value = (c->opt.probe_variant & 16) ? 1 : 0;
+  else if (n == "mm_chunks") *value = c->opt.mm_chunks;
+  else if (n == "h2d_copy_blocks") *value = c->opt.h2d_kernel;
+  else if (n == "d2h_copy_blocks") *value = c->opt.d2h_kernel;
+  else if (n == "prep_kernel") *value = c->opt.prep_kernel;
+  else if (n == "prep_tile_reads") *value = c->opt.prep_tile_reads;
+  else if (n == "item_limit") *value = (int64_t)c->opt.item_limit;
+  else if (n == "lanes") *value = c->opt.lanes;
+  else if (n == "coop") *value = c->opt.coop;
   else if (n.rfind("coop_profile_", 0) == 0) {
     const int k = atoi(n.c_str() + 13);
     unsigned long long v = 0;
@@ -325,7 +324,6 @@ static void cm_load_device_code(hipStream_t s) {
   });
 }
 
-static int select_device(int device_id);
 static int select_device(int device_id) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
@@ -447,10 +445,10 @@ extern "C" int cmgpu_create_shared(const cmgpu_ctx *parent, cmgpu_ctx **out) {
   view(c->bkt, parent->bkt); view(c->occ, parent->occ); view(c->ref, parent->ref);
   view(c->ref_off, parent->ref_off); view(c->ref_len, parent->ref_len);
   c->bmask = parent->bmask; c->n_occ = parent->n_occ; c->n_seq = parent->n_seq; c->ref_bytes = parent->ref_bytes;
-  c->opt_planes = parent->opt_planes;
+  c->opt.planes = parent->opt.planes;  // (the one option a child takes over: it is an independent context)
   // the reference's bit planes are built on the parent now, so that every child views them instead of building its own copy
   // (half a byte per reference base each); the re-hashed probe table likewise is the parent's
-  if (!parent->ref_pl_words && parent->opt_planes && parent->ref_bytes && parent->ref_planes.owned) {
+  if (!parent->ref_pl_words && parent->opt.planes && parent->ref_bytes && parent->ref_planes.owned) {
     cmgpu_ctx *pp = const_cast<cmgpu_ctx *>(parent);
     if (cm_build_ref_planes(pp) != CMGPU_OK) { pp->ref_planes.release(); pp->ref_pl_words = 0; pp->err.clear(); }
     (void)select_device(parent->device);
@@ -636,11 +634,11 @@ __global__ __launch_bounds__(256) void k_host_copy(const cm_u32x4 *__restrict__ 
 static int host_to_device(cmgpu_ctx *c, void *dst, const void *src, size_t bytes, hipStream_t s) {
   if (bytes == 0) return CMGPU_OK;
   void *dev_view = nullptr;
-  if (c->opt_h2d_kernel && bytes >= 65536 && (((uintptr_t)src | (uintptr_t)dst) & 15u) == 0 &&
+  if (c->opt.h2d_kernel && bytes >= 65536 && (((uintptr_t)src | (uintptr_t)dst) & 15u) == 0 &&
       hipHostGetDevicePointer(&dev_view, const_cast<void *>(src), 0) == hipSuccess && dev_view) {
     const uint64_t n16 = bytes >> 4;
     const uint32_t tail = (uint32_t)(bytes & 15u);
-    hipLaunchKernelGGL(k_host_copy, dim3((unsigned)c->opt_h2d_kernel), dim3(256), 0, s, (const cm_u32x4 *)dev_view, (cm_u32x4 *)dst, n16,
+    hipLaunchKernelGGL(k_host_copy, dim3((unsigned)c->opt.h2d_kernel), dim3(256), 0, s, (const cm_u32x4 *)dev_view, (cm_u32x4 *)dst, n16,
                        (const uint8_t *)dev_view + (n16 << 4), (uint8_t *)dst + (n16 << 4), tail);
     return CMGPU_OK;
   }
@@ -652,11 +650,11 @@ static int host_to_device(cmgpu_ctx *c, void *dst, const void *src, size_t bytes
 static int device_to_host(cmgpu_ctx *c, void *dst, const void *src, size_t bytes, hipStream_t s) {
   if (bytes == 0) return CMGPU_OK;
   void *dev_view = nullptr;
-  if (c->opt_d2h_kernel && bytes >= 65536 && (((uintptr_t)src | (uintptr_t)dst) & 15u) == 0 &&
+  if (c->opt.d2h_kernel && bytes >= 65536 && (((uintptr_t)src | (uintptr_t)dst) & 15u) == 0 &&
       hipHostGetDevicePointer(&dev_view, dst, 0) == hipSuccess && dev_view) {
     const uint64_t n16 = bytes >> 4;
     const uint32_t tail = (uint32_t)(bytes & 15u);
-    hipLaunchKernelGGL(k_host_copy, dim3((unsigned)c->opt_d2h_kernel), dim3(256), 0, s, (const cm_u32x4 *)src, (cm_u32x4 *)dev_view, n16,
+    hipLaunchKernelGGL(k_host_copy, dim3((unsigned)c->opt.d2h_kernel), dim3(256), 0, s, (const cm_u32x4 *)src, (cm_u32x4 *)dev_view, n16,
                        (const uint8_t *)src + (n16 << 4), (uint8_t *)dev_view + (n16 << 4), tail);
     return CMGPU_OK;
   }
@@ -764,31 +762,42 @@ extern "C" int cmgpu_swap_resident_batch(cmgpu_ctx *c, int slot) {
   return CMGPU_OK;
 }
 
-void cm_fill_dev_range(cmgpu_ctx *c, CmDev &d, uint32_t lo, uint32_t hi);
-void cm_fill_dev(cmgpu_ctx *c, CmDev &d) { cm_fill_dev_range(c, d, 0, c->n_pairs); }
+// The stage kernels' view (CmDev) of pairs [lo, hi) of the resident batch is made of three parts, by what changes when:
+// cm_ensure_goff (once per reference), cm_set_classes (once per range) and cm_bind_dev (after every buffer that may have moved).
 
-// the stage kernels' view of pairs [lo, hi) of the resident batch: per-pair inputs and outputs are offset views,
-// the intermediates (indexed from 0) are reused by every sub-batch
-void cm_fill_dev_range(cmgpu_ctx *c, CmDev &d, uint32_t lo, uint32_t hi) {
-  memset(&d, 0, sizeof(d));
+// CmDev::goff: the sequences end to end in index order (candidate rids are re-ranked only behind the pair filter), gaps between.
+// Built on the context's first range; stays empty when the reference does not fit 32 bits (or CM_NO_KEY32 is set)
+static void cm_ensure_goff(cmgpu_ctx *c) {
+  if (c->goff_tried) return;
+  c->goff_tried = true;
+  std::vector<uint32_t> go(c->n_seq + 1);
+  uint64_t acc = 0;
+  const bool lens_ok = c->n_seq && c->h_ref_len.size() == c->n_seq;  // (checked BEFORE the loop reads h_ref_len[i])
+  for (uint32_t i = 0; lens_ok && i < c->n_seq; ++i) { go[i] = (uint32_t)acc; acc += (uint64_t)c->h_ref_len[i] + CM_GOFF_GAP; if (acc >= 0xffff0000ull) break; }
+  if (lens_ok && acc < 0xffff0000ull && !getenv("CM_NO_KEY32")) {
+    go[c->n_seq] = (uint32_t)acc;
+    if (c->goff.ensure(go.size() * 4) == 0 && hipMemcpy(c->goff.p, go.data(), go.size() * 4, hipMemcpyHostToDevice) != hipSuccess) c->goff.release();
+  }
+}
+// the size classes of the long-list stages (cm_classes.h) from the context's options, batch and device
+static void cm_set_classes(const cmgpu_ctx *c, CmDev &d) {
+  CmClassIn in = {};
+  for (int q = 0; q < 3; ++q) in.heavy_max[q] = c->opt.heavy_max[q];
+  in.heavy_mid = c->opt.heavy_mid; in.s3b_cap = c->opt.s3b_cap;
+  in.max_read_len = c->max_read_len; in.n_seq = c->n_seq; in.has_goff = c->goff.p != nullptr;
+  in.lane_cap = cm_s3b_lane_cap(c->max_read_len);
+  cm_s3b_heavy_classes(in.hv_max, &in.hv_big);
+  cm_size_classes(in, d);
+}
+// the context's buffers and counters as the stage kernels see them: per-pair inputs and outputs are offset views, the
+// intermediates (indexed from 0) are reused by every sub-batch.  Fields a stage sets (mm_cap, read_pl, sam_*) and the size
+// classes are left alone
+static void cm_bind_dev(cmgpu_ctx *c, CmDev &d, uint32_t lo, uint32_t hi) {
   d.bkt = (const uint64_t *)(c->fmask ? c->bkt_fast.p : c->bkt.p); d.bmask = c->fmask ? c->fmask : c->bmask; d.occ = (const uint64_t *)c->occ.p; d.n_occ = c->n_occ;
   d.ref = (const uint8_t *)c->ref.p; d.ref_off = (const uint64_t *)c->ref_off.p; d.ref_len = (const uint32_t *)c->ref_len.p;
-  if (!c->goff_tried) {  // the sequences end to end in index order (candidate rids are re-ranked only behind the pair filter), gaps between
-    c->goff_tried = true;
-    std::vector<uint32_t> go(c->n_seq + 1);
-    uint64_t acc = 0;
-    const bool lens_ok = c->n_seq && c->h_ref_len.size() == c->n_seq;  // (checked BEFORE the loop reads h_ref_len[i])
-    for (uint32_t i = 0; lens_ok && i < c->n_seq; ++i) { go[i] = (uint32_t)acc; acc += (uint64_t)c->h_ref_len[i] + CM_GOFF_GAP; if (acc >= 0xffff0000ull) break; }
-    if (lens_ok && acc < 0xffff0000ull && !getenv("CM_NO_KEY32")) {
-      go[c->n_seq] = (uint32_t)acc;
-      if (c->goff.ensure(go.size() * 4) == 0 && hipMemcpy(c->goff.p, go.data(), go.size() * 4, hipMemcpyHostToDevice) != hipSuccess) c->goff.release();
-    }
-  }
-  d.goff = (const uint32_t *)c->goff.p;
-  d.n_seq = c->n_seq;
-  d.ref_pl = c->ref_pl_words && c->opt_planes ? (const CmPlRec *)c->ref_planes.p + CM_PL_LEAD : nullptr; d.ref_pl_words = c->ref_pl_words;
-  d.p = c->p;
-  d.p.single = c->single ? 1 : 0;
+  d.goff = (const uint32_t *)c->goff.p; d.n_seq = c->n_seq;
+  d.ref_pl = c->ref_pl_words && c->opt.planes ? (const CmPlRec *)c->ref_planes.p + CM_PL_LEAD : nullptr; d.ref_pl_words = c->ref_pl_words;
+  d.p = c->p; d.p.single = c->single ? 1 : 0;
   d.mq.len_coef = (const double *)c->len_coef.p; d.mq.nsec_break = (const uint32_t *)c->nsec_break.p; d.mq.n_break = c->n_break;
   d.n_pairs = hi - lo; d.first_read_id = c->first_read_id + lo;
   d.rb0 = (const uint8_t *)c->rb0.p; d.rb1 = (const uint8_t *)c->rb1.p;
@@ -805,60 +814,19 @@ void cm_fill_dev_range(cmgpu_ctx *c, CmDev &d, uint32_t lo, uint32_t hi) {
   PTR(min_err, int32_t) PTR(second_err, int32_t) PTR(n_best, int32_t) PTR(n_second, int32_t)
   PTR(pe_min, int32_t) PTR(pe_second, int32_t) PTR(pe_nbest, int32_t) PTR(pe_nsecond, int32_t)
   PTR(pe_first, uint32_t) PTR(pe_i1, uint32_t) PTR(pe_i2, uint32_t) PTR(pe_choice, uint32_t)
+  PTR(stats, unsigned long long) PTR(srt_cnt, uint32_t) PTR(srt_list, uint32_t) PTR(hv_cnt, uint32_t) PTR(hv_list, uint32_t) PTR(rs_cnt, uint32_t) PTR(rs_list, uint32_t)
 #undef PTR
   d.rec = (uint8_t *)c->rec.p + (size_t)lo * 24 * cm_rec_per_pair(c);
   d.rec_ok = (uint8_t *)c->rec_ok.p + (size_t)lo * cm_rec_per_pair(c);
-  d.stats = (unsigned long long *)c->stats.p;
-  d.srt_cnt = (uint32_t *)c->srt_cnt.p;
-  d.srt_list = (uint32_t *)c->srt_list.p;
-  d.hv_cnt = (uint32_t *)c->hv_cnt.p;
-  d.hv_list = (uint32_t *)c->hv_list.p;
-  d.rs_cnt = (uint32_t *)c->rs_cnt.p;
-  d.rs_list = (uint32_t *)c->rs_list.p;
   d.hv_stride = 2 * (hi - lo) + 1;
-  d.perm_reads = c->use_perm ? (const uint32_t *)c->perm_reads.p : nullptr;
-  d.perm_pairs = c->use_perm ? (const uint32_t *)c->perm_pairs.p : nullptr;
+  d.perm_reads = c->use_perm ? (const uint32_t *)c->perm_reads.p : nullptr; d.perm_pairs = c->use_perm ? (const uint32_t *)c->perm_pairs.p : nullptr;
   d.coop_slab = (uint8_t *)c->coop_slab.p; d.coop_slab_cap = CM_SLAB_CAP; d.coop_slab_blocks = CM_SLAB_BLOCKS;
-  d.cls_mask = c->cls_all || !c->opt_spec ? ~0ull : c->cls_seen;
+  d.cls_mask = c->cls_all || !c->opt.spec ? ~0ull : c->cls_seen;
   d.prof = (unsigned long long *)c->coop_prof.p;
   d.rs_pool = (uint64_t *)c->rs_pool.p; d.rs_pool_cap = c->rs_pool.p ? c->rs_pool_cap : 0u; d.rs_pool_off = (uint32_t *)c->rs_pool_off.p;
   d.abort = (const unsigned long long *)c->stats.p + CM_ST_ABORT;
-  d.coop_rb = c->opt_coop_rb > 0 ? (uint32_t)c->opt_coop_rb : 0u;
-  d.wq_dynamic = ((uint32_t)c->opt_coop >> 16) & 1u;
-  d.s3b_cap = c->opt_s3b_cap > 0 ? (uint32_t)c->opt_s3b_cap : cm_s3b_lane_cap(c->max_read_len);
-  if (c->n_seq < 0x80000000u) {  // the cooperative kernel keeps the strand in bit 31 of the sequence id
-    cm_s3b_heavy_classes(d.hv_max, &d.hv_big);
-    // tests force the classes: heavy_wave_max caps the wave class, heavy_block_max the two middle classes, heavy_big_max the largest
-    if (c->opt_heavy_max[0] > 0 && (uint32_t)c->opt_heavy_max[0] < d.hv_max[0]) d.hv_max[0] = (uint32_t)c->opt_heavy_max[0];
-    for (int q = 1; q <= 2; ++q) if (c->opt_heavy_max[1] > 0 && (uint32_t)c->opt_heavy_max[1] < d.hv_max[q]) d.hv_max[q] = (uint32_t)c->opt_heavy_max[1];
-    if (c->opt_heavy_max[2] > 0 && (uint32_t)c->opt_heavy_max[2] < d.hv_max[3]) d.hv_max[3] = (uint32_t)c->opt_heavy_max[2];
-    for (int q = 1; q < 4; ++q) if (d.hv_max[q] < d.hv_max[q - 1]) d.hv_max[q] = d.hv_max[q - 1];
-    if (c->opt_heavy_max[2] > 0 && (uint32_t)c->opt_heavy_max[2] < d.hv_big) d.hv_big = (uint32_t)c->opt_heavy_max[2];
-    const uint32_t hv_big_area = d.hv_big;  // (what a CU's shared memory holds once: the rescue lists' largest class is sized from it)
-    // 32-bit hit keys: 11 bytes per hit -- 7 040 hits leave room for TWO blocks of 1 024 lanes per CU (k_s3b_coop<1024, true> on profile 2:
-    // 53.6 -> 43.0 ms of S3b per step against one block with 8 192; the few longer lists go to the slab launch)
-    if (c->goff.p && d.hv_big > 7040u) d.hv_big = 7040u;
-    if (d.hv_big <= d.hv_max[3]) d.hv_big = 0;
-    if (c->opt_heavy_max[0] < 0) { d.hv_max[0] = d.hv_max[1] = d.hv_max[2] = d.hv_max[3] = 0; d.hv_big = 0; }  // everything long goes to the one-lane path
-    // the rescue lists' classes: the hit lists' up to 2048, then as many 20-byte entries as fit a CU's shared memory twice / once
-    d.rs_max3 = d.hv_max[3] < 3968u ? d.hv_max[3] : 3968u;
-    // (round 6, measured and NOT kept: 32-bit keys in k_s4b_coop as in k_s3b_coop -- 12 instead of 20 bytes per entry, classes of 6 400 / 3 968
-    //  entries at two / three blocks per CU.  The stage got SLOWER, profile 2 46.5 -> 49.7 ms and profile 1 9.7 -> 18.3 ms per step: unlike the
-    //  hit lists, the rescue lists are merged with the read's own candidates and written back as sequence << 32 | position, so every hit
-    //  pays a lookup of its sequence's offset on the way in and every candidate a search of the offset table on the way out, and the
-    //  groups' time is not the number of reads in flight here)
-    d.rs_big = d.hv_big ? (hv_big_area < 7680u ? hv_big_area : 7680u) : 0u;
-    if (d.rs_big <= d.rs_max3) d.rs_big = 0;
-    // the longest list a 16-lane group takes: 64 hits; 96 for reads of 100 bases and more (round 6, `tools/gpu_mid_knob.sh`: 2 x 150 hic reads
-    // carry ~37 hits each with a tail to ~100 -- 64 / 80 / 96 / 112: 102.6 / 101.8 / 110.3 / 101.3 M pairs/s, twice; at 50 bases 96 is neutral on the
-    // headline and the mammalian-like genomes and loses 4 % on the planted repeats).  The classes decide who works on a list, never the result
-    d.hv_mid = c->opt_heavy_mid < 0 ? 0u : (c->opt_heavy_mid > 0 ? (uint32_t)c->opt_heavy_mid : (c->max_read_len >= 100 ? 96u : 64u));
-    if (d.hv_mid > 256) d.hv_mid = 256;
-    if (d.hv_max[0] == 0) d.hv_mid = 0;
-    d.hv_sub = d.hv_max[0] >= 512 ? 256u : 0u;  // (the tests' small size classes: no sub-class)
-    // with the 16-lane groups taking the lists up to hv_mid, a lane keeps the short ones only (16 hits: 256-thread blocks)
-    if (d.hv_mid && c->opt_s3b_cap <= 0 && d.s3b_cap > 16) d.s3b_cap = 16;
-  } else { d.hv_max[0] = d.hv_max[1] = d.hv_max[2] = d.hv_max[3] = 0; d.hv_mid = 0; d.hv_big = 0; d.rs_max3 = 0; d.rs_big = 0; }
+  d.coop_rb = c->opt.coop_rb > 0 ? (uint32_t)c->opt.coop_rb : 0u;
+  d.wq_dynamic = ((uint32_t)c->opt.coop >> 16) & 1u;
   if (c->has_rank) {  // stages from verification on address the reference by rank
     d.rid_rank = (const uint32_t *)c->rid_rank.p;
     d.ref_off = (const uint64_t *)c->ref_off_r.p;
@@ -872,7 +840,6 @@ void cm_fill_dev_range(cmgpu_ctx *c, CmDev &d, uint32_t lo, uint32_t hi) {
     d.bc_key = c->bc_key.p ? (uint64_t *)c->bc_key.p + lo : nullptr; d.bc_ok = c->bc_ok.p ? (uint8_t *)c->bc_ok.p + lo : nullptr;
   }
 }
-
 static inline void mark(cmgpu_ctx *c, const char *name) {
   if (c->n_ev < CM_MAX_EVENTS) {
     (void)hipEventRecord(c->ev[c->n_ev], c->stream);
@@ -880,286 +847,334 @@ static inline void mark(cmgpu_ctx *c, const char *name) {
     ++c->n_ev;
   }
 }
-
 // exclusive scan of per-read counts (u32 offsets) together with their exact 64-bit total: the offsets are only
-// meaningful when the total fits the dense arrays' 32-bit indexing, which the caller checks on *total
-static int scan_with_total(cmgpu_ctx *c, const uint32_t *in, uint32_t *out, uint32_t n, unsigned long long *total) {
+// meaningful when the total fits the dense arrays' 32-bit indexing, which the caller checks on *total (wait false: once
+// it has waited for the stream itself)
+static int scan_with_total(cmgpu_ctx *c, const uint32_t *in, uint32_t *out, uint32_t n, unsigned long long *total, bool wait = true) {
   hipStream_t s = c->stream;
   unsigned long long *acc = (unsigned long long *)c->stats.p + CM_ST_TOTAL;  // spare counter slot
   HIPCHECK(c, hipMemsetAsync(acc, 0, 8, s));
   cm_launch_k_sum_u32(in, n, acc, s);
   cm_scan_u32(in, out, n, (uint32_t *)c->scan_tmp.p, s);
   HIPCHECK(c, hipMemcpyAsync(total, acc, 8, hipMemcpyDeviceToHost, s));
-  HIPCHECK(c, cm_stream_sync(s));
+  if (wait) HIPCHECK(c, cm_stream_sync(s));
   return CMGPU_OK;
 }
-
-#define CM_RC_SPLIT (-100)  // internal: a dense intermediate of this pair range exceeds the 32-bit item limit
-
-// The pipeline on pairs [rlo, rhi) of the resident batch.  Four small device->host reads size the
-// variable-length intermediates (minimizers, hits, candidate capacity, verification items).
-static int map_range(cmgpu_ctx *c, uint32_t rlo, uint32_t rhi, uint64_t *k_out, cmgpu_stats *stats, bool allow_spec = true) {
-  const uint32_t n = rhi - rlo, n2 = 2 * n;
-  const uint64_t limit = c->opt_item_limit;
+// internal results of a range: a dense intermediate exceeds the 32-bit item limit (map_split halves the range); the range
+// has to be mapped again with every long-list class on / with exact candidate sizes (map_range goes round again)
+#define CM_RC_SPLIT (-100)
+#define CM_RC_AGAIN_ALL_CLASSES (-101)
+#define CM_RC_AGAIN_EXACT_SIZES (-102)
+// One pass of the pipeline over pairs [rlo, rhi) of the resident batch: the stages below, in order, share this state
+struct RangeRun {
+  cmgpu_ctx *c;
+  uint32_t rlo, rhi, n, n2;  // the pair range, its pairs and reads
+  bool allow_spec;           // false: the re-run with exact sizes
+  uint64_t limit;            // cmgpu_set_option "item_limit"
+  hipStream_t s;             // the mapping stream
+  CmDev d;                   // (zeroed by stage_begin)
+  uint32_t n_mm = 0;                    // minimizers
+  bool s3a_done = false;                // the fused front end has counted the hits already
+  uint32_t n_heavy[CM_HV_LISTS] = {};   // lists 0..2, 10 by size, 3: one lane each, 4: the short lists of the 16-lane groups
+  unsigned long long hits_total = 0;
+  uint32_t n_hits = 0;
+  bool planes = false;                  // S5b aligns on bit planes (the range's reads are packed)
+  bool spec = false;                    // the candidate arrays keep the previous batch's size (nothing waited for)
+  uint32_t n_m = 0;                     // capacity of the candidate arrays
+  void bind() { cm_bind_dev(c, d, rlo, rhi); }  // after every buffer that may have moved
+};
+static int stage_begin(RangeRun &r) {
+  cmgpu_ctx *c = r.c;
   c->n_ev = 0;
   c->use_perm = false;
-  *k_out = 0;
-  int rc = ensure_pair_arrays(c, n);
+  const int rc = ensure_pair_arrays(c, r.n);
   if (rc) return rc;
-  hipStream_t s = c->stream;
-  CmDev d;
-  HIPCHECK(c, hipMemsetAsync(c->stats.p, 0, CM_ST_N * 8, s));
-  cm_fill_dev_range(c, d, rlo, rhi);
+  HIPCHECK(c, hipMemsetAsync(c->stats.p, 0, CM_ST_N * 8, r.s));
+  memset(&r.d, 0, sizeof(r.d));
+  cm_ensure_goff(c);
+  cm_set_classes(c, r.d);
+  r.bind();
   mark(c, "begin");
   if (c->has_barcodes) {  // K6: barcode correction (chromap.h:896-909)
-    cm_launch_k_s0b_barcode(d, n, s);
+    cm_launch_k_s0b_barcode(r.d, r.n, r.s);
     mark(c, "s0b_barcode");
   }
-  uint32_t n_mm = 0;
-  bool s3a_done = false;
-  uint32_t n_heavy[CM_HV_LISTS] = {};  // lists 0..2, 10 by size, 3: one lane each, 4: the short lists of the 16-lane groups
-  unsigned long long hits_total = 0;
-  const bool flat = c->opt_prep_kernel == 1 && cm_prep_flat_supported(d, c->max_read_len, (uint32_t)c->opt_prep_tile_reads);
-  if (flat || (cm_prep_mm_supported(d, c->max_read_len) && (c->max_read_len <= 69 || c->opt_long_fused))) {
-    // S0 + S1 fused: one pass of the minimizer state machine, block-level reservation of the dense arrays
-    uint64_t cap = (uint64_t)n2 * (c->max_read_len / 4 + 3);
-    const uint64_t bound = (uint64_t)c->bases0 + c->bases1 + 1;  // one emission per k-mer position at most
-    if (cap > bound) cap = bound;
-    // The pairs go through in chunks: chunk c's minimizers (K0 + K1, VALU-bound) are followed on a second
-    // stream by their index probe (K2, latency-bound gather), which runs next to chunk c+1's minimizer
-    // pass.  A chunk's minimizers are the cursor range its launch covered (copied to mm_marks on the device).
-    const uint32_t ppb = flat ? 128u : cm_prep_mm_pairs_per_block(d, c->max_read_len);
-    const uint32_t n_chunks = n >= (1u << 20) ? (uint32_t)c->opt_mm_chunks : (n >= (1u << 17) ? 2 : 1);
-    const uint64_t per_read_bound = c->max_read_len > (uint32_t)c->p.k ? c->max_read_len - (uint32_t)c->p.k + 1 : 1;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-      if (cap > limit) return CM_RC_SPLIT;
-      // per chunk: probe grid = what the chunk can emit at most, but never more than the arrays hold
-      uint32_t lo[CM_MM_CHUNKS + 1];
-      uint64_t max_entries[CM_MM_CHUNKS];
-      uint32_t part_off[CM_MM_CHUNKS + 1];
-      lo[0] = 0; part_off[0] = 0;
-      for (uint32_t ch = 0; ch < n_chunks; ++ch) {
-        uint64_t hi = (uint64_t)n * (ch + 1) / n_chunks;
-        hi = ch + 1 == n_chunks ? n : hi / ppb * ppb;
-        lo[ch + 1] = (uint32_t)hi;
-        uint64_t me = 2ull * (lo[ch + 1] - lo[ch]) * (attempt == 0 ? (uint64_t)(c->max_read_len / 4 + 3) : per_read_bound);
-        if (me > cap) me = cap;
-        max_entries[ch] = me;
-        part_off[ch + 1] = part_off[ch] + cm_probe_range_blocks(me, c->opt_probe_variant);
-      }
-      uint32_t chunk_pairs = 0;
-      for (uint32_t ch = 0; ch < n_chunks; ++ch) chunk_pairs = lo[ch + 1] - lo[ch] > chunk_pairs ? lo[ch + 1] - lo[ch] : chunk_pairs;
-      if (c->mm_hash.ensure((size_t)cap * 8 + 8) || c->mm_ps.ensure((size_t)cap * 4 + 4) || c->pr_val.ensure((size_t)cap * 8 + 8) ||
-          (!flat && c->mm_stage.ensure(cm_prep_mm_stage_bytes(d, c->max_read_len, chunk_pairs) + 8)) ||
-          c->pr_kind.ensure((size_t)cap + 4) || c->mm_cursor.ensure(8) || c->mm_marks.ensure((CM_MM_CHUNKS + 1) * 8) ||
-          c->partials.ensure(((size_t)part_off[n_chunks] + 1) * 8 + cm_stats_partial_words(n) * 8)) {
-        cm_set_error(c, "out of device memory (minimizers)"); return CMGPU_ENOMEM;
-      }
-      cm_fill_dev_range(c, d, rlo, rhi);
-      HIPCHECK(c, hipMemsetAsync(c->mm_cursor.p, 0, 8, s));
-      HIPCHECK(c, hipMemsetAsync(c->mm_marks.p, 0, 8, s));
-      HIPCHECK(c, hipMemsetAsync(d.stats + CM_ST_PROBE_STEPS, 0, 2 * 8, s));
-      unsigned long long *marks = (unsigned long long *)c->mm_marks.p;
-      for (uint32_t ch = 0; ch < n_chunks; ++ch) {
-        if (flat) cm_launch_k_prep_flat(d, lo[ch], lo[ch + 1], c->max_read_len, (uint32_t)c->opt_prep_tile_reads, (uint32_t)cap, (unsigned long long *)c->mm_cursor.p, s);
-        else cm_launch_k_prep_mm(d, lo[ch], lo[ch + 1], c->max_read_len, (uint32_t)cap, (unsigned long long *)c->mm_cursor.p, s, c->mm_stage.p);
-        cm_launch_k_copy_u64((const unsigned long long *)c->mm_cursor.p, marks + ch + 1, s);
-        HIPCHECK(c, hipEventRecord(c->chunk_ev[ch], s));
-        HIPCHECK(c, hipStreamWaitEvent(c->stream2, c->chunk_ev[ch], 0));
-        cm_launch_k_probe_range(d, marks + ch, max_entries[ch], (uint32_t)cap, (uint2 *)c->partials.p + part_off[ch], c->stream2, c->opt_probe_variant);
-      }
-      HIPCHECK(c, hipEventRecord(c->chunk_ev[CM_MM_CHUNKS], c->stream2));
-      HIPCHECK(c, hipStreamWaitEvent(s, c->chunk_ev[CM_MM_CHUNKS], 0));
-      cm_launch_k_probe_reduce(c->partials.p, part_off[n_chunks], d.stats + CM_ST_PROBE_STEPS, s);
-      // S3a (hit counts, size classes) and the scan of the counts follow at once: their totals come back with the minimizer
-      // marks in ONE read (a read's minimizer range is checked against the arrays' capacity, so an overflow leaves them idle)
-      d.mm_cap = (uint32_t)cap;
-      HIPCHECK(c, hipMemsetAsync(c->hv_cnt.p, 0, 256, s));
-      cm_launch_k_s3a_count(d, n2, s);
-      {
-        unsigned long long *acc = (unsigned long long *)c->stats.p + CM_ST_TOTAL;
-        HIPCHECK(c, hipMemsetAsync(acc, 0, 8, s));
-        cm_launch_k_sum_u32(d.hit_tot, n2, acc, s);
-        cm_scan_u32(d.hit_tot, d.hit_off, n2, (uint32_t *)c->scan_tmp.p, s);
-        HIPCHECK(c, hipMemcpyAsync(&hits_total, acc, 8, hipMemcpyDeviceToHost, s));
-        HIPCHECK(c, hipMemcpyAsync(n_heavy, c->hv_cnt.p, sizeof(n_heavy), hipMemcpyDeviceToHost, s));
-      }
-      s3a_done = true;
-      // one read-back: the marks (cursor after every chunk; the last one is the total)
-      unsigned long long hm[CM_MM_CHUNKS + 1];
-      HIPCHECK(c, hipMemcpyAsync(hm, c->mm_marks.p, ((size_t)n_chunks + 1) * 8, hipMemcpyDeviceToHost, s));  // (not the null stream: lanes run side by side)
-      HIPCHECK(c, cm_stream_sync(s));
-      const unsigned long long tot = hm[n_chunks];
-      bool grid_short = false;  // a chunk emitted more than its probe grid covers (cannot happen on attempt 1)
-      if (attempt == 0 && tot <= cap)
-        for (uint32_t ch = 0; ch < n_chunks; ++ch) grid_short = grid_short || hm[ch + 1] - hm[ch] > max_entries[ch];
-      if (tot <= cap && !grid_short) { n_mm = (uint32_t)tot; break; }
-      if (attempt == 1) { cm_set_error(c, "minimizer arrays overflowed twice"); return CMGPU_ECAPACITY; }
-      cap = bound;  // rerun with the worst-case sizes
-    }
-    mark(c, "s0_s1_s2_trim_minimizers_probe");
-  } else {
-    // S0 + S1a: length filter, adapter trimming, minimizer counts (reads staged through LDS)
-    cm_launch_k_prep_count(d, n, c->max_read_len, s);
-    unsigned long long mm_total = 0;
-    if ((rc = scan_with_total(c, d.mm_cnt, d.mm_off, n2, &mm_total))) return rc;
-    if (mm_total > limit) return CM_RC_SPLIT;
-    n_mm = (uint32_t)mm_total;
-    mark(c, "s0_s1a_trim_count");
-    if (c->mm_hash.ensure((size_t)n_mm * 8 + 8) || c->mm_ps.ensure((size_t)n_mm * 4 + 4) || c->pr_val.ensure((size_t)n_mm * 8 + 8) ||
-        c->pr_kind.ensure((size_t)n_mm + 4)) { cm_set_error(c, "out of device memory (minimizers)"); return CMGPU_ENOMEM; }
-    cm_fill_dev_range(c, d, rlo, rhi);
-    // S1b + S2: the minimizers are written to their dense positions chunk by chunk, and the index probe of a chunk (second
-    // stream) runs under the next chunk's fill pass -- the offsets are known, so a chunk's minimizer range is
-    // [mm_off[2 lo], mm_off[2 hi]) (k_mm_marks; read back once to size the probe grids)
-    const uint32_t n_chunks = n >= (1u << 20) ? (uint32_t)c->opt_mm_chunks : (n >= (1u << 17) ? 2 : 1);
-    uint32_t lo[CM_MM_CHUNKS + 1];
-    for (uint32_t ch = 0; ch <= n_chunks; ++ch) lo[ch] = (uint32_t)((uint64_t)n * ch / n_chunks);
-    if (c->mm_marks.ensure((CM_MM_CHUNKS + 1) * 8)) { cm_set_error(c, "out of device memory (minimizers)"); return CMGPU_ENOMEM; }
-    unsigned long long *marks = (unsigned long long *)c->mm_marks.p;
-    unsigned long long hm[CM_MM_CHUNKS + 1];
-    cm_launch_k_mm_marks(d.mm_off, lo, n_chunks + 1, marks, s);
-    HIPCHECK(c, hipMemcpyAsync(hm, marks, ((size_t)n_chunks + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIPCHECK(c, cm_stream_sync(s));
-    uint32_t part_off[CM_MM_CHUNKS + 1];
-    part_off[0] = 0;
-    for (uint32_t ch = 0; ch < n_chunks; ++ch) part_off[ch + 1] = part_off[ch] + cm_probe_range_blocks(hm[ch + 1] - hm[ch], c->opt_probe_variant);
-    if (c->partials.ensure(((size_t)part_off[n_chunks] + 1) * 8 + cm_stats_partial_words(n) * 8)) { cm_set_error(c, "out of device memory (partials)"); return CMGPU_ENOMEM; }
-    HIPCHECK(c, hipMemsetAsync(d.stats + CM_ST_PROBE_STEPS, 0, 2 * 8, s));
-    for (uint32_t ch = 0; ch < n_chunks; ++ch) {
-      cm_launch_k_mm_fill(d, lo[ch], lo[ch + 1], c->max_read_len, s);
-      HIPCHECK(c, hipEventRecord(c->chunk_ev[ch], s));
-      HIPCHECK(c, hipStreamWaitEvent(c->stream2, c->chunk_ev[ch], 0));
-      cm_launch_k_probe_range(d, marks + ch, hm[ch + 1] - hm[ch], n_mm, (uint2 *)c->partials.p + part_off[ch], c->stream2, c->opt_probe_variant);
-    }
-    HIPCHECK(c, hipEventRecord(c->chunk_ev[CM_MM_CHUNKS], c->stream2));
-    HIPCHECK(c, hipStreamWaitEvent(s, c->chunk_ev[CM_MM_CHUNKS], 0));
-    cm_launch_k_probe_reduce(c->partials.p, part_off[n_chunks], d.stats + CM_ST_PROBE_STEPS, s);
-    mark(c, "s1b_s2_minimizers_probe");
+  return CMGPU_OK;
+}
+// The pairs go through the minimizer front ends in chunks: chunk c's minimizers (K0 + K1, VALU-bound) are followed on a second
+// stream by their index probe (K2, latency-bound gather), which runs next to chunk c+1's minimizer pass
+struct MmChunks {
+  uint32_t n_chunks;
+  uint32_t lo[CM_MM_CHUNKS + 1];        // first pair of every chunk
+  uint64_t entries[CM_MM_CHUNKS];       // minimizers a chunk's probe grid covers
+  uint32_t part_off[CM_MM_CHUNKS + 1];  // the probe launches' partial sums in cmgpu_ctx::partials
+};
+static uint32_t mm_chunk_count(const RangeRun &r) { return r.n >= (1u << 20) ? (uint32_t)r.c->opt.mm_chunks : (r.n >= (1u << 17) ? 2 : 1); }
+static void mm_probe_grids(const cmgpu_ctx *c, MmChunks &k) {
+  k.part_off[0] = 0;
+  for (uint32_t ch = 0; ch < k.n_chunks; ++ch) k.part_off[ch + 1] = k.part_off[ch] + cm_probe_range_blocks(k.entries[ch], c->opt.probe_variant);
+}
+// for each chunk: fill(ch) writes its minimizers on the mapping stream, the probe of the range marks[ch] .. marks[ch + 1] follows on
+// the second stream; then the streams join and the probes' counters are summed
+template <class Fill>
+static int mm_fill_and_probe(RangeRun &r, const MmChunks &k, uint32_t mm_cap, Fill fill) {
+  cmgpu_ctx *c = r.c;
+  const unsigned long long *marks = (const unsigned long long *)c->mm_marks.p;
+  HIPCHECK(c, hipMemsetAsync(r.d.stats + CM_ST_PROBE_STEPS, 0, 2 * 8, r.s));
+  for (uint32_t ch = 0; ch < k.n_chunks; ++ch) {
+    fill(ch);
+    HIPCHECK(c, hipEventRecord(c->chunk_ev[ch], r.s));
+    HIPCHECK(c, hipStreamWaitEvent(c->stream2, c->chunk_ev[ch], 0));
+    cm_launch_k_probe_range(r.d, marks + ch, k.entries[ch], mm_cap, (uint2 *)c->partials.p + k.part_off[ch], c->stream2, c->opt.probe_variant);
   }
-  // the alignments of S5b run on bit planes: this range's reads, both orientations, packed on the second stream (idle from here
-  // on) under S3 and S4 -- the trimmed lengths are final
-  bool planes = c->ref_pl_words != 0 && c->opt_planes;  // (verify_planes 0 keeps the planes for the children but does not use them: no packed reads either)
-  if (planes && c->read_planes.ensure((size_t)n2 * cm_read_pl_stride((c->max_read_len + 31) / 32) * 4 + 16)) planes = false;  // (no room: this range on bytes)
-  if (planes) {
-    const uint32_t pw = (c->max_read_len + 31) / 32;
-    // on a stream of the highest priority: at the mapping streams' priority the kernel only got the slots three lanes' S3 / S4 kernels
-    // left over and S5 waited for it (2 x 150: 4 ms of a 21 ms step once the empty class launches no longer padded S4)
-    if (!c->stream_pack) {
-      int prio_least = 0, prio_greatest = 0;
-      (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-      HIPCHECK(c, hipStreamCreateWithPriority(&c->stream_pack, hipStreamNonBlocking, prio_greatest));
+  HIPCHECK(c, hipEventRecord(c->chunk_ev[CM_MM_CHUNKS], c->stream2));
+  HIPCHECK(c, hipStreamWaitEvent(r.s, c->chunk_ev[CM_MM_CHUNKS], 0));
+  cm_launch_k_probe_reduce(c->partials.p, k.part_off[k.n_chunks], r.d.stats + CM_ST_PROBE_STEPS, r.s);
+  return CMGPU_OK;
+}
+// S0 + S1 + S2 fused: one pass of the minimizer state machine, block-level reservation of the dense arrays.  A chunk's minimizers
+// are the cursor range its launch covered (copied to mm_marks on the device)
+static int stage_minimizers_fused(RangeRun &r, bool flat) {
+  cmgpu_ctx *c = r.c; CmDev &d = r.d; hipStream_t s = r.s;
+  const uint32_t n = r.n, n2 = r.n2;
+  int rc;
+  uint64_t cap = (uint64_t)n2 * (c->max_read_len / 4 + 3);
+  const uint64_t bound = (uint64_t)c->bases0 + c->bases1 + 1;  // one emission per k-mer position at most
+  if (cap > bound) cap = bound;
+  const uint32_t ppb = flat ? 128u : cm_prep_mm_pairs_per_block(d, c->max_read_len);
+  const uint64_t per_read_bound = c->max_read_len > (uint32_t)c->p.k ? c->max_read_len - (uint32_t)c->p.k + 1 : 1;
+  MmChunks k;
+  k.n_chunks = mm_chunk_count(r);
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    if (cap > r.limit) return CM_RC_SPLIT;
+    // per chunk: probe grid = what the chunk can emit at most, but never more than the arrays hold
+    k.lo[0] = 0;
+    uint32_t chunk_pairs = 0;
+    for (uint32_t ch = 0; ch < k.n_chunks; ++ch) {
+      uint64_t hi = (uint64_t)n * (ch + 1) / k.n_chunks;
+      hi = ch + 1 == k.n_chunks ? n : hi / ppb * ppb;
+      k.lo[ch + 1] = (uint32_t)hi;
+      const uint32_t pairs = k.lo[ch + 1] - k.lo[ch];
+      chunk_pairs = pairs > chunk_pairs ? pairs : chunk_pairs;
+      const uint64_t me = 2ull * pairs * (attempt == 0 ? (uint64_t)(c->max_read_len / 4 + 3) : per_read_bound);
+      k.entries[ch] = me > cap ? cap : me;
     }
-    HIPCHECK(c, hipEventRecord(c->chunk_ev[1], s));
-    HIPCHECK(c, hipStreamWaitEvent(c->stream_pack, c->chunk_ev[1], 0));
-    d.read_pl = (uint32_t *)c->read_planes.p; d.read_pl_w = pw;
-    cm_launch_k_pack_reads(d, n2, c->stream_pack);
-    HIPCHECK(c, hipEventRecord(c->chunk_ev[0], c->stream_pack));
-  }
-  // S3: hit counts -> offsets -> candidates
-  if (!s3a_done) {
+    mm_probe_grids(c, k);
+    if (c->mm_hash.ensure((size_t)cap * 8 + 8) || c->mm_ps.ensure((size_t)cap * 4 + 4) || c->pr_val.ensure((size_t)cap * 8 + 8) ||
+        (!flat && c->mm_stage.ensure(cm_prep_mm_stage_bytes(d, c->max_read_len, chunk_pairs) + 8)) ||
+        c->pr_kind.ensure((size_t)cap + 4) || c->mm_cursor.ensure(8) || c->mm_marks.ensure((CM_MM_CHUNKS + 1) * 8) ||
+        c->partials.ensure(((size_t)k.part_off[k.n_chunks] + 1) * 8 + cm_stats_partial_words(n) * 8)) {
+      cm_set_error(c, "out of device memory (minimizers)"); return CMGPU_ENOMEM;
+    }
+    r.bind();
+    HIPCHECK(c, hipMemsetAsync(c->mm_cursor.p, 0, 8, s));
+    HIPCHECK(c, hipMemsetAsync(c->mm_marks.p, 0, 8, s));
+    unsigned long long *cursor = (unsigned long long *)c->mm_cursor.p, *marks = (unsigned long long *)c->mm_marks.p;
+    rc = mm_fill_and_probe(r, k, (uint32_t)cap, [&](uint32_t ch) {
+      if (flat) cm_launch_k_prep_flat(d, k.lo[ch], k.lo[ch + 1], c->max_read_len, (uint32_t)c->opt.prep_tile_reads, (uint32_t)cap, cursor, s);
+      else cm_launch_k_prep_mm(d, k.lo[ch], k.lo[ch + 1], c->max_read_len, (uint32_t)cap, cursor, s, c->mm_stage.p);
+      cm_launch_k_copy_u64(cursor, marks + ch + 1, s);
+    });
+    if (rc) return rc;
+    // S3a (hit counts, size classes) and the scan of the counts follow at once: their totals come back with the minimizer
+    // marks in ONE read (a read's minimizer range is checked against the arrays' capacity, so an overflow leaves them idle)
+    d.mm_cap = (uint32_t)cap;
     HIPCHECK(c, hipMemsetAsync(c->hv_cnt.p, 0, 256, s));
     cm_launch_k_s3a_count(d, n2, s);
-    HIPCHECK(c, hipMemcpyAsync(n_heavy, c->hv_cnt.p, sizeof(n_heavy), hipMemcpyDeviceToHost, s));
-    if ((rc = scan_with_total(c, d.hit_tot, d.hit_off, n2, &hits_total))) return rc;
+    d.mm_cap = 0;  // (S3a alone checks it)
+    if ((rc = scan_with_total(c, d.hit_tot, d.hit_off, n2, &r.hits_total, false))) return rc;
+    HIPCHECK(c, hipMemcpyAsync(r.n_heavy, c->hv_cnt.p, sizeof(r.n_heavy), hipMemcpyDeviceToHost, s));
+    r.s3a_done = true;
+    // one read-back: the marks (cursor after every chunk; the last one is the total)
+    unsigned long long hm[CM_MM_CHUNKS + 1];
+    HIPCHECK(c, hipMemcpyAsync(hm, marks, ((size_t)k.n_chunks + 1) * 8, hipMemcpyDeviceToHost, s));  // (not the null stream: lanes run side by side)
+    HIPCHECK(c, cm_stream_sync(s));
+    const unsigned long long tot = hm[k.n_chunks];
+    bool grid_short = false;  // a chunk emitted more than its probe grid covers (cannot happen on attempt 1)
+    if (attempt == 0 && tot <= cap)
+      for (uint32_t ch = 0; ch < k.n_chunks; ++ch) grid_short = grid_short || hm[ch + 1] - hm[ch] > k.entries[ch];
+    if (tot <= cap && !grid_short) { r.n_mm = (uint32_t)tot; break; }
+    if (attempt == 1) { cm_set_error(c, "minimizer arrays overflowed twice"); return CMGPU_ECAPACITY; }
+    cap = bound;  // rerun with the worst-case sizes
   }
-  if (hits_total > limit) return CM_RC_SPLIT;  // 2 x 150 reads on a repeat-rich genome: ~500 hits per read x 8 M reads wraps 2^32
-  const uint32_t n_hits = (uint32_t)hits_total;
-  if (c->hbuf.ensure((size_t)n_hits * 8 + 8) || c->hcnt.ensure((size_t)n_hits + 4)) { cm_set_error(c, "out of device memory (hits)"); return CMGPU_ENOMEM; }
-  cm_fill_dev_range(c, d, rlo, rhi);
+  mark(c, "s0_s1_s2_trim_minimizers_probe");
+  return CMGPU_OK;
+}
+// S0 + S1a: length filter, adapter trimming, minimizer counts (reads staged through LDS); S1b + S2: the minimizers are written to
+// their dense positions chunk by chunk -- the offsets are known, so a chunk's minimizer range is [mm_off[2 lo], mm_off[2 hi])
+// (k_mm_marks; read back once to size the probe grids)
+static int stage_minimizers_two_pass(RangeRun &r) {
+  cmgpu_ctx *c = r.c; CmDev &d = r.d; hipStream_t s = r.s;
+  int rc;
+  cm_launch_k_prep_count(d, r.n, c->max_read_len, s);
+  unsigned long long mm_total = 0;
+  if ((rc = scan_with_total(c, d.mm_cnt, d.mm_off, r.n2, &mm_total))) return rc;
+  if (mm_total > r.limit) return CM_RC_SPLIT;
+  const uint32_t n_mm = r.n_mm = (uint32_t)mm_total;
+  mark(c, "s0_s1a_trim_count");
+  if (c->mm_hash.ensure((size_t)n_mm * 8 + 8) || c->mm_ps.ensure((size_t)n_mm * 4 + 4) || c->pr_val.ensure((size_t)n_mm * 8 + 8) ||
+      c->pr_kind.ensure((size_t)n_mm + 4)) { cm_set_error(c, "out of device memory (minimizers)"); return CMGPU_ENOMEM; }
+  r.bind();
+  MmChunks k;
+  k.n_chunks = mm_chunk_count(r);
+  for (uint32_t ch = 0; ch <= k.n_chunks; ++ch) k.lo[ch] = (uint32_t)((uint64_t)r.n * ch / k.n_chunks);
+  if (c->mm_marks.ensure((CM_MM_CHUNKS + 1) * 8)) { cm_set_error(c, "out of device memory (minimizers)"); return CMGPU_ENOMEM; }
+  unsigned long long *marks = (unsigned long long *)c->mm_marks.p;
+  unsigned long long hm[CM_MM_CHUNKS + 1];
+  cm_launch_k_mm_marks(d.mm_off, k.lo, k.n_chunks + 1, marks, s);
+  HIPCHECK(c, hipMemcpyAsync(hm, marks, ((size_t)k.n_chunks + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIPCHECK(c, cm_stream_sync(s));
+  for (uint32_t ch = 0; ch < k.n_chunks; ++ch) k.entries[ch] = hm[ch + 1] - hm[ch];
+  mm_probe_grids(c, k);
+  if (c->partials.ensure(((size_t)k.part_off[k.n_chunks] + 1) * 8 + cm_stats_partial_words(r.n) * 8)) { cm_set_error(c, "out of device memory (partials)"); return CMGPU_ENOMEM; }
+  if ((rc = mm_fill_and_probe(r, k, n_mm, [&](uint32_t ch) { cm_launch_k_mm_fill(d, k.lo[ch], k.lo[ch + 1], c->max_read_len, s); }))) return rc;
+  mark(c, "s1b_s2_minimizers_probe");
+  return CMGPU_OK;
+}
+// the alignments of S5b run on bit planes: this range's reads, both orientations, packed on a stream of their own under S3 and
+// S4 -- the trimmed lengths are final
+static int stage_pack_reads(RangeRun &r) {
+  cmgpu_ctx *c = r.c;
+  r.planes = c->ref_pl_words != 0 && c->opt.planes;  // (verify_planes 0 keeps the planes for the children but does not use them: no packed reads either)
+  if (r.planes && c->read_planes.ensure((size_t)r.n2 * cm_read_pl_stride((c->max_read_len + 31) / 32) * 4 + 16)) r.planes = false;  // (no room: this range on bytes)
+  if (!r.planes) return CMGPU_OK;
+  // on a stream of the highest priority: at the mapping streams' priority the kernel only got the slots three lanes' S3 / S4 kernels
+  // left over and S5 waited for it (2 x 150: 4 ms of a 21 ms step once the empty class launches no longer padded S4)
+  if (!c->stream_pack) {
+    int prio_least = 0, prio_greatest = 0;
+    (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
+    HIPCHECK(c, hipStreamCreateWithPriority(&c->stream_pack, hipStreamNonBlocking, prio_greatest));
+  }
+  HIPCHECK(c, hipEventRecord(c->chunk_ev[1], r.s));
+  HIPCHECK(c, hipStreamWaitEvent(c->stream_pack, c->chunk_ev[1], 0));
+  r.d.read_pl = (uint32_t *)c->read_planes.p; r.d.read_pl_w = (c->max_read_len + 31) / 32;  // (read by the S5 kernels only, behind their wait for chunk_ev[0])
+  cm_launch_k_pack_reads(r.d, r.n2, c->stream_pack);
+  HIPCHECK(c, hipEventRecord(c->chunk_ev[0], c->stream_pack));
+  return CMGPU_OK;
+}
+// S3: hit counts -> offsets -> candidates
+static int stage_s3_candidates(RangeRun &r) {
+  cmgpu_ctx *c = r.c; CmDev &d = r.d; hipStream_t s = r.s;
+  const uint32_t n2 = r.n2;
+  if (!r.s3a_done) {
+    HIPCHECK(c, hipMemsetAsync(c->hv_cnt.p, 0, 256, s));
+    cm_launch_k_s3a_count(d, n2, s);
+    HIPCHECK(c, hipMemcpyAsync(r.n_heavy, c->hv_cnt.p, sizeof(r.n_heavy), hipMemcpyDeviceToHost, s));
+    const int rc = scan_with_total(c, d.hit_tot, d.hit_off, n2, &r.hits_total);
+    if (rc) return rc;
+  }
+  if (r.hits_total > r.limit) return CM_RC_SPLIT;  // 2 x 150 reads on a repeat-rich genome: ~500 hits per read x 8 M reads wraps 2^32
+  r.n_hits = (uint32_t)r.hits_total;
+  if (c->hbuf.ensure((size_t)r.n_hits * 8 + 8) || c->hcnt.ensure((size_t)r.n_hits + 4)) { cm_set_error(c, "out of device memory (hits)"); return CMGPU_ENOMEM; }
+  r.bind();
   mark(c, "s3a_count");
   cm_launch_k_s3b_candidates(d, n2, c->max_read_len, s);
-  cm_launch_k_s3b_heavy(d, n_heavy, s, (c->opt_coop & 1) != 0, c->max_read_len);  // reads with long hit lists: a wave or a block each
+  const uint32_t *nh = r.n_heavy;
+  cm_launch_k_s3b_heavy(d, nh, s, (c->opt.coop & 1) != 0, c->max_read_len);  // reads with long hit lists: a wave or a block each
   // with more than a handful of such reads the later per-read / per-pair stages take them last, in waves of their own
   // (lists of class 0 -- up to heavy_wave_max hits, a wave each here -- cost the later per-lane stages little; a uniform genome
   // still has a few thousand of them per batch, and the permutation's scans and scatters cost more than they save there)
-  c->use_perm = (uint64_t)n_heavy[CM_L_HIT_B256B] + n_heavy[CM_L_HIT_SLAB] + n_heavy[CM_L_HIT_B512] + n_heavy[CM_L_HIT_B1024] > n2 / 65536 || (uint64_t)n_heavy[CM_L_HIT_WAVE] + n_heavy[CM_L_HIT_WAVE_SMALL] + n_heavy[CM_L_HIT_B256A] > n2 / 256;  // (lists 21, 0, 1: up to 1024 hits)
-  if (c->opt_heavy_last) c->use_perm = c->opt_heavy_last > 0;
+  c->use_perm = (uint64_t)nh[CM_L_HIT_B256B] + nh[CM_L_HIT_SLAB] + nh[CM_L_HIT_B512] + nh[CM_L_HIT_B1024] > n2 / 65536 || (uint64_t)nh[CM_L_HIT_WAVE] + nh[CM_L_HIT_WAVE_SMALL] + nh[CM_L_HIT_B256A] > n2 / 256;  // (lists 21, 0, 1: up to 1024 hits)
+  if (c->opt.heavy_last) c->use_perm = c->opt.heavy_last > 0;
   if (c->use_perm) {
     uint32_t *tmp = (uint32_t *)c->hv_tmp.p;
-    cm_build_heavy_last(d, n, (uint32_t *)c->scratch_a.p, tmp, (uint32_t *)c->scratch_b.p, tmp + n2 + 1, (uint32_t *)c->perm_reads.p,
+    cm_build_heavy_last(d, r.n, (uint32_t *)c->scratch_a.p, tmp, (uint32_t *)c->scratch_b.p, tmp + n2 + 1, (uint32_t *)c->perm_reads.p,
                         (uint32_t *)c->perm_pairs.p, (uint32_t *)c->scan_tmp.p, s);
   }
-  cm_fill_dev_range(c, d, rlo, rhi);
+  r.bind();  // (perm_reads / perm_pairs)
   mark(c, "s3b_candidates");
-  // S4: mate rescue, merge, paired-end filter
+  return CMGPU_OK;
+}
+// the pool of rescue hits found while counting (cmgpu_set_option "coop" bit 1): sized from what the previous range asked for (+ 25 %)
+static void size_rescue_pool(RangeRun &r) {
+  cmgpu_ctx *c = r.c;
+  // (+ a grant per wave that can take one, cm_coop_pool_take: what the waves leave unused of their last grants)
+  // slack: half a grant for every wave of the rescue-wave launch (rescue_wave_blocks: n / 512 + 64, at most 8192) -- but only once the
+  // waves have taken grants at all (a range whose searches never asked leaves rs_pool_want at 0: no 268 MB per lane for nothing)
+  uint64_t waves = (uint64_t)r.n2 / 512 + 64;
+  if (waves > 8192) waves = 8192;
+  const uint64_t slack = c->rs_pool_want ? waves * CM_POOL_GRANT / 2 : 0;
+  uint64_t want = c->rs_pool_want + c->rs_pool_want / 4 + slack;
+  // (a range that ran out of pool undercounts what it would have used -- the pieces behind the refusal are only estimated -- and
+  // growing the pool is a hipFree + hipMalloc of gigabytes, 0.3-0.5 s: grow once, generously)
+  if (c->rs_pool_want > c->rs_pool_cap) want = 2 * c->rs_pool_want + slack;
+  if (want < (1u << 22)) want = 1u << 22;  // (32 MB to begin with: a first grant per wave of a small batch; the pool then follows the demand)
+  if (want > 0xfffffff0ull) want = 0xfffffff0ull;
+  const auto dbg_t0 = std::chrono::steady_clock::now();
+  if (c->rs_pool.ensure((size_t)want * 8) == 0 && c->rs_pool_off.ensure((size_t)r.n2 * 2 * 4 + 16) == 0) c->rs_pool_cap = (uint32_t)(c->rs_pool.cap / 8 > 0xfffffff0ull ? 0xfffffff0ull : c->rs_pool.cap / 8);
+  else { c->rs_pool.release(); c->rs_pool_cap = 0; }  // (no pool: the fill pass searches again)
+  if (cm_debug_pool()) fprintf(stderr, "pool ensure want %llu: %.3f ms\n", (unsigned long long)want, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - dbg_t0).count());
+  r.bind();
+}
+// S4: mate rescue, merge, paired-end filter
+static int stage_s4_rescue_filter(RangeRun &r) {
+  cmgpu_ctx *c = r.c; CmDev &d = r.d; hipStream_t s = r.s;
+  const uint32_t n2 = r.n2;
+  const bool coop = (c->opt.coop & 2) != 0;
   HIPCHECK(c, hipMemsetAsync(c->rs_cnt.p, 0, CM_RS_SEGS * 64, s));
-  if (c->opt_coop & 2) {  // the pool of rescue hits found while counting: sized from what the previous range asked for (+ 25 %)
-    // (+ a grant per wave that can take one, cm_coop_pool_take: what the waves leave unused of their last grants)
-    // slack: half a grant for every wave of the rescue-wave launch (rescue_wave_blocks: n / 512 + 64, at most 8192) -- but only once the
-    // waves have taken grants at all (a range whose searches never asked leaves rs_pool_want at 0: no 268 MB per lane for nothing)
-    uint64_t waves = (uint64_t)n2 / 512 + 64;
-    if (waves > 8192) waves = 8192;
-    const uint64_t slack = c->rs_pool_want ? waves * CM_POOL_GRANT / 2 : 0;
-    uint64_t want = c->rs_pool_want + c->rs_pool_want / 4 + slack;
-    // (a range that ran out of pool undercounts what it would have used -- the pieces behind the refusal are only estimated -- and
-    // growing the pool is a hipFree + hipMalloc of gigabytes, 0.3-0.5 s: grow once, generously)
-    if (c->rs_pool_want > c->rs_pool_cap) want = 2 * c->rs_pool_want + slack;
-    if (want < (1u << 22)) want = 1u << 22;  // (32 MB to begin with: a first grant per wave of a small batch; the pool then follows the demand)
-    if (want > 0xfffffff0ull) want = 0xfffffff0ull;
-    const auto dbg_t0 = std::chrono::steady_clock::now();
-    if (c->rs_pool.ensure((size_t)want * 8) == 0 && c->rs_pool_off.ensure((size_t)n2 * 2 * 4 + 16) == 0) c->rs_pool_cap = (uint32_t)(c->rs_pool.cap / 8 > 0xfffffff0ull ? 0xfffffff0ull : c->rs_pool.cap / 8);
-    else { c->rs_pool.release(); c->rs_pool_cap = 0; }  // (no pool: the fill pass searches again)
-    if (cm_debug_pool()) fprintf(stderr, "pool ensure want %llu: %.3f ms\n", (unsigned long long)want, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - dbg_t0).count());
-    cm_fill_dev_range(c, d, rlo, rhi);
-  }
-  cm_launch_k_s4a_rescue_count(d, n2, s, (c->opt_coop & 2) != 0);  // decision per read + the packed list of reads that supplement
-  cm_launch_k_s4a_rescue_list(d, n2, s, (c->opt_coop & 2) != 0);   // their searches: a lane, a group of 16 lanes or a wave per read
+  if (coop) size_rescue_pool(r);
+  cm_launch_k_s4a_rescue_count(d, n2, s, coop);  // decision per read + the packed list of reads that supplement
+  cm_launch_k_s4a_rescue_list(d, n2, s, coop);   // their searches: a lane, a group of 16 lanes or a wave per read
   // The candidate arrays.  A batch of the size of the previous one reuses that batch's arrays (sized with 25 % to spare) without
   // waiting for its own total: the device compares the total with the capacity and, should it ever pass it, raises d.abort --
-  // every later kernel then leaves at once and the range is mapped again with exact sizes (the `spec` test below).
-  unsigned long long *acc = (unsigned long long *)c->stats.p + CM_ST_TOTAL;
-  const bool spec = allow_spec && c->opt_spec && c->pred_m_ok && (c->pred_n == n || c->pred_n == 0xffffffffu) && c->m_cap > 0 && c->m_cap <= limit;
+  // every later kernel then leaves at once and the range is mapped again with exact sizes (stage_finish).
   unsigned long long m_total = 0;
-  uint32_t n_m;
-  if (spec) {
+  r.spec = r.allow_spec && c->opt.spec && c->pred_m_ok && (c->pred_n == r.n || c->pred_n == 0xffffffffu) && c->m_cap > 0 && c->m_cap <= r.limit;
+  if (r.spec) {
+    unsigned long long *acc = (unsigned long long *)c->stats.p + CM_ST_TOTAL;
     HIPCHECK(c, hipMemsetAsync(acc, 0, 8, s));
     cm_launch_k_sum_u32(d.m_tot, n2, acc, s);
     cm_scan_u32(d.m_tot, d.m_off, n2, (uint32_t *)c->scan_tmp.p, s);
     cm_launch_k_check_cap(acc, c->m_cap, (unsigned long long *)c->stats.p + CM_ST_ABORT, s);
-    n_m = (uint32_t)c->m_cap;
+    r.n_m = (uint32_t)c->m_cap;
   } else {
-    if ((rc = scan_with_total(c, d.m_tot, d.m_off, n2, &m_total))) return rc;
-    if (m_total > limit) return CM_RC_SPLIT;
+    const int rc = scan_with_total(c, d.m_tot, d.m_off, n2, &m_total);
+    if (rc) return rc;
+    if (m_total > r.limit) return CM_RC_SPLIT;
     uint64_t want = m_total + m_total / 4 + 1024;  // room for the next batch
-    if (want > limit) want = limit;
+    if (want > r.limit) want = r.limit;
     if (want < m_total) want = m_total;
-    n_m = (uint32_t)want;
-    if (cm_ensure_candidate_arrays(c, n_m)) {
-      cm_set_error(c, "out of device memory (candidates)");
-      return CMGPU_ENOMEM;
-    }
-    c->m_cap = n_m;
+    r.n_m = (uint32_t)want;
+    if (cm_ensure_candidate_arrays(c, r.n_m)) { cm_set_error(c, "out of device memory (candidates)"); return CMGPU_ENOMEM; }
+    c->m_cap = r.n_m;
   }
-  if (cm_debug_pool()) fprintf(stderr, "spec %d m_cap %llu m_total %llu\n", (int)spec, (unsigned long long)c->m_cap, (unsigned long long)m_total);
-  cm_fill_dev_range(c, d, rlo, rhi);
+  if (cm_debug_pool()) fprintf(stderr, "spec %d m_cap %llu m_total %llu\n", (int)r.spec, (unsigned long long)c->m_cap, m_total);
+  r.bind();
   mark(c, "s4a_rescue_count");
-  cm_launch_k_s4b_rescue_merge(d, n2, s, (c->opt_coop & 2) != 0, c->max_read_len);
-  cm_launch_k_s4b_rescue_list(d, n2, s, (c->opt_coop & 2) != 0, c->max_read_len);
+  cm_launch_k_s4b_rescue_merge(d, n2, s, coop, c->max_read_len);
+  cm_launch_k_s4b_rescue_list(d, n2, s, coop, c->max_read_len);
   mark(c, "s4b_rescue_merge");
   HIPCHECK(c, hipMemsetAsync(c->srt_cnt.p, 0, 8, s));
-  cm_launch_k_s4c_reduce(d, n, s, (uint32_t)c->opt_coop & (c->p.split ? ~8u : ~0u));
+  cm_launch_k_s4c_reduce(d, r.n, s, (uint32_t)c->opt.coop & (c->p.split ? ~8u : ~0u));
   if (c->use_perm) cm_launch_k_sort_lists(d, 0, s);  // long candidate lists: a wave each, before S5a wants them in order
   mark(c, "s4c_pair_filter");
-  // S5: verification -- (a) shortcut / sort + work-item counts, (b) one banded alignment per
-  // candidate, (c) the sequential acceptance loop per read
-  if (planes) {  // (split alignments are verified in S5a already)
-    HIPCHECK(c, hipStreamWaitEvent(s, c->chunk_ev[0], 0));  // k_pack_reads (second stream) is done
-    d.read_pl = (uint32_t *)c->read_planes.p; d.read_pl_w = (c->max_read_len + 31) / 32;
-  }
-  cm_launch_k_s5a_prepare(d, n2, s, (c->opt_coop & 8) != 0 && !c->p.split);
-  cm_scan_u32(d.nv, d.v_off, n2, (uint32_t *)c->scan_tmp.p, s);  // the items' number stays on the device: never above n_m
+  return CMGPU_OK;
+}
+// S5: verification -- (a) shortcut / sort + work-item counts, (b) one banded alignment per candidate, (c) the sequential
+// acceptance loop per read
+static int stage_s5_verify(RangeRun &r) {
+  cmgpu_ctx *c = r.c; const CmDev &d = r.d; hipStream_t s = r.s;
+  const bool coop = (c->opt.coop & 8) != 0 && !c->p.split;  // (split alignments are verified in S5a already)
+  if (r.planes) HIPCHECK(c, hipStreamWaitEvent(s, c->chunk_ev[0], 0));  // k_pack_reads (its own stream) is done
+  cm_launch_k_s5a_prepare(d, r.n2, s, coop);
+  cm_scan_u32(d.nv, d.v_off, r.n2, (uint32_t *)c->scan_tmp.p, s);  // the items' number stays on the device: never above n_m
   mark(c, "s5a_prepare");
-  cm_launch_k_s5b_verify(d, n_m, n2, s);
+  cm_launch_k_s5b_verify(d, r.n_m, r.n2, s);
   mark(c, "s5b_verify");
   HIPCHECK(c, hipMemsetAsync(c->srt_cnt.p, 0, 8, s));
-  cm_launch_k_s5c_finalize(d, n2, s, (c->opt_coop & 8) != 0 && !c->p.split);
+  cm_launch_k_s5c_finalize(d, r.n2, s, coop);
   if (c->use_perm) cm_launch_k_sort_lists(d, 1, s);  // long draft-mapping lists, before S6a pairs them
   mark(c, "s5c_accept");
-  // S6: best pair, sampling of multi-mappers, records
+  return CMGPU_OK;
+}
+// S6: best pair, sampling of multi-mappers, records
+static int stage_s6_records(RangeRun &r) {
+  cmgpu_ctx *c = r.c; CmDev &d = r.d; hipStream_t s = r.s;
+  const uint32_t n = r.n;
+  const bool coop = (c->opt.coop & 16) != 0;
   if (c->p.sam) {  // per-slot record / CIGAR / MD pools and the backtrack cells of one alignment per pair
     // the slot pools hold the whole batch (cmgpu_map_resident sized them); this range's slots start at slot0
-    const uint64_t slots = c->single ? n : n2, slot0 = c->single ? rlo : 2ull * rlo;
+    const uint64_t slots = c->single ? n : r.n2, slot0 = c->single ? r.rlo : 2ull * r.rlo;
     const uint32_t md_cap = c->sam_md_cap;
     const uint32_t zw = (2 * c->p.e + 2 <= 18) ? 5 : 8;
     if (c->sam_z.ensure((size_t)c->max_read_len * zw * 4 * n + 16)) { cm_set_error(c, "out of device memory (SAM buffers)"); return CMGPU_ENOMEM; }
@@ -1168,13 +1183,18 @@ static int map_range(cmgpu_ctx *c, uint32_t rlo, uint32_t rhi, uint64_t *k_out, 
     d.sam_md = (uint8_t *)c->sam_md.p + slot0 * md_cap;
     d.sam_z = (uint32_t *)c->sam_z.p; d.sam_md_cap = md_cap;
   }
-  if (c->p.sam) cm_launch_k_s6a_pair_sam(d, n, s); else cm_launch_k_s6a_pair(d, n, s, (c->opt_coop & 16) != 0);
+  if (c->p.sam) cm_launch_k_s6a_pair_sam(d, n, s); else cm_launch_k_s6a_pair(d, n, s, coop);
   mark(c, "s6a_pairing");
   const uint32_t n_chunks = cm_num_chunks_host(n, (uint32_t)c->p.ref_batch, (uint32_t)c->p.grain);
   cm_launch_k_s6b_sample(d, n_chunks, s);
-  if (c->p.sam) cm_launch_k_s6c_multi_sam(d, n, s); else cm_launch_k_s6c_multi(d, n, s, (c->opt_coop & 16) != 0);
+  if (c->p.sam) cm_launch_k_s6c_multi_sam(d, n, s); else cm_launch_k_s6c_multi(d, n, s, coop);
   mark(c, "s6bc_multimappers");
-  cm_launch_k_stats(d, n, (unsigned long long *)c->partials.p, s);
+  return CMGPU_OK;
+}
+// the range's counters come back: is it done, or to be mapped again?  Then the launch set ages and the statistics add up
+static int stage_finish(RangeRun &r, uint64_t *k_out, cmgpu_stats *stats) {
+  cmgpu_ctx *c = r.c; hipStream_t s = r.s;
+  cm_launch_k_stats(r.d, r.n, (unsigned long long *)c->partials.p, s);
   unsigned long long hst[CM_ST_N];
   uint32_t h_cls[CM_HV_LISTS];
   HIPCHECK(c, hipMemcpyAsync(hst, c->stats.p, sizeof(hst), hipMemcpyDeviceToHost, s));
@@ -1182,51 +1202,64 @@ static int map_range(cmgpu_ctx *c, uint32_t rlo, uint32_t rhi, uint64_t *k_out, 
   HIPCHECK(c, cm_stream_sync(s));
   mark(c, "stats");
   HIPCHECK(c, cm_stream_sync(s));
-  {  // speculative launch set: a class with items whose kernels were not launched -> the range again with every class on
-    unsigned long long seen = 0;
+  const bool aborted = r.spec && hst[CM_ST_ABORT];  // this batch needs more room than the previous one left
+  if (!aborted) {  // speculative launch set: a class with items whose kernels were not launched -> the range again with every class on
+    unsigned long long seen = 0, keep = 0;
     for (uint32_t l = 6; l < CM_HV_LISTS; ++l) if (h_cls[l]) seen |= 1ull << (l == 31 ? 23 : l);  // (list 31's kernels are launched with list 23's)
-    const unsigned long long launched = c->cls_all || !c->opt_spec ? ~0ull : c->cls_seen;
-    if (!(spec && hst[CM_ST_ABORT]) && (seen & ~launched)) {
-      c->cls_all = true;
-      const int rc2 = map_range(c, rlo, rhi, k_out, stats, allow_spec);
-      c->cls_all = false;
-      return rc2;
+    if (seen & ~r.d.cls_mask) return CM_RC_AGAIN_ALL_CLASSES;
+    for (uint32_t l = 0; l < 64; ++l) {
+      if ((seen >> l) & 1ull) c->cls_age[l] = 32; else if (c->cls_age[l]) --c->cls_age[l];
+      if (c->cls_age[l]) keep |= 1ull << l;
     }
-    if (!(spec && hst[CM_ST_ABORT])) {
-      unsigned long long keep = 0;
-      for (uint32_t l = 0; l < 64; ++l) {
-        if ((seen >> l) & 1ull) c->cls_age[l] = 32; else if (c->cls_age[l]) --c->cls_age[l];
-        if (c->cls_age[l]) keep |= 1ull << l;
-      }
-      c->cls_seen = keep;
-    }
-  }
-  if (spec && hst[CM_ST_ABORT]) {  // this batch needs more room than the previous one left: again, with its own totals
+    c->cls_seen = keep;
+  } else {  // (an aborted range's lists say nothing: the launch set stays)
     c->pred_m_ok = false;
-    return map_range(c, rlo, rhi, k_out, stats, false);
+    return CM_RC_AGAIN_EXACT_SIZES;
   }
   c->pred_m_ok = true;
-  c->pred_n = n;
+  c->pred_n = r.n;
   c->rs_pool_want = hst[CM_ST_POOL];
   if (cm_debug_pool()) fprintf(stderr, "pool: cap %u entries, asked %llu\n", c->rs_pool_cap, (unsigned long long)hst[CM_ST_POOL]);
   if (hst[CM_ST_ERR]) { cm_set_error(c, "internal device error flag " + std::to_string((unsigned long long)hst[CM_ST_ERR])); return CMGPU_ECAPACITY; }
   *k_out = hst[CM_ST_RECORDS];
-  c->last_range_lo = rlo; c->last_range_hi = rhi;
-  c->last_n_mm = n_mm; c->last_n_hits = n_hits; c->last_n_cand_cap = n_m;
+  c->last_range_lo = r.rlo; c->last_range_hi = r.rhi;
+  c->last_n_mm = r.n_mm; c->last_n_hits = r.n_hits; c->last_n_cand_cap = r.n_m;
   if (stats) {
-    stats->num_candidates += hst[CM_ST_CAND];
-    stats->num_mappings += hst[CM_ST_MAPPINGS];
-    stats->num_mapped_reads += hst[CM_ST_MAPPED];
-    stats->num_uniquely_mapped_reads += hst[CM_ST_UNIQ];
-    stats->num_minimizers += n_mm;
-    stats->probe_steps += hst[CM_ST_PROBE_STEPS];
-    stats->occurrences_read += hst[CM_ST_OCC];
-    stats->num_pairs_rescued += hst[CM_ST_RESCUED];
-    stats->num_multi_mappers += hst[CM_ST_MULTI];
-    stats->num_barcode_in_whitelist += hst[CM_ST_BC_INWL];
-    stats->num_corrected_barcode += hst[CM_ST_BC_CORR];
+    stats->num_candidates += hst[CM_ST_CAND]; stats->num_mappings += hst[CM_ST_MAPPINGS];
+    stats->num_mapped_reads += hst[CM_ST_MAPPED]; stats->num_uniquely_mapped_reads += hst[CM_ST_UNIQ];
+    stats->num_minimizers += r.n_mm; stats->probe_steps += hst[CM_ST_PROBE_STEPS]; stats->occurrences_read += hst[CM_ST_OCC];
+    stats->num_pairs_rescued += hst[CM_ST_RESCUED]; stats->num_multi_mappers += hst[CM_ST_MULTI];
+    stats->num_barcode_in_whitelist += hst[CM_ST_BC_INWL]; stats->num_corrected_barcode += hst[CM_ST_BC_CORR];
   }
   return CMGPU_OK;
+}
+// The pipeline on pairs [rlo, rhi) of the resident batch.  Four small device->host reads size the variable-length intermediates
+// (minimizers, hits, candidate capacity, verification items).  A range that found items in a long-list class whose kernels it
+// had not launched, or that outgrew the candidate arrays it took over from the previous batch, goes through once more
+static int map_range(cmgpu_ctx *c, uint32_t rlo, uint32_t rhi, uint64_t *k_out, cmgpu_stats *stats) {
+  bool allow_spec = true;
+  int rc;
+  *k_out = 0;
+  for (;;) {
+    RangeRun r = {c, rlo, rhi, rhi - rlo, 2 * (rhi - rlo), allow_spec, c->opt.item_limit, c->stream};
+    rc = stage_begin(r);
+    if (!rc) {
+      const bool flat = c->opt.prep_kernel == 1 && cm_prep_flat_supported(r.d, c->max_read_len, (uint32_t)c->opt.prep_tile_reads);
+      const bool fused = flat || (cm_prep_mm_supported(r.d, c->max_read_len) && (c->max_read_len <= 69 || c->opt.long_fused));
+      rc = fused ? stage_minimizers_fused(r, flat) : stage_minimizers_two_pass(r);
+    }
+    if (!rc) rc = stage_pack_reads(r);
+    if (!rc) rc = stage_s3_candidates(r);
+    if (!rc) rc = stage_s4_rescue_filter(r);
+    if (!rc) rc = stage_s5_verify(r);
+    if (!rc) rc = stage_s6_records(r);
+    if (!rc) rc = stage_finish(r, k_out, stats);
+    if (rc == CM_RC_AGAIN_ALL_CLASSES) c->cls_all = true;
+    else if (rc == CM_RC_AGAIN_EXACT_SIZES) allow_spec = false;
+    else break;
+  }
+  c->cls_all = false;  // (this range's re-run only)
+  return rc;
 }
 
 // pairs [lo, hi): as one range, or -- when a dense intermediate would pass the item limit -- as two halves cut on a
@@ -1239,7 +1272,7 @@ static int map_split(cmgpu_ctx *c, uint32_t lo, uint32_t hi, uint64_t *k_total, 
   //  context only grow, the other lanes keep theirs, and a 16 M-pair call on the profile-2 genome failed just the same: DESIGN.md 9-4)
   if (rc != CM_RC_SPLIT) { *k_total += k; return rc; }
   if (n <= rb) {
-    cm_set_error(c, "a reference batch of " + std::to_string(n) + " pairs needs more than " + std::to_string((unsigned long long)c->opt_item_limit) +
+    cm_set_error(c, "a reference batch of " + std::to_string(n) + " pairs needs more than " + std::to_string((unsigned long long)c->opt.item_limit) +
                         " entries in one intermediate array (hits / candidates)");
     return CMGPU_ECAPACITY;
   }
@@ -1263,7 +1296,7 @@ static int lane_prepare(cmgpu_ctx *c, size_t i) {
   cmgpu_ctx *l = c->lanes[i];
   auto view = [](DevBuf &dst, const DevBuf &src) { dst.p = src.p; dst.cap = src.cap; dst.owned = false; };
   view(l->bkt_fast, c->bkt_fast); l->fmask = c->fmask;
-  view(l->ref_planes, c->ref_planes); l->ref_pl_words = c->ref_pl_words; l->opt_planes = c->opt_planes; l->opt_long_fused = c->opt_long_fused;
+  view(l->ref_planes, c->ref_planes); l->ref_pl_words = c->ref_pl_words;
   view(l->rb0, c->rb0); view(l->rb1, c->rb1); view(l->ro0, c->ro0); view(l->ro1, c->ro1);
   view(l->rec, c->rec); view(l->rec_ok, c->rec_ok);
   view(l->bcb, c->bcb); view(l->bcq, c->bcq); view(l->bco, c->bco); view(l->bc_key, c->bc_key); view(l->bc_ok, c->bc_ok);
@@ -1273,9 +1306,7 @@ static int lane_prepare(cmgpu_ctx *c, size_t i) {
   l->n_pairs = c->n_pairs; l->first_read_id = c->first_read_id; l->bases0 = c->bases0; l->bases1 = c->bases1;
   l->max_read_len = c->max_read_len; l->has_barcodes = c->has_barcodes; l->single = c->single;
   l->sam_slots = c->sam_slots; l->sam_md_cap = c->sam_md_cap;
-  l->opt_probe_variant = c->opt_probe_variant; l->opt_mm_chunks = c->opt_mm_chunks; l->opt_prep_kernel = c->opt_prep_kernel;
-  l->opt_s3b_cap = c->opt_s3b_cap; l->opt_prep_tile_reads = c->opt_prep_tile_reads; l->opt_item_limit = c->opt_item_limit; l->opt_heavy_last = c->opt_heavy_last; l->opt_heavy_mid = c->opt_heavy_mid; l->opt_coop = c->opt_coop; l->opt_coop_rb = c->opt_coop_rb; l->opt_spec = c->opt_spec;
-  for (int q = 0; q < 3; ++q) l->opt_heavy_max[q] = c->opt_heavy_max[q];
+  l->opt = c->opt;  // (`lanes` is never read in a lane: the lane threads call map_split directly)
   return CMGPU_OK;
 }
 
@@ -1308,17 +1339,17 @@ extern "C" int cmgpu_map_resident(cmgpu_ctx *c, uint64_t *n_out, cmgpu_stats *st
     c->sam_slots = slots;
     c->sam_md_cap = md_cap;
   }
-  if (c->opt_planes && !c->ref_pl_words && c->ref_bytes) {  // once per reference: its bit planes (k_s5b_verify)
+  if (c->opt.planes && !c->ref_pl_words && c->ref_bytes) {  // once per reference: its bit planes (k_s5b_verify)
     const int rc = cm_build_ref_planes(c);
     if (rc == CMGPU_ENOMEM) {  // no room for them: the alignments run on the bytes (same results, slower)
-      c->ref_planes.release(); c->ref_pl_words = 0; c->opt_planes = 0;
+      c->ref_planes.release(); c->ref_pl_words = 0; c->opt.planes = 0;
       fprintf(stderr, "chromap_amd: no device memory for the reference bit planes, verifying on bytes\n");
     } else if (rc) return rc;
   }
-  // Lanes: the batch cut on reference-batch boundaries into up to opt_lanes ranges that are mapped side by side, each on
+  // Lanes: the batch cut on reference-batch boundaries into up to `lanes` (cmgpu_set_option) ranges that are mapped side by side, each on
   // its own streams with its own intermediates -- the latency-bound stages of one range fill the gaps of the others'.
   const uint32_t rb = (uint32_t)c->p.ref_batch;
-  uint32_t L = (uint32_t)(c->opt_lanes < 1 ? 1 : c->opt_lanes);
+  uint32_t L = (uint32_t)(c->opt.lanes < 1 ? 1 : c->opt.lanes);
   const uint32_t n_rb = (n + rb - 1) / rb;
   if (L > n_rb) L = n_rb;
   if (n < (1u << 20)) L = 1;
@@ -1361,17 +1392,19 @@ extern "C" int cmgpu_map_resident(cmgpu_ctx *c, uint64_t *n_out, cmgpu_stats *st
   return CMGPU_OK;
 }
 
-// the batch's records, compacted on the device, in one copy (the order of the pairs is kept)
-__global__ void k_rec_flag2(const uint8_t *ok, uint32_t *flag, uint32_t n) {
+// the batch's records, compacted on the device, in one copy (the order of the pairs is kept; at most `cap` records are written)
+__global__ void k_rec_flag(const uint8_t *ok, uint32_t *flag, uint32_t n) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) flag[i] = ok[i];
 }
-__global__ void k_rec_compact2(const uint8_t *__restrict__ rec, const uint8_t *__restrict__ ok, const uint32_t *__restrict__ pos,
-                               uint8_t *__restrict__ dst, uint32_t n) {
+__global__ void k_rec_compact(const uint8_t *__restrict__ rec, const uint8_t *__restrict__ ok,
+                              const uint32_t *__restrict__ pos, uint8_t *__restrict__ dst, uint32_t n, uint64_t cap) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n || !ok[i]) return;
+  const uint32_t o = pos[i];
+  if (o >= cap) return;
   const uint64_t *s = reinterpret_cast<const uint64_t *>(rec + (uint64_t)i * 24);
-  uint64_t *d = reinterpret_cast<uint64_t *>(dst + (uint64_t)pos[i] * 24);
+  uint64_t *d = reinterpret_cast<uint64_t *>(dst + (uint64_t)o * 24);
   d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
 }
 // the resident batch's records, compacted into `dst` on the mapping stream (pair order kept); nothing is waited for
@@ -1382,10 +1415,10 @@ static int compact_records(cmgpu_ctx *c, DevBuf &dst) {
   if (dst.ensure((size_t)n * 24 + 16)) { cm_set_error(c, "out of device memory (records)"); return CMGPU_ENOMEM; }
   uint32_t *flag = (uint32_t *)c->scratch_a.p, *pos = (uint32_t *)c->scratch_b.p;  // free between batches
   hipStream_t s = c->stream;
-  hipLaunchKernelGGL(k_rec_flag2, dim3((n + 255) / 256), dim3(256), 0, s, (const uint8_t *)c->rec_ok.p, flag, n);
+  hipLaunchKernelGGL(k_rec_flag, dim3((n + 255) / 256), dim3(256), 0, s, (const uint8_t *)c->rec_ok.p, flag, n);
   cm_scan_u32(flag, pos, n, (uint32_t *)c->scan_tmp.p, s);
-  hipLaunchKernelGGL(k_rec_compact2, dim3((n + 255) / 256), dim3(256), 0, s, (const uint8_t *)c->rec.p, (const uint8_t *)c->rec_ok.p,
-                     (const uint32_t *)pos, (uint8_t *)dst.p, n);
+  hipLaunchKernelGGL(k_rec_compact, dim3((n + 255) / 256), dim3(256), 0, s, (const uint8_t *)c->rec.p, (const uint8_t *)c->rec_ok.p,
+                     (const uint32_t *)pos, (uint8_t *)dst.p, n, (uint64_t)n);
   return CMGPU_OK;
 }
 static int download_dense(cmgpu_ctx *c, cmgpu_record *out, uint64_t out_capacity, uint64_t *n_out) {
@@ -1744,21 +1777,6 @@ extern "C" int cmgpu_export_index(cmgpu_ctx *c, uint64_t *buckets_out, uint64_t 
 // dense copy of the resident records into a caller-provided DEVICE buffer (e.g. a torch
 // tensor's data_ptr) for the multi-GPU record exchange
 // ---------------------------------------------------------------------------------------
-__global__ void k_rec_flag(const uint8_t *ok, uint32_t *flag, uint32_t n) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) flag[i] = ok[i];
-}
-__global__ void k_rec_compact(const uint8_t *__restrict__ rec, const uint8_t *__restrict__ ok,
-                              const uint32_t *__restrict__ pos, uint8_t *__restrict__ dst, uint32_t n, uint64_t cap) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n || !ok[i]) return;
-  const uint32_t o = pos[i];
-  if (o >= cap) return;
-  const uint64_t *s = reinterpret_cast<const uint64_t *>(rec + (uint64_t)i * 24);
-  uint64_t *d = reinterpret_cast<uint64_t *>(dst + (uint64_t)o * 24);
-  d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
-}
-
 extern "C" int cmgpu_records_to_device(cmgpu_ctx *c, void *device_dst, uint64_t capacity, uint64_t *n_out) {
   if (!c || !device_dst || !n_out) return CMGPU_EINVAL;
   HIPCHECK(c, cm_enter(c));

@@ -107,7 +107,35 @@ struct CmBatchSlot {
   size_t bases0 = 0, bases1 = 0;
 };
 
+// cmgpu_set_option: the knobs of one context.  The lanes of a context take the whole struct (lane_prepare, cm_api.hip)
+struct CmOptions {
+  int long_fused = 1;          // reads longer than 69 bases: 1 the fused minimizer kernel (cmgpu_ctx::mm_stage), 0 the two-pass kernels
+  int planes = 1;              // k_s5b_verify aligns on bit planes (0: on the reference / read bytes)
+  int sam_group = 8;           // lanes that render one SAM line (k_sp_format: 8, 16 or 64; 11.8 / 15.7 / 33.4 ms for 4.8 GB of text in profiles/r08a_sam_kernel_stats.csv)
+  int d2h_kernel = 0;
+  int h2d_kernel = 0;          // blocks of k_host_copy for uploads from page-locked memory; 0 = hipMemcpyAsync (measured faster: the copy
+                               // kernel's waves slow the mapping kernels more than the copy engine's lower rate costs)
+  int probe_variant = 1;       // lookups per lane | 16: second probe step requested with the first (measured: more requests in
+                               // flight per lane only slow the probe down -- the table's random-access rate is the bound)
+  int mm_chunks = CM_MM_CHUNKS;
+  int prep_tile_reads = 32;    // reads per tile of the position-parallel minimizer kernel
+  int prep_kernel = 0;         // 0: lane-per-read minimizer kernels; 1: the position-parallel kernel where it applies (k_prep_flat:
+                               // half the instructions, but 7 barriers + one global reservation per tile -- measured slower)
+  uint64_t item_limit = 0xfffffff0ull;
+  int exchange_overlap = 0;    // exchange payload on a stream of its own (under the next batch's kernels)
+  int s3b_cap = 0;             // 0: by read length (cm_s3b_lane_cap)
+  int lanes = 1;               // sub-batches of one cmgpu_map_* call mapped side by side (own streams and intermediates each)
+  int heavy_mid = 0;           // 0: 64 hits (96 for reads of 100 bases and more); -1: no 16-lane class
+  int heavy_max[3] = {0, 0, 0};  // size classes of the cooperative hit-list kernel (0: the kernel's own)
+  int heavy_last = 0;          // heavy-last processing order: 0 auto, 1 always, -1 never
+  int spec = 1;                // candidate arrays sized from the previous batch (cmgpu_ctx::pred_m_ok); 0: every batch waits for its totals
+  int coop_rb = 0;             // tests: run-table size of the cooperative sorters (0: their own)
+  int coop = 0xff;             // cooperative (group per item, cm_coop.h) forms of the stages for long lists: bit 0 S3b hit lists,
+                               // 1 S4b rescue hits, 2 S4c pair filter, 3 S5c acceptance, 4 S6 pairing; 0: the round-2 kernels
+};
+
 struct cmgpu_ctx {
+  CmOptions opt;
   int device = 0;
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;     // index probe of chunk c runs here next to the minimizer pass of chunk c+1
@@ -129,9 +157,7 @@ struct cmgpu_ctx {
   // reads longer than 69 bases: k_prep_mm's emissions staged in global memory (one tile per block of a launch); cmgpu_set_option
   // "long_read_fused" 0: the two-pass kernels with their scan and host waits (the round-2 form)
   DevBuf mm_stage;
-  int opt_long_fused = 1;
   uint64_t ref_pl_words = 0;
-  int opt_planes = 1;
   int n_break = 0;
   uint64_t ref_bytes = 0;
   std::vector<uint64_t> h_ref_off;
@@ -176,7 +202,6 @@ struct cmgpu_ctx {
   uint32_t rd_base = 0;
   bool rd_paired = false;
   CmSamStore ss;
-  int opt_sam_group = 8;   // lanes that render one SAM line (k_sp_format: 8, 16 or 64; 11.8 / 15.7 / 33.4 ms for 4.8 GB of text in profiles/r08a_sam_kernel_stats.csv)
   // --SAM outputs of the last batch (cm_stages.h: cm_ref_start_end_sam)
   DevBuf sam_rec, sam_cigar, sam_md, sam_z;
   DevBuf pairs_rank;
@@ -203,9 +228,6 @@ struct cmgpu_ctx {
   // pipelined host-buffer entry (cmgpu_submit_pairs / cmgpu_map_submitted): the next batch is uploaded on a copy stream into the
   // last parking slot while the current one is mapped
   hipStream_t stream_h2d = nullptr;
-  int opt_d2h_kernel = 0;
-  int opt_h2d_kernel = 0;   // blocks of k_host_copy for uploads from page-locked memory; 0 = hipMemcpyAsync (measured faster: the copy
-                            // kernel's waves slow the mapping kernels more than the copy engine's lower rate costs)
   hipEvent_t ev_h2d[2] = {nullptr, nullptr};
   uint32_t sub_total = 0, sub_count = 0;  // batches submitted so far / submitted and not yet mapped (<= 2: parking slots 6 and 7 take turns)
   DevBuf rec_dense, maxlen_dev;
@@ -217,31 +239,13 @@ struct cmgpu_ctx {
   uint64_t pend_k[2] = {0, 0};
   uint32_t pend_total = 0, pend_count = 0;
   uint32_t *h_maxlen = nullptr;  // pinned: longest read of the submitted batch, computed on the device
-  // cmgpu_set_option
-  int opt_probe_variant = 1;       // lookups per lane | 16: second probe step requested with the first (measured: more requests in
-                                   // flight per lane only slow the probe down -- the table's random-access rate is the bound)
-  int opt_mm_chunks = CM_MM_CHUNKS;
-  int opt_prep_tile_reads = 32;    // reads per tile of the position-parallel minimizer kernel
-  int opt_prep_kernel = 0;         // 0: lane-per-read minimizer kernels; 1: the position-parallel kernel where it applies (k_prep_flat:
-                                   // half the instructions, but 7 barriers + one global reservation per tile -- measured slower)
-  uint64_t opt_item_limit = 0xfffffff0ull;
-  int opt_exchange_overlap = 0;      // exchange payload on a stream of its own (under the next batch's kernels)
-  int opt_s3b_cap = 0;               // 0: by read length (cm_s3b_lane_cap)
-  int opt_lanes = 1;                 // sub-batches of one cmgpu_map_* call mapped side by side (own streams and intermediates each)
   std::vector<cmgpu_ctx *> lanes;    // the further lanes' contexts (views of this context's index, reference, batch and record arrays)
   int shared_children = 0;           // contexts made by cmgpu_create_shared that view this one's buffers (the lanes among them refresh their views)
   cmgpu_ctx *shared_parent = nullptr;
-  int opt_heavy_mid = 0;             // 0: 64 hits (96 for reads of 100 bases and more); -1: no 16-lane class
-  int opt_heavy_max[3] = {0, 0, 0};  // size classes of the cooperative hit-list kernel (0: the kernel's own)
-  int opt_heavy_last = 0;            // heavy-last processing order: 0 auto, 1 always, -1 never
   // candidate arrays sized from the previous batch of the same size (+ 25 %): no host wait for their total; the device checks it
   bool pred_m_ok = false;
   uint32_t pred_n = 0;
   uint64_t m_cap = 0;
-  int opt_spec = 1;                  // 0: every batch waits for its totals
-  int opt_coop_rb = 0;               // tests: run-table size of the cooperative sorters (0: their own)
-  int opt_coop = 0xff;               // cooperative (group per item, cm_coop.h) forms of the stages for long lists: bit 0 S3b hit lists,
-                                     // 1 S4b rescue hits, 2 S4c pair filter, 3 S5c acceptance, 4 S6 pairing; 0: the round-2 kernels
   std::vector<uint32_t> h_rank;  // --chr-order: rank of every index rid (host copy of rid_rank)
   uint64_t sam_slots = 0;
   uint32_t sam_md_cap = 0;
@@ -295,7 +299,6 @@ static inline hipError_t cm_stream_sync(hipStream_t s) {
   return e != hipSuccess ? e : l;
 }
 int cm_ctx_init_common(cmgpu_ctx *c, const cmgpu_params *params, int kmer, int window, int device_id);
-void cm_fill_dev(cmgpu_ctx *c, CmDev &d);
 int cm_upload_reference(cmgpu_ctx *c, const cmgpu_ref_view *ref);
 int cm_build_ref_planes(cmgpu_ctx *c);
 // the probe table re-hashed into 2^shift times the buckets (0: released)

@@ -544,7 +544,7 @@ extern "C" int cmgpu_exchange_step(cmgpu_ctx *c, uint64_t *sent_per_rank, uint64
     // send buffer and the store's tail are its only operands; both are guarded above and in cm_exchange_quiesce) --
     // measured slower on one GPU with several lanes mapping beside it, so it is not the default.
     const RcclApi *api = rccl_api();
-    const bool overlap = c->opt_exchange_overlap != 0;
+    const bool overlap = c->opt.exchange_overlap != 0;
     hipStream_t ps = overlap ? x.stream : s;
     if (overlap) {
       EXCHECK(c, hipEventRecord(x.ev_part, s));

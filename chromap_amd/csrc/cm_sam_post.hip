@@ -488,7 +488,7 @@ extern "C" int cmgpu_store_format_sam(cmgpu_ctx *c, const char *const *ref_names
   // (the sort's buffers go before the text comes: a realistic run's text is several GB)
   k0.release(); k1.release(); vb == (uint32_t *)v0.p ? v0.release() : v1.release(); tmp.release();
   if (c->text.ensure(total + 64)) { cm_set_error(c, "out of device memory (SAM text: " + std::to_string((unsigned long long)total) + " bytes)"); return fail(CMGPU_ENOMEM); }
-  const int G = c->opt_sam_group;
+  const int G = c->opt.sam_group;
   const dim3 gf((unsigned)(((uint64_t)n * G + SP_BLOCK - 1) / SP_BLOCK));
 #define SP_LAUNCH(W)                                                                                                                             \
   hipLaunchKernelGGL(k_sp_format<W>, gf, b, 0, s, rec, bc, (const uint8_t *)st.var.p, (const uint64_t *)st.var_offs.p, (const uint32_t *)va, n, cfg, rs, \

@@ -20,6 +20,7 @@ static int g_dbg_force_replay = 0;  // tests: every second minimizer of a round 
 #define CM_DBG_FORCE_REPLAY g_dbg_force_replay
 #include "../../chromap_amd/csrc/cm_coop.h"
 #include "../../chromap_amd/csrc/cm_inflate.h"
+#include "../../chromap_amd/csrc/cm_classes.h"
 #include "emu_group.h"
 
 template <typename T>
@@ -219,7 +220,7 @@ static int emu_map_pairs(const cmgpu_index_view *index, const cmgpu_ref_view *re
   std::vector<uint8_t> refb(tot, 0);
   for (uint32_t i = 0; i < ref->n_sequences; ++i) memcpy(refb.data() + roff[i], ref->sequences[i], ref->lengths[i]);
   d.ref = refb.data(); d.ref_off = roff.data(); d.ref_len = ref->lengths; d.n_seq = ref->n_sequences;
-  std::vector<uint32_t> goff(ref->n_sequences + 1);  // CmDev::goff as cm_fill_dev_range builds it
+  std::vector<uint32_t> goff(ref->n_sequences + 1);  // CmDev::goff as cm_ensure_goff (cm_api.hip) builds it
   {
     uint64_t acc = 0;
     for (uint32_t i = 0; i < ref->n_sequences; ++i) { goff[i] = (uint32_t)acc; acc += (uint64_t)ref->lengths[i] + CM_GOFF_GAP; }
@@ -1235,4 +1236,22 @@ extern "C" int hostemu_bgzf_resolve(uint8_t *win_io, uint32_t isize, const uint3
   }, reverse != 0);
   memcpy(win_io, win.data(), isize);
   return rc;
+}
+
+// the size-class policy (cm_classes.h) on plain integers.  opts: heavy_wave_max, heavy_block_max, heavy_big_max, heavy_mid_max,
+// s3b_lane_cap; lane_cap: cm_s3b_lane_cap(max_read_len); hv_max_in / hv_big_in: what cm_s3b_heavy_classes reports.
+// out: hv_max[0..3], hv_big, rs_max3, rs_big, hv_mid, hv_sub, s3b_cap
+extern "C" void hostemu_size_classes(const int *opts, uint32_t max_read_len, uint32_t lane_cap, uint32_t n_seq, int has_goff,
+                                     const uint32_t *hv_max_in, uint32_t hv_big_in, uint32_t *out) {
+  CmClassIn in = {};
+  for (int q = 0; q < 3; ++q) in.heavy_max[q] = opts[q];
+  in.heavy_mid = opts[3]; in.s3b_cap = opts[4];
+  in.max_read_len = max_read_len; in.lane_cap = lane_cap; in.n_seq = n_seq; in.has_goff = has_goff != 0;
+  for (int q = 0; q < 4; ++q) in.hv_max[q] = hv_max_in[q];
+  in.hv_big = hv_big_in;
+  CmDev d;
+  memset(&d, 0xa5, sizeof(d));  // (every class field is written, whatever the struct held)
+  cm_size_classes(in, d);
+  for (int q = 0; q < 4; ++q) out[q] = d.hv_max[q];
+  out[4] = d.hv_big; out[5] = d.rs_max3; out[6] = d.rs_big; out[7] = d.hv_mid; out[8] = d.hv_sub; out[9] = d.s3b_cap;
 }
