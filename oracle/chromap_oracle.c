@@ -1190,6 +1190,13 @@ static int banded_align_dropoff_3end(int e, const char *pattern, const char *tex
   return min_err;
 }
 
+/* the two drop-off aligners for the tests of the primitives (tests/test_plain_align.py) */
+int ora_banded_align_dropoff(int e, const char *pattern, const char *text, int read_length, int from_3end,
+                             int *mapping_end_position, int *read_mapping_length) {
+  return from_3end ? banded_align_dropoff_3end(e, pattern, text, read_length, mapping_end_position, read_mapping_length)
+                   : banded_align_dropoff(e, pattern, text, read_length, mapping_end_position, read_mapping_length);
+}
+
 /* AdjustGapBeginning (alignment.cc:24-83), non-SAM use (no cigar). strand 0 = +.
  * read is NUL-terminated at read_total_len, ref at ref_len (the loops of the - branch
  * stop on the terminators). */

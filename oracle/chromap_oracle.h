@@ -210,6 +210,9 @@ int ora_banded_align(int e, const char *pattern, const char *text, int read_leng
 /* alignment.cc:656-718 */
 void ora_banded_traceback(int e, int min_num_errors, const char *pattern, const char *text,
                           int read_length, int *mapping_start_position);
+/* alignment.cc:197-283 (from_3end 0) and 285-376 (from_3end 1) */
+int ora_banded_align_dropoff(int e, const char *pattern, const char *text, int read_length, int from_3end,
+                             int *mapping_end_position, int *read_mapping_length);
 
 ora_ctx *ora_create(const ora_index *idx, const ora_ref *ref, const ora_params *p);
 void ora_destroy(ora_ctx *c);

@@ -27,7 +27,12 @@ GEN = os.path.join(ROOT, "tools", "gen_synth.py")
 SINGLE_END = {"s1_se_chip": 1, "s4_se_atac_q0": 2, "s4_se_inmem_q0": 1, "s1_se_sam": 1,
               "b1_se_bc": 1, "b3_se_bc_bulk_q0": 1, "b3_se_bc_inmem_q0": 2, "b1_se_bc_tagalign_q0": 1,
               "s4_se_tagalign_q0": 2, "s4_se_n2_q0": 2, "s4_se_drop2_q0": 2,
-              "p1_se_e5_q0": 1, "p5_se_n5_e5_q0": 2}
+              "p1_se_e5_q0": 1, "p5_se_n5_e5_q0": 2, "x6_gaps_se_sam_q0": 1}
+
+GAPS_CHIP = ["--genome", "300000", "--chroms", "2", "--pairs", "3000", "--readlen", "100", "--varlen", "--seed", "61", "--gap-share", "0.7",
+             "--gap-e", "8"]
+GAPS_HIC = ["--genome", "300000", "--chroms", "2", "--pairs", "3000", "--readlen", "100", "--frag-min", "200", "--frag-max", "500", "--hic",
+            "--seed", "62", "--gap-share", "0.7", "--gap-e", "4"]
 
 # name -> (generator args or None for the toy data, chromap mapping flags)
 CASES = {
@@ -178,6 +183,15 @@ CASES = {
                       "--frag-max", "500", "--hic", "--seed", "22", "--indel", "0.004", "--sub", "0.02"], ["--preset", "hic", "-e", "6", "-q", "0"]),
     "p5_se_n5_e5_q0": (["--genome", "300000", "--chroms", "2", "--pairs", "20000", "--readlen", "50", "--frag-min", "40",
                         "--seed", "5"], ["--preset", "chip", "-n", "5", "-e", "5", "-q", "0"]),
+    # gap-rich reads (tools/gen_synth.py --gap-share: gap runs of up to e bases, gaps in a read's first and last bases, edit sums
+    # around e).  The names sort after every other case: tests that take SAM_CASES[0], HIC_CASES[0] and the like keep their picks.
+    "x1_gaps_q0": (GAPS_CHIP, ["--preset", "chip", "-q", "0"]),
+    "x2_gaps_sam_q0": (GAPS_CHIP, ["--preset", "chip", "--SAM", "-q", "0"]),
+    "x3_gaps_hic_q0": (GAPS_HIC, ["--preset", "hic", "-q", "0"]),
+    "x4_gaps_hic_sam_q0": (GAPS_HIC, ["--preset", "hic", "--SAM", "-q", "0"]),
+    "x5_gaps_e15_sam_q0": (["--genome", "300000", "--chroms", "2", "--pairs", "3000", "--readlen", "150", "--seed", "63", "--gap-share", "0.7",
+                            "--gap-e", "15", "--gap-budget-p", "0.8", "--gap-len-p", "0.8"], ["-e", "15", "--SAM", "-q", "0"]),
+    "x6_gaps_se_sam_q0": (GAPS_CHIP, ["--SAM", "-q", "0"]),
 }
 
 

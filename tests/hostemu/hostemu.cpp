@@ -1255,3 +1255,108 @@ extern "C" void hostemu_size_classes(const int *opts, uint32_t max_read_len, uin
   for (int q = 0; q < 4; ++q) out[q] = d.hv_max[q];
   out[4] = d.hv_big; out[5] = d.rs_max3; out[6] = d.rs_big; out[7] = d.hv_mid; out[8] = d.hv_sub; out[9] = d.s3b_cap;
 }
+
+// ---------------------------------------------------------------------------------------
+// The alignment primitives on batches of (window, text) cases, for tests/test_plain_align.py: n windows of L + 2e bytes and n
+// texts of L bytes (the read AS ALIGNED; for strand 1 the stored read is its reverse complement, made here).  Case c's window
+// is laid into a reference buffer at offset 128 + (c + off0) % 32, so every window offset modulo 32 occurs, between filler
+// bytes; the read buffers are padded as the product's are.
+// ---------------------------------------------------------------------------------------
+namespace {
+struct EmuAlnCase {
+  std::vector<uint64_t> refw, stw;
+  std::vector<CmPlRec> rpv;
+  std::vector<uint32_t> tp;
+  uint8_t *ref = nullptr, *stored = nullptr;
+  CmPlRec *rp = nullptr;
+  uint32_t g = 0, W = 0;
+  static constexpr uint32_t ref_len = 512;
+  void set(uint32_t c, int L, const uint8_t *window, int wlen, const uint8_t *text, int strand, bool planes) {
+    refw.assign(ref_len / 8 + 8, 0);
+    ref = (uint8_t *)refw.data();
+    g = 128 + c % 32;
+    for (uint32_t i = 0; i < ref_len; ++i) ref[i] = (uint8_t)"ACGTNacgt"[(i * 7 + c) % 9];
+    memcpy(ref + g, window, (size_t)wlen);
+    stw.assign(((size_t)L + 31) / 8 + 3, 0);
+    stored = (uint8_t *)stw.data();
+    for (int i = 0; i < L; ++i) stored[i] = strand ? cm_negchar(text[L - 1 - i]) : text[i];
+    if (!planes) return;
+    rpv.assign((size_t)ref_len / 32 + 4 + CM_PL_LEAD, CmPlRec{0u, 0u, 0u, 0u});
+    rp = rpv.data() + CM_PL_LEAD;
+    for (uint32_t w = 0; w * 32 < ref_len; ++w) cm_pack_planes32(ref + 32 * w, ref_len - 32 * w, &rp[w].p0, &rp[w].p1, &rp[w].pn, &rp[w].pc);
+    CmDev d;
+    memset(&d, 0, sizeof(d));
+    uint32_t rlen[2] = {(uint32_t)L, 0};
+    uint32_t ro[3] = {0, (uint32_t)L, (uint32_t)L};
+    d.rlen = rlen; d.rb0 = stored; d.rb1 = stored; d.ro0 = ro; d.ro1 = ro;
+    W = ((uint32_t)L + 31) / 32;
+    tp.assign((size_t)cm_read_pl_stride(W) + 8, 0x5A5A5A5Au);
+    d.read_pl = tp.data(); d.read_pl_w = W;
+    cm_pack_read_planes(d, 0);
+  }
+};
+}  // namespace
+
+// cm_banded_align (planes == 0) / cm_banded_align_planes (planes == 1); end_out is -1 where the function left it unset
+extern "C" void hostemu_band_batch(int e, int L, uint32_t n, uint32_t off0, const uint8_t *windows, const uint8_t *texts, int strand,
+                                   int planes, int32_t *err_out, int32_t *end_out) {
+  EmuAlnCase k;
+  const int wl = L + 2 * e;
+  for (uint32_t c = 0; c < n; ++c) {
+    k.set(c + off0, L, windows + (size_t)c * wl, wl, texts + (size_t)c * L, strand, planes != 0);
+    int end = -1;
+    err_out[c] = planes ? cm_banded_align_planes(e, k.rp, k.g, k.tp.data() + (size_t)strand * 3 * k.W, k.W, L, &end)
+                        : cm_banded_align(e, k.ref + k.g, k.stored, L, strand == 1, 0, L, &end);
+    end_out[c] = end;
+  }
+}
+
+// cm_banded_traceback with the distances errs[c]
+extern "C" void hostemu_traceback_batch(int e, int L, uint32_t n, uint32_t off0, const uint8_t *windows, const uint8_t *texts, int strand,
+                                        const int32_t *errs, int32_t *start_out) {
+  EmuAlnCase k;
+  const int wl = L + 2 * e;
+  for (uint32_t c = 0; c < n; ++c) {
+    k.set(c + off0, L, windows + (size_t)c * wl, wl, texts + (size_t)c * L, strand, false);
+    start_out[c] = cm_banded_traceback(e, errs[c], k.ref + k.g, k.stored, L, strand == 1, 0, L);
+  }
+}
+
+// the four calls of cm_draft_strand_split, allow = 20 - e: shape 0: + strand, whole read; 1: + strand without the first `allow`
+// bases; 2: - strand from the 3' end, whole read; 3: - strand from the 3' end without the last `allow` bases of the text.
+// planes: cm_banded_align_dropoff_planes, else the byte form.
+extern "C" void hostemu_dropoff_batch(int e, int L, uint32_t n, uint32_t off0, const uint8_t *windows, const uint8_t *texts, int shape,
+                                      int planes, int32_t *err_out, int32_t *end_out, int32_t *len_out) {
+  EmuAlnCase k;
+  const int wl = L + 2 * e, strand = shape >= 2 ? 1 : 0, allow = (shape & 1) ? 20 - e : 0;
+  for (uint32_t c = 0; c < n; ++c) {
+    k.set(c + off0, L, windows + (size_t)c * wl, wl, texts + (size_t)c * L, strand, planes != 0);
+    int end = -1, len = -1, ne;
+    const uint8_t *pat = k.ref + k.g;
+    if (strand == 0) {
+      ne = planes ? cm_banded_align_dropoff_planes<false>(e, k.rp, (uint64_t)k.g + (uint32_t)allow, k.tp.data(), k.W, (uint32_t)allow, L - allow, &end, &len)
+                  : cm_banded_align_dropoff(e, pat + allow, k.stored, L, false, allow, L - allow, false, &end, &len);
+    } else {
+      ne = planes ? cm_banded_align_dropoff_planes<true>(e, k.rp, (uint64_t)k.g + (uint32_t)(L - allow) + 2 * (uint32_t)e - 1, k.tp.data(), k.W, (uint32_t)allow,
+                                                         L - allow, &end, &len)
+                  : cm_banded_align_dropoff(e, pat, k.stored, L, true, 0, L - allow, true, &end, &len);
+    }
+    err_out[c] = ne; end_out[c] = end; len_out[c] = len;
+  }
+}
+
+// cm_ksw_sg3 with the window size cm_ref_start_end_sam picks; cigar_out: CM_SAM_CIGAR_CAP words per case
+extern "C" void hostemu_ksw_batch(int e, int L, uint32_t n, uint32_t off0, const uint8_t *windows, const uint8_t *texts, int strand,
+                                  int32_t *score_out, int32_t *start_out, int32_t *end_out, uint32_t *cigar_out, int32_t *ncigar_out) {
+  EmuAlnCase k;
+  const int wl = L + 2 * e;
+  std::vector<uint32_t> z((size_t)(L > 0 ? L : 1) * 8 + 8);
+  for (uint32_t c = 0; c < n; ++c) {
+    k.set(c + off0, L, windows + (size_t)c * wl, wl, texts + (size_t)c * L, strand, false);
+    uint32_t *cg = cigar_out + (size_t)c * CM_SAM_CIGAR_CAP;
+    int nc = 0, st = -1, en = -1, sc;
+    if (2 * e + 2 <= 18) sc = cm_ksw_sg3<18>(k.ref + k.g, k.stored, L, strand == 1, e, z.data(), 1, cg, &nc, &st, &en);
+    else sc = cm_ksw_sg3<32>(k.ref + k.g, k.stored, L, strand == 1, e, z.data(), 1, cg, &nc, &st, &en);
+    score_out[c] = sc; start_out[c] = st; end_out[c] = en; ncigar_out[c] = nc;
+  }
+}

@@ -22,12 +22,22 @@ def lib():
                [os.path.join(ROOT, "tests", "hostemu", "emu_group.h")] + \
                [os.path.join(ROOT, "chromap_amd", "csrc", f) for f in ("cm_stages.h", "cm_coop.h", "cm_types.h", "cm_host.cpp",
                                                                        "cm_mapq_tables.h", "cm_inflate.h", "cm_classes.h")]
-        if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-            # -fno-strict-aliasing: the stage functions read and write their byte / word arrays through wider types (aligned 8-
-            # and 16-byte accesses), which the device compiler takes as written
-            subprocess.check_call(["g++", "-std=c++17", "-O2", "-g", "-fPIC", "-shared", "-ffp-contract=off", "-fno-strict-aliasing",
-                                   "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-pthread", "-o", so, srcs[0],
-                                   os.path.join(ROOT, "chromap_amd", "csrc", "cm_host.cpp")])
+        def stale():
+            return not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs)
+        if stale():
+            # several processes may get here at once (the ranks of tests/test_distributed_gloo.py): one builds, under a lock and
+            # into a file of its own that takes the library's name when it is complete; the others wait and find it built
+            import fcntl
+            with open(so + ".lock", "w") as lock:
+                fcntl.flock(lock, fcntl.LOCK_EX)
+                if stale():
+                    tmp = "%s.%d.tmp" % (so, os.getpid())
+                    # -fno-strict-aliasing: the stage functions read and write their byte / word arrays through wider types
+                    # (aligned 8- and 16-byte accesses), which the device compiler takes as written
+                    subprocess.check_call(["g++", "-std=c++17", "-O2", "-g", "-fPIC", "-shared", "-ffp-contract=off",
+                                           "-fno-strict-aliasing", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-pthread",
+                                           "-o", tmp, srcs[0], os.path.join(ROOT, "chromap_amd", "csrc", "cm_host.cpp")])
+                    os.replace(tmp, so)
         _L = _capi.declare(C.CDLL(so))
         P = C.POINTER
         _L.hostemu_map_pairs.restype = C.c_int

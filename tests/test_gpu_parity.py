@@ -228,6 +228,28 @@ def test_fuzz_long_hit_lists_every_path(cfg, setting, tmp_path):
     _fz.run_case(factory, cfg, tmp_path)
 
 
+ALIGNMENT_SETTINGS = ("verify_on_bytes", "long_reads_two_pass", "wave_bitonic", "one_lane", "capacity_guess_too_small")
+
+
+@pytest.mark.parametrize("setting", ALIGNMENT_SETTINGS)
+@pytest.mark.parametrize("cfg", fuzz_data.GAP_CONFIGS, ids=[str(c[0]) for c in fuzz_data.GAP_CONFIGS])
+def test_fuzz_gap_rich_alignment_settings(cfg, setting, tmp_path):
+    """the gap-rich configurations (gap runs, gaps at the read ends, edit sums at the threshold, gapped reads at chromosome ends;
+    e = 1, 4 with split alignment, 8 and 15) under the settings that change how alignments are computed or consumed: every
+    record field and the counters"""
+    from chromap_amd import ChromapGPU
+
+    def factory(idx, fa, preset, gkw, b1, o1, b2, o2):
+        g = ChromapGPU(idx, fa, preset=preset, **gkw)
+        for k_, v_ in HEAVY_SETTINGS[setting].items():
+            g.set_option(k_, v_)
+        rec, k = g.map_pairs(b1, o1, b2, o2)
+        st = g.stats.as_dict()
+        g.close()
+        return rec, k, st
+    _fz.run_case(factory, cfg, tmp_path)
+
+
 @pytest.mark.parametrize("bc_err", [1, 2])
 def test_barcode_correction_dense_whitelist_gpu(bc_err, tmp_path):
     """as tests/test_hostemu_fuzz.py::test_barcode_correction_dense_whitelist, on the device"""

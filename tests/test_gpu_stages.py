@@ -59,7 +59,7 @@ def _check(g, o, b1, o1, b2, o2, k, label, minimizers=True):
             assert gp[a0:a0 + c].tolist() == [int(x) & 0x1FFFFFFFF for x in ot[:c]], (label, i, mate, "position / strand")
 
 
-@pytest.mark.parametrize("case", ["s1_atac", "s4_atac_q0", "s3_chip", "h1_hic"])
+@pytest.mark.parametrize("case", ["s1_atac", "s4_atac_q0", "s3_chip", "h1_hic", "x1_gaps_q0", "x3_gaps_hic_q0"])
 def test_stage_trace_golden_cases(case):
     from chromap_amd import ChromapGPU
     meta = datasets.case_meta(case)

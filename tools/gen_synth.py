@@ -89,6 +89,46 @@ def mutate(rng, seq, sub, indel):
     return out
 
 
+def _geometric(rng, p, hi):
+    """1 .. hi, each value p times as likely as the one before"""
+    wts = p ** np.arange(hi)
+    return 1 + int(rng.choice(hi, p=wts / wts.sum()))
+
+
+def gapped(rng, src, n, e, budget_p, len_p):
+    """n bases of src (longer than n, so that deletions do not shorten the read) under an edit script of 1 .. e + 2 edits:
+    substitutions, insertions and deletions of 1 .. e bases, three gaps in ten in the read's first or last 3 bases"""
+    at = {}
+    dels = 0
+    for _ in range(_geometric(rng, budget_p, e + 2)):
+        kind = "sid"[int(rng.integers(0, 3))]
+        ln = 1 if kind == "s" else _geometric(rng, len_p, e)
+        if kind != "s" and rng.random() < 0.3:
+            pos = int(rng.integers(0, 3)) if rng.random() < 0.5 else n - 1 - int(rng.integers(0, 3))
+        else:
+            pos = int(rng.integers(0, n))
+        at.setdefault(max(0, min(n - 1, pos)), []).append((kind, ln))
+        dels += ln if kind == "d" else 0
+    keep_dels = len(src) >= n + dels + 1
+    out = []
+    s = 0
+    while len(out) < n and s < len(src):
+        sub = False
+        for kind, ln in at.pop(len(out), ()):
+            if kind == "i":
+                out.extend(ACGT[rng.integers(0, 4, size=ln)].tolist())
+            elif kind == "d":
+                s += ln if keep_dels else 0
+            else:
+                sub = True
+        base = int(src[s])
+        s += 1
+        if sub:
+            base = int(ACGT[rng.integers(0, 4)])
+        out.append(base)
+    return np.array(out[:n], dtype=np.uint8)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True, help="output prefix")
@@ -101,6 +141,11 @@ def main():
     ap.add_argument("--sub", type=float, default=0.01)
     ap.add_argument("--indel", type=float, default=0.001, help="per-base prob of one 1-bp indel per read")
     ap.add_argument("--seed", type=int, default=12345)
+    ap.add_argument("--gap-share", type=float, default=0.0,
+                    help="share of the reads that carry an edit script with gap runs (see gapped()); 0: none, and no random number more is drawn")
+    ap.add_argument("--gap-e", type=int, default=8, help="error threshold the scripts are made for: gaps of 1 .. e bases, 1 .. e + 2 edits")
+    ap.add_argument("--gap-budget-p", type=float, default=0.5, help="ratio between the probabilities of neighbouring edit budgets")
+    ap.add_argument("--gap-len-p", type=float, default=0.6, help="ratio between the probabilities of neighbouring gap lengths")
     ap.add_argument("--no-repeats", action="store_true")
     ap.add_argument("--dup-frac", type=float, default=0.05)
     ap.add_argument("--junk-frac", type=float, default=0.02)
@@ -203,8 +248,17 @@ def main():
                     rv = np.concatenate([rv[:cut], revcomp(frag)[:max(0, fl - cut)]])
         r1 = np.concatenate([fw, ADAPTER1])[:l1] if len(fw) < l1 else fw[:l1]
         r2 = np.concatenate([rv, ADAPTER2])[:l2] if len(rv) < l2 else rv[:l2]
-        r1 = mutate(rng, r1, a.sub, a.indel)
-        r2 = mutate(rng, r2, a.sub, a.indel)
+        g1 = g2 = False
+        if a.gap_share > 0:
+            slack = a.gap_e * (a.gap_e + 2) + 1
+            if len(fw) >= l1 and rng.random() < a.gap_share:
+                r1, g1 = gapped(rng, fw[:l1 + slack], l1, a.gap_e, a.gap_budget_p, a.gap_len_p), True
+            if len(rv) >= l2 and rng.random() < a.gap_share:
+                r2, g2 = gapped(rng, rv[:l2 + slack], l2, a.gap_e, a.gap_budget_p, a.gap_len_p), True
+        if not g1:
+            r1 = mutate(rng, r1, a.sub, a.indel)
+        if not g2:
+            r2 = mutate(rng, r2, a.sub, a.indel)
         if rng.random() < a.junk_frac:
             r1 = ACGT[rng.integers(0, 4, size=len(r1))]
             if rng.random() < 0.5:
