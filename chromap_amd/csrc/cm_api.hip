@@ -2033,7 +2033,6 @@ static int map_single_impl(cmgpu_ctx *c, const cmgpu_single_batch *in, const cmg
                            cmgpu_record_bc *out_bc, uint64_t out_capacity, uint64_t *n_out, cmgpu_stats *stats) {
   if (!c || !in || !n_out) return CMGPU_EINVAL;
   if (bc && c->wl_size != 0 && c->wl_num_sample == 0) { cm_set_error(c, "barcode abundance not computed (cmgpu_compute_barcode_abundance)"); return CMGPU_EINVAL; }
-  if (c->p.split) { cm_set_error(c, "single-end split alignment is not supported"); return CMGPU_EINVAL; }
   HIPCHECK(c, cm_enter(c));
   const uint32_t n = in->n_reads;
   c->n_pairs = n;

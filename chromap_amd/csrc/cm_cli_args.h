@@ -188,6 +188,8 @@ static Args parse(int argc, char **argv) {
              "       [-b barcode.fq --barcode-whitelist wl.txt] -o out [-e -s -f -l -q --min-read-length --trim-adapters\n"
              "       --remove-pcr-duplicates --Tn5-shift --low-mem --BED|--TagAlign|--pairs|--SAM --bc-error-threshold ...]\n"
              "       [--summary FILE [--turn-off-num-uniq-cache-slots] [--frip-est-params a;b;c;d;e]]\n"
+             "  --split-alignment  with -1 alone (single-end reads): BED, --TagAlign or --SAM whose coordinates and MAPQ carry each read's split site;\n"
+             "                  with -2 as well the output is --pairs (--preset hic)\n"
              "  --summary FILE  per-barcode CSV (one row for bulk data): barcode,total,duplicate,unmapped,lowmapq counted on the device;\n"
              "                  cachehit, fric, estfrip and numcacheslots are written as 0 (the minimizer cache is not modelled)\n");
       exit(0);

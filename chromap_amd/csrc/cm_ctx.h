@@ -188,6 +188,7 @@ struct cmgpu_ctx {
   DevBuf store, store_bc, text;
   uint64_t store_n = 0, store_cap = 0, text_bytes = 0, text_lines = 0;
   bool store_has_bc = false;
+  bool store_pairs_rec = false;  // the stored records are cmgpu_pairs_record entries (kind of the first append, like store_has_bc)
   CmFqStream fq[3];  // read 1, read 2, barcode
   // run-wide read-name store (cm_ingest.hip): the names of reads nm_base .. nm_base + nm_n - 1 back to back in nm_blob, nm_offs their
   // nm_n + 1 64-bit offsets; fed by cmgpu_fastq_commit from the one stream that keeps names, read where it lies by
@@ -308,7 +309,17 @@ int cm_store_reserve(cmgpu_ctx *c, uint64_t need, bool with_bc);
 // record slots of the resident batch: max_num_best_mappings per pair (cm_emit_record); flag / position scratch for a
 // compaction over them (scratch_a, scratch_b, scan_tmp sized for `slots` entries)
 static inline uint32_t cm_rec_per_pair(const cmgpu_ctx *c) { return (uint32_t)(c->p.max_best > 0 ? c->p.max_best : 1); }
-static inline bool cm_pairs_records(const cmgpu_ctx *c) { return c->p.split || c->p.pairs_out; }  // the records are cmgpu_pairs_record entries
+// the records are cmgpu_pairs_record entries: a paired-end batch with split alignment or --pairs.  A single-end batch holds ordinary
+// cmgpu_record entries whatever the parameters (cm_emit_single_record); c->single is the last committed batch's, as the records are
+static inline bool cm_pairs_records(const cmgpu_ctx *c) { return !c->single && (c->p.split || c->p.pairs_out); }
+// the record store's kind: fixed by the first append and kept until cmgpu_store_clear, whatever batches were committed since (the SAM
+// store's st.paired is the same idea); an empty store takes the resident batch's kind.  `pairs`: the kind of the records to be added
+static inline bool cm_store_pairs_records(const cmgpu_ctx *c) { return c->store_n ? c->store_pairs_rec : cm_pairs_records(c); }
+static inline bool cm_store_kind_mismatch(cmgpu_ctx *c, bool pairs) {
+  if (c->store_n == 0 || c->store_pairs_rec == pairs) return false;
+  cm_set_error(c, "record store mixes pairs records and ordinary records");
+  return true;
+}
 static inline uint64_t cm_rec_slots(const cmgpu_ctx *c) { return (uint64_t)c->n_pairs * cm_rec_per_pair(c); }
 int cm_ensure_slot_scratch(cmgpu_ctx *c, uint64_t slots);
 // cm_post.hip: n 32-byte {record, barcode} entries -> the store's record / barcode arrays at position store_n

@@ -505,6 +505,7 @@ extern "C" int cmgpu_exchange_step(cmgpu_ctx *c, uint64_t *sent_per_rank, uint64
   int local_rc = CMGPU_OK;
   uint8_t *dest = nullptr;
   if (c->store_n && tot_r && c->store_has_bc != bc) { cm_set_error(c, "record store mixes barcoded and bulk batches"); local_rc = CMGPU_EINVAL; }
+  if (!local_rc && tot_r && cm_store_kind_mismatch(c, false)) local_rc = CMGPU_EINVAL;  // only ordinary records travel (ex_common_init)
   if (!local_rc && tot_r) {
     if (c->store_n + tot_r > c->store_cap || (bc && !c->store_bc.p)) local_rc = cm_exchange_quiesce(c);  // the store moves: the previous payload must have landed
     if (!local_rc) local_rc = cm_store_reserve(c, c->store_n + tot_r, bc);
@@ -576,6 +577,7 @@ extern "C" int cmgpu_exchange_step(cmgpu_ctx *c, uint64_t *sent_per_rank, uint64
     if (x.ext.alltoallv(x.ext.user, x.send.p, send_cnt, dest, recv_cnt, world, rb) != 0) { cm_set_error(c, "exchange transport: alltoallv failed"); return CMGPU_EIO; }
   }
   if (x.transport != 1 && tot_r && bc) cm_store_split_bc(c, dest, tot_r, s);
+  if (c->store_n == 0 && tot_r) c->store_pairs_rec = false;
   c->store_n += tot_r;
   c->batch_exchanged = true;
   x.sent_total += tot_s;

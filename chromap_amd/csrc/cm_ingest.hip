@@ -908,7 +908,6 @@ extern "C" int cmgpu_fastq_commit(cmgpu_ctx *c, uint32_t n, uint32_t first_read_
     cm_set_error(c, "streams hold different numbers of taken records"); return CMGPU_EINVAL;
   }
   if (n > 0x3fffffffu) { cm_set_error(c, "batch too large"); return CMGPU_EINVAL; }
-  if (!paired && c->p.split) { cm_set_error(c, "single-end split alignment is not supported"); return CMGPU_EINVAL; }
   if (barcoded && c->wl_size != 0 && c->wl_num_sample == 0) { cm_set_error(c, "barcode abundance not computed"); return CMGPU_EINVAL; }
   // the batch's names join the run-wide store first: a commit that cannot keep them (a gap in the read ids, no memory) changes nothing
   for (int m = 0; m < 2; ++m)

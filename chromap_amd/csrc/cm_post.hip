@@ -562,6 +562,7 @@ extern "C" int cmgpu_store_clear(cmgpu_ctx *c) {
   (void)cm_exchange_quiesce(c);
   c->store_n = 0;
   c->store_has_bc = false;
+  c->store_pairs_rec = false;
   c->text_bytes = 0;
   c->text_lines = 0;
   return CMGPU_OK;
@@ -574,6 +575,8 @@ extern "C" int cmgpu_store_append_resident(cmgpu_ctx *c, uint64_t *n_total) {
   const uint32_t n = (uint32_t)cm_rec_slots(c);
   if (c->store_n && c->store_has_bc != c->has_barcodes) { cm_set_error(c, "record store mixes barcoded and bulk batches"); return CMGPU_EINVAL; }
   if (n) {
+    if (cm_store_kind_mismatch(c, cm_pairs_records(c))) return CMGPU_EINVAL;
+    if (c->store_n == 0) c->store_pairs_rec = cm_pairs_records(c);
     int rc = cm_store_reserve(c, c->store_n + n, c->has_barcodes);
     if (rc) return rc;
     rc = cm_ensure_slot_scratch(c, n);
@@ -600,6 +603,9 @@ extern "C" int cmgpu_store_append(cmgpu_ctx *c, const void *records, uint64_t n,
   { const int qrc = cm_exchange_quiesce(c); if (qrc) return qrc; }
   if (c->store_n && c->store_has_bc != (barcoded != 0)) { cm_set_error(c, "record store mixes barcoded and bulk batches"); return CMGPU_EINVAL; }
   if (n == 0) return CMGPU_OK;
+  // the caller's records are of the kind the context's batches have (cmgpu_download_records hands out no other)
+  if (cm_store_kind_mismatch(c, cm_pairs_records(c))) return CMGPU_EINVAL;
+  if (c->store_n == 0) c->store_pairs_rec = cm_pairs_records(c);
   int rc = cm_store_reserve(c, c->store_n + n, barcoded != 0);
   if (rc) return rc;
   const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -858,7 +864,7 @@ __global__ __launch_bounds__(PP_BLOCK) void k_pp_pairs_format(const uint8_t *__r
 static int pp_format_pairs(cmgpu_ctx *c, const char *const *names, uint32_t n_sequences, const cmgpu_params *p, bool resident,
                            const char *read_names, const uint64_t *read_name_offsets, uint32_t n_read_names,
                            uint32_t read_id_base, uint64_t *n_lines, uint64_t *n_bytes) {
-  if (!cm_pairs_records(c)) { cm_set_error(c, "pairs text needs pairs records (split alignment, or output_format = CMGPU_FORMAT_PAIRS)"); return CMGPU_EINVAL; }
+  if (!cm_store_pairs_records(c)) { cm_set_error(c, "pairs text needs pairs records (split alignment, or output_format = CMGPU_FORMAT_PAIRS)"); return CMGPU_EINVAL; }
   // (cell barcodes: they decided which pairs were mapped -- CorrectBarcodeAt, chromap.h:896-906 -- and go no further: a PairsMapping's barcode is
   //  neither printed nor part of its order or equality, pairs_mapping.h:40-50, GetBarcode() == 0; the store's key array is left alone)
   PPCHECK(c, cm_enter(c));

@@ -1680,7 +1680,7 @@ CM_HD bool cm_s4c_pre(const CmDev &d, uint32_t pair) {
   d.fcp[r1] = d.fcn[r1] = d.fcp[r2] = d.fcn[r2] = 0;
   d.alive[pair] = 0;
   d.force0[pair] = 0;
-  if (d.p.single) {  // chromap.h:442-445: candidates go straight to verification
+  if (d.p.single) {  // chromap.h:442-445: candidates go straight to verification (split alignment or not: the single side)
     if (d.mm_cnt[r1] == 0 || d.mcp[r1] + d.mcn[r1] == 0) return false;
     const uint64_t *mp = cm_m_pos(d, r1), *mn = cm_m_neg(d, r1);
     const uint8_t *mpc = cm_m_pcnt(d, r1), *mnc = cm_m_ncnt(d, r1);
@@ -2542,7 +2542,8 @@ CM_HD void cm_s5_verify(const CmDev &d, uint32_t r) {
     uint64_t *dpp = d.dpos + d.m_off[r], *dpn = d.dpos + d.m_off[r] + d.ncp[r] + d.resc_p[r];
     int16_t *dep = d.derr + d.m_off[r], *den = d.derr + d.m_off[r] + d.ncp[r] + d.resc_p[r];
     bool done = false;
-    if (d.p.split) {  // draft_mapping_generator.cc:31-39: no shortcut, scalar drop-off verification
+    if (d.p.split) {  // draft_mapping_generator.cc:31-39: no shortcut, scalar drop-off verification (single-end reads too: the split
+                      // side; the empty second mate of a single-end pair has no candidates and leaves no draft mapping)
       uint32_t *dsp = d.dsplit + d.m_off[r], *dsn = d.dsplit + d.m_off[r] + d.ncp[r] + d.resc_p[r];
       cm_sort_cand(pp, pc, ncp);
       cm_sort_cand(np, nc, ncn);
@@ -3322,10 +3323,49 @@ CM_HD void cm_split_pairing(const CmDev &d, uint32_t pair, int64_t want, CmPe &p
 }
 
 
+// single-end read with split alignment: the record of draft mapping mi on `strand` (ProcessBestMappingsForSingleEndRead with
+// read_split_site set, mapping_generator.h:304-306).  The split side: coordinates from the draft mapping's dsplit word
+// (cm_ref_start_end_split / _sam), MAPQ from cm_mapq_single_split.  The single side: max_num_error_difference = error_threshold
+// (:314-318; the paired caller passes 2), the strand's whole candidate list (no paired-end filter has run: cm_s4c_pre copies the
+// merged lists, so fcp / fcn are positive_candidates_.size() / negative_candidates_.size()), no x1.2 and no min-of-mates
+// (GetMAPQForPairedEndRead's), SAM slot `pair` and the ordinary 24-byte record.
+template <bool SAM>
+CM_HD void cm_emit_single_split_at(const CmDev &d, uint32_t pair, uint64_t slot, int strand, uint32_t mi) {
+  const uint32_t r = 2 * pair;
+  const uint32_t L = d.rlen[r];
+  const uint64_t dp = cm_d_pos(d, r, strand)[mi];
+  const int err = cm_d_err(d, r, strand)[mi];  // -(matched length)
+  const uint32_t w = (d.dsplit + d.m_off[r] + (strand ? d.ncp[r] + d.resc_p[r] : 0))[mi];
+  CmSamAln sa;
+  CmSpan sp;
+  if constexpr (SAM) sp = cm_ref_start_end_split_sam(d, pair, pair, dp, w, strand, cm_read_ptr(d, r), (int)L, &sa);
+  else sp = cm_ref_start_end_split(d, dp, w, strand, cm_read_ptr(d, r), (int)L);
+  const uint16_t al = (uint16_t)(sp.ref_end - sp.ref_start + 1);
+  const uint8_t mapq = cm_mapq_single_split(d, err, al, (int)L, d.p.e, d.second_err[r], d.n_best[r], d.n_second[r], d.rep_len[r],
+                                            strand == 0 ? d.fcp[r] : d.fcn[r]);
+  const uint8_t is_unique = d.n_best[r] == 1 ? 1 : 0;
+  uint8_t *o = d.rec + slot * 24;
+  uint32_t *o32 = reinterpret_cast<uint32_t *>(o);
+  uint16_t *o16 = reinterpret_cast<uint16_t *>(o);
+  o32[0] = d.first_read_id + pair;
+  o32[1] = sp.rid;
+  o32[2] = sp.ref_start;
+  o16[6] = al;
+  o[14] = mapq & 63;
+  o[15] = strand == 0 ? 1 : 0;
+  o[16] = is_unique;
+  o[17] = 1;
+  o16[9] = 0; o16[10] = 0; o16[11] = 0;
+  d.rec_ok[slot] = 1;
+  if constexpr (SAM)
+    cm_put_sam_record(d, pair, d.first_read_id + pair, sp, 0, -1, 0, strand == 0 ? 0u : 16u, mapq, strand == 0 ? 1 : 0, is_unique, sa, L);
+}
+
 // single-end: ProcessBestMappingsForSingleEndRead (mapping_generator.h:256-344) for the
 // `choice`-th best mapping (draft mappings in emission order, + strand first), MAPQ with
 // max_num_error_difference = error_threshold, EmplaceBackSingleEndMappingRecord
-// <MappingWithoutBarcode> (mapping_generator.cc:7-16)
+// <MappingWithoutBarcode> (mapping_generator.cc:7-16).  The choice among the best mappings is the same with split alignment
+// (errors are then -(matched length), and de > min_err still leaves the best); the record is cm_emit_single_split_at's.
 template <bool SAM>
 CM_HD void cm_emit_single_record(const CmDev &d, uint32_t pair, uint32_t choice, uint32_t nth = 0) {
   const uint32_t r = 2 * pair;
@@ -3339,6 +3379,7 @@ CM_HD void cm_emit_single_record(const CmDev &d, uint32_t pair, uint32_t choice,
     for (uint32_t mi = 0; mi < n; ++mi) {
       if ((int)de[mi] > me) continue;
       if (idx == choice) {
+        if (d.p.split) { cm_emit_single_split_at<SAM>(d, pair, slot, strand, mi); return; }
         const uint32_t L = d.rlen[r];
         CmSamAln sa;
         CmSpan sp;
@@ -3383,7 +3424,8 @@ CM_HD bool cm_s6a_pre(const CmDev &d, uint32_t pair) {
   d.pe_nbest[pair] = 0;
   if (!d.alive[pair]) return false;
   const uint32_t nd1 = d.ndp[r1] + d.ndn[r1], nd2 = d.ndp[r2] + d.ndn[r2];
-  if (d.p.single) {  // GenerateBestMappingsForSingleEndRead (mapping_generator.h:115-157)
+  if (d.p.single) {  // GenerateBestMappingsForSingleEndRead (mapping_generator.h:115-157); with split alignment too: the single side
+                     // (one read's best mappings, no pairing) -- cm_emit_single_record takes the split side for the record itself
     if (nd1 == 0) return false;
     d.pe_nbest[pair] = d.n_best[r1];
     d.pe_min[pair] = d.min_err[r1]; d.pe_second[pair] = d.second_err[r1]; d.pe_nsecond[pair] = d.n_second[r1];
@@ -3544,7 +3586,7 @@ CM_HD void cm_s6c_multi(const CmDev &d, uint32_t pair) {
   const uint32_t to_report = (uint32_t)nb < K ? (uint32_t)nb : K;
   for (uint32_t t = 0; t < to_report; ++t) {  // the chosen indices are increasing, so are the records of a pair
     const int64_t want = (int64_t)d.pe_choice[(uint64_t)pair * K + t];
-    if (d.p.single) { cm_emit_single_record<SAM>(d, pair, (uint32_t)want, t); continue; }
+    if (d.p.single) { cm_emit_single_record<SAM>(d, pair, (uint32_t)want, t); continue; }  // (single-end split alignment: here, not below)
     if (d.p.split) {
       CmPe sp;
       cm_split_pairing(d, pair, want, sp);

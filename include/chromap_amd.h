@@ -72,7 +72,9 @@ typedef struct cmgpu_params {
                                    * best mappings (mapping_generator.h:121-139,199-214); not with CMGPU_FORMAT_SAM */
   int32_t drop_repetitive_reads;  /* --drop-repetitive-reads */
   int32_t trim_adapters;          /* --trim-adapters */
-  int32_t split_alignment;        /* --split-alignment (records are then cmgpu_pairs_record) */
+  int32_t split_alignment;        /* --split-alignment: paired-end batches leave cmgpu_pairs_record entries; single-end batches (cmgpu_map_single,
+                                   * cmgpu_map_single_barcoded, a single-end cmgpu_fastq_commit) leave ordinary cmgpu_record entries whose coordinates
+                                   * and MAPQ carry the read's split site */
   int32_t mapq_threshold;         /* -q; used by cmgpu_write_bed_pe only */
   int32_t remove_pcr_duplicates;  /* used by the writers / cmgpu_store_format* only */
   int32_t tn5_shift;              /* used by cmgpu_write_bed_pe only */
@@ -81,7 +83,7 @@ typedef struct cmgpu_params {
   int32_t taskloop_grain_size;    /* 5000 (chromap.h:887): scope of the reservoir RNG */
   int32_t bc_error_threshold;     /* --bc-error-threshold (0, 1 or 2 on the device) */
   int32_t output_mappings_not_in_whitelist; /* --output-mappings-not-in-whitelist */
-  int32_t output_format;          /* 0: BED records (pairs records with split_alignment); CMGPU_FORMAT_SAM: --SAM (alignment coordinates, CIGAR,
+  int32_t output_format;          /* 0: BED records (pairs records for paired-end batches with split_alignment); CMGPU_FORMAT_SAM: --SAM (alignment coordinates, CIGAR,
                                    * NM, MD); CMGPU_FORMAT_PAIRS: pairs records from the ordinary (non-split) pairing */
   int32_t dedup_at_bulk_level;    /* single-cell BED, low-memory flavour: --remove-pcr-duplicates-at-bulk-level (the reference's
                                    * default without --preset atac); applied by cmgpu_store_format only */
@@ -116,11 +118,13 @@ typedef struct cmgpu_record {
   uint16_t negative_alignment_length;
 } cmgpu_record;
 
-/* With params.split_alignment (--preset hic) the record is the constructor argument list of
+/* With params.split_alignment (--preset hic) the record of a PAIRED-END batch is the constructor argument list of
  * PairsMapping (src/pairs_mapping.h:25-38) without read name and barcode, already flipped so
  * that (rid1,pos1) <= (rid2,pos2) (src/mapping_generator.cc:169-210); pos = ref start for a +
  * read, ref end for a - read, 0-based.  Same 24-byte slot as cmgpu_record: the `out` buffers of
- * cmgpu_map_pairs / cmgpu_download_records then hold cmgpu_pairs_record entries. */
+ * cmgpu_map_pairs / cmgpu_download_records then hold cmgpu_pairs_record entries.  A single-end batch of the same context
+ * (cmgpu_map_single, cmgpu_map_single_barcoded) holds cmgpu_record entries: fragment_length = ref_end - ref_start + 1 of the part of the
+ * read that was aligned. */
 typedef struct cmgpu_pairs_record {
   uint32_t read_id;
   uint32_t rid1, rid2;
@@ -489,14 +493,16 @@ int cmgpu_write_sam_header(const char *const *ref_names, const uint32_t *ref_len
 int cmgpu_store_clear(cmgpu_ctx *ctx);
 /* room for n_records ahead of time (the store otherwise doubles on demand: allocation + copy + synchronous free) */
 int cmgpu_store_reserve(cmgpu_ctx *ctx, uint64_t n_records, int barcoded);
-/* appends the records of the last cmgpu_map_* call (still resident); n_total = store size */
+/* appends the records of the last cmgpu_map_* call (still resident); n_total = store size.  The store keeps the kind of its first append -- bulk or
+   barcoded, cmgpu_pairs_record or cmgpu_record -- until cmgpu_store_clear: an append of another kind is CMGPU_EINVAL, and cmgpu_store_format_pairs*
+   judges the store by that kind whatever batch the context mapped last */
 int cmgpu_store_append_resident(cmgpu_ctx *ctx, uint64_t *n_total);
 /* appends n records from a host or device array; barcoded = 0: cmgpu_record entries,
  * barcoded = 1: cmgpu_record_bc entries -- e.g. the receive buffer of the multi-GPU exchange */
 int cmgpu_store_append(cmgpu_ctx *ctx, const void *records, uint64_t n, int on_device, int barcoded);
 int cmgpu_store_format(cmgpu_ctx *ctx, int kind, const char *const *names, uint32_t n_sequences, const cmgpu_params *params,
                        uint32_t barcode_length, uint64_t *n_lines, uint64_t *n_bytes);
-/* --preset hic: the store holds cmgpu_pairs_record entries (cmgpu_store_append_resident after a split-alignment batch);
+/* --preset hic: the store holds cmgpu_pairs_record entries (cmgpu_store_append_resident after a paired-end split-alignment batch);
  * sorted as MappingWriter<PairsMapping> sorts them (src/pairs_mapping.h:41-47), MAPQ filter, one text line per record
  * (src/mapping_writer.cc:400-423).  read_names: the names of reads read_id_base .. read_id_base + n_read_names - 1
  * concatenated, read_name_offsets[n_read_names + 1] into it.  The header lines: cmgpu_write_pairs_header.

@@ -42,6 +42,9 @@ def main():
     ap.add_argument("--summary", action="store_true", help="both runs also write --summary: barcodes, row order and the first five columns are compared "
                                                             "(the four cache columns are the reference's cache's, which chromap-amd does not model)")
     ap.add_argument("--hic", type=float, default=-1.0, help="Hi-C shaped pairs with this fraction of chimeric reads (default: fragments)")
+    ap.add_argument("--single-end", action="store_true", help="map read 1 alone (-1 without -2); the M_pairs_per_s_* figures are then M reads/s (the line's `unit`)")
+    ap.add_argument("--map-flags", default="", help="flags both programs are run with instead of --preset PRESET (which then only shapes the "
+                                                    "synthetic reads), e.g. '--split-alignment -q 0'")
     args = ap.parse_args()
     if args.threads <= 0:
         from chromap_amd.cpus import cpu_budget
@@ -127,7 +130,9 @@ def main():
         extra = ["-b", bc_path, "--barcode-whitelist", wl_path]
     t_setup = time.time() - t0
     n_pairs = args.pairs * args.batches
-    res = {"setup_s": round(t_setup, 1), "pairs": n_pairs, "threads": args.threads,
+    # "pairs" and the M_pairs_per_s_* keys keep their names for the readers of this line (bench.py, the scale tests); `unit` says what they
+    # count: with --single-end every "pair" is one read
+    res = {"setup_s": round(t_setup, 1), "pairs": n_pairs, "unit": "M reads/s" if args.single_end else "M pairs/s", "threads": args.threads,
            "index_bytes": os.path.getsize(idx), "fastq_bytes": os.path.getsize(r1) + os.path.getsize(r2)}
     sum_ref, sum_gpu = os.path.join(args.dir, "ref.summary.csv"), os.path.join(args.dir, "gpu.summary.csv")
     # ---- the reference
@@ -135,9 +140,12 @@ def main():
         extra_ref, extra_gpu = extra + ["--summary", sum_ref], extra + ["--summary", sum_gpu]
     else:
         extra_ref = extra_gpu = extra
+    mode = args.map_flags.split() if args.map_flags else ["--preset", args.preset]
+    reads = ["-1", r1] if args.single_end else ["-1", r1, "-2", r2]
+    res["command"] = " ".join(mode + (["-1", "r1.fq"] if args.single_end else ["-1", "r1.fq", "-2", "r2.fq"]))
     out_ref = os.path.join(args.dir, "ref.out")
     t0 = time.time()
-    p = subprocess.run([ref_bin, "--preset", args.preset, "-x", idx, "-r", fa, "-1", r1, "-2", r2, "-o", out_ref, "-t", str(args.threads)] + extra_ref,
+    p = subprocess.run([ref_bin] + mode + ["-x", idx, "-r", fa] + reads + ["-o", out_ref, "-t", str(args.threads)] + extra_ref,
                        stderr=subprocess.PIPE)
     wall = time.time() - t0
     log = p.stderr.decode(errors="replace")
@@ -145,7 +153,7 @@ def main():
         res["reference"] = {"error": log[-2000:]}
     else:
         m_all = re.search(r"Mapped all reads in ([0-9.]+)s", log)
-        per_batch = [float(x) for x in re.findall(r"Mapped \d+ read pairs in ([0-9.]+)s", log)]
+        per_batch = [float(x) for x in re.findall(r"Mapped \d+ read(?: pair)?s in ([0-9.]+)s", log)]
         res["reference"] = {"wall_s": round(wall, 2), "mapped_all_reads_s": float(m_all.group(1)) if m_all else None,
                             "sum_of_batch_times_s": round(sum(per_batch), 3), "batches": len(per_batch),
                             "M_pairs_per_s_mapping_loop": round(n_pairs / float(m_all.group(1)) / 1e6, 3) if m_all else None,
@@ -156,7 +164,7 @@ def main():
     out_gpu = os.path.join(args.dir, "gpu.out")
     cli = os.path.join(ROOT, "chromap_amd", "chromap-amd")
     t0 = time.time()
-    p = subprocess.run([cli, "--preset", args.preset, "-x", idx, "-r", fa, "-1", r1, "-2", r2, "-o", out_gpu] + extra_gpu, stderr=subprocess.PIPE)
+    p = subprocess.run([cli] + mode + ["-x", idx, "-r", fa] + reads + ["-o", out_gpu] + extra_gpu, stderr=subprocess.PIPE)
     wall = time.time() - t0
     log = p.stderr.decode(errors="replace")
     if p.returncode != 0:
@@ -186,7 +194,7 @@ def main():
         bgzf.compress_file(r2, z2)
         out_z = os.path.join(args.dir, "gpu_bgzf.out")
         zextra = list(extra)
-        p = subprocess.run([cli, "--preset", args.preset, "-x", idx, "-r", fa, "-1", z1, "-2", z2, "-o", out_z] + zextra, stderr=subprocess.PIPE)
+        p = subprocess.run([cli] + mode + ["-x", idx, "-r", fa, "-1", z1] + ([] if args.single_end else ["-2", z2]) + ["-o", out_z] + zextra, stderr=subprocess.PIPE)
         res["bgzf"] = {"rc": p.returncode, "identical": p.returncode == 0 and
                        subprocess.check_output(["md5sum", out_z]).split()[0].decode() == res["chromap_amd"]["bed_md5"]}
     shutil.rmtree(args.dir, ignore_errors=True)
