@@ -22,15 +22,6 @@
 
 static thread_local std::string g_last_error;  // errors without a ctx (creation), per calling thread
 
-#define HIPCHECK(ctx, call)                                                                      \
-  do {                                                                                           \
-    hipError_t e_ = (call);                                                                      \
-    if (e_ != hipSuccess) {                                                                      \
-      cm_set_error(ctx, std::string(#call) + ": " + hipGetErrorString(e_));                     \
-      return CMGPU_EHIP;                                                                         \
-    }                                                                                            \
-  } while (0)
-
 // environment knobs (include/chromap_amd_debug.h): read once
 static bool cm_debug_pool() { static const bool on = getenv("CM_DEBUG_POOL") != nullptr; return on; }
 static thread_local std::string t_last_error;  // the calling thread's own last message (calls on one ctx from several threads: cmgpu_fastq_scan*)
@@ -134,7 +125,7 @@ extern "C" int cmgpu_set_option(cmgpu_ctx *c, const char *name, int64_t value) {
     if (value > 0 && cm_ensure_candidate_arrays(c, (uint64_t)value)) { cm_set_error(c, "out of device memory (candidates)"); return CMGPU_ENOMEM; }
     c->pred_m_ok = value > 0; c->m_cap = (uint64_t)value; c->pred_n = 0xffffffffu;  // (any batch size)
   } else if (n == "coop_profile") {  // measurement aid: per-phase cycle sums of k_s3b_coop (cmgpu_get_option coop_profile_0 .. _15)
-    if (value) { if (c->coop_prof.ensure(64 * 8)) return CMGPU_ENOMEM; HIPCHECK(c, hipMemset(c->coop_prof.p, 0, 64 * 8)); } else c->coop_prof.release();
+    if (value) { if (c->coop_prof.ensure(64 * 8)) return CMGPU_ENOMEM; CM_HIPCHECK(c, hipMemset(c->coop_prof.p, 0, 64 * 8)); } else c->coop_prof.release();
   } else if (n == "coop_run_table") {  // tests: a small table makes the cooperative sorters decline reads (their fallback paths)
     c->opt.coop_rb = (int)value;
   } else if (n == "coop") {  // bit mask of the stages whose long lists go to groups of lanes (cm_coop.h)
@@ -207,8 +198,8 @@ __global__ __launch_bounds__(256) void k_rehash(const uint64_t *__restrict__ src
   }
 }
 int cm_build_fast_table(cmgpu_ctx *c, int shift) {
-  HIPCHECK(c, cm_enter(c));
-  HIPCHECK(c, cm_stream_sync(c->stream));
+  CM_HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_stream_sync(c->stream));
   // contexts made by cmgpu_create_shared view this table (the lanes refresh their views, lane_prepare; a caller's own children do not)
   if (c->shared_children > (int)c->lanes.size()) { cm_set_error(c, "probe_table_shift: set it before cmgpu_create_shared (contexts that share this index view the table)"); return CMGPU_EINVAL; }
   c->bkt_fast.release();
@@ -220,10 +211,10 @@ int cm_build_fast_table(cmgpu_ctx *c, int shift) {
   if (nf > (1ull << 32)) nf = 1ull << 32;  // khash starts at the low 32 bits of the hash
   if (nf <= nb) return CMGPU_OK;
   if (c->bkt_fast.ensure((size_t)nf * 16)) { cm_set_error(c, "out of device memory (re-hashed index table)"); return CMGPU_ENOMEM; }
-  HIPCHECK(c, hipMemsetAsync(c->bkt_fast.p, 0xff, (size_t)nf * 16, c->stream));
+  CM_HIPCHECK(c, hipMemsetAsync(c->bkt_fast.p, 0xff, (size_t)nf * 16, c->stream));
   hipLaunchKernelGGL(k_rehash, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, c->stream, (const uint64_t *)c->bkt.p, nb, (uint64_t *)c->bkt_fast.p,
                      (uint32_t)(nf - 1));
-  HIPCHECK(c, cm_stream_sync(c->stream));
+  CM_HIPCHECK(c, cm_stream_sync(c->stream));
   c->fmask = (uint32_t)(nf - 1);
   return CMGPU_OK;
 }
@@ -236,8 +227,8 @@ static int build_mapq_tables(cmgpu_ctx *c) {
   cm_build_nsec_break(brk);
   c->n_break = (int)brk.size();
   if (c->len_coef.ensure(coef.size() * 8) || c->nsec_break.ensure(brk.size() * 4)) return CMGPU_ENOMEM;
-  HIPCHECK(c, hipMemcpy(c->len_coef.p, coef.data(), coef.size() * 8, hipMemcpyHostToDevice));
-  HIPCHECK(c, hipMemcpy(c->nsec_break.p, brk.data(), brk.size() * 4, hipMemcpyHostToDevice));
+  CM_HIPCHECK(c, hipMemcpy(c->len_coef.p, coef.data(), coef.size() * 8, hipMemcpyHostToDevice));
+  CM_HIPCHECK(c, hipMemcpy(c->nsec_break.p, brk.data(), brk.size() * 4, hipMemcpyHostToDevice));
   return CMGPU_OK;
 }
 
@@ -277,8 +268,8 @@ int cm_ctx_init_common(cmgpu_ctx *c, const cmgpu_params *params, int kmer, int w
   p.sam = params->output_format == CMGPU_FORMAT_SAM ? 1 : 0;
   p.pairs_out = params->output_format == CMGPU_FORMAT_PAIRS && !params->split_alignment ? 1 : 0;  // (split alignment writes pairs records anyway)
   if (params->output_format != 0 && params->output_format != CMGPU_FORMAT_SAM && params->output_format != CMGPU_FORMAT_PAIRS) { cm_set_error(c, "unknown output_format"); return CMGPU_EINVAL; }
-  HIPCHECK(c, hipStreamCreate(&c->stream));
-  HIPCHECK(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));  // same priority as `stream`: a probe stream of higher or lower
+  CM_HIPCHECK(c, hipStreamCreate(&c->stream));
+  CM_HIPCHECK(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));  // same priority as `stream`: a probe stream of higher or lower
                                                                              // priority measured 3-5 % slower end to end
   // the FASTQ streams' HIP streams, made HERE, right behind the two mapping streams, when the process asks for it (CM_FQ_EARLY=1; chromap-amd sets
   // it): the runtime spreads streams of one priority over its hardware queues as they are made; made lazily by the first scans, read 1's and
@@ -288,10 +279,10 @@ int cm_ctx_init_common(cmgpu_ctx *c, const cmgpu_params *params, int kmer, int w
     // (a priority of their own for these streams, highest or lowest: measured on a 32 M-pair job, no difference)
     for (int m = 0; m < 3; ++m) if (hipStreamCreateWithFlags(&c->fq[m].hs, hipStreamNonBlocking) != hipSuccess) { c->fq[m].hs = nullptr; (void)hipGetLastError(); }
   }
-  for (hipEvent_t &e : c->chunk_ev) HIPCHECK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (hipEvent_t &e : c->chunk_ev) CM_HIPCHECK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
   if (c->stats.ensure(CM_ST_N * 8)) return CMGPU_ENOMEM;
-  HIPCHECK(c, hipMemset(c->stats.p, 0, CM_ST_N * 8));
-  for (int i = 0; i < CM_MAX_EVENTS; ++i) HIPCHECK(c, hipEventCreate(&c->ev[i]));
+  CM_HIPCHECK(c, hipMemset(c->stats.p, 0, CM_ST_N * 8));
+  for (int i = 0; i < CM_MAX_EVENTS; ++i) CM_HIPCHECK(c, hipEventCreate(&c->ev[i]));
   cm_load_device_code(c->stream);
   return build_mapq_tables(c);
 }
@@ -372,9 +363,9 @@ int cm_build_ref_planes(cmgpu_ctx *c) {
   const uint64_t words = (c->ref_bytes + 31) / 32 + 4;
   const size_t bytes = (size_t)(words + CM_PL_LEAD) * sizeof(CmPlRec);
   if (c->ref_planes.ensure(bytes)) { cm_set_error(c, "out of device memory (reference bit planes)"); return CMGPU_ENOMEM; }
-  HIPCHECK(c, hipMemsetAsync(c->ref_planes.p, 0, bytes, c->stream));
+  CM_HIPCHECK(c, hipMemsetAsync(c->ref_planes.p, 0, bytes, c->stream));
   cm_launch_k_pack_ref((const uint8_t *)c->ref.p, c->ref_bytes, (CmPlRec *)c->ref_planes.p + CM_PL_LEAD, c->stream);
-  HIPCHECK(c, cm_stream_sync(c->stream));  // the lanes read them from streams of their own
+  CM_HIPCHECK(c, cm_stream_sync(c->stream));  // the lanes read them from streams of their own
   c->ref_pl_words = words;
   return CMGPU_OK;
 }
@@ -485,13 +476,13 @@ extern "C" int cmgpu_set_chr_order(cmgpu_ctx *c, const uint32_t *rank, uint32_t 
     off[rank[i]] = c->h_ref_off[i];
     len[rank[i]] = c->h_ref_len[i];
   }
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   if (c->rid_rank.ensure((size_t)n * 4) || c->ref_off_r.ensure((size_t)n * 8) || c->ref_len_r.ensure((size_t)n * 4)) {
     cm_set_error(c, "out of device memory (chromosome order)"); return CMGPU_ENOMEM;
   }
-  HIPCHECK(c, hipMemcpy(c->rid_rank.p, rank, (size_t)n * 4, hipMemcpyHostToDevice));
-  HIPCHECK(c, hipMemcpy(c->ref_off_r.p, off.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-  HIPCHECK(c, hipMemcpy(c->ref_len_r.p, len.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  CM_HIPCHECK(c, hipMemcpy(c->rid_rank.p, rank, (size_t)n * 4, hipMemcpyHostToDevice));
+  CM_HIPCHECK(c, hipMemcpy(c->ref_off_r.p, off.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+  CM_HIPCHECK(c, hipMemcpy(c->ref_len_r.p, len.data(), (size_t)n * 4, hipMemcpyHostToDevice));
   c->has_rank = true;
   c->h_rank.assign(rank, rank + n);
   return CMGPU_OK;
@@ -500,9 +491,9 @@ extern "C" int cmgpu_set_chr_order(cmgpu_ctx *c, const uint32_t *rank, uint32_t 
 extern "C" int cmgpu_set_pairs_chr_order(cmgpu_ctx *c, const uint32_t *rank, uint32_t n) {
   if (!c || !rank) return CMGPU_EINVAL;
   if (n != c->n_seq) { cm_set_error(c, "rank table size differs from the number of reference sequences"); return CMGPU_EINVAL; }
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   if (c->pairs_rank.ensure((size_t)n * 4)) { cm_set_error(c, "out of device memory (pairs order)"); return CMGPU_ENOMEM; }
-  HIPCHECK(c, hipMemcpy(c->pairs_rank.p, rank, (size_t)n * 4, hipMemcpyHostToDevice));
+  CM_HIPCHECK(c, hipMemcpy(c->pairs_rank.p, rank, (size_t)n * 4, hipMemcpyHostToDevice));
   c->has_pairs_rank = true;
   return CMGPU_OK;
 }
@@ -577,15 +568,15 @@ __global__ __launch_bounds__(256) void k_max_len(const uint32_t *__restrict__ o1
 }
 static int launch_max_len(cmgpu_ctx *c, const DevBuf &o1, const DevBuf *o2, uint32_t n, hipStream_t s, int word = 0) {
   if (c->maxlen_dev.ensure(16)) { cm_set_error(c, "out of device memory"); return CMGPU_ENOMEM; }
-  if (!c->h_maxlen) HIPCHECK(c, hipHostMalloc((void **)&c->h_maxlen, 16, hipHostMallocDefault));
+  if (!c->h_maxlen) CM_HIPCHECK(c, hipHostMalloc((void **)&c->h_maxlen, 16, hipHostMallocDefault));
   uint32_t *dev = (uint32_t *)c->maxlen_dev.p + word;
-  HIPCHECK(c, hipMemsetAsync(dev, 0, 4, s));
+  CM_HIPCHECK(c, hipMemsetAsync(dev, 0, 4, s));
   if (n) {
     uint32_t blocks = (n + 256 * 16 - 1) / (256 * 16);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(k_max_len, dim3(blocks), dim3(256), 0, s, (const uint32_t *)o1.p, o2 ? (const uint32_t *)o2->p : (const uint32_t *)nullptr, n, dev);
   }
-  HIPCHECK(c, hipMemcpyAsync(c->h_maxlen + word, dev, 4, hipMemcpyDeviceToHost, s));
+  CM_HIPCHECK(c, hipMemcpyAsync(c->h_maxlen + word, dev, 4, hipMemcpyDeviceToHost, s));
   return CMGPU_OK;
 }
 
@@ -643,7 +634,7 @@ static int host_to_device(cmgpu_ctx *c, void *dst, const void *src, size_t bytes
     return CMGPU_OK;
   }
   (void)hipGetLastError();  // hipHostGetDevicePointer on pageable memory
-  HIPCHECK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
+  CM_HIPCHECK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
   return CMGPU_OK;
 }
 // the other direction (records): the same kernel writing to page-locked host memory when asked to (d2h_copy_blocks)
@@ -659,13 +650,13 @@ static int device_to_host(cmgpu_ctx *c, void *dst, const void *src, size_t bytes
     return CMGPU_OK;
   }
   (void)hipGetLastError();
-  HIPCHECK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
+  CM_HIPCHECK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
   return CMGPU_OK;
 }
 
 extern "C" int cmgpu_submit_pairs(cmgpu_ctx *c, const cmgpu_batch *in) {
   if (!c || !in) return CMGPU_EINVAL;
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   if (c->sub_count >= 2) { cm_set_error(c, "two submitted batches are waiting (cmgpu_map_submitted)"); return CMGPU_EINVAL; }
   const uint32_t n = in->n_pairs;
   if (n > 0x3fffffffu) { cm_set_error(c, "batch too large"); return CMGPU_EINVAL; }
@@ -675,8 +666,8 @@ extern "C" int cmgpu_submit_pairs(cmgpu_ctx *c, const cmgpu_batch *in) {
     // 4 M-pair batch; streams of another priority get queues of their own
     int prio_least = 0, prio_greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    HIPCHECK(c, hipStreamCreateWithPriority(&c->stream_h2d, hipStreamNonBlocking, prio_greatest));
-    for (hipEvent_t &e : c->ev_h2d) HIPCHECK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    CM_HIPCHECK(c, hipStreamCreateWithPriority(&c->stream_h2d, hipStreamNonBlocking, prio_greatest));
+    for (hipEvent_t &e : c->ev_h2d) CM_HIPCHECK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
   const int which = (int)(c->sub_total & 1u);
   CmBatchSlot &sl = c->slots[CM_BATCH_SLOTS - 1 - which];
@@ -695,7 +686,7 @@ extern "C" int cmgpu_submit_pairs(cmgpu_ctx *c, const cmgpu_batch *in) {
   if (rc0) return rc0;
   int rc = launch_max_len(c, sl.ro0, &sl.ro1, n, s, 1 + which);
   if (rc) return rc;
-  HIPCHECK(c, hipEventRecord(c->ev_h2d[which], s));
+  CM_HIPCHECK(c, hipEventRecord(c->ev_h2d[which], s));
   ++c->sub_total;
   ++c->sub_count;
   return CMGPU_OK;
@@ -706,9 +697,9 @@ extern "C" int cmgpu_map_submitted(cmgpu_ctx *c, cmgpu_record *out, uint64_t out
   if (!c) return CMGPU_EINVAL;
   if (c->sub_count == 0) { cm_set_error(c, "no submitted batch (cmgpu_submit_pairs)"); return CMGPU_EINVAL; }
   if (c->has_barcodes || c->single) { c->has_barcodes = false; c->single = false; }
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   const int which = (int)((c->sub_total - c->sub_count) & 1u);  // the oldest submitted batch
-  HIPCHECK(c, hipEventSynchronize(c->ev_h2d[which]));
+  CM_HIPCHECK(c, hipEventSynchronize(c->ev_h2d[which]));
   --c->sub_count;
   int rc = cmgpu_swap_resident_batch(c, CM_BATCH_SLOTS - 1 - which);
   if (rc) return rc;
@@ -723,7 +714,7 @@ extern "C" int cmgpu_map_submitted(cmgpu_ctx *c, cmgpu_record *out, uint64_t out
 
 extern "C" int cmgpu_upload_batch(cmgpu_ctx *c, const cmgpu_batch *in) {
   if (!c || !in) return CMGPU_EINVAL;
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   const uint32_t n = in->n_pairs;
   if (n > 0x3fffffffu) { cm_set_error(c, "batch too large"); return CMGPU_EINVAL; }
   c->n_pairs = n;
@@ -736,13 +727,13 @@ extern "C" int cmgpu_upload_batch(cmgpu_ctx *c, const cmgpu_batch *in) {
     cm_set_error(c, "out of device memory (reads)");
     return CMGPU_ENOMEM;
   }
-  HIPCHECK(c, hipMemcpyAsync(c->rb0.p, in->read1_bases, c->bases0, hipMemcpyHostToDevice, c->stream));
-  HIPCHECK(c, hipMemcpyAsync(c->rb1.p, in->read2_bases, c->bases1, hipMemcpyHostToDevice, c->stream));
-  HIPCHECK(c, hipMemcpyAsync(c->ro0.p, in->read1_offsets, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHECK(c, hipMemcpyAsync(c->ro1.p, in->read2_offsets, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  CM_HIPCHECK(c, hipMemcpyAsync(c->rb0.p, in->read1_bases, c->bases0, hipMemcpyHostToDevice, c->stream));
+  CM_HIPCHECK(c, hipMemcpyAsync(c->rb1.p, in->read2_bases, c->bases1, hipMemcpyHostToDevice, c->stream));
+  CM_HIPCHECK(c, hipMemcpyAsync(c->ro0.p, in->read1_offsets, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  CM_HIPCHECK(c, hipMemcpyAsync(c->ro1.p, in->read2_offsets, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
   const int rc = launch_max_len(c, c->ro0, &c->ro1, n, c->stream);
   if (rc) return rc;
-  HIPCHECK(c, cm_stream_sync(c->stream));
+  CM_HIPCHECK(c, cm_stream_sync(c->stream));
   c->max_read_len = *c->h_maxlen ? *c->h_maxlen : 1;
   return CMGPU_OK;
 }
@@ -752,8 +743,8 @@ extern "C" int cmgpu_swap_resident_batch(cmgpu_ctx *c, int slot) {
   if (!c || slot < 0 || slot >= CM_BATCH_SLOTS) return CMGPU_EINVAL;
   if (c->in_flight) { cm_set_error(c, "a batch is in flight"); return CMGPU_EINVAL; }
   if (c->has_barcodes || c->single) { cm_set_error(c, "only bulk paired-end batches can be parked"); return CMGPU_EINVAL; }
-  HIPCHECK(c, cm_enter(c));
-  HIPCHECK(c, cm_stream_sync(c->stream));
+  CM_HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_stream_sync(c->stream));
   CmBatchSlot &sl = c->slots[slot];
   std::swap(c->rb0, sl.rb0); std::swap(c->rb1, sl.rb1); std::swap(c->ro0, sl.ro0); std::swap(c->ro1, sl.ro1);
   std::swap(c->n_pairs, sl.n_pairs); std::swap(c->first_read_id, sl.first_read_id); std::swap(c->max_read_len, sl.max_read_len);
@@ -853,11 +844,11 @@ static inline void mark(cmgpu_ctx *c, const char *name) {
 static int scan_with_total(cmgpu_ctx *c, const uint32_t *in, uint32_t *out, uint32_t n, unsigned long long *total, bool wait = true) {
   hipStream_t s = c->stream;
   unsigned long long *acc = (unsigned long long *)c->stats.p + CM_ST_TOTAL;  // spare counter slot
-  HIPCHECK(c, hipMemsetAsync(acc, 0, 8, s));
+  CM_HIPCHECK(c, hipMemsetAsync(acc, 0, 8, s));
   cm_launch_k_sum_u32(in, n, acc, s);
   cm_scan_u32(in, out, n, (uint32_t *)c->scan_tmp.p, s);
-  HIPCHECK(c, hipMemcpyAsync(total, acc, 8, hipMemcpyDeviceToHost, s));
-  if (wait) HIPCHECK(c, cm_stream_sync(s));
+  CM_HIPCHECK(c, hipMemcpyAsync(total, acc, 8, hipMemcpyDeviceToHost, s));
+  if (wait) CM_HIPCHECK(c, cm_stream_sync(s));
   return CMGPU_OK;
 }
 // internal results of a range: a dense intermediate exceeds the 32-bit item limit (map_split halves the range); the range
@@ -889,7 +880,7 @@ static int stage_begin(RangeRun &r) {
   c->use_perm = false;
   const int rc = ensure_pair_arrays(c, r.n);
   if (rc) return rc;
-  HIPCHECK(c, hipMemsetAsync(c->stats.p, 0, CM_ST_N * 8, r.s));
+  CM_HIPCHECK(c, hipMemsetAsync(c->stats.p, 0, CM_ST_N * 8, r.s));
   memset(&r.d, 0, sizeof(r.d));
   cm_ensure_goff(c);
   cm_set_classes(c, r.d);
@@ -920,15 +911,15 @@ template <class Fill>
 static int mm_fill_and_probe(RangeRun &r, const MmChunks &k, uint32_t mm_cap, Fill fill) {
   cmgpu_ctx *c = r.c;
   const unsigned long long *marks = (const unsigned long long *)c->mm_marks.p;
-  HIPCHECK(c, hipMemsetAsync(r.d.stats + CM_ST_PROBE_STEPS, 0, 2 * 8, r.s));
+  CM_HIPCHECK(c, hipMemsetAsync(r.d.stats + CM_ST_PROBE_STEPS, 0, 2 * 8, r.s));
   for (uint32_t ch = 0; ch < k.n_chunks; ++ch) {
     fill(ch);
-    HIPCHECK(c, hipEventRecord(c->chunk_ev[ch], r.s));
-    HIPCHECK(c, hipStreamWaitEvent(c->stream2, c->chunk_ev[ch], 0));
+    CM_HIPCHECK(c, hipEventRecord(c->chunk_ev[ch], r.s));
+    CM_HIPCHECK(c, hipStreamWaitEvent(c->stream2, c->chunk_ev[ch], 0));
     cm_launch_k_probe_range(r.d, marks + ch, k.entries[ch], mm_cap, (uint2 *)c->partials.p + k.part_off[ch], c->stream2, c->opt.probe_variant);
   }
-  HIPCHECK(c, hipEventRecord(c->chunk_ev[CM_MM_CHUNKS], c->stream2));
-  HIPCHECK(c, hipStreamWaitEvent(r.s, c->chunk_ev[CM_MM_CHUNKS], 0));
+  CM_HIPCHECK(c, hipEventRecord(c->chunk_ev[CM_MM_CHUNKS], c->stream2));
+  CM_HIPCHECK(c, hipStreamWaitEvent(r.s, c->chunk_ev[CM_MM_CHUNKS], 0));
   cm_launch_k_probe_reduce(c->partials.p, k.part_off[k.n_chunks], r.d.stats + CM_ST_PROBE_STEPS, r.s);
   return CMGPU_OK;
 }
@@ -967,8 +958,8 @@ static int stage_minimizers_fused(RangeRun &r, bool flat) {
       cm_set_error(c, "out of device memory (minimizers)"); return CMGPU_ENOMEM;
     }
     r.bind();
-    HIPCHECK(c, hipMemsetAsync(c->mm_cursor.p, 0, 8, s));
-    HIPCHECK(c, hipMemsetAsync(c->mm_marks.p, 0, 8, s));
+    CM_HIPCHECK(c, hipMemsetAsync(c->mm_cursor.p, 0, 8, s));
+    CM_HIPCHECK(c, hipMemsetAsync(c->mm_marks.p, 0, 8, s));
     unsigned long long *cursor = (unsigned long long *)c->mm_cursor.p, *marks = (unsigned long long *)c->mm_marks.p;
     rc = mm_fill_and_probe(r, k, (uint32_t)cap, [&](uint32_t ch) {
       if (flat) cm_launch_k_prep_flat(d, k.lo[ch], k.lo[ch + 1], c->max_read_len, (uint32_t)c->opt.prep_tile_reads, (uint32_t)cap, cursor, s);
@@ -979,16 +970,16 @@ static int stage_minimizers_fused(RangeRun &r, bool flat) {
     // S3a (hit counts, size classes) and the scan of the counts follow at once: their totals come back with the minimizer
     // marks in ONE read (a read's minimizer range is checked against the arrays' capacity, so an overflow leaves them idle)
     d.mm_cap = (uint32_t)cap;
-    HIPCHECK(c, hipMemsetAsync(c->hv_cnt.p, 0, 256, s));
+    CM_HIPCHECK(c, hipMemsetAsync(c->hv_cnt.p, 0, 256, s));
     cm_launch_k_s3a_count(d, n2, s);
     d.mm_cap = 0;  // (S3a alone checks it)
     if ((rc = scan_with_total(c, d.hit_tot, d.hit_off, n2, &r.hits_total, false))) return rc;
-    HIPCHECK(c, hipMemcpyAsync(r.n_heavy, c->hv_cnt.p, sizeof(r.n_heavy), hipMemcpyDeviceToHost, s));
+    CM_HIPCHECK(c, hipMemcpyAsync(r.n_heavy, c->hv_cnt.p, sizeof(r.n_heavy), hipMemcpyDeviceToHost, s));
     r.s3a_done = true;
     // one read-back: the marks (cursor after every chunk; the last one is the total)
     unsigned long long hm[CM_MM_CHUNKS + 1];
-    HIPCHECK(c, hipMemcpyAsync(hm, marks, ((size_t)k.n_chunks + 1) * 8, hipMemcpyDeviceToHost, s));  // (not the null stream: lanes run side by side)
-    HIPCHECK(c, cm_stream_sync(s));
+    CM_HIPCHECK(c, hipMemcpyAsync(hm, marks, ((size_t)k.n_chunks + 1) * 8, hipMemcpyDeviceToHost, s));  // (not the null stream: lanes run side by side)
+    CM_HIPCHECK(c, cm_stream_sync(s));
     const unsigned long long tot = hm[k.n_chunks];
     bool grid_short = false;  // a chunk emitted more than its probe grid covers (cannot happen on attempt 1)
     if (attempt == 0 && tot <= cap)
@@ -1022,8 +1013,8 @@ static int stage_minimizers_two_pass(RangeRun &r) {
   unsigned long long *marks = (unsigned long long *)c->mm_marks.p;
   unsigned long long hm[CM_MM_CHUNKS + 1];
   cm_launch_k_mm_marks(d.mm_off, k.lo, k.n_chunks + 1, marks, s);
-  HIPCHECK(c, hipMemcpyAsync(hm, marks, ((size_t)k.n_chunks + 1) * 8, hipMemcpyDeviceToHost, s));
-  HIPCHECK(c, cm_stream_sync(s));
+  CM_HIPCHECK(c, hipMemcpyAsync(hm, marks, ((size_t)k.n_chunks + 1) * 8, hipMemcpyDeviceToHost, s));
+  CM_HIPCHECK(c, cm_stream_sync(s));
   for (uint32_t ch = 0; ch < k.n_chunks; ++ch) k.entries[ch] = hm[ch + 1] - hm[ch];
   mm_probe_grids(c, k);
   if (c->partials.ensure(((size_t)k.part_off[k.n_chunks] + 1) * 8 + cm_stats_partial_words(r.n) * 8)) { cm_set_error(c, "out of device memory (partials)"); return CMGPU_ENOMEM; }
@@ -1043,13 +1034,13 @@ static int stage_pack_reads(RangeRun &r) {
   if (!c->stream_pack) {
     int prio_least = 0, prio_greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    HIPCHECK(c, hipStreamCreateWithPriority(&c->stream_pack, hipStreamNonBlocking, prio_greatest));
+    CM_HIPCHECK(c, hipStreamCreateWithPriority(&c->stream_pack, hipStreamNonBlocking, prio_greatest));
   }
-  HIPCHECK(c, hipEventRecord(c->chunk_ev[1], r.s));
-  HIPCHECK(c, hipStreamWaitEvent(c->stream_pack, c->chunk_ev[1], 0));
+  CM_HIPCHECK(c, hipEventRecord(c->chunk_ev[1], r.s));
+  CM_HIPCHECK(c, hipStreamWaitEvent(c->stream_pack, c->chunk_ev[1], 0));
   r.d.read_pl = (uint32_t *)c->read_planes.p; r.d.read_pl_w = (c->max_read_len + 31) / 32;  // (read by the S5 kernels only, behind their wait for chunk_ev[0])
   cm_launch_k_pack_reads(r.d, r.n2, c->stream_pack);
-  HIPCHECK(c, hipEventRecord(c->chunk_ev[0], c->stream_pack));
+  CM_HIPCHECK(c, hipEventRecord(c->chunk_ev[0], c->stream_pack));
   return CMGPU_OK;
 }
 // S3: hit counts -> offsets -> candidates
@@ -1057,9 +1048,9 @@ static int stage_s3_candidates(RangeRun &r) {
   cmgpu_ctx *c = r.c; CmDev &d = r.d; hipStream_t s = r.s;
   const uint32_t n2 = r.n2;
   if (!r.s3a_done) {
-    HIPCHECK(c, hipMemsetAsync(c->hv_cnt.p, 0, 256, s));
+    CM_HIPCHECK(c, hipMemsetAsync(c->hv_cnt.p, 0, 256, s));
     cm_launch_k_s3a_count(d, n2, s);
-    HIPCHECK(c, hipMemcpyAsync(r.n_heavy, c->hv_cnt.p, sizeof(r.n_heavy), hipMemcpyDeviceToHost, s));
+    CM_HIPCHECK(c, hipMemcpyAsync(r.n_heavy, c->hv_cnt.p, sizeof(r.n_heavy), hipMemcpyDeviceToHost, s));
     const int rc = scan_with_total(c, d.hit_tot, d.hit_off, n2, &r.hits_total);
     if (rc) return rc;
   }
@@ -1111,7 +1102,7 @@ static int stage_s4_rescue_filter(RangeRun &r) {
   cmgpu_ctx *c = r.c; CmDev &d = r.d; hipStream_t s = r.s;
   const uint32_t n2 = r.n2;
   const bool coop = (c->opt.coop & 2) != 0;
-  HIPCHECK(c, hipMemsetAsync(c->rs_cnt.p, 0, CM_RS_SEGS * 64, s));
+  CM_HIPCHECK(c, hipMemsetAsync(c->rs_cnt.p, 0, CM_RS_SEGS * 64, s));
   if (coop) size_rescue_pool(r);
   cm_launch_k_s4a_rescue_count(d, n2, s, coop);  // decision per read + the packed list of reads that supplement
   cm_launch_k_s4a_rescue_list(d, n2, s, coop);   // their searches: a lane, a group of 16 lanes or a wave per read
@@ -1122,7 +1113,7 @@ static int stage_s4_rescue_filter(RangeRun &r) {
   r.spec = r.allow_spec && c->opt.spec && c->pred_m_ok && (c->pred_n == r.n || c->pred_n == 0xffffffffu) && c->m_cap > 0 && c->m_cap <= r.limit;
   if (r.spec) {
     unsigned long long *acc = (unsigned long long *)c->stats.p + CM_ST_TOTAL;
-    HIPCHECK(c, hipMemsetAsync(acc, 0, 8, s));
+    CM_HIPCHECK(c, hipMemsetAsync(acc, 0, 8, s));
     cm_launch_k_sum_u32(d.m_tot, n2, acc, s);
     cm_scan_u32(d.m_tot, d.m_off, n2, (uint32_t *)c->scan_tmp.p, s);
     cm_launch_k_check_cap(acc, c->m_cap, (unsigned long long *)c->stats.p + CM_ST_ABORT, s);
@@ -1144,7 +1135,7 @@ static int stage_s4_rescue_filter(RangeRun &r) {
   cm_launch_k_s4b_rescue_merge(d, n2, s, coop, c->max_read_len);
   cm_launch_k_s4b_rescue_list(d, n2, s, coop, c->max_read_len);
   mark(c, "s4b_rescue_merge");
-  HIPCHECK(c, hipMemsetAsync(c->srt_cnt.p, 0, 8, s));
+  CM_HIPCHECK(c, hipMemsetAsync(c->srt_cnt.p, 0, 8, s));
   cm_launch_k_s4c_reduce(d, r.n, s, (uint32_t)c->opt.coop & (c->p.split ? ~8u : ~0u));
   if (c->use_perm) cm_launch_k_sort_lists(d, 0, s);  // long candidate lists: a wave each, before S5a wants them in order
   mark(c, "s4c_pair_filter");
@@ -1155,13 +1146,13 @@ static int stage_s4_rescue_filter(RangeRun &r) {
 static int stage_s5_verify(RangeRun &r) {
   cmgpu_ctx *c = r.c; const CmDev &d = r.d; hipStream_t s = r.s;
   const bool coop = (c->opt.coop & 8) != 0 && !c->p.split;  // (split alignments are verified in S5a already)
-  if (r.planes) HIPCHECK(c, hipStreamWaitEvent(s, c->chunk_ev[0], 0));  // k_pack_reads (its own stream) is done
+  if (r.planes) CM_HIPCHECK(c, hipStreamWaitEvent(s, c->chunk_ev[0], 0));  // k_pack_reads (its own stream) is done
   cm_launch_k_s5a_prepare(d, r.n2, s, coop);
   cm_scan_u32(d.nv, d.v_off, r.n2, (uint32_t *)c->scan_tmp.p, s);  // the items' number stays on the device: never above n_m
   mark(c, "s5a_prepare");
   cm_launch_k_s5b_verify(d, r.n_m, r.n2, s);
   mark(c, "s5b_verify");
-  HIPCHECK(c, hipMemsetAsync(c->srt_cnt.p, 0, 8, s));
+  CM_HIPCHECK(c, hipMemsetAsync(c->srt_cnt.p, 0, 8, s));
   cm_launch_k_s5c_finalize(d, r.n2, s, coop);
   if (c->use_perm) cm_launch_k_sort_lists(d, 1, s);  // long draft-mapping lists, before S6a pairs them
   mark(c, "s5c_accept");
@@ -1178,7 +1169,7 @@ static int stage_s6_records(RangeRun &r) {
     const uint32_t md_cap = c->sam_md_cap;
     const uint32_t zw = (2 * c->p.e + 2 <= 18) ? 5 : 8;
     if (c->sam_z.ensure((size_t)c->max_read_len * zw * 4 * n + 16)) { cm_set_error(c, "out of device memory (SAM buffers)"); return CMGPU_ENOMEM; }
-    HIPCHECK(c, hipMemsetAsync((uint8_t *)c->sam_rec.p + slot0 * 40, 0, slots * 40, s));
+    CM_HIPCHECK(c, hipMemsetAsync((uint8_t *)c->sam_rec.p + slot0 * 40, 0, slots * 40, s));
     d.sam_rec = (uint8_t *)c->sam_rec.p + slot0 * 40; d.sam_cigar = (uint32_t *)c->sam_cigar.p + slot0 * CM_SAM_CIGAR_CAP;
     d.sam_md = (uint8_t *)c->sam_md.p + slot0 * md_cap;
     d.sam_z = (uint32_t *)c->sam_z.p; d.sam_md_cap = md_cap;
@@ -1197,11 +1188,11 @@ static int stage_finish(RangeRun &r, uint64_t *k_out, cmgpu_stats *stats) {
   cm_launch_k_stats(r.d, r.n, (unsigned long long *)c->partials.p, s);
   unsigned long long hst[CM_ST_N];
   uint32_t h_cls[CM_HV_LISTS];
-  HIPCHECK(c, hipMemcpyAsync(hst, c->stats.p, sizeof(hst), hipMemcpyDeviceToHost, s));
-  HIPCHECK(c, hipMemcpyAsync(h_cls, c->hv_cnt.p, sizeof(h_cls), hipMemcpyDeviceToHost, s));
-  HIPCHECK(c, cm_stream_sync(s));
+  CM_HIPCHECK(c, hipMemcpyAsync(hst, c->stats.p, sizeof(hst), hipMemcpyDeviceToHost, s));
+  CM_HIPCHECK(c, hipMemcpyAsync(h_cls, c->hv_cnt.p, sizeof(h_cls), hipMemcpyDeviceToHost, s));
+  CM_HIPCHECK(c, cm_stream_sync(s));
   mark(c, "stats");
-  HIPCHECK(c, cm_stream_sync(s));
+  CM_HIPCHECK(c, cm_stream_sync(s));
   const bool aborted = r.spec && hst[CM_ST_ABORT];  // this batch needs more room than the previous one left
   if (!aborted) {  // speculative launch set: a class with items whose kernels were not launched -> the range again with every class on
     unsigned long long seen = 0, keep = 0;
@@ -1312,7 +1303,7 @@ static int lane_prepare(cmgpu_ctx *c, size_t i) {
 
 extern "C" int cmgpu_map_resident(cmgpu_ctx *c, uint64_t *n_out, cmgpu_stats *stats) {
   if (!c) return CMGPU_EINVAL;
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   const uint32_t n = c->n_pairs;
   c->n_ev = 0;
   c->n_records = 0;
@@ -1392,45 +1383,24 @@ extern "C" int cmgpu_map_resident(cmgpu_ctx *c, uint64_t *n_out, cmgpu_stats *st
   return CMGPU_OK;
 }
 
-// the batch's records, compacted on the device, in one copy (the order of the pairs is kept; at most `cap` records are written)
-__global__ void k_rec_flag(const uint8_t *ok, uint32_t *flag, uint32_t n) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) flag[i] = ok[i];
-}
-__global__ void k_rec_compact(const uint8_t *__restrict__ rec, const uint8_t *__restrict__ ok,
-                              const uint32_t *__restrict__ pos, uint8_t *__restrict__ dst, uint32_t n, uint64_t cap) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n || !ok[i]) return;
-  const uint32_t o = pos[i];
-  if (o >= cap) return;
-  const uint64_t *s = reinterpret_cast<const uint64_t *>(rec + (uint64_t)i * 24);
-  uint64_t *d = reinterpret_cast<uint64_t *>(dst + (uint64_t)o * 24);
-  d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
-}
 // the resident batch's records, compacted into `dst` on the mapping stream (pair order kept); nothing is waited for
 static int compact_records(cmgpu_ctx *c, DevBuf &dst) {
   const uint32_t n = (uint32_t)cm_rec_slots(c);
   if (n == 0) return CMGPU_OK;
   { const int rc = cm_ensure_slot_scratch(c, n); if (rc) return rc; }
   if (dst.ensure((size_t)n * 24 + 16)) { cm_set_error(c, "out of device memory (records)"); return CMGPU_ENOMEM; }
-  uint32_t *flag = (uint32_t *)c->scratch_a.p, *pos = (uint32_t *)c->scratch_b.p;  // free between batches
-  hipStream_t s = c->stream;
-  hipLaunchKernelGGL(k_rec_flag, dim3((n + 255) / 256), dim3(256), 0, s, (const uint8_t *)c->rec_ok.p, flag, n);
-  cm_scan_u32(flag, pos, n, (uint32_t *)c->scan_tmp.p, s);
-  hipLaunchKernelGGL(k_rec_compact, dim3((n + 255) / 256), dim3(256), 0, s, (const uint8_t *)c->rec.p, (const uint8_t *)c->rec_ok.p,
-                     (const uint32_t *)pos, (uint8_t *)dst.p, n, (uint64_t)n);
-  return CMGPU_OK;
+  return cm_compact_records(c, dst.p, nullptr, n, c->stream, nullptr);
 }
 static int download_dense(cmgpu_ctx *c, cmgpu_record *out, uint64_t out_capacity, uint64_t *n_out) {
   if (n_out) *n_out = 0;
   if (cm_rec_slots(c) == 0) return CMGPU_OK;
-  if (c->pend_count && c->stream_d2h) HIPCHECK(c, hipStreamSynchronize(c->stream_d2h));  // (a pending asynchronous download reads rec_dense)
+  if (c->pend_count && c->stream_d2h) CM_HIPCHECK(c, hipStreamSynchronize(c->stream_d2h));  // (a pending asynchronous download reads rec_dense)
   { const int rc = compact_records(c, c->rec_dense); if (rc) return rc; }
   hipStream_t s = c->stream;
   const uint64_t k = c->n_records;  // counted by the mapping call
   if (k > out_capacity) { cm_set_error(c, "record buffer too small"); return CMGPU_ECAPACITY; }
   if (k) { const int rc = device_to_host(c, out, c->rec_dense.p, (size_t)k * 24, s); if (rc) return rc; }
-  HIPCHECK(c, cm_stream_sync(s));
+  CM_HIPCHECK(c, cm_stream_sync(s));
   if (n_out) *n_out = k;
   return CMGPU_OK;
 }
@@ -1448,23 +1418,23 @@ extern "C" int cmgpu_map_submitted_async(cmgpu_ctx *c, cmgpu_record *out, uint64
   if (k > out_capacity) { cm_set_error(c, "record buffer too small"); return CMGPU_ECAPACITY; }
   if (!c->stream_d2h) {
     int prio_least = 0, prio_greatest = 0;
-    HIPCHECK(c, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-    HIPCHECK(c, hipStreamCreateWithPriority(&c->stream_d2h, hipStreamNonBlocking, prio_greatest));
-    HIPCHECK(c, hipEventCreateWithFlags(&c->ev_comp, hipEventDisableTiming));
-    for (hipEvent_t &e : c->ev_d2h) HIPCHECK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    CM_HIPCHECK(c, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+    CM_HIPCHECK(c, hipStreamCreateWithPriority(&c->stream_d2h, hipStreamNonBlocking, prio_greatest));
+    CM_HIPCHECK(c, hipEventCreateWithFlags(&c->ev_comp, hipEventDisableTiming));
+    for (hipEvent_t &e : c->ev_d2h) CM_HIPCHECK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
   const uint32_t slot = c->pend_total & 1u;
   DevBuf &dst = slot ? c->rec_dense_b : c->rec_dense;
   if (k) {
     rc = compact_records(c, dst);
     if (rc) return rc;
-    HIPCHECK(c, hipEventRecord(c->ev_comp, c->stream));
-    HIPCHECK(c, hipStreamWaitEvent(c->stream_d2h, c->ev_comp, 0));
-    HIPCHECK(c, hipMemcpyAsync(out, dst.p, (size_t)k * 24, hipMemcpyDeviceToHost, c->stream_d2h));
+    CM_HIPCHECK(c, hipEventRecord(c->ev_comp, c->stream));
+    CM_HIPCHECK(c, hipStreamWaitEvent(c->stream_d2h, c->ev_comp, 0));
+    CM_HIPCHECK(c, hipMemcpyAsync(out, dst.p, (size_t)k * 24, hipMemcpyDeviceToHost, c->stream_d2h));
     // the next mapping call's lanes write the per-pair record arrays from streams of their own: the compaction has to be through
-    HIPCHECK(c, hipEventSynchronize(c->ev_comp));
+    CM_HIPCHECK(c, hipEventSynchronize(c->ev_comp));
   }
-  HIPCHECK(c, hipEventRecord(c->ev_d2h[slot], c->stream_d2h));
+  CM_HIPCHECK(c, hipEventRecord(c->ev_d2h[slot], c->stream_d2h));
   c->pend_k[slot] = k;
   ++c->pend_total; ++c->pend_count;
   return CMGPU_OK;
@@ -1472,9 +1442,9 @@ extern "C" int cmgpu_map_submitted_async(cmgpu_ctx *c, cmgpu_record *out, uint64
 extern "C" int cmgpu_records_wait(cmgpu_ctx *c, uint64_t *n_out) {
   if (!c) return CMGPU_EINVAL;
   if (c->pend_count == 0) { cm_set_error(c, "no record download pending (cmgpu_map_submitted_async)"); return CMGPU_EINVAL; }
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   const uint32_t slot = (c->pend_total - c->pend_count) & 1u;
-  HIPCHECK(c, hipEventSynchronize(c->ev_d2h[slot]));
+  CM_HIPCHECK(c, hipEventSynchronize(c->ev_d2h[slot]));
   --c->pend_count;
   if (n_out) *n_out = c->pend_k[slot];
   return CMGPU_OK;
@@ -1482,7 +1452,7 @@ extern "C" int cmgpu_records_wait(cmgpu_ctx *c, uint64_t *n_out) {
 
 extern "C" int cmgpu_download_records(cmgpu_ctx *c, cmgpu_record *out, uint64_t out_capacity, uint64_t *n_out) {
   if (!c || !out || !n_out) return CMGPU_EINVAL;
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   return download_dense(c, out, out_capacity, n_out);
 }
 
@@ -1539,12 +1509,12 @@ extern "C" int cmgpu_sam_layout(const cmgpu_ctx *c, uint64_t *n_slots, uint32_t 
 extern "C" int cmgpu_download_sam(cmgpu_ctx *c, cmgpu_sam_record *records, uint32_t *cigar_pool, char *md_pool) {
   if (!c || !records || !cigar_pool || !md_pool) return CMGPU_EINVAL;
   if (!c->p.sam) { cm_set_error(c, "the ctx was not created with output_format = CMGPU_FORMAT_SAM"); return CMGPU_EINVAL; }
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   const uint64_t ns = c->sam_slots;
   if (ns == 0) return CMGPU_OK;
-  HIPCHECK(c, hipMemcpy(records, c->sam_rec.p, ns * 40, hipMemcpyDeviceToHost));
-  HIPCHECK(c, hipMemcpy(cigar_pool, c->sam_cigar.p, ns * CM_SAM_CIGAR_CAP * 4, hipMemcpyDeviceToHost));
-  HIPCHECK(c, hipMemcpy(md_pool, c->sam_md.p, ns * c->sam_md_cap, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(c, hipMemcpy(records, c->sam_rec.p, ns * 40, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(c, hipMemcpy(cigar_pool, c->sam_cigar.p, ns * CM_SAM_CIGAR_CAP * 4, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(c, hipMemcpy(md_pool, c->sam_md.p, ns * c->sam_md_cap, hipMemcpyDeviceToHost));
   for (uint64_t i = 0; i < ns; ++i)
     if (records[i].valid == 2) { cm_set_error(c, "an alignment needs more than CMGPU_SAM_CIGAR_CAP CIGAR operations"); return CMGPU_ECAPACITY; }
   return CMGPU_OK;
@@ -1553,8 +1523,8 @@ extern "C" int cmgpu_download_sam(cmgpu_ctx *c, cmgpu_sam_record *records, uint3
 extern "C" int cmgpu_download_barcode_keys(cmgpu_ctx *c, uint64_t *keys) {
   if (!c || !keys) return CMGPU_EINVAL;
   if (!c->has_barcodes) { cm_set_error(c, "the last batch had no barcodes"); return CMGPU_EINVAL; }
-  HIPCHECK(c, cm_enter(c));
-  if (c->n_pairs) HIPCHECK(c, hipMemcpy(keys, c->bc_key.p, (size_t)c->n_pairs * 8, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(c, cm_enter(c));
+  if (c->n_pairs) CM_HIPCHECK(c, hipMemcpy(keys, c->bc_key.p, (size_t)c->n_pairs * 8, hipMemcpyDeviceToHost));
   return CMGPU_OK;
 }
 
@@ -1565,7 +1535,7 @@ extern "C" int cmgpu_download_barcode_keys(cmgpu_ctx *c, uint64_t *keys) {
 // ---------------------------------------------------------------------------------------
 extern "C" int cmgpu_debug_trace(cmgpu_ctx *c, cmgpu_trace *out, uint64_t capacity) {
   if (!c || !out) return CMGPU_EINVAL;
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   const uint32_t n = c->n_pairs;
   if (capacity < n) { cm_set_error(c, "trace buffer too small"); return CMGPU_ECAPACITY; }
   if (c->single) { cm_set_error(c, "the trace is defined for paired-end batches"); return CMGPU_EINVAL; }
@@ -1576,7 +1546,7 @@ extern "C" int cmgpu_debug_trace(cmgpu_ctx *c, cmgpu_trace *out, uint64_t capaci
   std::vector<uint32_t> rlen(n2), mm(n2), mcp(n2), mcn(n2), fcp(n2), fcn(n2), ndp(n2), ndn(n2), rep(n2);
   std::vector<int32_t> me(n2), nb(n2), se(n2), ns(n2), pmin(n), pnb(n), psec(n), pns(n);
   std::vector<uint8_t> f0(n);
-#define DL(v, buf) HIPCHECK(c, hipMemcpy(v.data(), c->buf.p, v.size() * sizeof(v[0]), hipMemcpyDeviceToHost));
+#define DL(v, buf) CM_HIPCHECK(c, hipMemcpy(v.data(), c->buf.p, v.size() * sizeof(v[0]), hipMemcpyDeviceToHost));
   DL(rlen, rlen) DL(mm, mm_cnt) DL(mcp, mcp) DL(mcn, mcn) DL(fcp, fcp) DL(fcn, fcn) DL(ndp, ndp) DL(ndn, ndn) DL(rep, rep_len)
   DL(me, min_err) DL(nb, n_best) DL(se, second_err) DL(ns, n_second) DL(pmin, pe_min) DL(pnb, pe_nbest) DL(psec, pe_second) DL(pns, pe_nsecond)
   DL(f0, force0)
@@ -1605,7 +1575,7 @@ extern "C" int cmgpu_debug_trace(cmgpu_ctx *c, cmgpu_trace *out, uint64_t capaci
 // distribution tools (tools/list_hist.py) -- measurement aid, declared in include/chromap_amd_debug.h
 extern "C" int cmgpu_debug_array(cmgpu_ctx *c, const char *name, uint32_t *out, uint64_t capacity, uint64_t *n_out) {
   if (!c || !name || !out) return CMGPU_EINVAL;
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   const std::string nm(name);
   struct { const char *n; DevBuf *b; int per_pair; } tab[] = {
     {"rlen", &c->rlen, 0}, {"mm_cnt", &c->mm_cnt, 0}, {"hit_tot", &c->hit_tot, 0}, {"ncp", &c->ncp, 0}, {"ncn", &c->ncn, 0},
@@ -1616,7 +1586,7 @@ extern "C" int cmgpu_debug_array(cmgpu_ctx *c, const char *name, uint32_t *out, 
       const uint64_t n = t.per_pair ? c->n_pairs : 2ull * c->n_pairs;
       if (n_out) *n_out = n;
       if (capacity < n || !t.b->p || t.b->cap < n * 4) { cm_set_error(c, "debug array: buffer too small or array not resident"); return CMGPU_ECAPACITY; }
-      HIPCHECK(c, hipMemcpy(out, t.b->p, n * 4, hipMemcpyDeviceToHost));
+      CM_HIPCHECK(c, hipMemcpy(out, t.b->p, n * 4, hipMemcpyDeviceToHost));
       return CMGPU_OK;
     }
   cm_set_error(c, "debug array: unknown name " + nm);
@@ -1626,31 +1596,31 @@ extern "C" int cmgpu_debug_array(cmgpu_ctx *c, const char *name, uint32_t *out, 
 // one read's minimizers of the last mapped batch: (hash, position << 1 | strand) in emission order
 extern "C" int cmgpu_debug_minimizers(cmgpu_ctx *c, uint32_t read, uint64_t *hash_out, uint32_t *ps_out, uint32_t capacity, uint32_t *n_out) {
   if (!c || !n_out || read >= 2 * c->n_pairs) return CMGPU_EINVAL;
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   if (c->last_range_lo != 0 || c->last_range_hi != c->n_pairs) { cm_set_error(c, "the batch was mapped in sub-batches"); return CMGPU_EINVAL; }
   uint32_t cnt = 0, off = 0;
-  HIPCHECK(c, hipMemcpy(&cnt, (const uint32_t *)c->mm_cnt.p + read, 4, hipMemcpyDeviceToHost));
-  HIPCHECK(c, hipMemcpy(&off, (const uint32_t *)c->mm_off.p + read, 4, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(c, hipMemcpy(&cnt, (const uint32_t *)c->mm_cnt.p + read, 4, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(c, hipMemcpy(&off, (const uint32_t *)c->mm_off.p + read, 4, hipMemcpyDeviceToHost));
   *n_out = cnt;
   if (cnt > capacity) { cm_set_error(c, "minimizer buffer too small"); return CMGPU_ECAPACITY; }
-  if (cnt && hash_out) HIPCHECK(c, hipMemcpy(hash_out, (const uint64_t *)c->mm_hash.p + off, (size_t)cnt * 8, hipMemcpyDeviceToHost));
-  if (cnt && ps_out) HIPCHECK(c, hipMemcpy(ps_out, (const uint32_t *)c->mm_ps.p + off, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+  if (cnt && hash_out) CM_HIPCHECK(c, hipMemcpy(hash_out, (const uint64_t *)c->mm_hash.p + off, (size_t)cnt * 8, hipMemcpyDeviceToHost));
+  if (cnt && ps_out) CM_HIPCHECK(c, hipMemcpy(ps_out, (const uint32_t *)c->mm_ps.p + off, (size_t)cnt * 4, hipMemcpyDeviceToHost));
   return CMGPU_OK;
 }
 // all of them at once: counts / offsets per read (2 n_pairs each) and the dense arrays (n_total entries)
 extern "C" int cmgpu_debug_minimizers_all(cmgpu_ctx *c, uint32_t *cnt_out, uint32_t *off_out, uint64_t *hash_out, uint32_t *ps_out, uint64_t capacity,
                                           uint64_t *n_total) {
   if (!c || !cnt_out || !off_out || !n_total) return CMGPU_EINVAL;
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   if (c->last_range_lo != 0 || c->last_range_hi != c->n_pairs) { cm_set_error(c, "the batch was mapped in sub-batches"); return CMGPU_EINVAL; }
   const size_t n2 = 2 * (size_t)c->n_pairs;
   *n_total = c->last_n_mm;
   if (n2 == 0) return CMGPU_OK;
-  HIPCHECK(c, hipMemcpy(cnt_out, c->mm_cnt.p, n2 * 4, hipMemcpyDeviceToHost));
-  HIPCHECK(c, hipMemcpy(off_out, c->mm_off.p, n2 * 4, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(c, hipMemcpy(cnt_out, c->mm_cnt.p, n2 * 4, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(c, hipMemcpy(off_out, c->mm_off.p, n2 * 4, hipMemcpyDeviceToHost));
   if (c->last_n_mm > capacity) { cm_set_error(c, "minimizer buffer too small"); return CMGPU_ECAPACITY; }
-  if (c->last_n_mm && hash_out) HIPCHECK(c, hipMemcpy(hash_out, c->mm_hash.p, c->last_n_mm * 8, hipMemcpyDeviceToHost));
-  if (c->last_n_mm && ps_out) HIPCHECK(c, hipMemcpy(ps_out, c->mm_ps.p, c->last_n_mm * 4, hipMemcpyDeviceToHost));
+  if (c->last_n_mm && hash_out) CM_HIPCHECK(c, hipMemcpy(hash_out, c->mm_hash.p, c->last_n_mm * 8, hipMemcpyDeviceToHost));
+  if (c->last_n_mm && ps_out) CM_HIPCHECK(c, hipMemcpy(ps_out, c->mm_ps.p, c->last_n_mm * 4, hipMemcpyDeviceToHost));
   return CMGPU_OK;
 }
 
@@ -1669,12 +1639,12 @@ extern "C" int cmgpu_last_timings(const cmgpu_ctx *c, const char **names, float 
 
 extern "C" int cmgpu_download_batch(cmgpu_ctx *c, char *r1, uint32_t *o1, char *r2, uint32_t *o2) {
   if (!c) return CMGPU_EINVAL;
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   const uint32_t n = c->n_pairs;
-  if (r1) HIPCHECK(c, hipMemcpy(r1, c->rb0.p, c->bases0, hipMemcpyDeviceToHost));
-  if (r2) HIPCHECK(c, hipMemcpy(r2, c->rb1.p, c->bases1, hipMemcpyDeviceToHost));
-  if (o1) HIPCHECK(c, hipMemcpy(o1, c->ro0.p, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost));
-  if (o2) HIPCHECK(c, hipMemcpy(o2, c->ro1.p, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost));
+  if (r1) CM_HIPCHECK(c, hipMemcpy(r1, c->rb0.p, c->bases0, hipMemcpyDeviceToHost));
+  if (r2) CM_HIPCHECK(c, hipMemcpy(r2, c->rb1.p, c->bases1, hipMemcpyDeviceToHost));
+  if (o1) CM_HIPCHECK(c, hipMemcpy(o1, c->ro0.p, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost));
+  if (o2) CM_HIPCHECK(c, hipMemcpy(o2, c->ro1.p, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost));
   return CMGPU_OK;
 }
 
@@ -1696,10 +1666,10 @@ extern "C" int cmgpu_probe_bench_variant(cmgpu_ctx *c, uint64_t n, int repeat, i
 static int probe_bench_impl(cmgpu_ctx *c, const uint64_t *hashes, uint64_t n, int repeat, int variant, double *avg_ms,
                             uint64_t *probe_steps, uint64_t *hits, uint64_t *occurrences) {
   if (!c || n == 0 || n > 0xffffff00ull || repeat < 1) return CMGPU_EINVAL;
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   if (hashes) {
     if (c->mm_hash.ensure(n * 8)) { cm_set_error(c, "out of device memory (probe hashes)"); return CMGPU_ENOMEM; }
-    HIPCHECK(c, hipMemcpy(c->mm_hash.p, hashes, n * 8, hipMemcpyHostToDevice));
+    CM_HIPCHECK(c, hipMemcpy(c->mm_hash.p, hashes, n * 8, hipMemcpyHostToDevice));
   } else if (c->mm_hash.cap < n * 8) {
     cm_set_error(c, "no resident hashes");
     return CMGPU_EINVAL;
@@ -1707,7 +1677,7 @@ static int probe_bench_impl(cmgpu_ctx *c, const uint64_t *hashes, uint64_t n, in
   if (c->pr_val.ensure(n * 8) || c->pr_kind.ensure(n)) { cm_set_error(c, "out of device memory (probe results)"); return CMGPU_ENOMEM; }
   hipStream_t s = c->stream;
   unsigned long long *ctr = (unsigned long long *)c->stats.p;
-  HIPCHECK(c, hipMemsetAsync(ctr, 0, CM_ST_N * 8, s));
+  CM_HIPCHECK(c, hipMemsetAsync(ctr, 0, CM_ST_N * 8, s));
   // warm-up + counted launch
   if (c->partials.ensure(cm_probe_partial_words((uint32_t)n) * 8)) { cm_set_error(c, "out of device memory (partials)"); return CMGPU_ENOMEM; }
   const bool file_layout = (variant & 32) != 0 || !c->fmask;  // + 32: the file's table even when a re-hashed one is resident
@@ -1717,16 +1687,16 @@ static int probe_bench_impl(cmgpu_ctx *c, const uint64_t *hashes, uint64_t n, in
   cm_launch_k_probe(tab, tmask, (const uint64_t *)c->mm_hash.p, (uint64_t *)c->pr_val.p,
                     (uint8_t *)c->pr_kind.p, (uint32_t)n, c->partials.p, ctr + CM_ST_PROBE_STEPS, s, variant);
   unsigned long long h[CM_ST_N];
-  HIPCHECK(c, hipMemcpyAsync(h, ctr, sizeof(h), hipMemcpyDeviceToHost, s));
-  HIPCHECK(c, cm_stream_sync(s));
-  HIPCHECK(c, hipEventRecord(c->ev[0], s));
+  CM_HIPCHECK(c, hipMemcpyAsync(h, ctr, sizeof(h), hipMemcpyDeviceToHost, s));
+  CM_HIPCHECK(c, cm_stream_sync(s));
+  CM_HIPCHECK(c, hipEventRecord(c->ev[0], s));
   for (int i = 0; i < repeat; ++i)
     cm_launch_k_probe(tab, tmask, (const uint64_t *)c->mm_hash.p, (uint64_t *)c->pr_val.p,
                       (uint8_t *)c->pr_kind.p, (uint32_t)n, nullptr, nullptr, s, variant);
-  HIPCHECK(c, hipEventRecord(c->ev[1], s));
-  HIPCHECK(c, hipEventSynchronize(c->ev[1]));
+  CM_HIPCHECK(c, hipEventRecord(c->ev[1], s));
+  CM_HIPCHECK(c, hipEventSynchronize(c->ev[1]));
   float ms = 0;
-  HIPCHECK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+  CM_HIPCHECK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
   if (avg_ms) *avg_ms = ms / repeat;
   if (probe_steps) *probe_steps = h[CM_ST_PROBE_STEPS];
   if (hits) *hits = h[CM_ST_PROBE_HITS];
@@ -1743,8 +1713,8 @@ extern "C" int cmgpu_reference_lengths(cmgpu_ctx *c, uint32_t *lengths, uint32_t
 
 extern "C" int cmgpu_export_reference(cmgpu_ctx *c, uint32_t seq, char *out, uint32_t capacity) {
   if (!c || seq >= c->n_seq || !out || capacity < c->h_ref_len[seq]) return CMGPU_EINVAL;
-  HIPCHECK(c, cm_enter(c));
-  HIPCHECK(c, hipMemcpy(out, (const uint8_t *)c->ref.p + c->h_ref_off[seq], c->h_ref_len[seq], hipMemcpyDeviceToHost));
+  CM_HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, hipMemcpy(out, (const uint8_t *)c->ref.p + c->h_ref_off[seq], c->h_ref_len[seq], hipMemcpyDeviceToHost));
   return CMGPU_OK;
 }
 
@@ -1767,9 +1737,9 @@ extern "C" int cmgpu_index_info(cmgpu_ctx *c, int32_t *kmer_size, int32_t *windo
 // empty bucket); occurrences_out: n_occurrences uint64
 extern "C" int cmgpu_export_index(cmgpu_ctx *c, uint64_t *buckets_out, uint64_t *occurrences_out) {
   if (!c || !buckets_out) return CMGPU_EINVAL;
-  HIPCHECK(c, cm_enter(c));
-  HIPCHECK(c, hipMemcpy(buckets_out, c->bkt.p, ((size_t)c->bmask + 1) * 16, hipMemcpyDeviceToHost));
-  if (occurrences_out && c->n_occ) HIPCHECK(c, hipMemcpy(occurrences_out, c->occ.p, (size_t)c->n_occ * 8, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, hipMemcpy(buckets_out, c->bkt.p, ((size_t)c->bmask + 1) * 16, hipMemcpyDeviceToHost));
+  if (occurrences_out && c->n_occ) CM_HIPCHECK(c, hipMemcpy(occurrences_out, c->occ.p, (size_t)c->n_occ * 8, hipMemcpyDeviceToHost));
   return CMGPU_OK;
 }
 
@@ -1779,19 +1749,15 @@ extern "C" int cmgpu_export_index(cmgpu_ctx *c, uint64_t *buckets_out, uint64_t 
 // ---------------------------------------------------------------------------------------
 extern "C" int cmgpu_records_to_device(cmgpu_ctx *c, void *device_dst, uint64_t capacity, uint64_t *n_out) {
   if (!c || !device_dst || !n_out) return CMGPU_EINVAL;
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   const uint32_t n = (uint32_t)cm_rec_slots(c);
   *n_out = 0;
   if (n == 0) return CMGPU_OK;
-  { const int rc = cm_ensure_slot_scratch(c, n); if (rc) return rc; }
-  uint32_t *flag = (uint32_t *)c->scratch_a.p, *pos = (uint32_t *)c->scratch_b.p;  // free between batches
-  hipLaunchKernelGGL(k_rec_flag, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const uint8_t *)c->rec_ok.p, flag, n);
-  cm_scan_u32(flag, pos, n, (uint32_t *)c->scan_tmp.p, c->stream);
-  hipLaunchKernelGGL(k_rec_compact, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const uint8_t *)c->rec.p,
-                     (const uint8_t *)c->rec_ok.p, (const uint32_t *)pos, (uint8_t *)device_dst, n, capacity);
+  const uint32_t *n_valid = nullptr;
+  { const int rc = cm_compact_records(c, device_dst, nullptr, capacity, c->stream, &n_valid); if (rc) return rc; }
   uint32_t k = 0;
-  HIPCHECK(c, hipMemcpyAsync(&k, pos + n, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHECK(c, cm_stream_sync(c->stream));
+  CM_HIPCHECK(c, hipMemcpyAsync(&k, n_valid, 4, hipMemcpyDeviceToHost, c->stream));
+  CM_HIPCHECK(c, cm_stream_sync(c->stream));
   *n_out = k;
   if (k > capacity) { cm_set_error(c, "device record buffer too small"); return CMGPU_ECAPACITY; }
   return CMGPU_OK;
@@ -1845,16 +1811,16 @@ static bool gather_dispatch(cmgpu_ctx *c, uint64_t n, uint64_t seed, int loads, 
 // loads_per_lane 1 / 2 / 4 / 8 / 16 (16 only with 16-byte accesses); access_bytes 16 or 64
 extern "C" int cmgpu_gather_sweep(cmgpu_ctx *c, uint64_t n, int repeat, int loads_per_lane, int access_bytes, double *avg_ms) {
   if (!c || n == 0 || repeat < 1 || !avg_ms || (access_bytes != 16 && access_bytes != 64)) return CMGPU_EINVAL;
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   hipStream_t s = c->stream;
   if (!gather_dispatch(c, n, 1ull, loads_per_lane, access_bytes == 64)) { cm_set_error(c, "unsupported gather shape"); return CMGPU_EINVAL; }
-  HIPCHECK(c, cm_stream_sync(s));
-  HIPCHECK(c, hipEventRecord(c->ev[0], s));
+  CM_HIPCHECK(c, cm_stream_sync(s));
+  CM_HIPCHECK(c, hipEventRecord(c->ev[0], s));
   for (int i = 0; i < repeat; ++i) gather_dispatch(c, n, (uint64_t)(i + 2) * 7919ull, loads_per_lane, access_bytes == 64);
-  HIPCHECK(c, hipEventRecord(c->ev[1], s));
-  HIPCHECK(c, hipEventSynchronize(c->ev[1]));
+  CM_HIPCHECK(c, hipEventRecord(c->ev[1], s));
+  CM_HIPCHECK(c, hipEventSynchronize(c->ev[1]));
   float ms = 0;
-  HIPCHECK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+  CM_HIPCHECK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
   *avg_ms = ms / repeat;
   return CMGPU_OK;
 }
@@ -1868,7 +1834,7 @@ extern "C" int cmgpu_gather_bench(cmgpu_ctx *c, uint64_t n, int repeat, double *
 // ---------------------------------------------------------------------------------------
 extern "C" int cmgpu_set_whitelist(cmgpu_ctx *c, const uint64_t *keys, uint32_t n_keys, uint32_t barcode_length) {
   if (!c || !keys || n_keys == 0 || barcode_length == 0 || barcode_length > 32) { cm_set_error(c, "bad whitelist"); return CMGPU_EINVAL; }
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   uint32_t nb = 16;
   while (nb < 2ull * n_keys + 16) nb <<= 1;
   std::vector<uint64_t> tab((size_t)nb * 2);
@@ -1884,9 +1850,9 @@ extern "C" int cmgpu_set_whitelist(cmgpu_ctx *c, const uint64_t *keys, uint32_t 
   std::vector<double> pw(81);
   for (int q = 0; q <= 80; ++q) pw[q] = pow(10.0, ((-q) / 10.0));
   if (c->wl.ensure(tab.size() * 8) || c->pow10_tab.ensure(pw.size() * 8) || c->wl_num.ensure(8)) { cm_set_error(c, "out of device memory (whitelist)"); return CMGPU_ENOMEM; }
-  HIPCHECK(c, hipMemcpy(c->wl.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
-  HIPCHECK(c, hipMemcpy(c->pow10_tab.p, pw.data(), pw.size() * 8, hipMemcpyHostToDevice));
-  HIPCHECK(c, hipMemset(c->wl_num.p, 0, 8));
+  CM_HIPCHECK(c, hipMemcpy(c->wl.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+  CM_HIPCHECK(c, hipMemcpy(c->pow10_tab.p, pw.data(), pw.size() * 8, hipMemcpyHostToDevice));
+  CM_HIPCHECK(c, hipMemset(c->wl_num.p, 0, 8));
   c->wl_mask = nb - 1;
   c->wl_size = size;
   c->bc_len = barcode_length;
@@ -1926,15 +1892,15 @@ extern "C" int cmgpu_copy_whitelist(cmgpu_ctx *dst, cmgpu_ctx *src) {
   const size_t bytes = ((size_t)src->wl_mask + 1) * 16;
   std::vector<uint64_t> tab(bytes / 8);
   std::vector<double> pw(81);
-  HIPCHECK(src, cm_enter(src));
-  HIPCHECK(src, hipMemcpy(tab.data(), src->wl.p, bytes, hipMemcpyDeviceToHost));
-  HIPCHECK(src, hipMemcpy(pw.data(), src->pow10_tab.p, pw.size() * 8, hipMemcpyDeviceToHost));
-  HIPCHECK(dst, cm_enter(dst));
+  CM_HIPCHECK(src, cm_enter(src));
+  CM_HIPCHECK(src, hipMemcpy(tab.data(), src->wl.p, bytes, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(src, hipMemcpy(pw.data(), src->pow10_tab.p, pw.size() * 8, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(dst, cm_enter(dst));
   if (dst->wl.ensure(bytes) || dst->pow10_tab.ensure(pw.size() * 8) || dst->wl_num.ensure(8)) { cm_set_error(dst, "out of device memory (whitelist)"); return CMGPU_ENOMEM; }
-  HIPCHECK(dst, hipMemcpy(dst->wl.p, tab.data(), bytes, hipMemcpyHostToDevice));
-  HIPCHECK(dst, hipMemcpy(dst->pow10_tab.p, pw.data(), pw.size() * 8, hipMemcpyHostToDevice));
+  CM_HIPCHECK(dst, hipMemcpy(dst->wl.p, tab.data(), bytes, hipMemcpyHostToDevice));
+  CM_HIPCHECK(dst, hipMemcpy(dst->pow10_tab.p, pw.data(), pw.size() * 8, hipMemcpyHostToDevice));
   const unsigned long long ns = src->wl_num_sample;
-  HIPCHECK(dst, hipMemcpy(dst->wl_num.p, &ns, 8, hipMemcpyHostToDevice));
+  CM_HIPCHECK(dst, hipMemcpy(dst->wl_num.p, &ns, 8, hipMemcpyHostToDevice));
   dst->wl_mask = src->wl_mask; dst->wl_size = src->wl_size; dst->bc_len = src->bc_len; dst->wl_num_sample = src->wl_num_sample;
   dst->skip_barcode_check = src->skip_barcode_check;
   return CMGPU_OK;
@@ -1949,12 +1915,12 @@ extern "C" int cmgpu_set_barcode_check(cmgpu_ctx *c, int enabled) {
 extern "C" int cmgpu_compute_barcode_abundance(cmgpu_ctx *c, const char *bases, const uint32_t *offsets, uint32_t n,
                                                uint64_t *num_sample_barcodes) {
   if (!c || !bases || !offsets || c->wl_size == 0) { cm_set_error(c, "no whitelist set"); return CMGPU_EINVAL; }
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   DevBuf db, dofs;
   const size_t nbytes = n ? offsets[n] : 0;
   if (db.ensure(nbytes + 16) || dofs.ensure(((size_t)n + 1) * 4)) { cm_set_error(c, "out of device memory (barcodes)"); return CMGPU_ENOMEM; }
-  HIPCHECK(c, hipMemcpy(db.p, bases, nbytes, hipMemcpyHostToDevice));
-  HIPCHECK(c, hipMemcpy(dofs.p, offsets, ((size_t)n + 1) * 4, hipMemcpyHostToDevice));
+  CM_HIPCHECK(c, hipMemcpy(db.p, bases, nbytes, hipMemcpyHostToDevice));
+  CM_HIPCHECK(c, hipMemcpy(dofs.p, offsets, ((size_t)n + 1) * 4, hipMemcpyHostToDevice));
   bool done = false;
   const int rc = bc_abundance_run(c, (const uint8_t *)db.p, (const uint32_t *)dofs.p, n, &done);
   db.release(); dofs.release();
@@ -1965,7 +1931,7 @@ extern "C" int cmgpu_compute_barcode_abundance(cmgpu_ctx *c, const char *bases, 
 // same over the barcodes last taken from FASTQ stream 2 (cmgpu_fastq_take); call per chunk until *done
 extern "C" int cmgpu_barcode_abundance_resident(cmgpu_ctx *c, uint64_t *num_sample_barcodes, int *done) {
   if (!c || !done || c->wl_size == 0) { cm_set_error(c, "no whitelist set"); return CMGPU_EINVAL; }
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   bool d = false;
   const int rc = bc_abundance_run(c, (const uint8_t *)c->st_bcb.p, (const uint32_t *)c->st_bco.p, c->fq[2].taken, &d);  // (taken, not committed: the staging buffers)
   *done = d ? 1 : 0;
@@ -1985,9 +1951,9 @@ extern "C" int cmgpu_map_pairs_barcoded(cmgpu_ctx *c, const cmgpu_batch *in, con
   if (n == 0) return CMGPU_OK;
   const size_t nbytes = bc->offsets[n];
   if (c->bcb.ensure(nbytes + 16) || c->bcq.ensure(nbytes + 16) || c->bco.ensure(((size_t)n + 1) * 4)) { cm_set_error(c, "out of device memory (barcodes)"); return CMGPU_ENOMEM; }
-  HIPCHECK(c, hipMemcpy(c->bcb.p, bc->bases, nbytes, hipMemcpyHostToDevice));
-  HIPCHECK(c, hipMemcpy(c->bcq.p, bc->qualities, nbytes, hipMemcpyHostToDevice));
-  HIPCHECK(c, hipMemcpy(c->bco.p, bc->offsets, ((size_t)n + 1) * 4, hipMemcpyHostToDevice));
+  CM_HIPCHECK(c, hipMemcpy(c->bcb.p, bc->bases, nbytes, hipMemcpyHostToDevice));
+  CM_HIPCHECK(c, hipMemcpy(c->bcq.p, bc->qualities, nbytes, hipMemcpyHostToDevice));
+  CM_HIPCHECK(c, hipMemcpy(c->bco.p, bc->offsets, ((size_t)n + 1) * 4, hipMemcpyHostToDevice));
   c->has_barcodes = true;
   uint64_t k = 0;
   rc = cmgpu_map_resident(c, &k, stats);
@@ -1998,9 +1964,9 @@ extern "C" int cmgpu_map_pairs_barcoded(cmgpu_ctx *c, const cmgpu_batch *in, con
   std::vector<cmgpu_record> rec(ns);
   std::vector<uint8_t> ok(ns);
   std::vector<uint64_t> keys(n);
-  HIPCHECK(c, hipMemcpy(rec.data(), c->rec.p, ns * 24, hipMemcpyDeviceToHost));
-  HIPCHECK(c, hipMemcpy(ok.data(), c->rec_ok.p, ns, hipMemcpyDeviceToHost));
-  HIPCHECK(c, hipMemcpy(keys.data(), c->bc_key.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(c, hipMemcpy(rec.data(), c->rec.p, ns * 24, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(c, hipMemcpy(ok.data(), c->rec_ok.p, ns, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(c, hipMemcpy(keys.data(), c->bc_key.p, (size_t)n * 8, hipMemcpyDeviceToHost));
   uint64_t o = 0;
   for (size_t i = 0; i < ns; ++i) {
     if (!ok[i]) continue;
@@ -2033,7 +1999,7 @@ static int map_single_impl(cmgpu_ctx *c, const cmgpu_single_batch *in, const cmg
                            cmgpu_record_bc *out_bc, uint64_t out_capacity, uint64_t *n_out, cmgpu_stats *stats) {
   if (!c || !in || !n_out) return CMGPU_EINVAL;
   if (bc && c->wl_size != 0 && c->wl_num_sample == 0) { cm_set_error(c, "barcode abundance not computed (cmgpu_compute_barcode_abundance)"); return CMGPU_EINVAL; }
-  HIPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   const uint32_t n = in->n_reads;
   c->n_pairs = n;
   c->has_barcodes = false;
@@ -2050,18 +2016,18 @@ static int map_single_impl(cmgpu_ctx *c, const cmgpu_single_batch *in, const cmg
     cm_set_error(c, "out of device memory (reads)");
     return CMGPU_ENOMEM;
   }
-  HIPCHECK(c, hipMemcpyAsync(c->rb0.p, in->bases, c->bases0, hipMemcpyHostToDevice, c->stream));
-  HIPCHECK(c, hipMemcpyAsync(c->ro0.p, in->offsets, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHECK(c, hipMemsetAsync(c->ro1.p, 0, ((size_t)n + 1) * 4, c->stream));
+  CM_HIPCHECK(c, hipMemcpyAsync(c->rb0.p, in->bases, c->bases0, hipMemcpyHostToDevice, c->stream));
+  CM_HIPCHECK(c, hipMemcpyAsync(c->ro0.p, in->offsets, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  CM_HIPCHECK(c, hipMemsetAsync(c->ro1.p, 0, ((size_t)n + 1) * 4, c->stream));
   if (bc) {
     const size_t nbytes = bc->offsets[n];
     if (c->bcb.ensure(nbytes + 16) || c->bcq.ensure(nbytes + 16) || c->bco.ensure(((size_t)n + 1) * 4)) { cm_set_error(c, "out of device memory (barcodes)"); return CMGPU_ENOMEM; }
-    HIPCHECK(c, hipMemcpyAsync(c->bcb.p, bc->bases, nbytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(c->bcq.p, bc->qualities, nbytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(c->bco.p, bc->offsets, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    CM_HIPCHECK(c, hipMemcpyAsync(c->bcb.p, bc->bases, nbytes, hipMemcpyHostToDevice, c->stream));
+    CM_HIPCHECK(c, hipMemcpyAsync(c->bcq.p, bc->qualities, nbytes, hipMemcpyHostToDevice, c->stream));
+    CM_HIPCHECK(c, hipMemcpyAsync(c->bco.p, bc->offsets, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
     c->has_barcodes = true;
   }
-  HIPCHECK(c, cm_stream_sync(c->stream));
+  CM_HIPCHECK(c, cm_stream_sync(c->stream));
   uint64_t k = 0;
   int rc = cmgpu_map_resident(c, &k, stats);
   if (rc) return rc;
@@ -2072,9 +2038,9 @@ static int map_single_impl(cmgpu_ctx *c, const cmgpu_single_batch *in, const cmg
   std::vector<cmgpu_record> rec(ns);
   std::vector<uint8_t> ok(ns);
   std::vector<uint64_t> keys(n);
-  HIPCHECK(c, hipMemcpy(rec.data(), c->rec.p, ns * 24, hipMemcpyDeviceToHost));
-  HIPCHECK(c, hipMemcpy(ok.data(), c->rec_ok.p, ns, hipMemcpyDeviceToHost));
-  HIPCHECK(c, hipMemcpy(keys.data(), c->bc_key.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(c, hipMemcpy(rec.data(), c->rec.p, ns * 24, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(c, hipMemcpy(ok.data(), c->rec_ok.p, ns, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(c, hipMemcpy(keys.data(), c->bc_key.p, (size_t)n * 8, hipMemcpyDeviceToHost));
   uint64_t o = 0;
   for (size_t i = 0; i < ns; ++i) {
     if (!ok[i]) continue;

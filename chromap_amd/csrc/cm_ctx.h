@@ -22,6 +22,26 @@ struct DevBuf {
   void release();
 };
 
+// A function's temporary device buffer: released when the scope ends, on every return path.  (DevBuf itself stays trivially copyable --
+// the context assigns DevBufs and holds views of other contexts' -- so it cannot own; a CmTmpBuf neither copies nor converts to one.)
+struct CmTmpBuf : private DevBuf {
+  using DevBuf::p;
+  using DevBuf::cap;
+  using DevBuf::ensure;
+  using DevBuf::release;
+  CmTmpBuf() = default;
+  CmTmpBuf(const CmTmpBuf &) = delete;
+  CmTmpBuf &operator=(const CmTmpBuf &) = delete;
+  ~CmTmpBuf() { release(); }
+  // the buffer outlives the scope after all: it is the caller's DevBuf from here on, and this one is empty
+  DevBuf hand_over() {
+    const DevBuf b = *this;
+    p = nullptr;
+    cap = 0;
+    return b;
+  }
+};
+
 // one FASTQ text stream being parsed on the device (cm_ingest.hip)
 struct CmFqStream {
   DevBuf text, cnt, off, nl, keep, pos, recidx, len, bad;
@@ -287,6 +307,16 @@ struct cmgpu_ctx {
 
 void cm_set_error(cmgpu_ctx *ctx, const std::string &msg);
 
+// a HIP call of a function that returns a CMGPU_* code: on failure the call's text and HIP's message become the context's error
+#define CM_HIPCHECK(ctx, call)                                                               \
+  do {                                                                                       \
+    hipError_t e_ = (call);                                                                  \
+    if (e_ != hipSuccess) {                                                                  \
+      cm_set_error(ctx, std::string(#call) + ": " + hipGetErrorString(e_));                  \
+      return CMGPU_EHIP;                                                                     \
+    }                                                                                        \
+  } while (0)
+
 // Kernel launches report a bad configuration (LDS size, grid) only through hipGetLastError; every
 // synchronisation point of the library therefore checks it too, and every entry point starts from a
 // clean slate so that only this call's own launches are seen.
@@ -322,6 +352,10 @@ static inline bool cm_store_kind_mismatch(cmgpu_ctx *c, bool pairs) {
 }
 static inline uint64_t cm_rec_slots(const cmgpu_ctx *c) { return (uint64_t)c->n_pairs * cm_rec_per_pair(c); }
 int cm_ensure_slot_scratch(cmgpu_ctx *c, uint64_t slots);
+// cm_post.hip: the valid record slots of the resident batch, in slot order, dense at dst on stream s (flags and positions in scratch_a /
+// scratch_b); a record whose position is >= cap is skipped.  bc_dst (optional): the barcode key of each record's pair, at the record's
+// position.  *n_valid_dev (optional): where on the device the number of valid slots stands once the stream got there.  Nothing is waited for
+int cm_compact_records(cmgpu_ctx *c, void *dst, uint64_t *bc_dst, uint64_t cap, hipStream_t s, const uint32_t **n_valid_dev);
 // cm_post.hip: n 32-byte {record, barcode} entries -> the store's record / barcode arrays at position store_n
 void cm_store_split_bc(cmgpu_ctx *c, const void *in32, uint64_t n, hipStream_t s);
 // cm_ingest.hip: b with room for `need` bytes, its first `used` bytes preserved (geometric growth from `first` bytes; the copy runs on s and

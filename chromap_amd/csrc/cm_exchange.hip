@@ -30,15 +30,6 @@
 #define EX_BLOCK 256
 #define EX_MAX_WORLD 64
 
-#define EXCHECK(ctx, call)                                                                   \
-  do {                                                                                       \
-    hipError_t e_ = (call);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      cm_set_error(ctx, std::string(#call) + ": " + hipGetErrorString(e_));                  \
-      return CMGPU_EHIP;                                                                     \
-    }                                                                                        \
-  } while (0)
-
 // ---------------------------------------------------------------------------------------
 // RCCL entry points, resolved once
 // ---------------------------------------------------------------------------------------
@@ -226,7 +217,7 @@ static int ex_owner_upload(cmgpu_ctx *c, uint32_t world) {
   CmExchange &x = c->ex;
   x.h_owner = cm_owner_table(c, world);
   if (x.owner.ensure(x.h_owner.size() + 16)) { cm_set_error(c, "out of device memory (owner table)"); return CMGPU_ENOMEM; }
-  EXCHECK(c, hipMemcpy(x.owner.p, x.h_owner.data(), x.h_owner.size(), hipMemcpyHostToDevice));
+  CM_HIPCHECK(c, hipMemcpy(x.owner.p, x.h_owner.data(), x.h_owner.size(), hipMemcpyHostToDevice));
   return CMGPU_OK;
 }
 
@@ -234,7 +225,7 @@ static int ex_owner_upload(cmgpu_ctx *c, uint32_t world) {
 static int ex_partition(cmgpu_ctx *c, uint32_t n, uint32_t world, const uint8_t *d_owner, uint8_t *dst, uint32_t rb,
                         unsigned long long *d_counts, unsigned long long *d_cursors) {
   hipStream_t s = c->stream;
-  EXCHECK(c, hipMemsetAsync(d_counts, 0, (EX_MAX_WORLD + 1) * 8, s));
+  CM_HIPCHECK(c, hipMemsetAsync(d_counts, 0, (EX_MAX_WORLD + 1) * 8, s));
   if (n) {
     const dim3 g((n + EX_PER_BLOCK - 1) / EX_PER_BLOCK), b(EX_BLOCK);
     hipLaunchKernelGGL(k_ex_count, g, b, 0, s, (const uint8_t *)c->rec.p, (const uint8_t *)c->rec_ok.p, n, d_owner, c->n_seq, world, d_counts);
@@ -249,7 +240,7 @@ static int ex_partition(cmgpu_ctx *c, uint32_t n, uint32_t world, const uint8_t 
 // caller performs itself; same owner rule and kernels as cmgpu_exchange_step
 extern "C" int cmgpu_records_partition(cmgpu_ctx *c, uint32_t world, void *device_dst, uint64_t capacity, uint64_t *counts) {
   if (!c || !device_dst || !counts || world == 0 || world > EX_MAX_WORLD) return CMGPU_EINVAL;
-  EXCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   for (uint32_t r = 0; r < world; ++r) counts[r] = 0;
   if (c->n_pairs == 0) return CMGPU_OK;
   if (capacity < cm_rec_slots(c)) { cm_set_error(c, "send buffer too small (one slot per pair of the batch -- times max_num_best_mappings -- is needed)"); return CMGPU_ECAPACITY; }
@@ -259,12 +250,12 @@ extern "C" int cmgpu_records_partition(cmgpu_ctx *c, uint32_t world, void *devic
   if (dcnt.ensure(2 * (EX_MAX_WORLD + 1) * 8 + t.size() + 16)) { cm_set_error(c, "out of device memory (partition)"); return CMGPU_ENOMEM; }
   unsigned long long *d_counts = (unsigned long long *)dcnt.p, *d_cursors = d_counts + EX_MAX_WORLD + 1;
   uint8_t *d_owner = (uint8_t *)(d_cursors + EX_MAX_WORLD + 1);
-  EXCHECK(c, hipMemcpyAsync(d_owner, t.data(), t.size(), hipMemcpyHostToDevice, c->stream));
+  CM_HIPCHECK(c, hipMemcpyAsync(d_owner, t.data(), t.size(), hipMemcpyHostToDevice, c->stream));
   int rc = ex_partition(c, (uint32_t)cm_rec_slots(c), world, d_owner, (uint8_t *)device_dst, 24, d_counts, d_cursors);
   if (rc) return rc;
   unsigned long long h[EX_MAX_WORLD];
-  EXCHECK(c, hipMemcpyAsync(h, d_counts, (size_t)world * 8, hipMemcpyDeviceToHost, c->stream));
-  EXCHECK(c, cm_stream_sync(c->stream));
+  CM_HIPCHECK(c, hipMemcpyAsync(h, d_counts, (size_t)world * 8, hipMemcpyDeviceToHost, c->stream));
+  CM_HIPCHECK(c, cm_stream_sync(c->stream));
   for (uint32_t r = 0; r < world; ++r) counts[r] = h[r];
   return CMGPU_OK;
 }
@@ -276,7 +267,7 @@ static int ex_common_init(cmgpu_ctx *c, int rank, int world) {
   if (!c || world < 1 || world > EX_MAX_WORLD || rank < 0 || rank >= world) { cm_set_error(c, "bad rank / world"); return CMGPU_EINVAL; }
   if (c->ex.transport != 0) { cm_set_error(c, "the exchange is already initialised"); return CMGPU_EINVAL; }
   if (cm_pairs_records(c)) { cm_set_error(c, "pairs records are post-processed by one rank; no chromosome owners"); return CMGPU_EINVAL; }
-  EXCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   CmExchange &x = c->ex;
   x.rank = rank;
   x.world = world;
@@ -285,11 +276,11 @@ static int ex_common_init(cmgpu_ctx *c, int rank, int world) {
   int rc = ex_owner_upload(c, (uint32_t)world);
   if (rc) return rc;
   if (x.counts.ensure((2 * (EX_MAX_WORLD + 1) + EX_MAX_WORLD * (EX_MAX_WORLD + 1)) * 8)) { cm_set_error(c, "out of device memory (exchange counts)"); return CMGPU_ENOMEM; }
-  if (!x.h_matrix) EXCHECK(c, hipHostMalloc((void **)&x.h_matrix, EX_MAX_WORLD * (EX_MAX_WORLD + 1) * 8, hipHostMallocDefault));
+  if (!x.h_matrix) CM_HIPCHECK(c, hipHostMalloc((void **)&x.h_matrix, EX_MAX_WORLD * (EX_MAX_WORLD + 1) * 8, hipHostMallocDefault));
   if (!x.stream) {
-    EXCHECK(c, hipStreamCreate(&x.stream));
-    EXCHECK(c, hipEventCreateWithFlags(&x.ev_part, hipEventDisableTiming));
-    EXCHECK(c, hipEventCreateWithFlags(&x.ev_payload, hipEventDisableTiming));
+    CM_HIPCHECK(c, hipStreamCreate(&x.stream));
+    CM_HIPCHECK(c, hipEventCreateWithFlags(&x.ev_part, hipEventDisableTiming));
+    CM_HIPCHECK(c, hipEventCreateWithFlags(&x.ev_payload, hipEventDisableTiming));
   }
   x.payload_pending = false;
   return CMGPU_OK;
@@ -388,8 +379,8 @@ extern "C" int cmgpu_exchange_finalize(cmgpu_ctx *c) {
 // transport must not bring a second runtime into the process); kind 1: host -> device, 2: device -> host
 extern "C" int cmgpu_memcpy(cmgpu_ctx *c, void *dst, const void *src, uint64_t bytes, int kind) {
   if (!c || (bytes && (!dst || !src)) || (kind != 1 && kind != 2)) return CMGPU_EINVAL;
-  EXCHECK(c, cm_enter(c));
-  if (bytes) EXCHECK(c, hipMemcpy(dst, src, bytes, kind == 1 ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost));
+  CM_HIPCHECK(c, cm_enter(c));
+  if (bytes) CM_HIPCHECK(c, hipMemcpy(dst, src, bytes, kind == 1 ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost));
   return CMGPU_OK;
 }
 
@@ -442,7 +433,7 @@ extern "C" int cmgpu_exchange_step(cmgpu_ctx *c, uint64_t *sent_per_rank, uint64
   if (!c) return CMGPU_EINVAL;
   CmExchange &x = c->ex;
   if (x.transport == 0) { cm_set_error(c, "the exchange is not initialised (cmgpu_exchange_init*)"); return CMGPU_EINVAL; }
-  EXCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   hipStream_t s = c->stream;
   // a batch takes part once: a second step without a new cmgpu_map_* call contributes an empty batch (a rank that
   // ran out of input keeps calling while the others finish)
@@ -457,23 +448,23 @@ extern "C" int cmgpu_exchange_step(cmgpu_ctx *c, uint64_t *sent_per_rank, uint64
   }
   if (x.send.ensure((size_t)(n ? n : 1) * 32 + 16)) { cm_set_error(c, "out of device memory (exchange send buffer)"); return CMGPU_ENOMEM; }
   // the previous round's payload still reads the send buffer (and it was issued on the payload stream)
-  if (x.payload_pending) EXCHECK(c, hipStreamWaitEvent(s, x.ev_payload, 0));
+  if (x.payload_pending) CM_HIPCHECK(c, hipStreamWaitEvent(s, x.ev_payload, 0));
   unsigned long long *d_counts = (unsigned long long *)x.counts.p, *d_cursors = d_counts + EX_MAX_WORLD + 1, *d_matrix = d_cursors + EX_MAX_WORLD + 1;
   int rc = ex_partition(c, n, world, (const uint8_t *)x.owner.p, (uint8_t *)x.send.p, rb_local ? rb_local : 24u, d_counts, d_cursors);
   if (rc) return rc;
   // ---- counts: row r of the matrix = what rank r sends to everyone (+ its record kind)
   unsigned long long *M = x.h_matrix;
   M[0] = rb_local;
-  EXCHECK(c, hipMemcpyAsync(d_counts + world, M, 8, hipMemcpyHostToDevice, s));
+  CM_HIPCHECK(c, hipMemcpyAsync(d_counts + world, M, 8, hipMemcpyHostToDevice, s));
   if (x.transport == 1) {
     const RcclApi *api = rccl_api();
     NCCLCHECK(c, api, api->AllGather(d_counts, d_matrix, stride, ncclUint64, (ncclComm_t)x.comm, s));
-    EXCHECK(c, hipMemcpyAsync(M, d_matrix, (size_t)world * stride * 8, hipMemcpyDeviceToHost, s));
-    EXCHECK(c, cm_stream_sync(s));
+    CM_HIPCHECK(c, hipMemcpyAsync(M, d_matrix, (size_t)world * stride * 8, hipMemcpyDeviceToHost, s));
+    CM_HIPCHECK(c, cm_stream_sync(s));
   } else {
     uint64_t mine[EX_MAX_WORLD + 1];
-    EXCHECK(c, hipMemcpyAsync(M, d_counts, (size_t)stride * 8, hipMemcpyDeviceToHost, s));
-    EXCHECK(c, cm_stream_sync(s));
+    CM_HIPCHECK(c, hipMemcpyAsync(M, d_counts, (size_t)stride * 8, hipMemcpyDeviceToHost, s));
+    CM_HIPCHECK(c, cm_stream_sync(s));
     for (uint32_t r = 0; r < stride; ++r) mine[r] = M[r];
     std::vector<uint64_t> full((size_t)world * stride, 0);
     if (x.ext.allgather_counts(x.ext.user, mine, full.data(), stride) != 0) { cm_set_error(c, "exchange transport: allgather_counts failed"); return CMGPU_EIO; }
@@ -523,10 +514,10 @@ extern "C" int cmgpu_exchange_step(cmgpu_ctx *c, uint64_t *sent_per_rank, uint64
     if (x.transport == 1) {
       const RcclApi *api = rccl_api();
       M[0] = mine;
-      EXCHECK(c, hipMemcpyAsync(d_counts, M, 8, hipMemcpyHostToDevice, s));
+      CM_HIPCHECK(c, hipMemcpyAsync(d_counts, M, 8, hipMemcpyHostToDevice, s));
       NCCLCHECK(c, api, api->AllGather(d_counts, d_matrix, 1, ncclUint64, (ncclComm_t)x.comm, s));
-      EXCHECK(c, hipMemcpyAsync(M, d_matrix, (size_t)world * 8, hipMemcpyDeviceToHost, s));
-      EXCHECK(c, cm_stream_sync(s));
+      CM_HIPCHECK(c, hipMemcpyAsync(M, d_matrix, (size_t)world * 8, hipMemcpyDeviceToHost, s));
+      CM_HIPCHECK(c, cm_stream_sync(s));
       for (uint32_t r = 0; r < world; ++r) status[r] = M[r];
     } else {
       uint64_t all[EX_MAX_WORLD * 2];
@@ -548,8 +539,8 @@ extern "C" int cmgpu_exchange_step(cmgpu_ctx *c, uint64_t *sent_per_rank, uint64
     const bool overlap = c->opt.exchange_overlap != 0;
     hipStream_t ps = overlap ? x.stream : s;
     if (overlap) {
-      EXCHECK(c, hipEventRecord(x.ev_part, s));
-      EXCHECK(c, hipStreamWaitEvent(ps, x.ev_part, 0));
+      CM_HIPCHECK(c, hipEventRecord(x.ev_part, s));
+      CM_HIPCHECK(c, hipStreamWaitEvent(ps, x.ev_part, 0));
     }
     // (the posts follow cm_exchange_plan: the all-gathers above were its first entries)
     const std::vector<cmgpu_exchange_op> plan = cm_exchange_plan(me, world, mat.data(), stride);
@@ -569,7 +560,7 @@ extern "C" int cmgpu_exchange_step(cmgpu_ctx *c, uint64_t *sent_per_rank, uint64
     if (in_group) NCCLCHECK(c, api, api->GroupEnd());
     if (tot_r && bc) cm_store_split_bc(c, dest, tot_r, ps);
     if (overlap) {
-      EXCHECK(c, hipEventRecord(x.ev_payload, ps));
+      CM_HIPCHECK(c, hipEventRecord(x.ev_payload, ps));
       x.payload_pending = true;
     }
   } else {

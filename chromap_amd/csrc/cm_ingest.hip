@@ -30,15 +30,6 @@
 #include "cm_fastx.h"
 
 #define FQ_BLOCK 256
-#define FQCHECK(ctx, call)                                                                   \
-  do {                                                                                       \
-    hipError_t e_ = (call);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      cm_set_error(ctx, std::string(#call) + ": " + hipGetErrorString(e_));                  \
-      return CMGPU_EHIP;                                                                     \
-    }                                                                                        \
-  } while (0)
-
 __device__ __forceinline__ uint32_t fq_nl_mask(const uint8_t *__restrict__ text, uint64_t base, uint64_t n) {
   uint32_t m = 0;
   if (base + 16 <= n) {
@@ -322,7 +313,7 @@ static hipStream_t fq_hs(cmgpu_ctx *c, CmFqStream &f) {
 extern "C" int cmgpu_fastq_scan(cmgpu_ctx *c, int stream, const char *text, uint64_t n_bytes, int final_chunk, uint32_t *n_records) {
   if (!c || stream < 0 || stream > 2 || (!text && n_bytes) || !n_records) return CMGPU_EINVAL;
   if (n_bytes > 0xfffffff0ull) { cm_set_error(c, "FASTQ chunk must be smaller than 4 GiB"); return CMGPU_EINVAL; }
-  FQCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   CmFqStream &f = c->fq[stream];
   *n_records = 0;
   f.dev_mode = false; f.dev_len = 0;
@@ -330,7 +321,7 @@ extern "C" int cmgpu_fastq_scan(cmgpu_ctx *c, int stream, const char *text, uint
   f.general = false; f.fx_lines = 0; f.fx_stop = 0;
   if (n_bytes == 0) return CMGPU_OK;
   if (f.text.ensure(n_bytes + 32)) { cm_set_error(c, "out of device memory (FASTQ text)"); return CMGPU_ENOMEM; }
-  FQCHECK(c, hipMemcpyAsync(f.text.p, text, n_bytes, hipMemcpyHostToDevice, fq_hs(c, f)));
+  CM_HIPCHECK(c, hipMemcpyAsync(f.text.p, text, n_bytes, hipMemcpyHostToDevice, fq_hs(c, f)));
   return fq_scan_resident(c, stream, n_bytes, final_chunk, text[n_bytes - 1], n_records);
 }
 
@@ -350,9 +341,9 @@ static int fq_scan_general(cmgpu_ctx *c, int stream, uint32_t n_lines, bool fina
       f.scan_tmp.ensure(cm_scan_tmp_words(n_lines) * 4)) { cm_set_error(c, "out of device memory (FASTQ records)"); return CMGPU_ENOMEM; }
   const uint32_t none = 0xffffffffu;
   const uint32_t res0[4] = {none, 0u, none, 0u};
-  FQCHECK(c, hipMemcpyAsync(f.fx_res.p, res0, 16, hipMemcpyHostToDevice, s));
-  FQCHECK(c, hipMemsetAsync(f.fx_entry.p, 0xff, (size_t)n_tiles * 4, s));
-  FQCHECK(c, hipMemsetAsync(f.keep.p, 0, per_line, s));
+  CM_HIPCHECK(c, hipMemcpyAsync(f.fx_res.p, res0, 16, hipMemcpyHostToDevice, s));
+  CM_HIPCHECK(c, hipMemsetAsync(f.fx_entry.p, 0xff, (size_t)n_tiles * 4, s));
+  CM_HIPCHECK(c, hipMemsetAsync(f.keep.p, 0, per_line, s));
   const dim3 gl((n_lines + FQ_BLOCK - 1) / FQ_BLOCK), b(FQ_BLOCK);
   const int want_qual = stream == 2 || f.keep_reads ? 1 : 0;
   hipLaunchKernelGGL(k_fx_lines, gl, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, n_lines, (uint32_t *)f.fx_li.p);
@@ -365,9 +356,9 @@ static int fq_scan_general(cmgpu_ctx *c, int stream, uint32_t n_lines, bool fina
   cm_scan_u32((const uint32_t *)f.keep.p, (uint32_t *)f.pos.p, n_lines, (uint32_t *)f.scan_tmp.p, s);
   hipLaunchKernelGGL(k_fq_compact, gl, b, 0, s, (const uint32_t *)f.keep.p, (const uint32_t *)f.pos.p, n_lines, (uint32_t *)f.recidx.p);
   uint32_t res[4] = {none, 0, none, 0}, n_rec = 0;
-  FQCHECK(c, hipMemcpyAsync(res, f.fx_res.p, 16, hipMemcpyDeviceToHost, s));
-  FQCHECK(c, hipMemcpyAsync(&n_rec, (uint32_t *)f.pos.p + n_lines, 4, hipMemcpyDeviceToHost, s));
-  FQCHECK(c, cm_stream_sync(s));
+  CM_HIPCHECK(c, hipMemcpyAsync(res, f.fx_res.p, 16, hipMemcpyDeviceToHost, s));
+  CM_HIPCHECK(c, hipMemcpyAsync(&n_rec, (uint32_t *)f.pos.p + n_lines, 4, hipMemcpyDeviceToHost, s));
+  CM_HIPCHECK(c, cm_stream_sync(s));
   const bool early = res[0] != none, refused = early && res[1] != CM_FX_INCOMPLETE;
   if (res[2] != none && !(refused && res[0] < res[2])) {
     cm_set_error(c, "record without quality (FASTA) at line " + std::to_string(res[2]) + " of the chunk, and " +
@@ -404,8 +395,8 @@ static int fq_scan_resident(cmgpu_ctx *c, int stream, uint64_t n_bytes, int fina
   hipLaunchKernelGGL(k_fq_count, g, b, 0, s, (const uint8_t *)f.text.p, n_bytes, n_thr, (uint32_t *)f.cnt.p);
   cm_scan_u32((const uint32_t *)f.cnt.p, (uint32_t *)f.off.p, n_thr, (uint32_t *)f.scan_tmp.p, s);
   uint32_t n_nl = 0;
-  FQCHECK(c, hipMemcpyAsync(&n_nl, (uint32_t *)f.off.p + n_thr, 4, hipMemcpyDeviceToHost, s));
-  FQCHECK(c, cm_stream_sync(s));
+  CM_HIPCHECK(c, hipMemcpyAsync(&n_nl, (uint32_t *)f.off.p + n_thr, 4, hipMemcpyDeviceToHost, s));
+  CM_HIPCHECK(c, cm_stream_sync(s));
   if (f.nl.ensure(((size_t)n_nl + 2) * 4)) { cm_set_error(c, "out of device memory (FASTQ lines)"); return CMGPU_ENOMEM; }
   hipLaunchKernelGGL(k_fq_fill, g, b, 0, s, (const uint8_t *)f.text.p, n_bytes, n_thr, (const uint32_t *)f.off.p, (uint32_t *)f.nl.p);
   // a final chunk whose last line has no terminator: the end of the text closes it
@@ -414,8 +405,8 @@ static int fq_scan_resident(cmgpu_ctx *c, int stream, uint64_t n_bytes, int fina
   const uint32_t n_lines = n_nl + (unterminated ? 1u : 0u);  // (the lines of the text; the four-line path below may count an empty one more)
   if (final_chunk && (last_char != '\n' || n_nl % 4 == 3)) {
     const uint32_t endpos = (uint32_t)n_bytes;
-    FQCHECK(c, hipMemcpyAsync((uint32_t *)f.nl.p + n_nl, &endpos, 4, hipMemcpyHostToDevice, s));
-    FQCHECK(c, cm_stream_sync(s));
+    CM_HIPCHECK(c, hipMemcpyAsync((uint32_t *)f.nl.p + n_nl, &endpos, 4, hipMemcpyHostToDevice, s));
+    CM_HIPCHECK(c, cm_stream_sync(s));
     ++n_nl;
   }
   f.n_nl = n_nl;
@@ -427,7 +418,7 @@ static int fq_scan_resident(cmgpu_ctx *c, int stream, uint64_t n_bytes, int fina
   if (f.keep.ensure(((size_t)n_raw + 1) * 4) || f.pos.ensure(((size_t)n_raw + 1) * 4) || f.recidx.ensure((size_t)n_raw * 4) || f.bad.ensure(8) ||
       f.scan_tmp.ensure(cm_scan_tmp_words(n_raw) * 4)) { cm_set_error(c, "out of device memory (FASTQ records)"); return CMGPU_ENOMEM; }
   const uint32_t none = 0xffffffffu;
-  FQCHECK(c, hipMemsetAsync(f.bad.p, 0xff, 8, s));
+  CM_HIPCHECK(c, hipMemsetAsync(f.bad.p, 0xff, 8, s));
   const dim3 gr((n_raw + FQ_BLOCK - 1) / FQ_BLOCK);
   hipLaunchKernelGGL(k_fq_records, gr, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, n_raw,
                      free_layout ? 3 : stream == 2 || f.keep_reads ? 1 : 0,  // (FREE: a quality of another length is kseq's -2 for every stream)
@@ -435,10 +426,10 @@ static int fq_scan_resident(cmgpu_ctx *c, int stream, uint64_t n_bytes, int fina
   cm_scan_u32((const uint32_t *)f.keep.p, (uint32_t *)f.pos.p, n_raw, (uint32_t *)f.scan_tmp.p, s);
   hipLaunchKernelGGL(k_fq_compact, gr, b, 0, s, (const uint32_t *)f.keep.p, (const uint32_t *)f.pos.p, n_raw, (uint32_t *)f.recidx.p);
   uint32_t bad = 0, bad_q = 0, n_rec = 0;
-  FQCHECK(c, hipMemcpyAsync(&bad, f.bad.p, 4, hipMemcpyDeviceToHost, s));
-  FQCHECK(c, hipMemcpyAsync(&bad_q, (uint32_t *)f.bad.p + 1, 4, hipMemcpyDeviceToHost, s));
-  FQCHECK(c, hipMemcpyAsync(&n_rec, (uint32_t *)f.pos.p + n_raw, 4, hipMemcpyDeviceToHost, s));
-  FQCHECK(c, cm_stream_sync(s));
+  CM_HIPCHECK(c, hipMemcpyAsync(&bad, f.bad.p, 4, hipMemcpyDeviceToHost, s));
+  CM_HIPCHECK(c, hipMemcpyAsync(&bad_q, (uint32_t *)f.bad.p + 1, 4, hipMemcpyDeviceToHost, s));
+  CM_HIPCHECK(c, hipMemcpyAsync(&n_rec, (uint32_t *)f.pos.p + n_raw, 4, hipMemcpyDeviceToHost, s));
+  CM_HIPCHECK(c, cm_stream_sync(s));
   if (bad != none && free_layout) return fq_scan_general(c, stream, n_lines, final_chunk != 0, unterminated, n_records);
   if (bad != none && bad == bad_q && stream != 2) {  // (only seen with keep_reads on: the qualities of reads are not looked at otherwise)
     cm_set_error(c, "truncated quality: the quality line is not as long as the sequence at record " + std::to_string(bad) +
@@ -571,7 +562,7 @@ static int fq_text_room(cmgpu_ctx *c, CmFqStream &f, uint64_t need, uint64_t kee
   {
     hipError_t e = keep ? hipMemcpyAsync(bigger.p, f.text.p, keep, hipMemcpyDeviceToDevice, fq_hs(c, f)) : hipSuccess;
     if (e == hipSuccess) e = cm_stream_sync(fq_hs(c, f));
-    if (e != hipSuccess) { bigger.release(); FQCHECK(c, e); }
+    if (e != hipSuccess) { bigger.release(); CM_HIPCHECK(c, e); }
   }
   f.text.release();
   f.text = bigger;
@@ -589,8 +580,8 @@ static int fq_retain_rest(cmgpu_ctx *c, CmFqStream &f, uint64_t consumed, bool e
     bool blank = true;
     for (uint64_t o = 0; blank && o < rest; o += tail.size()) {
       const size_t m = rest - o < tail.size() ? (size_t)(rest - o) : tail.size();
-      FQCHECK(c, hipMemcpyAsync(tail.data(), (const uint8_t *)f.text.p + consumed + o, m, hipMemcpyDeviceToHost, fq_hs(c, f)));
-      FQCHECK(c, cm_stream_sync(fq_hs(c, f)));
+      CM_HIPCHECK(c, hipMemcpyAsync(tail.data(), (const uint8_t *)f.text.p + consumed + o, m, hipMemcpyDeviceToHost, fq_hs(c, f)));
+      CM_HIPCHECK(c, cm_stream_sync(fq_hs(c, f)));
       for (size_t i = 0; i < m; ++i) { const char ch = tail[i]; blank = blank && (ch == '\n' || ch == '\r' || ch == ' ' || ch == '\t'); }
     }
     if (!blank) { cm_set_error(c, "text after the last whole FASTQ record of the file"); return CMGPU_EFORMAT; }
@@ -601,8 +592,8 @@ static int fq_retain_rest(cmgpu_ctx *c, CmFqStream &f, uint64_t consumed, bool e
   if (rest) {
     // (sized like the first buffer: the two swap, and a buffer that is large enough is left alone)
     if (f.text2.cap < rest + 32 && f.text2.ensure(rest + 32 > f.text.cap ? rest + 32 : f.text.cap)) { cm_set_error(c, "out of device memory (FASTQ text)"); return CMGPU_ENOMEM; }
-    FQCHECK(c, hipMemcpyAsync(f.text2.p, (const uint8_t *)f.text.p + consumed, rest, hipMemcpyDeviceToDevice, fq_hs(c, f)));
-    FQCHECK(c, cm_stream_sync(fq_hs(c, f)));
+    CM_HIPCHECK(c, hipMemcpyAsync(f.text2.p, (const uint8_t *)f.text.p + consumed, rest, hipMemcpyDeviceToDevice, fq_hs(c, f)));
+    CM_HIPCHECK(c, cm_stream_sync(fq_hs(c, f)));
     DevBuf t = f.text; f.text = f.text2; f.text2 = t;
   }
   f.dev_len = rest;
@@ -611,7 +602,7 @@ static int fq_retain_rest(cmgpu_ctx *c, CmFqStream &f, uint64_t consumed, bool e
 }
 extern "C" int cmgpu_fastq_scan_bgzf(cmgpu_ctx *c, int stream, const void *blocks, uint64_t n_bytes, int final_chunk, uint32_t *n_records) {
   if (!c || stream < 0 || stream > 2 || (!blocks && n_bytes) || !n_records) return CMGPU_EINVAL;
-  FQCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   CmFqStream &f = c->fq[stream];
   hipStream_t s = fq_hs(c, f);
   *n_records = 0;
@@ -647,17 +638,17 @@ extern "C" int cmgpu_fastq_scan_bgzf(cmgpu_ctx *c, int stream, const void *block
     }
     static const CmCrcX2n x2n = []() { CmCrcX2n x; cm_crc_x2n_table(x); return x; }();
     const uint32_t none = 0xffffffffu;
-    FQCHECK(c, hipMemcpyAsync(f.comp.p, blocks, n_bytes, hipMemcpyHostToDevice, s));
-    FQCHECK(c, hipMemcpyAsync(f.btab.p, tab.data(), tab.size() * sizeof(FqBgzfBlock), hipMemcpyHostToDevice, s));
-    FQCHECK(c, hipMemcpyAsync(f.bad.p, &none, 4, hipMemcpyHostToDevice, s));
+    CM_HIPCHECK(c, hipMemcpyAsync(f.comp.p, blocks, n_bytes, hipMemcpyHostToDevice, s));
+    CM_HIPCHECK(c, hipMemcpyAsync(f.btab.p, tab.data(), tab.size() * sizeof(FqBgzfBlock), hipMemcpyHostToDevice, s));
+    CM_HIPCHECK(c, hipMemcpyAsync(f.bad.p, &none, 4, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_bgzf_tokens, dim3((unsigned)((tab.size() + FQ_INF_LANES - 1) / FQ_INF_LANES)), dim3(FQ_INF_LANES), 0, s,
                        (const uint8_t *)f.comp.p, (const FqBgzfBlock *)f.btab.p, (uint32_t)tab.size(), (uint8_t *)f.text.p, (uint32_t *)f.toks.p,
                        (uint32_t *)f.ntok.p, (uint32_t *)f.bad.p);
     hipLaunchKernelGGL(k_bgzf_resolve, dim3((unsigned)tab.size()), dim3(64), 0, s, (const FqBgzfBlock *)f.btab.p, (uint8_t *)f.text.p,
                        (const uint32_t *)f.toks.p, (const uint32_t *)f.ntok.p, x2n, (uint32_t *)f.bad.p);
     uint32_t st = 0;
-    FQCHECK(c, hipMemcpyAsync(&st, f.bad.p, 4, hipMemcpyDeviceToHost, s));
-    FQCHECK(c, cm_stream_sync(s));
+    CM_HIPCHECK(c, hipMemcpyAsync(&st, f.bad.p, 4, hipMemcpyDeviceToHost, s));
+    CM_HIPCHECK(c, cm_stream_sync(s));
     if (st != none) {
       static const char *what[] = {"", "the stream runs past the block's end", "the inflated size differs from the block's ISIZE", "invalid code", "CRC mismatch"};
       cm_set_error(c, std::string("damaged BGZF block ") + std::to_string(st >> 3) + " of the chunk (" + what[(st & 7) < 5 ? (st & 7) : 3] + ")");
@@ -669,8 +660,8 @@ extern "C" int cmgpu_fastq_scan_bgzf(cmgpu_ctx *c, int stream, const void *block
   f.general = false; f.fx_lines = 0; f.fx_stop = 0;
   if (out == 0) return CMGPU_OK;
   char last_char = 0;
-  FQCHECK(c, hipMemcpyAsync(&last_char, (const uint8_t *)f.text.p + out - 1, 1, hipMemcpyDeviceToHost, s));
-  FQCHECK(c, cm_stream_sync(s));
+  CM_HIPCHECK(c, hipMemcpyAsync(&last_char, (const uint8_t *)f.text.p + out - 1, 1, hipMemcpyDeviceToHost, s));
+  CM_HIPCHECK(c, cm_stream_sync(s));
   return fq_scan_resident(c, stream, out, final_chunk, last_char, n_records);
 }
 
@@ -679,7 +670,7 @@ extern "C" int cmgpu_fastq_scan_bgzf(cmgpu_ctx *c, int stream, const void *block
 //  would wait for the mapping stream, and no hipFree, which waits for the device)
 extern "C" int cmgpu_fastq_take(cmgpu_ctx *c, int stream, uint32_t n, uint64_t *bytes_consumed) {
   if (!c || stream < 0 || stream > 2 || !bytes_consumed) return CMGPU_EINVAL;
-  FQCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   CmFqStream &f = c->fq[stream];
   hipStream_t s = fq_hs(c, f);
   if (n > f.n_rec) { cm_set_error(c, "more records requested than the chunk holds"); return CMGPU_EINVAL; }
@@ -698,8 +689,8 @@ extern "C" int cmgpu_fastq_take(cmgpu_ctx *c, int stream, uint32_t n, uint64_t *
   if (f.general) {}
   else if (n == f.n_rec) { if (f.n_raw) { last_raw = f.n_raw - 1; have_last = true; } }
   else if (n > 0) {
-    FQCHECK(c, hipMemcpyAsync(&last_raw, (uint32_t *)f.recidx.p + (n - 1), 4, hipMemcpyDeviceToHost, s));
-    FQCHECK(c, cm_stream_sync(s));
+    CM_HIPCHECK(c, hipMemcpyAsync(&last_raw, (uint32_t *)f.recidx.p + (n - 1), 4, hipMemcpyDeviceToHost, s));
+    CM_HIPCHECK(c, cm_stream_sync(s));
     have_last = true;
   }
   uint64_t consumed = 0;
@@ -707,31 +698,31 @@ extern "C" int cmgpu_fastq_take(cmgpu_ctx *c, int stream, uint32_t n, uint64_t *
     // the line where seek state stands behind the taken records: where the countable records end, or the line after the last one taken
     uint32_t line = f.fx_stop;
     if (n < f.n_rec && n > 0) {
-      FQCHECK(c, hipMemcpyAsync(&last_raw, (uint32_t *)f.recidx.p + (n - 1), 4, hipMemcpyDeviceToHost, s));
-      FQCHECK(c, cm_stream_sync(s));
-      FQCHECK(c, hipMemcpyAsync(&line, (uint32_t *)f.fx_nxt.p + last_raw, 4, hipMemcpyDeviceToHost, s));
-      FQCHECK(c, cm_stream_sync(s));
+      CM_HIPCHECK(c, hipMemcpyAsync(&last_raw, (uint32_t *)f.recidx.p + (n - 1), 4, hipMemcpyDeviceToHost, s));
+      CM_HIPCHECK(c, cm_stream_sync(s));
+      CM_HIPCHECK(c, hipMemcpyAsync(&line, (uint32_t *)f.fx_nxt.p + last_raw, 4, hipMemcpyDeviceToHost, s));
+      CM_HIPCHECK(c, cm_stream_sync(s));
     } else if (n < f.n_rec) line = 0;
     if (line > 0) {
       uint32_t endnl = 0;
-      FQCHECK(c, hipMemcpyAsync(&endnl, (uint32_t *)f.nl.p + (line - 1), 4, hipMemcpyDeviceToHost, s));
-      FQCHECK(c, cm_stream_sync(s));
+      CM_HIPCHECK(c, hipMemcpyAsync(&endnl, (uint32_t *)f.nl.p + (line - 1), 4, hipMemcpyDeviceToHost, s));
+      CM_HIPCHECK(c, cm_stream_sync(s));
       consumed = (uint64_t)endnl + 1;
       if (consumed > f.n_bytes) consumed = f.n_bytes;
     }
   }
   if (have_last) {
     uint32_t endnl = 0;
-    FQCHECK(c, hipMemcpyAsync(&endnl, (uint32_t *)f.nl.p + (4 * (size_t)last_raw + 3), 4, hipMemcpyDeviceToHost, s));
-    FQCHECK(c, cm_stream_sync(s));
+    CM_HIPCHECK(c, hipMemcpyAsync(&endnl, (uint32_t *)f.nl.p + (4 * (size_t)last_raw + 3), 4, hipMemcpyDeviceToHost, s));
+    CM_HIPCHECK(c, cm_stream_sync(s));
     consumed = (uint64_t)endnl + 1;
     if (consumed > f.n_bytes) consumed = f.n_bytes;
   }
   *bytes_consumed = consumed;
   if (offs.ensure(((size_t)n + 1) * 4)) { cm_set_error(c, "out of device memory (read offsets)"); return CMGPU_ENOMEM; }
   if (n == 0) {
-    FQCHECK(c, hipMemsetAsync(offs.p, 0, 4, s));
-    FQCHECK(c, cm_stream_sync(s));
+    CM_HIPCHECK(c, hipMemsetAsync(offs.p, 0, 4, s));
+    CM_HIPCHECK(c, cm_stream_sync(s));
     return f.dev_mode ? fq_retain_rest(c, f, consumed, f.final_chunk && n == f.n_rec, bytes_consumed) : CMGPU_OK;
   }
   if (f.len.ensure(((size_t)n + 1) * 4) || f.scan_tmp.ensure(cm_scan_tmp_words(n) * 4) || f.bad.ensure(4) ||
@@ -779,7 +770,7 @@ extern "C" int cmgpu_fastq_take(cmgpu_ctx *c, int stream, uint32_t n, uint64_t *
   else if (names)
     hipLaunchKernelGGL(k_fq_name_gather<false>, g, b, 0, s, (const uint8_t *)f.text.p, (const uint32_t *)f.nl.p, (const uint32_t *)f.recidx.p,
                        (const uint32_t *)f.nm_off.p, n, (uint8_t *)f.st_nm.p);
-  FQCHECK(c, cm_stream_sync(s));
+  CM_HIPCHECK(c, cm_stream_sync(s));
   f.taken_bases = total;
   f.taken_max_len = mx;
   f.taken_name_bytes = name_total;
@@ -797,7 +788,7 @@ static int fq_names_reserve(cmgpu_ctx *c, CmFqStream &f, uint64_t need_n, uint64
     if (nb.ensure((cap + 1) * 8)) { cm_set_error(c, "out of device memory (read-name store: offsets of " + std::to_string((unsigned long long)cap) + " names)"); return CMGPU_ENOMEM; }
     hipError_t e = c->nm_offs.p ? hipMemcpyAsync(nb.p, c->nm_offs.p, (c->nm_n + 1) * 8, hipMemcpyDeviceToDevice, s) : hipMemsetAsync(nb.p, 0, 8, s);
     if (e == hipSuccess) e = cm_stream_sync(s);
-    if (e != hipSuccess) { nb.release(); FQCHECK(c, e); }
+    if (e != hipSuccess) { nb.release(); CM_HIPCHECK(c, e); }
     c->nm_offs.release();
     c->nm_offs = nb;
     c->nm_cap_n = cap;
@@ -810,7 +801,7 @@ static int fq_names_reserve(cmgpu_ctx *c, CmFqStream &f, uint64_t need_n, uint64
     if (nb.ensure(cap)) { cm_set_error(c, "out of device memory (read-name store: " + std::to_string((unsigned long long)cap) + " bytes of names)"); return CMGPU_ENOMEM; }
     hipError_t e = c->nm_bytes ? hipMemcpyAsync(nb.p, c->nm_blob.p, c->nm_bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
     if (e == hipSuccess) e = cm_stream_sync(s);
-    if (e != hipSuccess) { nb.release(); FQCHECK(c, e); }
+    if (e != hipSuccess) { nb.release(); CM_HIPCHECK(c, e); }
     c->nm_blob.release();
     c->nm_blob = nb;
   }
@@ -831,8 +822,8 @@ static int fq_names_append(cmgpu_ctx *c, CmFqStream &f, uint32_t n, uint32_t fir
   hipLaunchKernelGGL(k_fq_name_append, dim3(n / FQ_BLOCK + 1), dim3(FQ_BLOCK), 0, s, (const uint32_t *)f.nm_off.p, n, c->nm_bytes,
                      (uint64_t *)c->nm_offs.p + c->nm_n);
   if (f.taken_name_bytes)
-    FQCHECK(c, hipMemcpyAsync((uint8_t *)c->nm_blob.p + c->nm_bytes, f.st_nm.p, f.taken_name_bytes, hipMemcpyDeviceToDevice, s));
-  FQCHECK(c, cm_stream_sync(s));
+    CM_HIPCHECK(c, hipMemcpyAsync((uint8_t *)c->nm_blob.p + c->nm_bytes, f.st_nm.p, f.taken_name_bytes, hipMemcpyDeviceToDevice, s));
+  CM_HIPCHECK(c, cm_stream_sync(s));
   c->nm_n += n;
   c->nm_bytes += f.taken_name_bytes;
   return CMGPU_OK;
@@ -847,7 +838,7 @@ int cm_grow_buf(cmgpu_ctx *c, DevBuf &b, uint64_t used, uint64_t need, uint64_t 
   if (nb.ensure(cap)) { cm_set_error(c, std::string("out of device memory (") + what + ": " + std::to_string((unsigned long long)cap) + " bytes)"); return CMGPU_ENOMEM; }
   hipError_t e = used && b.p ? hipMemcpyAsync(nb.p, b.p, used, hipMemcpyDeviceToDevice, s) : hipSuccess;
   if (e == hipSuccess) e = cm_stream_sync(s);
-  if (e != hipSuccess) { nb.release(); FQCHECK(c, e); }
+  if (e != hipSuccess) { nb.release(); CM_HIPCHECK(c, e); }
   b.release();
   b = nb;
   return CMGPU_OK;
@@ -886,13 +877,13 @@ static int fq_reads_append(cmgpu_ctx *c, int mates, uint32_t n, uint32_t first_r
     const dim3 g(n / FQ_BLOCK + 1), b(FQ_BLOCK);
     hipLaunchKernelGGL(k_fq_name_append, g, b, 0, s, (const uint32_t *)f.nm_off.p, n, r.name_bytes, (uint64_t *)r.name_offs.p + c->rd_n);
     hipLaunchKernelGGL(k_fq_name_append, g, b, 0, s, (const uint32_t *)so.p, n, r.base_bytes, (uint64_t *)r.offs.p + c->rd_n);
-    if (f.taken_name_bytes) FQCHECK(c, hipMemcpyAsync((uint8_t *)r.names.p + r.name_bytes, f.st_nm.p, f.taken_name_bytes, hipMemcpyDeviceToDevice, s));
+    if (f.taken_name_bytes) CM_HIPCHECK(c, hipMemcpyAsync((uint8_t *)r.names.p + r.name_bytes, f.st_nm.p, f.taken_name_bytes, hipMemcpyDeviceToDevice, s));
     if (f.taken_bases) {
-      FQCHECK(c, hipMemcpyAsync((uint8_t *)r.bases.p + r.base_bytes, sb.p, f.taken_bases, hipMemcpyDeviceToDevice, s));
-      FQCHECK(c, hipMemcpyAsync((uint8_t *)r.quals.p + r.base_bytes, f.st_q.p, f.taken_bases, hipMemcpyDeviceToDevice, s));
+      CM_HIPCHECK(c, hipMemcpyAsync((uint8_t *)r.bases.p + r.base_bytes, sb.p, f.taken_bases, hipMemcpyDeviceToDevice, s));
+      CM_HIPCHECK(c, hipMemcpyAsync((uint8_t *)r.quals.p + r.base_bytes, f.st_q.p, f.taken_bases, hipMemcpyDeviceToDevice, s));
     }
   }
-  for (int m = 0; m < mates; ++m) FQCHECK(c, cm_stream_sync(fq_hs(c, c->fq[m])));
+  for (int m = 0; m < mates; ++m) CM_HIPCHECK(c, cm_stream_sync(fq_hs(c, c->fq[m])));
   if (c->rd_n == 0) { c->rd_base = first_read_id; c->rd_paired = mates == 2; }
   for (int m = 0; m < mates; ++m) { c->rd[m].name_bytes += c->fq[m].taken_name_bytes; c->rd[m].base_bytes += c->fq[m].taken_bases; }
   c->rd_n += n;
@@ -903,7 +894,7 @@ static int fq_reads_append(cmgpu_ctx *c, int mates, uint32_t n, uint32_t first_r
 // for host SoA buffers); cmgpu_map_resident maps it
 extern "C" int cmgpu_fastq_commit(cmgpu_ctx *c, uint32_t n, uint32_t first_read_id, int paired, int barcoded) {
   if (!c) return CMGPU_EINVAL;
-  FQCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   if (c->fq[0].taken != n || (paired && c->fq[1].taken != n) || (barcoded && c->fq[2].taken != n)) {
     cm_set_error(c, "streams hold different numbers of taken records"); return CMGPU_EINVAL;
   }
@@ -936,7 +927,7 @@ extern "C" int cmgpu_fastq_commit(cmgpu_ctx *c, uint32_t n, uint32_t first_read_
   c->max_read_len = mx ? mx : 1;
   if (!paired) {
     if (c->ro1.ensure(((size_t)n + 1) * 4) || c->rb1.ensure(16)) { cm_set_error(c, "out of device memory (reads)"); return CMGPU_ENOMEM; }
-    FQCHECK(c, hipMemset(c->ro1.p, 0, ((size_t)n + 1) * 4));
+    CM_HIPCHECK(c, hipMemset(c->ro1.p, 0, ((size_t)n + 1) * 4));
   }
   return CMGPU_OK;
 }
@@ -968,10 +959,10 @@ extern "C" int cmgpu_names_info(const cmgpu_ctx *c, uint64_t *n_names, uint64_t 
 extern "C" int cmgpu_download_names(cmgpu_ctx *c, char *blob, uint64_t blob_capacity, uint64_t *offsets) {
   if (!c || !offsets || (!blob && c->nm_bytes)) return CMGPU_EINVAL;
   if (blob_capacity < c->nm_bytes) { cm_set_error(c, "name buffer too small"); return CMGPU_ECAPACITY; }
-  FQCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   offsets[0] = 0;
-  if (c->nm_n) FQCHECK(c, hipMemcpy(offsets, c->nm_offs.p, (c->nm_n + 1) * 8, hipMemcpyDeviceToHost));
-  if (c->nm_bytes) FQCHECK(c, hipMemcpy(blob, c->nm_blob.p, c->nm_bytes, hipMemcpyDeviceToHost));
+  if (c->nm_n) CM_HIPCHECK(c, hipMemcpy(offsets, c->nm_offs.p, (c->nm_n + 1) * 8, hipMemcpyDeviceToHost));
+  if (c->nm_bytes) CM_HIPCHECK(c, hipMemcpy(blob, c->nm_blob.p, c->nm_bytes, hipMemcpyDeviceToHost));
   return CMGPU_OK;
 }
 
@@ -1007,17 +998,17 @@ extern "C" int cmgpu_download_reads(cmgpu_ctx *c, int mate, char *names, uint64_
   const uint64_t n = mate == 0 || c->rd_paired ? c->rd_n : 0;
   if ((!names && r.name_bytes) || ((!bases || !quals) && r.base_bytes)) return CMGPU_EINVAL;
   if (names_capacity < r.name_bytes || bases_capacity < r.base_bytes) { cm_set_error(c, "read buffer too small"); return CMGPU_ECAPACITY; }
-  FQCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   name_offsets[0] = 0;
   offsets[0] = 0;
   if (n) {
-    FQCHECK(c, hipMemcpy(name_offsets, r.name_offs.p, (n + 1) * 8, hipMemcpyDeviceToHost));
-    FQCHECK(c, hipMemcpy(offsets, r.offs.p, (n + 1) * 8, hipMemcpyDeviceToHost));
+    CM_HIPCHECK(c, hipMemcpy(name_offsets, r.name_offs.p, (n + 1) * 8, hipMemcpyDeviceToHost));
+    CM_HIPCHECK(c, hipMemcpy(offsets, r.offs.p, (n + 1) * 8, hipMemcpyDeviceToHost));
   }
-  if (r.name_bytes) FQCHECK(c, hipMemcpy(names, r.names.p, r.name_bytes, hipMemcpyDeviceToHost));
+  if (r.name_bytes) CM_HIPCHECK(c, hipMemcpy(names, r.names.p, r.name_bytes, hipMemcpyDeviceToHost));
   if (r.base_bytes) {
-    FQCHECK(c, hipMemcpy(bases, r.bases.p, r.base_bytes, hipMemcpyDeviceToHost));
-    FQCHECK(c, hipMemcpy(quals, r.quals.p, r.base_bytes, hipMemcpyDeviceToHost));
+    CM_HIPCHECK(c, hipMemcpy(bases, r.bases.p, r.base_bytes, hipMemcpyDeviceToHost));
+    CM_HIPCHECK(c, hipMemcpy(quals, r.quals.p, r.base_bytes, hipMemcpyDeviceToHost));
   }
   return CMGPU_OK;
 }

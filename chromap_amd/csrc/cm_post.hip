@@ -29,19 +29,11 @@
 #include "cm_ctx.h"
 #include "cm_kernels.h"
 #include "cm_summary.h"
+#include "cm_text_job.h"
 
 #define PP_RUN_SERIAL 128u  // records of a duplicate run its head walks alone (k_pp_select); longer runs: k_pp_select_long
 #define PP_BLOCK 256
 #define PP_LDS_BYTES 32768
-
-#define PPCHECK(ctx, call)                                                                   \
-  do {                                                                                       \
-    hipError_t e_ = (call);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      cm_set_error(ctx, std::string(#call) + ": " + hipGetErrorString(e_));                  \
-      return CMGPU_EHIP;                                                                     \
-    }                                                                                        \
-  } while (0)
 
 struct PpCfg {
   int kind;       // CMGPU_TEXT_BED_PE / _SE / _PE_BC
@@ -130,11 +122,6 @@ __device__ __forceinline__ bool pp_same_run(const PpRec &a, uint64_t bca, const 
   return !pp_has_bc(cfg.kind) || bca == bcb;               // :154-159
 }
 
-__device__ __forceinline__ uint32_t pp_digits(uint32_t v) {
-  return v < 10 ? 1 : v < 100 ? 2 : v < 1000 ? 3 : v < 10000 ? 4 : v < 100000 ? 5 : v < 1000000 ? 6 : v < 10000000 ? 7
-       : v < 100000000 ? 8 : v < 1000000000 ? 9 : 10;
-}
-
 __device__ __forceinline__ uint32_t pp_abundance(const PpCfg &cfg, uint64_t key) {
   const uint64_t x = key * 0x9E3779B97F4A7C15ull;
   uint32_t b = (uint32_t)(x >> 32) & cfg.wl_mask;
@@ -166,13 +153,13 @@ __device__ __forceinline__ void pp_finish(uint32_t j, PpRec r, uint32_t wi, uint
     // two lines (mapping_writer.cc:84-117, 138-168): the + read's and the - read's alignment; bulk data
     // prints num_dups on the second line, single-cell data prints neither barcode nor num_dups
     const uint32_t pe = r.start + r.pal, ne = r.start + r.len, ns = ne - r.nal;
-    len = 2 * (nm + 1 + 2 + pp_digits(r.mapq) + 1 + 1 + 1) + pp_digits(r.start) + 1 + pp_digits(pe) + 1 + pp_digits(ns) + 1 + pp_digits(ne) + 1;
-    if (cfg.kind == CMGPU_TEXT_TAGALIGN_PE) len += 1 + pp_digits(dups);
+    len = 2 * (nm + 1 + 2 + cm_digits10(r.mapq) + 1 + 1 + 1) + cm_digits10(r.start) + 1 + cm_digits10(pe) + 1 + cm_digits10(ns) + 1 + cm_digits10(ne) + 1;
+    if (cfg.kind == CMGPU_TEXT_TAGALIGN_PE) len += 1 + cm_digits10(dups);
   } else {
-    len = nm + 1 + pp_digits(r.start) + 1 + pp_digits(r.start + r.len) + 1;
-    if (cfg.kind == CMGPU_TEXT_BED_PE_BC || cfg.kind == CMGPU_TEXT_BED_SE_BC) len += cfg.bc_len + 1 + pp_digits(dups) + 1;  // chr start end barcode dups
-    else if (cfg.kind == CMGPU_TEXT_TAGALIGN_SE_BC) len += 2 + pp_digits(r.mapq) + 2 + 1;     // chr start end N mapq strand (mapping_writer.cc:26-34)
-    else len += 2 + pp_digits(r.mapq) + 3 + pp_digits(dups) + 1;                              // chr start end N mapq strand dups
+    len = nm + 1 + cm_digits10(r.start) + 1 + cm_digits10(r.start + r.len) + 1;
+    if (cfg.kind == CMGPU_TEXT_BED_PE_BC || cfg.kind == CMGPU_TEXT_BED_SE_BC) len += cfg.bc_len + 1 + cm_digits10(dups) + 1;  // chr start end barcode dups
+    else if (cfg.kind == CMGPU_TEXT_TAGALIGN_SE_BC) len += 2 + cm_digits10(r.mapq) + 2 + 1;     // chr start end N mapq strand (mapping_writer.cc:26-34)
+    else len += 2 + cm_digits10(r.mapq) + 3 + cm_digits10(dups) + 1;                              // chr start end N mapq strand dups
   }
   win[j] = wi;
   dups_out[j] = dups;
@@ -407,12 +394,6 @@ __global__ __launch_bounds__(64) void k_pp_select_long(const uint8_t *__restrict
   }
 }
 
-__device__ __forceinline__ uint8_t *pp_put_u32(uint8_t *p, uint32_t v) {
-  const uint32_t d = pp_digits(v);
-  for (uint32_t i = d; i-- > 0;) { p[i] = (uint8_t)('0' + v % 10); v /= 10; }
-  return p + d;
-}
-
 __device__ __forceinline__ void pp_render(uint8_t *p, const PpRec &r, uint64_t bcv, uint32_t dups, const PpCfg &cfg,
                                           const uint8_t *__restrict__ names, const uint32_t *__restrict__ name_off) {
   const uint32_t n0 = name_off[r.rid], n1 = name_off[r.rid + 1];
@@ -422,23 +403,23 @@ __device__ __forceinline__ void pp_render(uint8_t *p, const PpRec &r, uint64_t b
       const bool plus = (half == 0) == (r.dir != 0);  // the + read's line comes first when read 1 is on the + strand
       for (uint32_t i = n0; i < n1; ++i) *p++ = names[i];
       *p++ = '\t';
-      p = pp_put_u32(p, plus ? r.start : ns);
+      p = cm_put_u32(p, plus ? r.start : ns);
       *p++ = '\t';
-      p = pp_put_u32(p, plus ? pe : ne);
+      p = cm_put_u32(p, plus ? pe : ne);
       *p++ = '\t'; *p++ = 'N'; *p++ = '\t';
-      p = pp_put_u32(p, r.mapq);
+      p = cm_put_u32(p, r.mapq);
       *p++ = '\t';
       *p++ = plus ? '+' : '-';
-      if (half == 1 && cfg.kind == CMGPU_TEXT_TAGALIGN_PE) { *p++ = '\t'; p = pp_put_u32(p, dups); }
+      if (half == 1 && cfg.kind == CMGPU_TEXT_TAGALIGN_PE) { *p++ = '\t'; p = cm_put_u32(p, dups); }
       *p++ = '\n';
     }
     return;
   }
   for (uint32_t i = n0; i < n1; ++i) *p++ = names[i];
   *p++ = '\t';
-  p = pp_put_u32(p, r.start);
+  p = cm_put_u32(p, r.start);
   *p++ = '\t';
-  p = pp_put_u32(p, r.start + r.len);
+  p = cm_put_u32(p, r.start + r.len);
   *p++ = '\t';
   if (cfg.kind == CMGPU_TEXT_BED_PE_BC || cfg.kind == CMGPU_TEXT_BED_SE_BC) {
     for (uint32_t b = 0; b < cfg.bc_len; ++b) *p++ = "ACGT"[(bcv >> ((cfg.bc_len - 1 - b) * 2)) & 3];  // Seed2Sequence
@@ -446,13 +427,13 @@ __device__ __forceinline__ void pp_render(uint8_t *p, const PpRec &r, uint64_t b
   } else {
     *p++ = 'N';
     *p++ = '\t';
-    p = pp_put_u32(p, r.mapq);
+    p = cm_put_u32(p, r.mapq);
     *p++ = '\t';
     *p++ = r.dir ? '+' : '-';
     if (cfg.kind == CMGPU_TEXT_TAGALIGN_SE_BC) { *p = '\n'; return; }
     *p++ = '\t';
   }
-  p = pp_put_u32(p, dups);
+  p = cm_put_u32(p, dups);
   *p = '\n';
 }
 
@@ -492,12 +473,14 @@ __global__ __launch_bounds__(PP_BLOCK) void k_pp_format(const uint8_t *__restric
   for (uint32_t i = head + (body << 4) + threadIdx.x; i < tot; i += PP_BLOCK) dst[i] = lds[i];
 }
 
+// the valid record slots, dense (cm_compact_records): slot i goes to position pos[i] unless that is past the destination's cap records
 __global__ void k_pp_compact(const uint8_t *__restrict__ rec, const uint8_t *__restrict__ ok, const uint32_t *__restrict__ pos,
                              const uint64_t *__restrict__ bc_in, uint8_t *__restrict__ dst, uint64_t *__restrict__ bc_dst, uint32_t n,
-                             uint32_t per_pair) {  // per_pair record slots share one barcode key
+                             uint32_t per_pair, uint64_t cap) {  // per_pair record slots share one barcode key
   const uint32_t i = blockIdx.x * PP_BLOCK + threadIdx.x;
   if (i >= n || !ok[i]) return;
   const uint32_t o = pos[i];
+  if (o >= cap) return;
   const uint64_t *s = reinterpret_cast<const uint64_t *>(rec + (uint64_t)i * 24);
   uint64_t *d = reinterpret_cast<uint64_t *>(dst + (uint64_t)o * 24);
   d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
@@ -524,18 +507,17 @@ int cm_store_reserve(cmgpu_ctx *c, uint64_t need, bool with_bc) {
   if (need > c->store_cap) {
     uint64_t cap = c->store_cap ? c->store_cap * 2 : 1u << 20;
     if (cap < need) cap = need;
-    DevBuf nb, nbc;
+    CmTmpBuf nb, nbc;
     if (nb.ensure(cap * 24 + 16) || ((with_bc || c->store_has_bc) && nbc.ensure(cap * 8))) {
-      nb.release(); nbc.release();
       cm_set_error(c, "out of device memory (record store)");
       return CMGPU_ENOMEM;
     }
     if (c->store_n) {
-      PPCHECK(c, hipMemcpy(nb.p, c->store.p, c->store_n * 24, hipMemcpyDeviceToDevice));
-      if (c->store_has_bc) PPCHECK(c, hipMemcpy(nbc.p, c->store_bc.p, c->store_n * 8, hipMemcpyDeviceToDevice));
+      CM_HIPCHECK(c, hipMemcpy(nb.p, c->store.p, c->store_n * 24, hipMemcpyDeviceToDevice));
+      if (c->store_has_bc) CM_HIPCHECK(c, hipMemcpy(nbc.p, c->store_bc.p, c->store_n * 8, hipMemcpyDeviceToDevice));
     }
     c->store.release(); c->store_bc.release();
-    c->store = nb; c->store_bc = nbc;
+    c->store = nb.hand_over(); c->store_bc = nbc.hand_over();
     c->store_cap = cap;
   } else if (with_bc && !c->store_bc.p) {
     if (c->store_bc.ensure(c->store_cap * 8)) { cm_set_error(c, "out of device memory (record store)"); return CMGPU_ENOMEM; }
@@ -548,7 +530,7 @@ int cm_store_reserve(cmgpu_ctx *c, uint64_t need, bool with_bc) {
 // demand doubles it with an allocation, a device-to-device copy and a synchronous free each time)
 extern "C" int cmgpu_store_reserve(cmgpu_ctx *c, uint64_t n_records, int barcoded) {
   if (!c) return CMGPU_EINVAL;
-  PPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   { const int qrc = cm_exchange_quiesce(c); if (qrc) return qrc; }
   if (c->store_n && c->store_has_bc != (barcoded != 0)) { cm_set_error(c, "record store mixes barcoded and bulk batches"); return CMGPU_EINVAL; }
   const bool had_bc = c->store_has_bc;
@@ -570,7 +552,7 @@ extern "C" int cmgpu_store_clear(cmgpu_ctx *c) {
 
 extern "C" int cmgpu_store_append_resident(cmgpu_ctx *c, uint64_t *n_total) {
   if (!c) return CMGPU_EINVAL;
-  PPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   { const int qrc = cm_exchange_quiesce(c); if (qrc) return qrc; }
   const uint32_t n = (uint32_t)cm_rec_slots(c);
   if (c->store_n && c->store_has_bc != c->has_barcodes) { cm_set_error(c, "record store mixes barcoded and bulk batches"); return CMGPU_EINVAL; }
@@ -579,18 +561,13 @@ extern "C" int cmgpu_store_append_resident(cmgpu_ctx *c, uint64_t *n_total) {
     if (c->store_n == 0) c->store_pairs_rec = cm_pairs_records(c);
     int rc = cm_store_reserve(c, c->store_n + n, c->has_barcodes);
     if (rc) return rc;
-    rc = cm_ensure_slot_scratch(c, n);
+    const uint32_t *n_valid = nullptr;
+    rc = cm_compact_records(c, (uint8_t *)c->store.p + c->store_n * 24, c->has_barcodes ? (uint64_t *)c->store_bc.p + c->store_n : (uint64_t *)nullptr,
+                            n, c->stream, &n_valid);
     if (rc) return rc;
-    uint32_t *flag = (uint32_t *)c->scratch_a.p, *pos = (uint32_t *)c->scratch_b.p;  // free between batches
-    const dim3 g((n + PP_BLOCK - 1) / PP_BLOCK), b(PP_BLOCK);
-    hipLaunchKernelGGL(k_pp_flag, g, b, 0, c->stream, (const uint8_t *)c->rec_ok.p, flag, n);
-    cm_scan_u32(flag, pos, n, (uint32_t *)c->scan_tmp.p, c->stream);
-    hipLaunchKernelGGL(k_pp_compact, g, b, 0, c->stream, (const uint8_t *)c->rec.p, (const uint8_t *)c->rec_ok.p, (const uint32_t *)pos,
-                       (const uint64_t *)c->bc_key.p, (uint8_t *)c->store.p + c->store_n * 24,
-                       c->has_barcodes ? (uint64_t *)c->store_bc.p + c->store_n : (uint64_t *)nullptr, n, cm_rec_per_pair(c));
     uint32_t k = 0;
-    PPCHECK(c, hipMemcpyAsync(&k, pos + n, 4, hipMemcpyDeviceToHost, c->stream));
-    PPCHECK(c, cm_stream_sync(c->stream));
+    CM_HIPCHECK(c, hipMemcpyAsync(&k, n_valid, 4, hipMemcpyDeviceToHost, c->stream));
+    CM_HIPCHECK(c, cm_stream_sync(c->stream));
     c->store_n += k;
   }
   if (n_total) *n_total = c->store_n;
@@ -599,7 +576,7 @@ extern "C" int cmgpu_store_append_resident(cmgpu_ctx *c, uint64_t *n_total) {
 
 extern "C" int cmgpu_store_append(cmgpu_ctx *c, const void *records, uint64_t n, int on_device, int barcoded) {
   if (!c || (!records && n)) return CMGPU_EINVAL;
-  PPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   { const int qrc = cm_exchange_quiesce(c); if (qrc) return qrc; }
   if (c->store_n && c->store_has_bc != (barcoded != 0)) { cm_set_error(c, "record store mixes barcoded and bulk batches"); return CMGPU_EINVAL; }
   if (n == 0) return CMGPU_OK;
@@ -610,19 +587,17 @@ extern "C" int cmgpu_store_append(cmgpu_ctx *c, const void *records, uint64_t n,
   if (rc) return rc;
   const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   if (!barcoded) {
-    PPCHECK(c, hipMemcpy((uint8_t *)c->store.p + c->store_n * 24, records, n * 24, kind));
+    CM_HIPCHECK(c, hipMemcpy((uint8_t *)c->store.p + c->store_n * 24, records, n * 24, kind));
   } else {
-    DevBuf tmp;
+    CmTmpBuf tmp;
     const void *src = records;
     if (!on_device) {
       if (tmp.ensure(n * 32)) { cm_set_error(c, "out of device memory (record staging)"); return CMGPU_ENOMEM; }
-      PPCHECK(c, hipMemcpy(tmp.p, records, n * 32, hipMemcpyHostToDevice));
+      CM_HIPCHECK(c, hipMemcpy(tmp.p, records, n * 32, hipMemcpyHostToDevice));
       src = tmp.p;
     }
-    hipLaunchKernelGGL(k_pp_split_bc, dim3((unsigned)((n + PP_BLOCK - 1) / PP_BLOCK)), dim3(PP_BLOCK), 0, c->stream, (const uint8_t *)src,
-                       (uint32_t)n, (uint8_t *)c->store.p + c->store_n * 24, (uint64_t *)c->store_bc.p + c->store_n);
-    PPCHECK(c, cm_stream_sync(c->stream));
-    tmp.release();
+    cm_store_split_bc(c, src, n, c->stream);
+    CM_HIPCHECK(c, cm_stream_sync(c->stream));
   }
   c->store_n += n;
   return CMGPU_OK;
@@ -631,25 +606,13 @@ extern "C" int cmgpu_store_append(cmgpu_ctx *c, const void *records, uint64_t n,
 // ---------------------------------------------------------------------------------------
 // sort + select + format
 // ---------------------------------------------------------------------------------------
-static int pp_sort_pass(cmgpu_ctx *c, DevBuf &tmp, uint64_t *kin, uint64_t *kout, uint32_t *vin, uint32_t *vout, size_t n, unsigned bits) {
-  size_t tb = 0;
-  PPCHECK(c, rocprim::radix_sort_pairs(nullptr, tb, kin, kout, vin, vout, n, 0, bits, c->stream));
-  if (tmp.ensure(tb + 256)) { cm_set_error(c, "out of device memory (sort)"); return CMGPU_ENOMEM; }
-  PPCHECK(c, rocprim::radix_sort_pairs(tmp.p, tb, kin, kout, vin, vout, n, 0, bits, c->stream));
-  return CMGPU_OK;
-}
-
-struct PpLinesOp {
-  __host__ __device__ uint64_t operator()(uint64_t l) const { return l ? 1 : 0; }
-};
-
 extern "C" int cmgpu_store_format(cmgpu_ctx *c, int kind, const char *const *names, uint32_t n_sequences, const cmgpu_params *p,
                                   uint32_t barcode_length, uint64_t *n_lines, uint64_t *n_bytes) {
   if (!c || !names || !p || !n_lines || !n_bytes) return CMGPU_EINVAL;
   if (kind < CMGPU_TEXT_BED_PE || kind > CMGPU_TEXT_TAGALIGN_SE_BC) { cm_set_error(c, "unknown text kind"); return CMGPU_EINVAL; }
   if (pp_has_bc(kind) != c->store_has_bc && c->store_n) { cm_set_error(c, "text kind does not match the stored records"); return CMGPU_EINVAL; }
   if (pp_has_bc(kind) && (barcode_length == 0 || barcode_length > 32)) { cm_set_error(c, "barcode length must be 1..32"); return CMGPU_EINVAL; }
-  PPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   { const int qrc = cm_exchange_quiesce(c); if (qrc) return qrc; }
   hipStream_t s = c->stream;
   *n_lines = 0;
@@ -673,88 +636,50 @@ extern "C" int cmgpu_store_format(cmgpu_ctx *c, int kind, const char *const *nam
   cfg.wl = (const uint64_t *)c->wl.p;
   cfg.wl_mask = c->wl_mask;
   if (cfg.bulk && c->wl_size == 0) { cm_set_error(c, "bulk-level duplicate removal needs the whitelist abundances (cmgpu_set_whitelist)"); return CMGPU_EINVAL; }
-  // names -> device
-  std::vector<uint32_t> noff(n_sequences + 1, 0);
-  std::string blob;
-  for (uint32_t i = 0; i < n_sequences; ++i) { blob += names[i]; noff[i + 1] = (uint32_t)blob.size(); }
-  DevBuf d_names, d_noff, k0, k1, v0, v1, tmp, win, dups, llen, loff, longs;
-  auto fail = [&](int rc) { longs.release(); d_names.release(); d_noff.release(); k0.release(); k1.release(); v0.release(); v1.release(); tmp.release();
-                            win.release(); dups.release(); llen.release(); loff.release(); return rc; };
-  if (d_names.ensure(blob.size() + 16) || d_noff.ensure(noff.size() * 4) || k0.ensure((size_t)n * 8) || k1.ensure((size_t)n * 8) ||
-      v0.ensure((size_t)n * 4) || v1.ensure((size_t)n * 4)) { cm_set_error(c, "out of device memory (post-processing)"); return fail(CMGPU_ENOMEM); }
-  if (hipMemcpyAsync(d_names.p, blob.data(), blob.size(), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(d_noff.p, noff.data(), noff.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess) { cm_set_error(c, "name upload failed"); return fail(CMGPU_EHIP); }
+  CmTextJob job;
+  int rc;
+  if ((rc = job.begin(c, names, n_sequences, n, 1, false))) return rc;
   const dim3 g((n + PP_BLOCK - 1) / PP_BLOCK), b(PP_BLOCK);
   const uint8_t *store = (const uint8_t *)c->store.p;
   const uint64_t *bc = (const uint64_t *)c->store_bc.p;
-  uint64_t *ka = (uint64_t *)k0.p, *kb = (uint64_t *)k1.p;
-  uint32_t *va = (uint32_t *)v0.p, *vb = (uint32_t *)v1.p;
-  int rc;
-  hipLaunchKernelGGL(k_pp_key0, g, b, 0, s, store, n, ka, va);
-  if ((rc = pp_sort_pass(c, tmp, ka, kb, va, vb, n, 40))) return fail(rc);
-  std::swap(va, vb);
+  hipLaunchKernelGGL(k_pp_key0, g, b, 0, s, store, n, job.keys(), job.idx());
+  if ((rc = job.sort_pass(40))) return rc;
   if (pp_has_bc(kind)) {
-    hipLaunchKernelGGL(k_pp_key_bc, g, b, 0, s, bc, (const uint32_t *)va, n, ka);
-    if ((rc = pp_sort_pass(c, tmp, ka, kb, va, vb, n, 2 * barcode_length))) return fail(rc);
-    std::swap(va, vb);
+    hipLaunchKernelGGL(k_pp_key_bc, g, b, 0, s, bc, (const uint32_t *)job.idx(), n, job.keys());
+    if ((rc = job.sort_pass(2 * barcode_length))) return rc;
   }
-  unsigned rid_bits = 1;
-  while (rid_bits < 32 && (1ull << rid_bits) < (uint64_t)n_sequences + 1) ++rid_bits;
-  hipLaunchKernelGGL(k_pp_key_top, g, b, 0, s, store, (const uint32_t *)va, n, cfg, 0, ka);
-  if ((rc = pp_sort_pass(c, tmp, ka, kb, va, vb, n, 48 + (rid_bits > 16 ? 16 : rid_bits)))) return fail(rc);
-  std::swap(va, vb);
-  if (rid_bits > 16) {
-    hipLaunchKernelGGL(k_pp_key_top, g, b, 0, s, store, (const uint32_t *)va, n, cfg, 1, ka);
-    if ((rc = pp_sort_pass(c, tmp, ka, kb, va, vb, n, rid_bits - 16))) return fail(rc);
-    std::swap(va, vb);
+  hipLaunchKernelGGL(k_pp_key_top, g, b, 0, s, store, (const uint32_t *)job.idx(), n, cfg, 0, job.keys());
+  if ((rc = job.sort_pass(48 + (job.rid_bits > 16 ? 16 : job.rid_bits)))) return rc;
+  if (job.rid_bits > 16) {
+    hipLaunchKernelGGL(k_pp_key_top, g, b, 0, s, store, (const uint32_t *)job.idx(), n, cfg, 1, job.keys());
+    if ((rc = job.sort_pass(job.rid_bits - 16))) return rc;
   }
-  PPCHECK(c, cm_stream_sync(s));
-  tmp.release(); k0.release(); k1.release();
-  (va == (uint32_t *)v0.p ? v1 : v0).release();
+  CM_HIPCHECK(c, cm_stream_sync(s));
+  job.release_sort();
   // ---- select
-  if (win.ensure((size_t)n * 4) || dups.ensure((size_t)n * 4) || llen.ensure(((size_t)n + 1) * 8) || loff.ensure(((size_t)n + 1) * 8)) {
-    cm_set_error(c, "out of device memory (post-processing)"); return fail(CMGPU_ENOMEM);
-  }
+  CmTmpBuf win, dups, longs;
+  if (win.ensure((size_t)n * 4) || dups.ensure((size_t)n * 4)) return job.enomem("post-processing");
+  if ((rc = job.alloc_lengths())) return rc;
   // heads of long duplicate runs: at most n / PP_RUN_SERIAL of them, + the counter
-  if (longs.ensure(((size_t)n / PP_RUN_SERIAL + 2) * 4)) { cm_set_error(c, "out of device memory (post-processing)"); return fail(CMGPU_ENOMEM); }
+  if (longs.ensure(((size_t)n / PP_RUN_SERIAL + 2) * 4)) return job.enomem("post-processing");
   uint32_t *long_cnt = (uint32_t *)longs.p, *long_list = long_cnt + 1;
-  if (hipMemsetAsync(long_cnt, 0, 4, s) != hipSuccess) { cm_set_error(c, "memset failed"); return fail(CMGPU_EHIP); }
+  if (hipMemsetAsync(long_cnt, 0, 4, s) != hipSuccess) { cm_set_error(c, "memset failed"); return CMGPU_EHIP; }
   // --summary: the selection credits every run to its survivor's barcode.  The keys are in the table since their reads were counted;
   // a store filled by the multi-GPU exchange also holds records of reads another context counted
   CmSmDev sm;
   if ((rc = cm_summary_dev(c, c->ex.transport ? n : 0, pp_has_bc(kind) && c->wl_size && !p->output_mappings_not_in_whitelist ? c->wl_size : 0,
-                           !pp_has_bc(kind), &sm))) return fail(rc);
-  hipLaunchKernelGGL(k_pp_select, g, b, 0, s, store, bc, (const uint32_t *)va, n, cfg, (const uint32_t *)d_noff.p, (uint32_t *)win.p,
-                     (uint32_t *)dups.p, (uint64_t *)llen.p, long_list, long_cnt, sm);
-  hipLaunchKernelGGL(k_pp_select_long, dim3(1024), dim3(64), 0, s, store, bc, (const uint32_t *)va, n, cfg, (const uint32_t *)d_noff.p,
-                     (uint32_t *)win.p, (uint32_t *)dups.p, (uint64_t *)llen.p, (const uint32_t *)long_list, (const uint32_t *)long_cnt, sm);
-  if (hipMemsetAsync((uint64_t *)llen.p + n, 0, 8, s) != hipSuccess) { cm_set_error(c, "memset failed"); return fail(CMGPU_EHIP); }
-  size_t tb = 0, tb2 = 0;
-  (void)rocprim::exclusive_scan(nullptr, tb, (const uint64_t *)llen.p, (uint64_t *)loff.p, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s);
-  auto lines_in = rocprim::make_transform_iterator((const uint64_t *)llen.p, PpLinesOp());
-  DevBuf d_count;
-  (void)rocprim::reduce(nullptr, tb2, lines_in, (uint64_t *)nullptr, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
-  if (tmp.ensure((tb > tb2 ? tb : tb2) + 256) || d_count.ensure(8)) { d_count.release(); cm_set_error(c, "out of device memory (scan)"); return fail(CMGPU_ENOMEM); }
-  hipError_t e = rocprim::exclusive_scan(tmp.p, tb, (const uint64_t *)llen.p, (uint64_t *)loff.p, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s);
-  if (e == hipSuccess) e = rocprim::reduce(tmp.p, tb2, lines_in, (uint64_t *)d_count.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
+                           !pp_has_bc(kind), &sm))) return rc;
+  hipLaunchKernelGGL(k_pp_select, g, b, 0, s, store, bc, (const uint32_t *)job.idx(), n, cfg, job.seq_off(), (uint32_t *)win.p,
+                     (uint32_t *)dups.p, (uint64_t *)job.llen.p, long_list, long_cnt, sm);
+  hipLaunchKernelGGL(k_pp_select_long, dim3(1024), dim3(64), 0, s, store, bc, (const uint32_t *)job.idx(), n, cfg, job.seq_off(),
+                     (uint32_t *)win.p, (uint32_t *)dups.p, (uint64_t *)job.llen.p, (const uint32_t *)long_list, (const uint32_t *)long_cnt, sm);
   uint64_t total = 0, lines = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(&total, (uint64_t *)loff.p + n, 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(&lines, d_count.p, 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = cm_stream_sync(s);
-  d_count.release();
-  if (e != hipSuccess) { cm_set_error(c, std::string("post-processing scan: ") + hipGetErrorString(e)); return fail(CMGPU_EHIP); }
-  if ((rc = cm_summary_check(c))) return fail(rc);
-  if (c->text.ensure(total + 64)) { cm_set_error(c, "out of device memory (text)"); return fail(CMGPU_ENOMEM); }
+  if ((rc = job.scan_lines(&total, &lines))) return rc;
+  if ((rc = job.alloc_text(total))) return rc;
   // ---- format
-  hipLaunchKernelGGL(k_pp_format, g, b, 0, s, store, bc, (const uint32_t *)win.p, (const uint32_t *)dups.p, (const uint64_t *)llen.p,
-                     (const uint64_t *)loff.p, n, cfg, (const uint8_t *)d_names.p, (const uint32_t *)d_noff.p, (uint8_t *)c->text.p);
-  e = cm_stream_sync(s);
-  if (e != hipSuccess) { cm_set_error(c, std::string("text formatting: ") + hipGetErrorString(e)); return fail(CMGPU_EHIP); }
-  c->text_bytes = total;
-  c->text_lines = lines;
-  *n_lines = lines;
-  *n_bytes = total;
-  return fail(CMGPU_OK);
+  hipLaunchKernelGGL(k_pp_format, g, b, 0, s, store, bc, (const uint32_t *)win.p, (const uint32_t *)dups.p, (const uint64_t *)job.llen.p,
+                     (const uint64_t *)job.loff.p, n, cfg, (const uint8_t *)job.names.p, job.seq_off(), (uint8_t *)c->text.p);
+  return job.publish(total, lines, n_lines, n_bytes);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -828,8 +753,8 @@ __global__ __launch_bounds__(PP_BLOCK) void k_pp_pairs_len(const uint8_t *__rest
     if (!win) { line_len[j] = 0; return; }
   }
   const uint32_t rn = (uint32_t)(rn_off[q + 1] - rn_off[q]);
-  line_len[j] = rn + 1 + (name_off[r.rid1 + 1] - name_off[r.rid1]) + 1 + pp_digits(r.pos1 + 1) + 1 + (name_off[r.rid2 + 1] - name_off[r.rid2]) + 1 +
-                pp_digits(r.pos2 + 1) + 2 + 2 + 4 + pp_digits(r.mapq) + 1 + pp_digits(r.mapq) + 1;
+  line_len[j] = rn + 1 + (name_off[r.rid1 + 1] - name_off[r.rid1]) + 1 + cm_digits10(r.pos1 + 1) + 1 + (name_off[r.rid2 + 1] - name_off[r.rid2]) + 1 +
+                cm_digits10(r.pos2 + 1) + 2 + 2 + 4 + cm_digits10(r.mapq) + 1 + cm_digits10(r.mapq) + 1;
 }
 __global__ __launch_bounds__(PP_BLOCK) void k_pp_pairs_format(const uint8_t *__restrict__ store, const uint32_t *__restrict__ idx, uint32_t n,
                                                                 const uint64_t *__restrict__ line_len, const uint64_t *__restrict__ line_off,
@@ -845,17 +770,17 @@ __global__ __launch_bounds__(PP_BLOCK) void k_pp_pairs_format(const uint8_t *__r
   *p++ = '\t';
   for (uint32_t i = name_off[r.rid1]; i < name_off[r.rid1 + 1]; ++i) *p++ = names[i];
   *p++ = '\t';
-  p = pp_put_u32(p, r.pos1 + 1);
+  p = cm_put_u32(p, r.pos1 + 1);
   *p++ = '\t';
   for (uint32_t i = name_off[r.rid2]; i < name_off[r.rid2 + 1]; ++i) *p++ = names[i];
   *p++ = '\t';
-  p = pp_put_u32(p, r.pos2 + 1);
+  p = cm_put_u32(p, r.pos2 + 1);
   *p++ = '\t'; *p++ = r.st1 ? '+' : '-';
   *p++ = '\t'; *p++ = r.st2 ? '+' : '-';
   *p++ = '\t'; *p++ = 'U'; *p++ = 'U'; *p++ = '\t';
-  p = pp_put_u32(p, r.mapq);
+  p = cm_put_u32(p, r.mapq);
   *p++ = '\t';
-  p = pp_put_u32(p, r.mapq);
+  p = cm_put_u32(p, r.mapq);
   *p++ = '\n';
 }
 
@@ -867,7 +792,7 @@ static int pp_format_pairs(cmgpu_ctx *c, const char *const *names, uint32_t n_se
   if (!cm_store_pairs_records(c)) { cm_set_error(c, "pairs text needs pairs records (split alignment, or output_format = CMGPU_FORMAT_PAIRS)"); return CMGPU_EINVAL; }
   // (cell barcodes: they decided which pairs were mapped -- CorrectBarcodeAt, chromap.h:896-906 -- and go no further: a PairsMapping's barcode is
   //  neither printed nor part of its order or equality, pairs_mapping.h:40-50, GetBarcode() == 0; the store's key array is left alone)
-  PPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   { const int qrc = cm_exchange_quiesce(c); if (qrc) return qrc; }
   hipStream_t s = c->stream;
   *n_lines = 0;
@@ -876,76 +801,42 @@ static int pp_format_pairs(cmgpu_ctx *c, const char *const *names, uint32_t n_se
   c->text_lines = 0;
   const uint32_t n = (uint32_t)c->store_n;
   if (n == 0) return CMGPU_OK;
-  std::vector<uint32_t> noff(n_sequences + 1, 0);
-  std::string blob;
-  for (uint32_t i = 0; i < n_sequences; ++i) { blob += names[i]; noff[i + 1] = (uint32_t)blob.size(); }
   const uint64_t rn_bytes = !resident && n_read_names ? read_name_offsets[n_read_names] : 0;
-  DevBuf d_names, d_noff, d_rn, d_rnoff, k0, k1, v0, v1, tmp, llen, loff;
-  auto fail = [&](int rc) { d_names.release(); d_noff.release(); d_rn.release(); d_rnoff.release(); k0.release(); k1.release(); v0.release();
-                            v1.release(); tmp.release(); llen.release(); loff.release(); return rc; };
-  if (d_names.ensure(blob.size() + 16) || d_noff.ensure(noff.size() * 4) || d_rn.ensure(rn_bytes + 16) ||
-      d_rnoff.ensure(resident ? 8 : ((size_t)n_read_names + 1) * 8) ||
-      k0.ensure((size_t)n * 8) || k1.ensure((size_t)n * 8) || v0.ensure((size_t)n * 4) || v1.ensure((size_t)n * 4) || llen.ensure(((size_t)n + 1) * 8) ||
-      loff.ensure(((size_t)n + 1) * 8)) { cm_set_error(c, "out of device memory (post-processing)"); return fail(CMGPU_ENOMEM); }
+  CmTextJob job;
+  CmTmpBuf d_rn, d_rnoff;  // (allocated before the job uploads anything)
+  if (d_rn.ensure(rn_bytes + 16) || d_rnoff.ensure(resident ? 8 : ((size_t)n_read_names + 1) * 8)) { cm_set_error(c, "out of device memory (post-processing)"); return CMGPU_ENOMEM; }
+  int rc;
+  if ((rc = job.begin(c, names, n_sequences, n, 1, true))) return rc;
   const uint64_t zero = 0;
-  if (hipMemcpyAsync(d_names.p, blob.data(), blob.size(), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(d_noff.p, noff.data(), noff.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
-      (rn_bytes && hipMemcpyAsync(d_rn.p, read_names, rn_bytes, hipMemcpyHostToDevice, s) != hipSuccess) ||
+  if ((rn_bytes && hipMemcpyAsync(d_rn.p, read_names, rn_bytes, hipMemcpyHostToDevice, s) != hipSuccess) ||
       hipMemcpyAsync(d_rnoff.p, !resident && n_read_names ? (const void *)read_name_offsets : (const void *)&zero,
                      resident ? 8 : ((size_t)n_read_names + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess) {
-    cm_set_error(c, "name upload failed"); return fail(CMGPU_EHIP);
+    cm_set_error(c, "name upload failed"); return CMGPU_EHIP;
   }
   // (no names at all: the one zero offset uploaded above stands for an empty table)
   const uint8_t *rn = resident && n_read_names ? (const uint8_t *)c->nm_blob.p : (const uint8_t *)d_rn.p;
   const uint64_t *rn_off = resident && n_read_names ? (const uint64_t *)c->nm_offs.p : (const uint64_t *)d_rnoff.p;
   const dim3 g((n + PP_BLOCK - 1) / PP_BLOCK), b(PP_BLOCK);
   const uint8_t *store = (const uint8_t *)c->store.p;
-  uint64_t *ka = (uint64_t *)k0.p, *kb = (uint64_t *)k1.p;
-  uint32_t *va = (uint32_t *)v0.p, *vb = (uint32_t *)v1.p;
-  unsigned rid_bits = 1;
-  while (rid_bits < 32 && (1ull << rid_bits) < (uint64_t)n_sequences + 1) ++rid_bits;
-  int rc;
+  const unsigned rid_bits = job.rid_bits;
   // least significant key first: (mapq, read_id), then (pos1, pos2), then (rid1, rid2) -- stable radix passes
-  hipLaunchKernelGGL(k_pp_pairs_key, g, b, 0, s, store, (const uint32_t *)nullptr, n, 0, rid_bits, ka, va);
-  if ((rc = pp_sort_pass(c, tmp, ka, kb, va, vb, n, 40))) return fail(rc);
-  std::swap(va, vb);
-  hipLaunchKernelGGL(k_pp_pairs_key, g, b, 0, s, store, (const uint32_t *)va, n, 1, rid_bits, ka, (uint32_t *)nullptr);
-  if ((rc = pp_sort_pass(c, tmp, ka, kb, va, vb, n, 64))) return fail(rc);
-  std::swap(va, vb);
-  hipLaunchKernelGGL(k_pp_pairs_key, g, b, 0, s, store, (const uint32_t *)va, n, 2, rid_bits, ka, (uint32_t *)nullptr);
-  if ((rc = pp_sort_pass(c, tmp, ka, kb, va, vb, n, 2 * rid_bits))) return fail(rc);
-  std::swap(va, vb);
+  hipLaunchKernelGGL(k_pp_pairs_key, g, b, 0, s, store, (const uint32_t *)nullptr, n, 0, rid_bits, job.keys(), job.idx());
+  if ((rc = job.sort_pass(40))) return rc;
+  hipLaunchKernelGGL(k_pp_pairs_key, g, b, 0, s, store, (const uint32_t *)job.idx(), n, 1, rid_bits, job.keys(), (uint32_t *)nullptr);
+  if ((rc = job.sort_pass(64))) return rc;
+  hipLaunchKernelGGL(k_pp_pairs_key, g, b, 0, s, store, (const uint32_t *)job.idx(), n, 2, rid_bits, job.keys(), (uint32_t *)nullptr);
+  if ((rc = job.sort_pass(2 * rid_bits))) return rc;
   CmSmDev sm;
-  if ((rc = cm_summary_dev(c, 0, 0, true, &sm))) return fail(rc);
-  hipLaunchKernelGGL(k_pp_pairs_len, g, b, 0, s, store, (const uint32_t *)va, n, p->mapq_threshold, n_sequences, (const uint32_t *)d_noff.p,
-                     rn_off, read_id_base, n_read_names, (uint64_t *)llen.p,
+  if ((rc = cm_summary_dev(c, 0, 0, true, &sm))) return rc;
+  hipLaunchKernelGGL(k_pp_pairs_len, g, b, 0, s, store, (const uint32_t *)job.idx(), n, p->mapq_threshold, n_sequences, job.seq_off(),
+                     rn_off, read_id_base, n_read_names, (uint64_t *)job.llen.p,
                      p->remove_pcr_duplicates ? (p->low_memory_mode ? 1 : 2) : 0, sm);
-  if (hipMemsetAsync((uint64_t *)llen.p + n, 0, 8, s) != hipSuccess) { cm_set_error(c, "memset failed"); return fail(CMGPU_EHIP); }
-  size_t tb = 0, tb2 = 0;
-  auto lines_in = rocprim::make_transform_iterator((const uint64_t *)llen.p, PpLinesOp());
-  (void)rocprim::exclusive_scan(nullptr, tb, (const uint64_t *)llen.p, (uint64_t *)loff.p, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s);
-  (void)rocprim::reduce(nullptr, tb2, lines_in, (uint64_t *)nullptr, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
-  DevBuf d_count;
-  if (tmp.ensure((tb > tb2 ? tb : tb2) + 256) || d_count.ensure(8)) { d_count.release(); cm_set_error(c, "out of device memory (scan)"); return fail(CMGPU_ENOMEM); }
-  hipError_t e = rocprim::exclusive_scan(tmp.p, tb, (const uint64_t *)llen.p, (uint64_t *)loff.p, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s);
-  if (e == hipSuccess) e = rocprim::reduce(tmp.p, tb2, lines_in, (uint64_t *)d_count.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
   uint64_t total = 0, lines = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(&total, (uint64_t *)loff.p + n, 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(&lines, d_count.p, 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = cm_stream_sync(s);
-  d_count.release();
-  if (e != hipSuccess) { cm_set_error(c, std::string("post-processing scan: ") + hipGetErrorString(e)); return fail(CMGPU_EHIP); }
-  if ((rc = cm_summary_check(c))) return fail(rc);
-  if (c->text.ensure(total + 64)) { cm_set_error(c, "out of device memory (text)"); return fail(CMGPU_ENOMEM); }
-  hipLaunchKernelGGL(k_pp_pairs_format, g, b, 0, s, store, (const uint32_t *)va, n, (const uint64_t *)llen.p, (const uint64_t *)loff.p,
-                     (const uint8_t *)d_names.p, (const uint32_t *)d_noff.p, rn, rn_off, read_id_base, (uint8_t *)c->text.p);
-  e = cm_stream_sync(s);
-  if (e != hipSuccess) { cm_set_error(c, std::string("text formatting: ") + hipGetErrorString(e)); return fail(CMGPU_EHIP); }
-  c->text_bytes = total;
-  c->text_lines = lines;
-  *n_lines = lines;
-  *n_bytes = total;
-  return fail(CMGPU_OK);
+  if ((rc = job.scan_lines(&total, &lines))) return rc;
+  if ((rc = job.alloc_text(total))) return rc;
+  hipLaunchKernelGGL(k_pp_pairs_format, g, b, 0, s, store, (const uint32_t *)job.idx(), n, (const uint64_t *)job.llen.p, (const uint64_t *)job.loff.p,
+                     (const uint8_t *)job.names.p, job.seq_off(), rn, rn_off, read_id_base, (uint8_t *)c->text.p);
+  return job.publish(total, lines, n_lines, n_bytes);
 }
 
 extern "C" int cmgpu_store_format_pairs(cmgpu_ctx *c, const char *const *names, uint32_t n_sequences, const cmgpu_params *p,
@@ -965,8 +856,8 @@ extern "C" int cmgpu_store_format_pairs_resident(cmgpu_ctx *c, const char *const
 extern "C" int cmgpu_store_text(cmgpu_ctx *c, char *out, uint64_t capacity) {
   if (!c || (!out && c->text_bytes)) return CMGPU_EINVAL;
   if (capacity < c->text_bytes) { cm_set_error(c, "text buffer too small"); return CMGPU_ECAPACITY; }
-  PPCHECK(c, cm_enter(c));
-  if (c->text_bytes) PPCHECK(c, hipMemcpy(out, c->text.p, c->text_bytes, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(c, cm_enter(c));
+  if (c->text_bytes) CM_HIPCHECK(c, hipMemcpy(out, c->text.p, c->text_bytes, hipMemcpyDeviceToHost));
   return CMGPU_OK;
 }
 
@@ -976,7 +867,7 @@ extern "C" int cmgpu_store_text(cmgpu_ctx *c, char *out, uint64_t capacity) {
 //  buffered writes to one file are serialised by the kernel -- tools/probes/write_probe.cpp, 1 / 4 / 16 threads 25 / 25 / 32 ms per 256 MB)
 extern "C" int cmgpu_store_write_text(cmgpu_ctx *c, const char *path, int append) {
   if (!c || !path) return CMGPU_EINVAL;
-  PPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   FILE *f = fopen(path, append ? "ab" : "wb");
   if (!f) { cm_set_error(c, std::string("cannot open ") + path); return CMGPU_EIO; }
   const size_t slab = 16u << 20;
@@ -1042,6 +933,19 @@ void cm_store_split_bc(cmgpu_ctx *c, const void *in32, uint64_t n, hipStream_t s
   if (!n) return;
   hipLaunchKernelGGL(k_pp_split_bc, dim3((unsigned)((n + PP_BLOCK - 1) / PP_BLOCK)), dim3(PP_BLOCK), 0, s, (const uint8_t *)in32, (uint32_t)n,
                      (uint8_t *)c->store.p + c->store_n * 24, (uint64_t *)c->store_bc.p + c->store_n);
+}
+
+int cm_compact_records(cmgpu_ctx *c, void *dst, uint64_t *bc_dst, uint64_t cap, hipStream_t s, const uint32_t **n_valid_dev) {
+  const uint32_t n = (uint32_t)cm_rec_slots(c);
+  { const int rc = cm_ensure_slot_scratch(c, n); if (rc) return rc; }
+  uint32_t *flag = (uint32_t *)c->scratch_a.p, *pos = (uint32_t *)c->scratch_b.p;  // free between batches
+  const dim3 g((n + PP_BLOCK - 1) / PP_BLOCK), b(PP_BLOCK);
+  hipLaunchKernelGGL(k_pp_flag, g, b, 0, s, (const uint8_t *)c->rec_ok.p, flag, n);
+  cm_scan_u32(flag, pos, n, (uint32_t *)c->scan_tmp.p, s);
+  hipLaunchKernelGGL(k_pp_compact, g, b, 0, s, (const uint8_t *)c->rec.p, (const uint8_t *)c->rec_ok.p, (const uint32_t *)pos,
+                     (const uint64_t *)c->bc_key.p, (uint8_t *)dst, bc_dst, n, cm_rec_per_pair(c), cap);
+  if (n_valid_dev) *n_valid_dev = pos + n;
+  return CMGPU_OK;
 }
 
 // the device code of this translation unit is loaded by the HIP runtime at the first launch of one of its kernels (milliseconds to tens of

@@ -22,16 +22,9 @@
 #include "cm_ctx.h"
 #include "cm_kernels.h"
 #include "cm_summary.h"
+#include "cm_text_job.h"
 
 #define SP_BLOCK 256
-#define SPCHECK(ctx, call)                                                                   \
-  do {                                                                                       \
-    hipError_t e_ = (call);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      cm_set_error(ctx, std::string(#call) + ": " + hipGetErrorString(e_));                  \
-      return CMGPU_EHIP;                                                                     \
-    }                                                                                        \
-  } while (0)
 
 struct SpRec {  // cmgpu_sam_record (40 bytes, include/chromap_amd.h), read with five 8-byte loads
   uint32_t read_id, rid, pos, mpos, nm;
@@ -48,14 +41,6 @@ __device__ __forceinline__ SpRec sp_load(const uint8_t *rec, uint64_t i) {
   r.md_len = (uint32_t)e & 0xffffu; r.mapq = (uint32_t)(e >> 16) & 0xffu; r.strand = (uint32_t)(e >> 24) & 0xffu;
   r.valid = (uint32_t)(e >> 40) & 0xffu; r.trim_len = (uint32_t)(e >> 48);
   return r;
-}
-__device__ __forceinline__ uint32_t sp_digits(uint32_t v) {
-  return v < 10 ? 1 : v < 100 ? 2 : v < 1000 ? 3 : v < 10000 ? 4 : v < 100000 ? 5 : v < 1000000 ? 6 : v < 10000000 ? 7 : v < 100000000 ? 8 : v < 1000000000 ? 9 : 10;
-}
-__device__ __forceinline__ uint8_t *sp_put_u32(uint8_t *p, uint32_t v) {
-  const uint32_t d = sp_digits(v);
-  for (uint32_t i = d; i-- > 0;) { p[i] = (uint8_t)('0' + v % 10); v /= 10; }
-  return p + d;
 }
 __device__ __forceinline__ uint32_t sp_var_bytes(uint32_t n_cigar, uint32_t md_len) { return 4u * n_cigar + ((md_len + 3u) & ~3u); }
 
@@ -120,7 +105,7 @@ extern "C" int cmgpu_sam_store_info(const cmgpu_ctx *c, uint64_t *n_records, uin
 extern "C" int cmgpu_sam_store_append_resident(cmgpu_ctx *c, uint64_t *n_total) {
   if (!c) return CMGPU_EINVAL;
   if (!c->p.sam) { cm_set_error(c, "the ctx was not created with output_format = CMGPU_FORMAT_SAM"); return CMGPU_EINVAL; }
-  SPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   CmSamStore &st = c->ss;
   const uint64_t slots = c->n_pairs ? c->sam_slots : 0;
   if (st.n && slots && (st.has_bc != c->has_barcodes || st.paired != !c->single)) {
@@ -140,10 +125,8 @@ extern "C" int cmgpu_sam_store_append_resident(cmgpu_ctx *c, uint64_t *n_total) 
     if (e != hipSuccess) { cm_set_error(c, std::string("SAM record store: ") + hipGetErrorString(e)); return CMGPU_EHIP; }
     hipLaunchKernelGGL(k_sp_flag, g, b, 0, s, (const uint8_t *)c->sam_rec.p, n, flag, (uint64_t *)vlen.p, (uint32_t *)ovf.p);
     cm_scan_u32(flag, pos, n, (uint32_t *)c->scan_tmp.p, s);
-    size_t tb = 0;
-    (void)rocprim::exclusive_scan(nullptr, tb, (const uint64_t *)vlen.p, (uint64_t *)voff.p, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s);
-    if (tmp.ensure(tb + 256)) { cm_set_error(c, "out of device memory (SAM record store: scan)"); return CMGPU_ENOMEM; }
-    e = rocprim::exclusive_scan(tmp.p, tb, (const uint64_t *)vlen.p, (uint64_t *)voff.p, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s);
+    rc = cm_scan_u64(c, (const uint64_t *)vlen.p, (uint64_t *)voff.p, (size_t)n + 1, tmp, s, "SAM record store: scan");
+    if (rc) return rc;
     uint32_t k = 0, over = 0;
     uint64_t vbytes = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&k, pos + n, 4, hipMemcpyDeviceToHost, s);
@@ -219,7 +202,7 @@ __device__ __forceinline__ uint32_t sp_seq_len(const SpRec &r, const uint32_t *_
   for (uint32_t t = 0; t < r.n_cigar; ++t) {
     const uint32_t w = cg[t], op = w & 0xfu;
     if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) ql += w >> 4;
-    ct += sp_digits(w >> 4) + 1u;
+    ct += cm_digits10(w >> 4) + 1u;
   }
   *cig_text = r.n_cigar ? ct : 1u;
   return ql < r.trim_len ? ql : r.trim_len;
@@ -281,9 +264,9 @@ __global__ __launch_bounds__(SP_BLOCK) void k_sp_len(const uint8_t *__restrict__
   const uint32_t sl = sp_seq_len(r, reinterpret_cast<const uint32_t *>(var + var_offs[i]), &cig_text);
   const uint32_t nm_len = (uint32_t)(rs.name_offs[mate][q + 1] - rs.name_offs[mate][q]);
   const uint32_t rnext = r.mrid < 0 || (uint32_t)r.mrid == r.rid ? 1u : name_off[r.mrid + 1] - name_off[r.mrid];
-  const uint32_t tl = r.tlen < 0 ? 1u + sp_digits((uint32_t)(-(int64_t)r.tlen)) : sp_digits((uint32_t)r.tlen);
-  line_len[j] = (uint64_t)nm_len + 1 + sp_digits(r.flag) + 1 + (name_off[r.rid + 1] - name_off[r.rid]) + 1 + sp_digits(r.pos + 1) + 1 + sp_digits(r.mapq) + 1 +
-                cig_text + 1 + rnext + 1 + sp_digits(r.mrid < 0 ? 0u : r.mpos + 1) + 1 + tl + 1 + sl + 1 + sl + 6 + sp_digits(r.nm) + 6 + r.md_len +
+  const uint32_t tl = r.tlen < 0 ? 1u + cm_digits10((uint32_t)(-(int64_t)r.tlen)) : cm_digits10((uint32_t)r.tlen);
+  line_len[j] = (uint64_t)nm_len + 1 + cm_digits10(r.flag) + 1 + (name_off[r.rid + 1] - name_off[r.rid]) + 1 + cm_digits10(r.pos + 1) + 1 + cm_digits10(r.mapq) + 1 +
+                cig_text + 1 + rnext + 1 + cm_digits10(r.mrid < 0 ? 0u : r.mpos + 1) + 1 + tl + 1 + sl + 1 + sl + 6 + cm_digits10(r.nm) + 6 + r.md_len +
                 (cfg.bc_len ? 6 + cfg.bc_len : 0) + 1;
 }
 
@@ -343,47 +326,47 @@ __global__ __launch_bounds__(SP_BLOCK) void k_sp_format(const uint8_t *__restric
   const bool other = r.mrid >= 0 && (uint32_t)r.mrid != r.rid;
   const uint32_t mn0 = other ? name_off[r.mrid] : 0u, mn1 = other ? name_off[r.mrid + 1] : 1u;
   const uint32_t pnext = r.mrid < 0 ? 0u : r.mpos + 1u;
-  const uint32_t tl = r.tlen < 0 ? 1u + sp_digits((uint32_t)(-(int64_t)r.tlen)) : sp_digits((uint32_t)r.tlen);
+  const uint32_t tl = r.tlen < 0 ? 1u + cm_digits10((uint32_t)(-(int64_t)r.tlen)) : cm_digits10((uint32_t)r.tlen);
   uint8_t *line = text + line_off[j];
   uint8_t *mid = line + nm_len;  // '\t' FLAG ... TLEN '\t'
-  const uint32_t mid_len = 1 + sp_digits(r.flag) + 1 + (rn1 - rn0) + 1 + sp_digits(r.pos + 1) + 1 + sp_digits(r.mapq) + 1 + cig_text + 1 + (mn1 - mn0) + 1 +
-                           sp_digits(pnext) + 1 + tl + 1;
+  const uint32_t mid_len = 1 + cm_digits10(r.flag) + 1 + (rn1 - rn0) + 1 + cm_digits10(r.pos + 1) + 1 + cm_digits10(r.mapq) + 1 + cig_text + 1 + (mn1 - mn0) + 1 +
+                           cm_digits10(pnext) + 1 + tl + 1;
   uint8_t *seq = mid + mid_len, *qual = seq + sl + 1, *tail = qual + sl;
   sp_copy<0, G>(line, rs.names[mate] + no, nm_len, lane);
   // the printed bases are the first sl of the L mapped ones as they stand in the SAM line: on the - strand the line starts at the read's base L - 1
   const uint8_t *bs = rs.bases[mate] + ro, *qs = rs.quals[mate] + ro;
   if (r.strand) { sp_copy<0, G>(seq, bs, sl, lane); sp_copy<0, G>(qual, qs, sl, lane); }
   else { sp_copy<2, G>(seq, bs + (L - sl), sl, lane); sp_copy<1, G>(qual, qs + (L - sl), sl, lane); }
-  sp_copy<0, G>(tail + 6 + sp_digits(r.nm) + 6, md, r.md_len, lane);
-  uint8_t *rname_at = mid + 1 + sp_digits(r.flag) + 1;
+  sp_copy<0, G>(tail + 6 + cm_digits10(r.nm) + 6, md, r.md_len, lane);
+  uint8_t *rname_at = mid + 1 + cm_digits10(r.flag) + 1;
   sp_copy<0, G>(rname_at, names + rn0, rn1 - rn0, lane);
-  if (other) sp_copy<0, G>(rname_at + (rn1 - rn0) + 1 + sp_digits(r.pos + 1) + 1 + sp_digits(r.mapq) + 1 + cig_text + 1, names + mn0, mn1 - mn0, lane);
+  if (other) sp_copy<0, G>(rname_at + (rn1 - rn0) + 1 + cm_digits10(r.pos + 1) + 1 + cm_digits10(r.mapq) + 1 + cig_text + 1, names + mn0, mn1 - mn0, lane);
   if (lane == 0) {
     uint8_t *p = mid;
     *p++ = '\t';
-    p = sp_put_u32(p, r.flag);
+    p = cm_put_u32(p, r.flag);
     *p++ = '\t';
     p += rn1 - rn0;  // (RNAME: the group's copy above)
     *p++ = '\t';
-    p = sp_put_u32(p, r.pos + 1);
+    p = cm_put_u32(p, r.pos + 1);
     *p++ = '\t';
-    p = sp_put_u32(p, r.mapq);
+    p = cm_put_u32(p, r.mapq);
     *p++ = '\t';
     if (r.n_cigar == 0) *p++ = '*';
-    for (uint32_t t = 0; t < r.n_cigar; ++t) { p = sp_put_u32(p, cg[t] >> 4); *p++ = "MIDNSHP=XB??????"[cg[t] & 0xfu]; }
+    for (uint32_t t = 0; t < r.n_cigar; ++t) { p = cm_put_u32(p, cg[t] >> 4); *p++ = "MIDNSHP=XB??????"[cg[t] & 0xfu]; }
     *p++ = '\t';
     if (r.mrid < 0) *p++ = '*';
     else if (!other) *p++ = '=';
     else p += mn1 - mn0;  // (RNEXT by name: the group's copy above)
     *p++ = '\t';
-    p = sp_put_u32(p, pnext);
+    p = cm_put_u32(p, pnext);
     *p++ = '\t';
-    if (r.tlen < 0) { *p++ = '-'; p = sp_put_u32(p, (uint32_t)(-(int64_t)r.tlen)); } else p = sp_put_u32(p, (uint32_t)r.tlen);
+    if (r.tlen < 0) { *p++ = '-'; p = cm_put_u32(p, (uint32_t)(-(int64_t)r.tlen)); } else p = cm_put_u32(p, (uint32_t)r.tlen);
     *p++ = '\t';
     seq[sl] = '\t';
     p = tail;
     *p++ = '\t'; *p++ = 'N'; *p++ = 'M'; *p++ = ':'; *p++ = 'i'; *p++ = ':';
-    p = sp_put_u32(p, r.nm);
+    p = cm_put_u32(p, r.nm);
     *p++ = '\t'; *p++ = 'M'; *p++ = 'D'; *p++ = ':'; *p++ = 'Z'; *p++ = ':';
     p += r.md_len;
     if (cfg.bc_len) {
@@ -395,22 +378,11 @@ __global__ __launch_bounds__(SP_BLOCK) void k_sp_format(const uint8_t *__restric
   }
 }
 
-static int sp_sort_pass(cmgpu_ctx *c, DevBuf &tmp, uint64_t *kin, uint64_t *kout, uint32_t *vin, uint32_t *vout, size_t n, unsigned bits) {
-  size_t tb = 0;
-  SPCHECK(c, rocprim::radix_sort_pairs(nullptr, tb, kin, kout, vin, vout, n, 0, bits, c->stream));
-  if (tmp.ensure(tb + 256)) { cm_set_error(c, "out of device memory (sort)"); return CMGPU_ENOMEM; }
-  SPCHECK(c, rocprim::radix_sort_pairs(tmp.p, tb, kin, kout, vin, vout, n, 0, bits, c->stream));
-  return CMGPU_OK;
-}
-struct SpLinesOp {
-  __host__ __device__ uint64_t operator()(uint64_t l) const { return l ? 1 : 0; }
-};
-
 extern "C" int cmgpu_store_format_sam(cmgpu_ctx *c, const char *const *ref_names, const uint32_t *ref_lengths, uint32_t n_sequences, const cmgpu_params *p,
                                       uint32_t barcode_length, uint64_t *n_lines, uint64_t *n_bytes) {
   (void)ref_lengths;  // (the @SQ lines are the caller's: cmgpu_write_sam_header)
   if (!c || !ref_names || !p || !n_lines || !n_bytes) return CMGPU_EINVAL;
-  SPCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   CmSamStore &st = c->ss;
   if (st.has_bc && (barcode_length == 0 || barcode_length > 32)) { cm_set_error(c, "the SAM record store holds barcodes: barcode_length must be 1..32"); return CMGPU_EINVAL; }
   hipStream_t s = c->stream;
@@ -421,34 +393,20 @@ extern "C" int cmgpu_store_format_sam(cmgpu_ctx *c, const char *const *ref_names
   const uint32_t n = (uint32_t)st.n;
   if (n == 0) return CMGPU_OK;
   if (c->rd_n == 0 || (st.paired && !c->rd_paired)) { cm_set_error(c, "the read store is empty: SAM text needs the reads of the run (cmgpu_fastq_keep_reads)"); return CMGPU_EINVAL; }
-  std::vector<uint32_t> noff(n_sequences + 1, 0);
-  std::string blob;
-  for (uint32_t i = 0; i < n_sequences; ++i) { blob += ref_names[i]; noff[i + 1] = (uint32_t)blob.size(); }
-  DevBuf d_names, d_noff, k0, k1, v0, v1, tmp, llen, loff, d_count;
-  auto fail = [&](int rc) { for (DevBuf *b : {&d_names, &d_noff, &k0, &k1, &v0, &v1, &tmp, &llen, &loff, &d_count}) b->release(); return rc; };
-  if (d_names.ensure(blob.size() + 16) || d_noff.ensure(noff.size() * 4) || k0.ensure((size_t)n * 8) || k1.ensure((size_t)n * 8) || v0.ensure((size_t)n * 4) ||
-      v1.ensure((size_t)n * 4) || llen.ensure(((size_t)n + 1) * 8) || loff.ensure(((size_t)n + 1) * 8) || d_count.ensure(16)) {
-    cm_set_error(c, "out of device memory (post-processing)"); return fail(CMGPU_ENOMEM);
-  }
-  if (hipMemcpyAsync(d_names.p, blob.data(), blob.size(), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(d_noff.p, noff.data(), noff.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess) { cm_set_error(c, "name upload failed"); return fail(CMGPU_EHIP); }
+  CmTextJob job;
+  int rc;
+  if ((rc = job.begin(c, ref_names, n_sequences, n, 2, true))) return rc;
   const dim3 g((n + SP_BLOCK - 1) / SP_BLOCK), b(SP_BLOCK);
   const uint8_t *rec = (const uint8_t *)st.rec.p;
   const uint64_t *bc = st.has_bc ? (const uint64_t *)st.bc.p : (const uint64_t *)nullptr;
-  uint64_t *ka = (uint64_t *)k0.p, *kb = (uint64_t *)k1.p;
-  uint32_t *va = (uint32_t *)v0.p, *vb = (uint32_t *)v1.p;
-  unsigned rid_bits = 1;
-  while (rid_bits < 32 && (1ull << rid_bits) < (uint64_t)n_sequences + 2) ++rid_bits;
   // least significant key first, stable passes: (mapq, read_id), (mpos, flag & 64), mrid, barcode, (rid, pos)
-  const unsigned bits[5] = {40, 33, rid_bits, st.has_bc ? 2 * barcode_length : 0, 32 + rid_bits};
+  const unsigned bits[5] = {40, 33, job.rid_bits, st.has_bc ? 2 * barcode_length : 0, 32 + job.rid_bits};
   bool have_idx = false;
   for (int which = 0; which < 5; ++which) {
     if (bits[which] == 0) continue;
-    hipLaunchKernelGGL(k_sp_key, g, b, 0, s, rec, bc, have_idx ? (const uint32_t *)va : (const uint32_t *)nullptr, n, which, n_sequences, ka,
-                       have_idx ? (uint32_t *)nullptr : va);
-    const int rc = sp_sort_pass(c, tmp, ka, kb, va, vb, n, bits[which]);
-    if (rc) return fail(rc);
-    std::swap(va, vb);
+    hipLaunchKernelGGL(k_sp_key, g, b, 0, s, rec, bc, have_idx ? (const uint32_t *)job.idx() : (const uint32_t *)nullptr, n, which, n_sequences, job.keys(),
+                       have_idx ? (uint32_t *)nullptr : job.idx());
+    if ((rc = job.sort_pass(bits[which]))) return rc;
     have_idx = true;
   }
   SpCfg cfg;
@@ -460,48 +418,30 @@ extern "C" int cmgpu_store_format_sam(cmgpu_ctx *c, const char *const *ref_names
     rs.names[m] = (const uint8_t *)r.names.p; rs.bases[m] = (const uint8_t *)r.bases.p; rs.quals[m] = (const uint8_t *)r.quals.p;
     rs.name_offs[m] = (const uint64_t *)r.name_offs.p; rs.offs[m] = (const uint64_t *)r.offs.p;
   }
-  if (hipMemsetAsync(d_count.p, 0, 16, s) != hipSuccess) { cm_set_error(c, "memset failed"); return fail(CMGPU_EHIP); }
+  // the job's second count word: records that belong to no read of the read store (k_sp_len)
+  if ((rc = job.zero_counts())) return rc;
   CmSmDev sm;  // --summary: the length kernel credits every run to its barcode (the keys are in the table since their reads were counted)
-  { const int rc = cm_summary_dev(c, 0, 0, !st.has_bc, &sm); if (rc) return fail(rc); }
-  hipLaunchKernelGGL(k_sp_len, g, b, 0, s, rec, bc, (const uint8_t *)st.var.p, (const uint64_t *)st.var_offs.p, (const uint32_t *)va, n, cfg, rs,
-                     (const uint32_t *)d_noff.p, (uint64_t *)llen.p, (unsigned long long *)d_count.p + 1, sm);
-  if (hipMemsetAsync((uint64_t *)llen.p + n, 0, 8, s) != hipSuccess) { cm_set_error(c, "memset failed"); return fail(CMGPU_EHIP); }
-  size_t tb = 0, tb2 = 0;
-  auto lines_in = rocprim::make_transform_iterator((const uint64_t *)llen.p, SpLinesOp());
-  (void)rocprim::exclusive_scan(nullptr, tb, (const uint64_t *)llen.p, (uint64_t *)loff.p, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s);
-  (void)rocprim::reduce(nullptr, tb2, lines_in, (uint64_t *)nullptr, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
-  if (tmp.ensure((tb > tb2 ? tb : tb2) + 256)) { cm_set_error(c, "out of device memory (scan)"); return fail(CMGPU_ENOMEM); }
-  hipError_t e = rocprim::exclusive_scan(tmp.p, tb, (const uint64_t *)llen.p, (uint64_t *)loff.p, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s);
-  if (e == hipSuccess) e = rocprim::reduce(tmp.p, tb2, lines_in, (uint64_t *)d_count.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
+  if ((rc = cm_summary_dev(c, 0, 0, !st.has_bc, &sm))) return rc;
+  hipLaunchKernelGGL(k_sp_len, g, b, 0, s, rec, bc, (const uint8_t *)st.var.p, (const uint64_t *)st.var_offs.p, (const uint32_t *)job.idx(), n, cfg, rs,
+                     job.seq_off(), (uint64_t *)job.llen.p, job.extra_word(), sm);
   uint64_t total = 0, lines = 0, foreign = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(&total, (uint64_t *)loff.p + n, 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(&lines, d_count.p, 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(&foreign, (uint64_t *)d_count.p + 1, 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = cm_stream_sync(s);
-  if (e != hipSuccess) { cm_set_error(c, std::string("post-processing scan: ") + hipGetErrorString(e)); return fail(CMGPU_EHIP); }
-  { const int rc = cm_summary_check(c); if (rc) return fail(rc); }
+  if ((rc = job.scan_lines(&total, &lines, &foreign))) return rc;
   if (foreign) {
     cm_set_error(c, std::to_string((unsigned long long)foreign) + " SAM records belong to no read of the read store (reads " + std::to_string(c->rd_base) + " .. " +
                         std::to_string((unsigned long long)c->rd_base + c->rd_n) + ") or to a mate sequence the reference does not have: the record store and the read store are not of one run");
-    return fail(CMGPU_EINVAL);
+    return CMGPU_EINVAL;
   }
   // (the sort's buffers go before the text comes: a realistic run's text is several GB)
-  k0.release(); k1.release(); vb == (uint32_t *)v0.p ? v0.release() : v1.release(); tmp.release();
-  if (c->text.ensure(total + 64)) { cm_set_error(c, "out of device memory (SAM text: " + std::to_string((unsigned long long)total) + " bytes)"); return fail(CMGPU_ENOMEM); }
+  job.release_sort();
+  if ((rc = job.alloc_text(total, "SAM text: " + std::to_string((unsigned long long)total) + " bytes"))) return rc;
   const int G = c->opt.sam_group;
   const dim3 gf((unsigned)(((uint64_t)n * G + SP_BLOCK - 1) / SP_BLOCK));
 #define SP_LAUNCH(W)                                                                                                                             \
-  hipLaunchKernelGGL(k_sp_format<W>, gf, b, 0, s, rec, bc, (const uint8_t *)st.var.p, (const uint64_t *)st.var_offs.p, (const uint32_t *)va, n, cfg, rs, \
-                     (const uint8_t *)d_names.p, (const uint32_t *)d_noff.p, (const uint64_t *)llen.p, (const uint64_t *)loff.p, (uint8_t *)c->text.p)
+  hipLaunchKernelGGL(k_sp_format<W>, gf, b, 0, s, rec, bc, (const uint8_t *)st.var.p, (const uint64_t *)st.var_offs.p, (const uint32_t *)job.idx(), n, cfg, rs, \
+                     (const uint8_t *)job.names.p, job.seq_off(), (const uint64_t *)job.llen.p, (const uint64_t *)job.loff.p, (uint8_t *)c->text.p)
   if (G == 16) SP_LAUNCH(16); else if (G == 64) SP_LAUNCH(64); else SP_LAUNCH(8);
 #undef SP_LAUNCH
-  e = cm_stream_sync(s);
-  if (e != hipSuccess) { cm_set_error(c, std::string("text formatting: ") + hipGetErrorString(e)); return fail(CMGPU_EHIP); }
-  c->text_bytes = total;
-  c->text_lines = lines;
-  *n_lines = lines;
-  *n_bytes = total;
-  return fail(CMGPU_OK);
+  return job.publish(total, lines, n_lines, n_bytes);
 }
 
 // the @SQ lines (mapping_writer.cc:312-322: OutputHeader of MappingWriter<SAMMapping>); the text follows with cmgpu_store_write_text(path, append = 1)

@@ -12,15 +12,6 @@
 #include "cm_summary.h"
 
 #define SM_BLOCK 256
-#define SMCHECK(ctx, call)                                                                   \
-  do {                                                                                       \
-    hipError_t e_ = (call);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      cm_set_error(ctx, std::string(#call) + ": " + hipGetErrorString(e_));                  \
-      return CMGPU_EHIP;                                                                     \
-    }                                                                                        \
-  } while (0)
-
 // TOTAL: one read (pair) per thread, counted under its corrected barcode key, under the non-whitelist row when CorrectBarcodeAt failed
 // and such reads are not mapped (chromap.h:396-401, 1139-1142), under key 0 when the batch has no barcodes.  Equal keys are combined
 // before the table is touched: inside a wave by comparing against the lowest uncounted lane's key (one step per distinct key), and
@@ -114,10 +105,10 @@ static int sm_alloc(cmgpu_ctx *c, CmSummary &sm, uint32_t cap) {
     return CMGPU_ENOMEM;
   }
   hipStream_t s = c->stream;
-  SMCHECK(c, hipMemsetAsync(sm.keys.p, 0xff, (size_t)cap * 8, s));
-  SMCHECK(c, hipMemsetAsync(sm.first.p, 0xff, (size_t)cap * 8, s));
-  SMCHECK(c, hipMemsetAsync(sm.cnt.p, 0, (size_t)cap * 16, s));
-  SMCHECK(c, hipMemsetAsync(sm.meta.p, 0, CM_SM_META_WORDS * 4, s));
+  CM_HIPCHECK(c, hipMemsetAsync(sm.keys.p, 0xff, (size_t)cap * 8, s));
+  CM_HIPCHECK(c, hipMemsetAsync(sm.first.p, 0xff, (size_t)cap * 8, s));
+  CM_HIPCHECK(c, hipMemsetAsync(sm.cnt.p, 0, (size_t)cap * 16, s));
+  CM_HIPCHECK(c, hipMemsetAsync(sm.meta.p, 0, CM_SM_META_WORDS * 4, s));
   sm.cap = cap;
   sm.key_bound = 0;
   sm.slot0 = ~0u;
@@ -145,8 +136,8 @@ int cm_summary_dev(cmgpu_ctx *c, uint64_t new_keys, uint64_t total_bound, bool k
   } else {
     if (2 * (sm.key_bound + new_keys + 1) > sm.cap) {
       uint32_t k = 0;
-      SMCHECK(c, hipMemcpyAsync(&k, (uint32_t *)sm.meta.p + CM_SM_META_N, 4, hipMemcpyDeviceToHost, s));
-      SMCHECK(c, cm_stream_sync(s));
+      CM_HIPCHECK(c, hipMemcpyAsync(&k, (uint32_t *)sm.meta.p + CM_SM_META_N, 4, hipMemcpyDeviceToHost, s));
+      CM_HIPCHECK(c, cm_stream_sync(s));
       sm.key_bound = k;
     }
     want = sm.key_bound + new_keys + 1;
@@ -164,8 +155,8 @@ int cm_summary_dev(cmgpu_ctx *c, uint64_t new_keys, uint64_t total_bound, bool k
     sm_view(sm, &t);
     hipLaunchKernelGGL(k_sm_rehash, dim3((old.cap + SM_BLOCK - 1) / SM_BLOCK), dim3(SM_BLOCK), 0, s, o, t);
     // (the non-whitelist counter and the flag move as they are; the number of keys was counted again by the insertions)
-    SMCHECK(c, hipMemcpyAsync((uint32_t *)sm.meta.p + 1, (uint32_t *)old.meta.p + 1, 2 * 4, hipMemcpyDeviceToDevice, s));
-    SMCHECK(c, cm_stream_sync(s));
+    CM_HIPCHECK(c, hipMemcpyAsync((uint32_t *)sm.meta.p + 1, (uint32_t *)old.meta.p + 1, 2 * 4, hipMemcpyDeviceToDevice, s));
+    CM_HIPCHECK(c, cm_stream_sync(s));
     old.keys.release(); old.first.release(); old.cnt.release(); old.meta.release();
     sm.key_bound = old.key_bound;  // (sm_alloc started the new table's bound at 0; the slot of key 0 is another one now)
   }
@@ -174,8 +165,8 @@ int cm_summary_dev(cmgpu_ctx *c, uint64_t new_keys, uint64_t total_bound, bool k
   if (key0) {
     if (sm.slot0 == ~0u) {
       hipLaunchKernelGGL(k_sm_key0, dim3(1), dim3(1), 0, s, *out);
-      SMCHECK(c, hipMemcpyAsync(&sm.slot0, (uint32_t *)sm.meta.p + CM_SM_META_SLOT0, 4, hipMemcpyDeviceToHost, s));
-      SMCHECK(c, cm_stream_sync(s));
+      CM_HIPCHECK(c, hipMemcpyAsync(&sm.slot0, (uint32_t *)sm.meta.p + CM_SM_META_SLOT0, 4, hipMemcpyDeviceToHost, s));
+      CM_HIPCHECK(c, cm_stream_sync(s));
     }
     out->slot0 = sm.slot0;
   }
@@ -185,8 +176,8 @@ int cm_summary_dev(cmgpu_ctx *c, uint64_t new_keys, uint64_t total_bound, bool k
 int cm_summary_check(cmgpu_ctx *c) {
   if (!c->sm.on) return CMGPU_OK;
   uint32_t full = 0;  // (on the context's stream: a copy on the null stream would wait for the ingest's streams too)
-  SMCHECK(c, hipMemcpyAsync(&full, (uint32_t *)c->sm.meta.p + CM_SM_META_FULL, 4, hipMemcpyDeviceToHost, c->stream));
-  SMCHECK(c, cm_stream_sync(c->stream));
+  CM_HIPCHECK(c, hipMemcpyAsync(&full, (uint32_t *)c->sm.meta.p + CM_SM_META_FULL, 4, hipMemcpyDeviceToHost, c->stream));
+  CM_HIPCHECK(c, cm_stream_sync(c->stream));
   if (full) { cm_set_error(c, "summary: the barcode table ran out of slots; its counts are incomplete"); return CMGPU_ECAPACITY; }
   return CMGPU_OK;
 }
@@ -206,13 +197,13 @@ int cm_summary_total(cmgpu_ctx *c) {
                      c->has_barcodes ? (const uint8_t *)c->bc_ok.p : (const uint8_t *)nullptr, n, (uint64_t)c->first_read_id, c->p.bc_keep);
   // (waited for, because the ingest's streams may refill the barcode keys once the call returns.  The flag of a full table is looked at
   //  where the table is read -- cmgpu_summary_download and the format calls: the table is grown before it can fill)
-  SMCHECK(c, cm_stream_sync(c->stream));
+  CM_HIPCHECK(c, cm_stream_sync(c->stream));
   return CMGPU_OK;
 }
 
 extern "C" int cmgpu_summary_enable(cmgpu_ctx *c, int on) {
   if (!c) return CMGPU_EINVAL;
-  SMCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   CmSummary &sm = c->sm;
   if (!on) { sm.on = false; return CMGPU_OK; }
   if (sm.on) return CMGPU_OK;
@@ -220,7 +211,7 @@ extern "C" int cmgpu_summary_enable(cmgpu_ctx *c, int on) {
   const uint32_t cap = sm_pow2(2 * ((uint64_t)c->wl_size + 1));
   const int rc = sm_alloc(c, sm, cap);
   if (rc) return rc;
-  SMCHECK(c, cm_stream_sync(c->stream));
+  CM_HIPCHECK(c, cm_stream_sync(c->stream));
   sm.on = true;
   return CMGPU_OK;
 }
@@ -228,10 +219,10 @@ extern "C" int cmgpu_summary_enable(cmgpu_ctx *c, int on) {
 extern "C" int cmgpu_summary_clear(cmgpu_ctx *c) {
   if (!c) return CMGPU_EINVAL;
   if (!c->sm.on) return CMGPU_OK;
-  SMCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   const int rc = sm_alloc(c, c->sm, c->sm.cap);
   if (rc) return rc;
-  SMCHECK(c, cm_stream_sync(c->stream));
+  CM_HIPCHECK(c, cm_stream_sync(c->stream));
   return CMGPU_OK;
 }
 
@@ -240,10 +231,10 @@ extern "C" int cmgpu_summary_info(cmgpu_ctx *c, uint64_t *n_keys, uint64_t *n_sl
   if (n_keys) *n_keys = 0;
   if (n_slots) *n_slots = 0;
   if (!c->sm.on) return CMGPU_OK;
-  SMCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   uint32_t k = 0;
-  SMCHECK(c, hipMemcpyAsync(&k, (uint32_t *)c->sm.meta.p + CM_SM_META_N, 4, hipMemcpyDeviceToHost, c->stream));
-  SMCHECK(c, cm_stream_sync(c->stream));
+  CM_HIPCHECK(c, hipMemcpyAsync(&k, (uint32_t *)c->sm.meta.p + CM_SM_META_N, 4, hipMemcpyDeviceToHost, c->stream));
+  CM_HIPCHECK(c, cm_stream_sync(c->stream));
   if (n_keys) *n_keys = k;
   if (n_slots) *n_slots = c->sm.cap;
   return CMGPU_OK;
@@ -254,11 +245,11 @@ extern "C" int cmgpu_summary_download(cmgpu_ctx *c, cmgpu_summary_entry *out, ui
   *n_out = 0;
   if (nonwhitelist_total) *nonwhitelist_total = 0;
   if (!c->sm.on) { cm_set_error(c, "the context has no summary (cmgpu_summary_enable)"); return CMGPU_EINVAL; }
-  SMCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   { const int rc = cm_summary_check(c); if (rc) return rc; }
   uint32_t meta[CM_SM_META_WORDS];
-  SMCHECK(c, hipMemcpyAsync(meta, c->sm.meta.p, sizeof(meta), hipMemcpyDeviceToHost, c->stream));
-  SMCHECK(c, cm_stream_sync(c->stream));
+  CM_HIPCHECK(c, hipMemcpyAsync(meta, c->sm.meta.p, sizeof(meta), hipMemcpyDeviceToHost, c->stream));
+  CM_HIPCHECK(c, cm_stream_sync(c->stream));
   const uint32_t k = meta[CM_SM_META_N];
   if (nonwhitelist_total) *nonwhitelist_total = meta[CM_SM_META_NONWL];
   if (k > capacity) { *n_out = k; cm_set_error(c, "summary buffer too small"); return CMGPU_ECAPACITY; }

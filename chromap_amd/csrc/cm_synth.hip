@@ -25,15 +25,6 @@
 #define SY_CHUNK 2048u   // reference positions per thread
 #define SY_WARM 96u      // warm-up positions in front of a chunk (>= 2w + k)
 
-#define SYCHECK(ctx, call)                                                                  \
-  do {                                                                                      \
-    hipError_t e_ = (call);                                                                 \
-    if (e_ != hipSuccess) {                                                                 \
-      cm_set_error(ctx, std::string(#call) + ": " + hipGetErrorString(e_));                \
-      return CMGPU_EHIP;                                                                    \
-    }                                                                                       \
-  } while (0)
-
 CM_HD uint64_t sy_mix(uint64_t x) {  // splitmix64 finalizer: counter-based RNG
   x += 0x9E3779B97F4A7C15ull;
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -231,15 +222,15 @@ static int sy_build_index(cmgpu_ctx *c) {
   DevBuf d_chunks, d_cnt, d_off, d_tmp;
   if (d_chunks.ensure((size_t)nch * sizeof(SyChunk)) || d_cnt.ensure(((size_t)nch + 1) * 4) || d_off.ensure(((size_t)nch + 1) * 4) ||
       d_tmp.ensure(cm_scan_tmp_words(nch) * 4)) { cm_set_error(c, "out of device memory (index build)"); return CMGPU_ENOMEM; }
-  SYCHECK(c, hipMemcpyAsync(d_chunks.p, chunks.data(), (size_t)nch * sizeof(SyChunk), hipMemcpyHostToDevice, s));
+  CM_HIPCHECK(c, hipMemcpyAsync(d_chunks.p, chunks.data(), (size_t)nch * sizeof(SyChunk), hipMemcpyHostToDevice, s));
   const dim3 g((nch + SY_BLOCK - 1) / SY_BLOCK), b(SY_BLOCK);
   hipLaunchKernelGGL(k_sy_ref_minimizers, g, b, 0, s, (const uint8_t *)c->ref.p, (const uint64_t *)c->ref_off.p,
                      (const uint32_t *)c->ref_len.p, (const SyChunk *)d_chunks.p, nch, k, w, 0, (uint32_t *)d_cnt.p,
                      (const uint32_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr);
   cm_scan_u32((const uint32_t *)d_cnt.p, (uint32_t *)d_off.p, nch, (uint32_t *)d_tmp.p, s);
   uint32_t n_mm = 0;
-  SYCHECK(c, hipMemcpyAsync(&n_mm, (uint32_t *)d_off.p + nch, 4, hipMemcpyDeviceToHost, s));
-  SYCHECK(c, cm_stream_sync(s));
+  CM_HIPCHECK(c, hipMemcpyAsync(&n_mm, (uint32_t *)d_off.p + nch, 4, hipMemcpyDeviceToHost, s));
+  CM_HIPCHECK(c, cm_stream_sync(s));
   if (n_mm == 0) { cm_set_error(c, "reference has no minimizers"); return CMGPU_EINVAL; }
   if (n_mm > 0x7fffffffu) { cm_set_error(c, "more than INT_MAX minimizers (index.cc:33)"); return CMGPU_ECAPACITY; }
   DevBuf h0, t0, h1, t1;
@@ -251,19 +242,19 @@ static int sy_build_index(cmgpu_ctx *c) {
                      (const uint32_t *)d_off.p, (uint64_t *)h0.p, (uint64_t *)t0.p);
   // ---- sort by (hash, hit): LSD -- stable sort by hit, then stable sort by hash
   size_t tb = 0;
-  SYCHECK(c, rocprim::radix_sort_pairs(nullptr, tb, (uint64_t *)t0.p, (uint64_t *)t1.p, (uint64_t *)h0.p, (uint64_t *)h1.p,
+  CM_HIPCHECK(c, rocprim::radix_sort_pairs(nullptr, tb, (uint64_t *)t0.p, (uint64_t *)t1.p, (uint64_t *)h0.p, (uint64_t *)h1.p,
                                        (size_t)n_mm, 0, 64, s));
   DevBuf sort_tmp;
   if (sort_tmp.ensure(tb + 256)) { cm_set_error(c, "out of device memory (sort)"); return CMGPU_ENOMEM; }
-  SYCHECK(c, rocprim::radix_sort_pairs(sort_tmp.p, tb, (uint64_t *)t0.p, (uint64_t *)t1.p, (uint64_t *)h0.p, (uint64_t *)h1.p,
+  CM_HIPCHECK(c, rocprim::radix_sort_pairs(sort_tmp.p, tb, (uint64_t *)t0.p, (uint64_t *)t1.p, (uint64_t *)h0.p, (uint64_t *)h1.p,
                                        (size_t)n_mm, 0, 64, s));
   size_t tb2 = tb;
-  SYCHECK(c, rocprim::radix_sort_pairs(nullptr, tb2, (uint64_t *)h1.p, (uint64_t *)h0.p, (uint64_t *)t1.p, (uint64_t *)t0.p,
+  CM_HIPCHECK(c, rocprim::radix_sort_pairs(nullptr, tb2, (uint64_t *)h1.p, (uint64_t *)h0.p, (uint64_t *)t1.p, (uint64_t *)t0.p,
                                        (size_t)n_mm, 0, 2 * k, s));
   if (sort_tmp.ensure(tb2 + 256)) { cm_set_error(c, "out of device memory (sort)"); return CMGPU_ENOMEM; }
-  SYCHECK(c, rocprim::radix_sort_pairs(sort_tmp.p, tb2, (uint64_t *)h1.p, (uint64_t *)h0.p, (uint64_t *)t1.p, (uint64_t *)t0.p,
+  CM_HIPCHECK(c, rocprim::radix_sort_pairs(sort_tmp.p, tb2, (uint64_t *)h1.p, (uint64_t *)h0.p, (uint64_t *)t1.p, (uint64_t *)t0.p,
                                        (size_t)n_mm, 0, 2 * k, s));
-  SYCHECK(c, cm_stream_sync(s));
+  CM_HIPCHECK(c, cm_stream_sync(s));
   sort_tmp.release(); h1.release(); t1.release();
   // ---- singleton / multi flags, occurrence offsets, key count
   DevBuf multi, starts, opos, spos, tmp2;
@@ -276,9 +267,9 @@ static int sy_build_index(cmgpu_ctx *c) {
   cm_scan_u32((const uint32_t *)multi.p, (uint32_t *)opos.p, n_mm, (uint32_t *)tmp2.p, s);
   cm_scan_u32((const uint32_t *)starts.p, (uint32_t *)spos.p, n_mm, (uint32_t *)tmp2.p, s);
   uint32_t n_occ = 0, n_keys = 0;
-  SYCHECK(c, hipMemcpyAsync(&n_occ, (uint32_t *)opos.p + n_mm, 4, hipMemcpyDeviceToHost, s));
-  SYCHECK(c, hipMemcpyAsync(&n_keys, (uint32_t *)spos.p + n_mm, 4, hipMemcpyDeviceToHost, s));
-  SYCHECK(c, cm_stream_sync(s));
+  CM_HIPCHECK(c, hipMemcpyAsync(&n_occ, (uint32_t *)opos.p + n_mm, 4, hipMemcpyDeviceToHost, s));
+  CM_HIPCHECK(c, hipMemcpyAsync(&n_keys, (uint32_t *)spos.p + n_mm, 4, hipMemcpyDeviceToHost, s));
+  CM_HIPCHECK(c, cm_stream_sync(s));
   spos.release(); starts.release();
   const uint32_t nb = sy_buckets_for(n_keys);
   if (nb == 0) { cm_set_error(c, "too many distinct minimizers for a 32-bit khash"); return CMGPU_ECAPACITY; }
@@ -287,13 +278,13 @@ static int sy_build_index(cmgpu_ctx *c) {
   }
   const uint64_t words = (uint64_t)nb * 2;
   hipLaunchKernelGGL(k_sy_fill_empty, dim3((unsigned)((words + SY_BLOCK - 1) / SY_BLOCK)), b, 0, s, (uint64_t *)c->bkt.p, words);
-  SYCHECK(c, hipMemsetAsync(c->stats.p, 0, CM_ST_N * 8, s));
+  CM_HIPCHECK(c, hipMemsetAsync(c->stats.p, 0, CM_ST_N * 8, s));
   hipLaunchKernelGGL(k_sy_insert, gm, b, 0, s, (const uint64_t *)h0.p, (const uint64_t *)t0.p, n_mm, (const uint32_t *)multi.p,
                      (const uint32_t *)opos.p, (uint64_t *)c->bkt.p, nb - 1, (uint64_t *)c->occ.p,
                      (unsigned long long *)c->stats.p);
   unsigned long long err = 0;
-  SYCHECK(c, hipMemcpyAsync(&err, c->stats.p, 8, hipMemcpyDeviceToHost, s));
-  SYCHECK(c, cm_stream_sync(s));
+  CM_HIPCHECK(c, hipMemcpyAsync(&err, c->stats.p, 8, hipMemcpyDeviceToHost, s));
+  CM_HIPCHECK(c, cm_stream_sync(s));
   if (err) { cm_set_error(c, "hash table overflow during index build"); return CMGPU_ECAPACITY; }
   c->bmask = nb - 1;
   c->n_occ = n_occ;
@@ -575,7 +566,7 @@ __global__ __launch_bounds__(SY_BLOCK) void k_sy_reads_hic(const uint8_t *__rest
 extern "C" int cmgpu_generate_resident_batch_hic(cmgpu_ctx *c, uint32_t n_pairs, uint32_t read_length, double sub_rate, double indel_rate,
                                                  double chimeric_fraction, uint64_t seed) {
   if (!c || read_length < 30 || read_length > 250 || (uint64_t)n_pairs * read_length > 0xfffffff0ull) { cm_set_error(c, "bad argument"); return CMGPU_EINVAL; }
-  SYCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   for (uint32_t i = 0; i < c->n_seq; ++i)
     if (c->h_ref_len[i] < 2 * read_length) { cm_set_error(c, "a sequence is shorter than two read lengths"); return CMGPU_EINVAL; }
   c->n_pairs = n_pairs;
@@ -593,7 +584,7 @@ extern "C" int cmgpu_generate_resident_batch_hic(cmgpu_ctx *c, uint32_t n_pairs,
                      (const uint8_t *)c->ref.p, (const uint64_t *)c->ref_off.p, (const uint32_t *)c->ref_len.p, c->n_seq, total,
                      n_pairs, read_length, thresh(sub_rate), thresh(indel_rate), thresh(chimeric_fraction), seed, (uint8_t *)c->rb0.p,
                      (uint8_t *)c->rb1.p, (uint32_t *)c->ro0.p, (uint32_t *)c->ro1.p);
-  SYCHECK(c, cm_stream_sync(c->stream));
+  CM_HIPCHECK(c, cm_stream_sync(c->stream));
   return CMGPU_OK;
 }
 
@@ -608,7 +599,7 @@ extern "C" int cmgpu_generate_resident_batch_indels(cmgpu_ctx *c, uint32_t n_pai
     cm_set_error(c, "bad argument");
     return CMGPU_EINVAL;
   }
-  SYCHECK(c, cm_enter(c));
+  CM_HIPCHECK(c, cm_enter(c));
   c->n_pairs = n_pairs;
   c->first_read_id = 0;
   c->bases0 = c->bases1 = (size_t)n_pairs * read_length;
@@ -625,7 +616,7 @@ extern "C" int cmgpu_generate_resident_batch_indels(cmgpu_ctx *c, uint32_t n_pai
                      (const uint8_t *)c->ref.p, (const uint64_t *)c->ref_off.p, (const uint32_t *)c->ref_len.p, c->n_seq, total,
                      n_pairs, read_length, frag_min, frag_max, thr, ithr, seed, (uint8_t *)c->rb0.p, (uint8_t *)c->rb1.p,
                      (uint32_t *)c->ro0.p, (uint32_t *)c->ro1.p);
-  SYCHECK(c, cm_stream_sync(c->stream));
+  CM_HIPCHECK(c, cm_stream_sync(c->stream));
   return CMGPU_OK;
 }
 

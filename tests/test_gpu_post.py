@@ -204,6 +204,56 @@ def test_bulk_level_dedup_of_single_cell_records_long_runs(span, q, tmp_path):
     assert got == want
 
 
+PAIRS_DTYPE = np.dtype([("read_id", "<u4"), ("rid1", "<u4"), ("rid2", "<u4"), ("pos1", "<u4"), ("pos2", "<u4"), ("strand1", "u1"),
+                        ("strand2", "u1"), ("mapq", "u1"), ("is_unique", "u1")])  # cmgpu_pairs_record
+
+
+@pytest.mark.parametrize("dedup,lowmem,q", [(0, 1, 0), (1, 1, 0), (1, 0, 0), (1, 1, 30), (1, 0, 30)])
+def test_device_pairs_text_equals_host_writer_on_random_records(dedup, lowmem, q, tmp_path):
+    """the pairs formatter's duplicate rules (k_pp_pairs_len: low-memory merge keeps the first record of the run's largest MAPQ, the
+    in-memory rule the run's last) on random records whose (rid1, pos1, rid2, pos2) runs are a few hundred records long, against
+    the host writer"""
+    from chromap_amd import ChromapGPU, _capi
+    assert PAIRS_DTYPE.itemsize == 24
+    fa, _, _ = datasets.case_inputs("toy_chip")
+    g = ChromapGPU(datasets.case_index("toy_chip"), fa, preset="hic")
+    try:
+        assert g.params.split_alignment  # the store then holds pairs records
+        n, n_seq, span = 20000, 3, 4
+        g.names = [b"seq%d" % i for i in range(n_seq)]
+        g.reference_lengths = lambda: (C.c_uint32 * n_seq)(*([1000] * n_seq))  # of the made-up sequences (the host writer's header lines)
+        p = _capi.default_params("hic", remove_pcr_duplicates=dedup, low_memory_mode=lowmem, mapq_threshold=q)
+        rng = np.random.default_rng(4242)
+        rec = np.zeros(n, PAIRS_DTYPE)
+        rec["read_id"] = rng.permutation(n).astype(np.uint32)
+        rec["rid1"] = rng.integers(0, n_seq, n)
+        rec["rid2"] = rng.integers(0, n_seq, n)
+        rec["pos1"] = rng.integers(10, 10 + span, n)
+        rec["pos2"] = rng.integers(10, 10 + span, n)
+        rec["strand1"] = rng.integers(0, 2, n)
+        rec["strand2"] = rng.integers(0, 2, n)
+        rec["mapq"] = rng.choice([0, 1, 3, 30, 60], n)
+        rec["is_unique"] = rng.integers(0, 2, n)
+        read_names = [b"r%d" % i for i in range(n)]
+        host = rec.copy()  # (the host writer sorts its records in place)
+        out = str(tmp_path / "h.pairs")
+        g.write_pairs(host.ctypes.data, n, read_names, out, params=p)
+        want = b"".join(ln for ln in open(out, "rb").read().splitlines(True) if not ln.startswith(b"#"))
+        g.store_clear()
+        half = n // 2
+        g.store_append(rec.ctypes.data, half)
+        g.store_append(rec.ctypes.data + half * 24, n - half)
+        lines, nbytes = g.store_format_pairs(read_names, params=p)
+        got = g.store_text()
+        assert nbytes == len(want) and lines == want.count(b"\n") and lines > 0
+        assert got == want
+        # formatting again gives the same text (the store is not consumed)
+        assert g.store_format_pairs(read_names, params=p) == (lines, nbytes)
+        assert g.store_text() == want
+    finally:
+        g.close()
+
+
 def test_empty_store_formats_to_nothing():
     from chromap_amd import ChromapGPU, _capi
     fa, _, _ = datasets.case_inputs("toy_chip")
