@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/chromap_amd.h"
+#include "cm_barcode_translate.h"
 #include "cm_ctx.h"
 #include "cm_kernels.h"
 #include "cm_classes.h"
@@ -1903,6 +1904,63 @@ extern "C" int cmgpu_copy_whitelist(cmgpu_ctx *dst, cmgpu_ctx *src) {
   CM_HIPCHECK(dst, hipMemcpy(dst->wl_num.p, &ns, 8, hipMemcpyHostToDevice));
   dst->wl_mask = src->wl_mask; dst->wl_size = src->wl_size; dst->bc_len = src->bc_len; dst->wl_num_sample = src->wl_num_sample;
   dst->skip_barcode_check = src->skip_barcode_check;
+  return CMGPU_OK;
+}
+
+// --barcode-translate: the table of the device-side text writers (cm_barcode_translate.h).  The image is cmgpu_barcode_translation_pack's
+extern "C" int cmgpu_set_barcode_translation(cmgpu_ctx *c, const char *table_text, uint64_t n_bytes) {
+  if (!c) return CMGPU_EINVAL;
+  CM_HIPCHECK(c, cm_enter(c));
+  if (!table_text || n_bytes == 0) {  // no table from here on
+    c->bt_tab.release(); c->bt_blob.release();
+    c->bt_mask = 0; c->bt_entries = 0; c->bt_from = 0; c->bt_blob_bytes = 0;
+    return CMGPU_OK;
+  }
+  uint64_t nb = 0, bb = 0;
+  uint32_t from = 0;
+  int rc = cmgpu_barcode_translation_pack(table_text, n_bytes, nullptr, 0, nullptr, 0, &nb, &bb, &from);
+  if (rc) { cm_set_error(c, "the barcode translation table has no usable line (to<TAB or ,>from)"); return rc; }
+  std::vector<uint64_t> tab((size_t)nb * 2);
+  std::vector<char> blob((size_t)bb + 16, 0);
+  rc = cmgpu_barcode_translation_pack(table_text, n_bytes, tab.data(), nb, blob.data(), bb, &nb, &bb, &from);
+  if (rc) { cm_set_error(c, "barcode translation table: packing failed"); return rc; }
+  uint32_t entries = 0;
+  for (uint64_t i = 0; i < nb; ++i) entries += tab[2 * i + 1] != CM_BT_EMPTY;
+  if (c->bt_tab.ensure(tab.size() * 8) || c->bt_blob.ensure(blob.size())) {
+    c->bt_entries = 0;
+    cm_set_error(c, "out of device memory (barcode translation table)");
+    return CMGPU_ENOMEM;
+  }
+  c->bt_entries = 0;  // (a failed upload leaves no table)
+  CM_HIPCHECK(c, hipMemcpy(c->bt_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+  CM_HIPCHECK(c, hipMemcpy(c->bt_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
+  c->bt_mask = (uint32_t)(nb - 1); c->bt_entries = entries; c->bt_from = from; c->bt_blob_bytes = bb;
+  return CMGPU_OK;
+}
+extern "C" int cmgpu_barcode_translation_info(const cmgpu_ctx *c, uint32_t *n_entries, uint32_t *from_length, uint64_t *n_bytes_hbm) {
+  if (!c) return CMGPU_EINVAL;
+  if (n_entries) *n_entries = c->bt_entries;
+  if (from_length) *from_length = c->bt_from;
+  if (n_bytes_hbm) *n_bytes_hbm = c->bt_entries ? ((uint64_t)c->bt_mask + 1) * 16 + c->bt_blob_bytes : 0;
+  return CMGPU_OK;
+}
+// the table of another context (one context per GPU: the file is read and packed once); a source without a table clears the destination's
+extern "C" int cmgpu_copy_barcode_translation(cmgpu_ctx *dst, cmgpu_ctx *src) {
+  if (!dst || !src) return CMGPU_EINVAL;
+  if (dst == src) return CMGPU_OK;
+  if (src->bt_entries == 0) return cmgpu_set_barcode_translation(dst, nullptr, 0);
+  const size_t tb = ((size_t)src->bt_mask + 1) * 16, bb = (size_t)src->bt_blob_bytes + 16;
+  std::vector<uint64_t> tab(tb / 8);
+  std::vector<char> blob(bb);
+  CM_HIPCHECK(src, cm_enter(src));
+  CM_HIPCHECK(src, hipMemcpy(tab.data(), src->bt_tab.p, tb, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(src, hipMemcpy(blob.data(), src->bt_blob.p, bb, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(dst, cm_enter(dst));
+  dst->bt_entries = 0;
+  if (dst->bt_tab.ensure(tb) || dst->bt_blob.ensure(bb)) { cm_set_error(dst, "out of device memory (barcode translation table)"); return CMGPU_ENOMEM; }
+  CM_HIPCHECK(dst, hipMemcpy(dst->bt_tab.p, tab.data(), tb, hipMemcpyHostToDevice));
+  CM_HIPCHECK(dst, hipMemcpy(dst->bt_blob.p, blob.data(), bb, hipMemcpyHostToDevice));
+  dst->bt_mask = src->bt_mask; dst->bt_entries = src->bt_entries; dst->bt_from = src->bt_from; dst->bt_blob_bytes = src->bt_blob_bytes;
   return CMGPU_OK;
 }
 

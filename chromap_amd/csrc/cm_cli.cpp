@@ -6,7 +6,6 @@
 
 #include <chrono>
 #include <functional>
-#include <unordered_map>
 
 #include "cm_cli_reader.h"
 #include "cm_cli_args.h"
@@ -608,6 +607,16 @@ static void print_statistics(const Run &r) {
             (unsigned long long)st.num_barcode_in_whitelist, (unsigned long long)st.num_corrected_barcode);
 }
 
+// the whole (inflated) text of the --barcode-translate file, gzip-compressed or plain
+static std::string read_translation_table(const Args &a) {
+  std::string table;
+  gzFile tf = gzopen(a.translate_path.c_str(), "r");
+  if (!tf) die("Cannot open barcode translation file " + a.translate_path);
+  char tb[1 << 16];
+  for (int got; (got = gzread(tf, tb, sizeof(tb))) > 0;) table.append(tb, (size_t)got);
+  gzclose(tf);
+  return table;
+}
 // ---- the writers: each returns the number of lines written (negative: the file could not be written)
 // sort + duplicate removal + MAPQ filter + SAM lines on the device, from the reads and records in HBM
 static int64_t write_sam_device(Run &r) {
@@ -643,12 +652,7 @@ static int64_t write_sam_host(Run &r) {
   };
   if (!r.barcoded) return write(cmgpu_write_sam, a.out_path.c_str());
   if (a.translate_path.empty()) return write(cmgpu_write_sam_barcoded, s.bc.data(), r.bc_len, a.out_path.c_str());
-  std::string table;  // CB:Z: through the translation table (read here: the table may be gzip-compressed)
-  gzFile tf = gzopen(a.translate_path.c_str(), "r");
-  if (!tf) die("Cannot open barcode translation file " + a.translate_path);
-  char tb[1 << 16];
-  for (int got; (got = gzread(tf, tb, sizeof(tb))) > 0;) table.append(tb, (size_t)got);
-  gzclose(tf);
+  const std::string table = read_translation_table(a);  // CB:Z: through the translation table
   const int64_t lines = write(cmgpu_write_sam_barcoded_translated, s.bc.data(), r.bc_len, table.data(), (uint64_t)table.size(), a.out_path.c_str());
   if (lines == CMGPU_EFORMAT) die("Barcode does not exist in the translation table.");
   return lines;
@@ -670,57 +674,14 @@ static int64_t write_pairs(Run &r) {
   ck(ctx, cmgpu_store_write_text(ctx, r.a.out_path.c_str(), 1));
   return (int64_t)nl;
 }
-// --barcode-translate (BarcodeTranslator, barcode_translator.h:43-101): the device rendered the corrected barcodes;
-// column 4 is rewritten on the way to the file.  Table lines are "to<TAB or ,>from"; a barcode made of several
-// segments of the table's length is translated segment by segment and joined with '-'.
-static void write_translated_bed(Run &r, uint64_t nbytes) {
-  std::unordered_map<std::string, std::string> table;
-  size_t from_len = 0;
-  gzFile tf = gzopen(r.a.translate_path.c_str(), "r");
-  if (!tf) die("Cannot open barcode translation file " + r.a.translate_path);
-  char lb[512];
-  while (gzgets(tf, lb, sizeof(lb))) {
-    size_t l = strlen(lb);
-    if (l && lb[l - 1] == '\n') lb[--l] = 0;
-    size_t i = 0;
-    while (i < l && lb[i] != ',' && lb[i] != '\t') ++i;
-    if (i >= l) continue;
-    from_len = l - i - 1;
-    table[std::string(lb + i + 1, from_len)] = std::string(lb, i);
-  }
-  gzclose(tf);
-  std::vector<char> text(nbytes + 1);
-  ck(r.ctx(), cmgpu_store_text(r.ctx(), text.data(), nbytes));
-  FILE *of = fopen(r.a.out_path.c_str(), "wb");
-  if (!of) die("cannot write " + r.a.out_path);
-  std::string outb;
-  outb.reserve(1 << 20);
-  const char *p = text.data(), *end = text.data() + nbytes;
-  while (p < end) {
-    const char *nlp = (const char *)memchr(p, '\n', (size_t)(end - p));
-    if (!nlp) nlp = end;
-    const char *c1 = (const char *)memchr(p, '\t', (size_t)(nlp - p));
-    const char *c2 = c1 ? (const char *)memchr(c1 + 1, '\t', (size_t)(nlp - c1 - 1)) : nullptr;
-    const char *c3 = c2 ? (const char *)memchr(c2 + 1, '\t', (size_t)(nlp - c2 - 1)) : nullptr;
-    const char *c4 = c3 ? (const char *)memchr(c3 + 1, '\t', (size_t)(nlp - c3 - 1)) : nullptr;
-    if (!c4 || from_len == 0) { outb.append(p, (size_t)(nlp - p)); }
-    else {
-      outb.append(p, (size_t)(c3 + 1 - p));
-      const size_t bl = (size_t)(c4 - c3 - 1);
-      for (size_t sgm = 0; sgm < bl / from_len; ++sgm) {
-        auto it = table.find(std::string(c3 + 1 + sgm * from_len, from_len));
-        if (it == table.end()) die("Barcode does not exist in the translation table.");
-        if (sgm) outb.push_back('-');
-        outb.append(it->second);
-      }
-      outb.append(c4, (size_t)(nlp - c4));
-    }
-    outb.push_back('\n');
-    if (outb.size() > (1 << 20) - 4096) { fwrite(outb.data(), 1, outb.size(), of); outb.clear(); }
-    p = nlp + 1;
-  }
-  if (!outb.empty()) fwrite(outb.data(), 1, outb.size(), of);
-  fclose(of);
+// --barcode-translate for BED (BarcodeTranslator, barcode_translator.h:42-101): the table goes to the first context and is copied to the
+// others; every context then renders column 4 of its section through it (cmgpu_store_format)
+static void set_translation_tables(Run &r) {
+  const std::string table = read_translation_table(r.a);
+  const int rc = cmgpu_set_barcode_translation(r.ctx(), table.data(), (uint64_t)table.size());
+  if (rc == CMGPU_EINVAL) die("barcode translation file " + r.a.translate_path + " has no line of the form to<TAB or ,>from");
+  ck(r.ctx(), rc);
+  for (size_t gi = 1; gi < r.ctxs.size(); ++gi) ck(r.ctxs[gi], cmgpu_copy_barcode_translation(r.ctxs[gi], r.ctx()));
 }
 // BED / TagAlign: sort + duplicate removal + MAPQ filter + Tn5 shift + text, all on the device
 static int64_t write_bed(Run &r) {
@@ -731,6 +692,7 @@ static int64_t write_bed(Run &r) {
                    : a.out_tagalign && barcoded ? CMGPU_TEXT_TAGALIGN_SE_BC
                    : barcoded ? (paired ? CMGPU_TEXT_BED_PE_BC : CMGPU_TEXT_BED_SE_BC) : paired ? CMGPU_TEXT_BED_PE : CMGPU_TEXT_BED_SE;
   const double t0 = now_s();
+  if (barcoded && !a.translate_path.empty() && (kind == CMGPU_TEXT_BED_PE_BC || kind == CMGPU_TEXT_BED_SE_BC)) set_translation_tables(r);
   // every context sorts, de-duplicates and renders the chromosomes it owns (all of them with one context)
   std::vector<int> rcs(NG, CMGPU_OK);
   std::vector<uint64_t> nls(NG, 0), nbs(NG, 0);
@@ -739,17 +701,13 @@ static int64_t write_bed(Run &r) {
   });
   uint64_t nl = 0, nbytes = 0;
   for (size_t gi = 0; gi < NG; ++gi) {
-    ck(r.ctxs[gi], rcs[gi]);
+    ck(r.ctxs[gi], rcs[gi]);  // (CMGPU_EFORMAT: "Barcode does not exist in the translation table.", the reference's words)
     nl += nls[gi];
     nbytes += nbs[gi];
   }
   const double t1 = now_s();
-  if (barcoded && !a.translate_path.empty() && (kind == CMGPU_TEXT_BED_PE_BC || kind == CMGPU_TEXT_BED_SE_BC)) {
-    write_translated_bed(r, nbytes);  // (one context: validate())
-  } else {
-    // sections in rank order: the owners hold contiguous, increasing chromosome ranges
-    for (cmgpu_ctx *cx : r.ctxs) ck(cx, cmgpu_store_write_text(cx, a.out_path.c_str(), 1));  // (emptied at the start)
-  }
+  // sections in rank order: the owners hold contiguous, increasing chromosome ranges
+  for (cmgpu_ctx *cx : r.ctxs) ck(cx, cmgpu_store_write_text(cx, a.out_path.c_str(), 1));  // (emptied at the start)
   r.t_post = now_s() - t0;
   fprintf(stderr, "Sorted, deduplicated and formatted %llu bytes on the device in %.3fs, wrote them in %.3fs.\n", (unsigned long long)nbytes,
           t1 - t0, now_s() - t1);

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/chromap_amd.h"
+#include "cm_barcode_translate.h"
 
 extern "C" void cmgpu_default_params(cmgpu_params *p) {  // mapping_parameters.h:19-61
   memset(p, 0, sizeof(*p));
@@ -498,6 +499,56 @@ static int parse_barcode_table(const char *text, uint64_t bytes, CmBarcodeTable 
   }
   t->mask = t->from_len >= 32 ? ~0ull : (1ull << (2 * t->from_len)) - 1;
   return t->from_len ? CMGPU_OK : CMGPU_EINVAL;
+}
+
+// The table as the device holds it (cm_barcode_translate.h has the layout): the image cmgpu_set_barcode_translation uploads, made here
+// so that it can be made, and looked at, without a device.  Keys go in in increasing order: the image depends on the table alone
+extern "C" int cmgpu_barcode_translation_pack(const char *table_text, uint64_t n_bytes, uint64_t *buckets, uint64_t bucket_capacity, char *blob,
+                                              uint64_t blob_capacity, uint64_t *n_buckets, uint64_t *blob_bytes, uint32_t *from_length) {
+  if (!table_text && n_bytes) return CMGPU_EINVAL;
+  CmBarcodeTable t;
+  const int rc = parse_barcode_table(table_text, n_bytes, &t);
+  if (rc) return rc;
+  std::vector<uint64_t> keys;
+  keys.reserve(t.to.size());
+  uint64_t total = 0;
+  for (const auto &kv : t.to) { keys.push_back(kv.first); total += kv.second.size(); }
+  if (keys.size() > (1u << 30) || total > 0xfffffff0ull) return CMGPU_EINVAL;  // (offsets and lengths are 32-bit)
+  std::sort(keys.begin(), keys.end());
+  uint64_t nb = 16;
+  while (nb < 2 * (uint64_t)keys.size()) nb <<= 1;
+  if (n_buckets) *n_buckets = nb;
+  if (blob_bytes) *blob_bytes = total;
+  if (from_length) *from_length = t.from_len;
+  if (!buckets || (!blob && total)) return CMGPU_OK;  // sizes only
+  if (bucket_capacity < nb || blob_capacity < total) return CMGPU_ECAPACITY;
+  for (uint64_t i = 0; i < 2 * nb; ++i) buckets[i] = CM_BT_EMPTY;
+  uint64_t off = 0;
+  for (const uint64_t key : keys) {
+    const std::string &to = t.to[key];
+    uint64_t b = ((key * CM_BT_HASH_MUL) >> 32) & (nb - 1);
+    while (buckets[2 * b + 1] != CM_BT_EMPTY) b = (b + 1) & (nb - 1);
+    buckets[2 * b] = key;
+    buckets[2 * b + 1] = (off << 32) | (uint64_t)to.size();
+    if (!to.empty()) memcpy(blob + off, to.data(), to.size());
+    off += to.size();
+  }
+  return CMGPU_OK;
+}
+
+// one barcode through a packed table on the host, with the functions the device writers use
+extern "C" int cmgpu_barcode_translate_host(const uint64_t *buckets, uint64_t n_buckets, const char *blob, uint32_t from_length, uint64_t barcode_key,
+                                            uint32_t barcode_length, char *out, uint64_t capacity, uint64_t *n_out) {
+  if (!buckets || n_buckets == 0 || (n_buckets & (n_buckets - 1)) || n_buckets > (1ull << 32) || from_length == 0 || barcode_length == 0 ||
+      barcode_length > 32 || !n_out || (!out && capacity)) return CMGPU_EINVAL;
+  const CmBtDev t{buckets, (const uint8_t *)blob, (uint32_t)(n_buckets - 1), from_length};
+  uint32_t len = 0;
+  *n_out = 0;
+  if (!cm_bt_length(t, barcode_key, barcode_length, &len)) return CMGPU_EFORMAT;
+  *n_out = len;
+  if (capacity < len) return CMGPU_ECAPACITY;
+  (void)cm_bt_render(t, barcode_key, barcode_length, (uint8_t *)out);
+  return CMGPU_OK;
 }
 
 // --summary for SAM text written on the host: between cmgpu_host_summary_begin and _end the SAM writers called by this thread credit

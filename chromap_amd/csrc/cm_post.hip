@@ -47,6 +47,8 @@ struct PpCfg {
   int last_section;   // this store ends the output (always, unless a higher rank of a multi-GPU run owns records too)
   const uint64_t *wl;  // whitelist table {key, abundance} (cm_api.hip: cmgpu_set_whitelist), linear probing
   uint32_t wl_mask;
+  CmBtDev bt;          // --barcode-translate: column 4 of the barcoded BED kinds through the table (bt.tab == nullptr: Seed2Sequence)
+  unsigned long long *bt_miss;  // surviving lines whose barcode the table does not have (the job's spare count word)
 };
 
 struct PpRec {  // cmgpu_record, read with two 8-byte loads + one 8-byte load
@@ -75,6 +77,7 @@ __device__ __forceinline__ PpRec pp_load(const uint8_t *store, uint32_t i) {
 
 __host__ __device__ __forceinline__ bool pp_se_bc(int kind) { return kind == CMGPU_TEXT_BED_SE_BC || kind == CMGPU_TEXT_TAGALIGN_SE_BC; }
 __host__ __device__ __forceinline__ bool pp_has_bc(int kind) { return kind == CMGPU_TEXT_BED_PE_BC || kind == CMGPU_TEXT_TAGALIGN_PE_BC || pp_se_bc(kind); }
+__host__ __device__ __forceinline__ bool pp_prints_bc(int kind) { return kind == CMGPU_TEXT_BED_PE_BC || kind == CMGPU_TEXT_BED_SE_BC; }
 __host__ __device__ __forceinline__ bool pp_is_se(int kind) { return kind == CMGPU_TEXT_BED_SE || pp_se_bc(kind); }
 __host__ __device__ __forceinline__ bool pp_tagalign(int kind) { return kind == CMGPU_TEXT_TAGALIGN_PE || kind == CMGPU_TEXT_TAGALIGN_PE_BC; }
 // Tn5Shift (bed_mapping.h:48-54, 100-106, 165-170, 224-229)
@@ -140,8 +143,10 @@ __device__ __forceinline__ void pp_sm_run(const CmSmDev &sm, const PpCfg &cfg, u
   cm_sm_credit(sm, !pp_has_bc(cfg.kind), bcv, dups, (int)mapq >= cfg.mapq_thr);
 }
 
-// the survivor of sorted position j: MAPQ filter, Tn5 shift, line length; win / dups / line_len of the position
-__device__ __forceinline__ void pp_finish(uint32_t j, PpRec r, uint32_t wi, uint32_t dups, bool bulk_done, const PpCfg &cfg,
+// the survivor of sorted position j: MAPQ filter, Tn5 shift, line length; win / dups / line_len of the position.  bcv: the survivor's
+// barcode.  With a translation table a barcode it does not have is counted, for a line that would be printed only (the reference
+// exits in Translate, which it calls for a mapping it is about to print)
+__device__ __forceinline__ void pp_finish(uint32_t j, PpRec r, uint32_t wi, uint64_t bcv, uint32_t dups, bool bulk_done, const PpCfg &cfg,
                                           const uint32_t *__restrict__ name_off, uint32_t *__restrict__ win,
                                           uint32_t *__restrict__ dups_out, uint64_t *__restrict__ line_len) {
   if ((!bulk_done && (int)r.mapq < cfg.mapq_thr) || r.rid >= cfg.n_seq) { line_len[j] = 0; return; }
@@ -157,7 +162,11 @@ __device__ __forceinline__ void pp_finish(uint32_t j, PpRec r, uint32_t wi, uint
     if (cfg.kind == CMGPU_TEXT_TAGALIGN_PE) len += 1 + cm_digits10(dups);
   } else {
     len = nm + 1 + cm_digits10(r.start) + 1 + cm_digits10(r.start + r.len) + 1;
-    if (cfg.kind == CMGPU_TEXT_BED_PE_BC || cfg.kind == CMGPU_TEXT_BED_SE_BC) len += cfg.bc_len + 1 + cm_digits10(dups) + 1;  // chr start end barcode dups
+    if (pp_prints_bc(cfg.kind)) {  // chr start end barcode dups
+      uint32_t bl = cfg.bc_len;
+      if (cfg.bt.tab && !cm_bt_length(cfg.bt, bcv, cfg.bc_len, &bl)) { atomicAdd(cfg.bt_miss, 1ull); line_len[j] = 0; return; }
+      len += bl + 1 + cm_digits10(dups) + 1;
+    }
     else if (cfg.kind == CMGPU_TEXT_TAGALIGN_SE_BC) len += 2 + cm_digits10(r.mapq) + 2 + 1;     // chr start end N mapq strand (mapping_writer.cc:26-34)
     else len += 2 + cm_digits10(r.mapq) + 3 + cm_digits10(dups) + 1;                              // chr start end N mapq strand dups
   }
@@ -261,7 +270,7 @@ __global__ __launch_bounds__(PP_BLOCK) void k_pp_select(const uint8_t *__restric
     }
   }
   if (sm.keys && !bulk_done && r.rid < cfg.n_seq) pp_sm_run(sm, cfg, pp_has_bc(cfg.kind) ? bc[wi] : 0, dups, r.mapq);
-  pp_finish(j, r, wi, dups, bulk_done, cfg, name_off, win, dups_out, line_len);
+  pp_finish(j, r, wi, cfg.bt.tab ? bc[wi] : 0, dups, bulk_done, cfg, name_off, win, dups_out, line_len);
 }
 
 // Duplicate runs longer than PP_RUN_SERIAL, one wave each: the lanes test 64 records per step for membership (the run is the
@@ -352,7 +361,7 @@ __global__ __launch_bounds__(64) void k_pp_select_long(const uint8_t *__restrict
           pp_sm_run(sm, cfg, bc[ci], run_end - j, filter_mapq);
         }
         if ((int)filter_mapq < cfg.mapq_thr) line_len[j] = 0;
-        else pp_finish(j, r, wi, run_end - j, true, cfg, name_off, win, dups_out, line_len);
+        else pp_finish(j, r, wi, cfg.bt.tab ? bc[wi] : 0, run_end - j, true, cfg, name_off, win, dups_out, line_len);
       }
       continue;
     }
@@ -389,13 +398,18 @@ __global__ __launch_bounds__(64) void k_pp_select_long(const uint8_t *__restrict
       if (cfg.inmem) { wi = idx[run_end - 1]; r = pp_load(store, wi); }
       else if (my_mapq > (int)r0.mapq) { wi = idx[my_pos]; r = pp_load(store, wi); }
       if (sm.keys && r.rid < cfg.n_seq) pp_sm_run(sm, cfg, pp_has_bc(cfg.kind) ? bc[wi] : 0, run_end - j, r.mapq);
-      pp_finish(j, r, wi, run_end - j, false, cfg, name_off, win, dups_out, line_len);
+      pp_finish(j, r, wi, cfg.bt.tab ? bc[wi] : 0, run_end - j, false, cfg, name_off, win, dups_out, line_len);
     }
   }
 }
 
-__device__ __forceinline__ void pp_render(uint8_t *p, const PpRec &r, uint64_t bcv, uint32_t dups, const PpCfg &cfg,
-                                          const uint8_t *__restrict__ names, const uint32_t *__restrict__ name_off) {
+// leave_bc (translated barcodes only): room is left for column 4 instead of writing it, and the column's place is returned -- the
+// block's waves fill it in (pp_fill_columns).  line_len: the line's bytes, from which the column's end follows without a lookup
+__device__ __forceinline__ uint8_t *pp_render(uint8_t *p, const PpRec &r, uint64_t bcv, uint32_t dups, const PpCfg &cfg,
+                                              const uint8_t *__restrict__ names, const uint32_t *__restrict__ name_off, bool leave_bc,
+                                              uint32_t line_len) {
+  uint8_t *col = nullptr;
+  uint8_t *const line = p;
   const uint32_t n0 = name_off[r.rid], n1 = name_off[r.rid + 1];
   if (pp_tagalign(cfg.kind)) {
     const uint32_t pe = r.start + r.pal, ne = r.start + r.len, ns = ne - r.nal;
@@ -413,7 +427,7 @@ __device__ __forceinline__ void pp_render(uint8_t *p, const PpRec &r, uint64_t b
       if (half == 1 && cfg.kind == CMGPU_TEXT_TAGALIGN_PE) { *p++ = '\t'; p = cm_put_u32(p, dups); }
       *p++ = '\n';
     }
-    return;
+    return col;
   }
   for (uint32_t i = n0; i < n1; ++i) *p++ = names[i];
   *p++ = '\t';
@@ -421,8 +435,15 @@ __device__ __forceinline__ void pp_render(uint8_t *p, const PpRec &r, uint64_t b
   *p++ = '\t';
   p = cm_put_u32(p, r.start + r.len);
   *p++ = '\t';
-  if (cfg.kind == CMGPU_TEXT_BED_PE_BC || cfg.kind == CMGPU_TEXT_BED_SE_BC) {
-    for (uint32_t b = 0; b < cfg.bc_len; ++b) *p++ = "ACGT"[(bcv >> ((cfg.bc_len - 1 - b) * 2)) & 3];  // Seed2Sequence
+  if (pp_prints_bc(cfg.kind)) {
+    if (!cfg.bt.tab) {
+      for (uint32_t b = 0; b < cfg.bc_len; ++b) *p++ = "ACGT"[(bcv >> ((cfg.bc_len - 1 - b) * 2)) & 3];  // Seed2Sequence
+    } else if (leave_bc) {
+      col = p;
+      p = line + line_len - (1 + cm_digits10(dups) + 1);  // what follows the column: tab, dups, newline
+    } else {
+      p = cm_bt_render(cfg.bt, bcv, cfg.bc_len, p);
+    }
     *p++ = '\t';
   } else {
     *p++ = 'N';
@@ -430,11 +451,37 @@ __device__ __forceinline__ void pp_render(uint8_t *p, const PpRec &r, uint64_t b
     p = cm_put_u32(p, r.mapq);
     *p++ = '\t';
     *p++ = r.dir ? '+' : '-';
-    if (cfg.kind == CMGPU_TEXT_TAGALIGN_SE_BC) { *p = '\n'; return; }
+    if (cfg.kind == CMGPU_TEXT_TAGALIGN_SE_BC) { *p = '\n'; return col; }
     *p++ = '\t';
   }
   p = cm_put_u32(p, dups);
   *p = '\n';
+  return col;
+}
+
+// A block whose lines do not fit the LDS staging (translated names of a few hundred bytes) writes them to the text directly.  The
+// fixed columns are a few bytes per line and stay with the line's lane; the translated barcode is the bulk of such a line, and a
+// lane that copied it alone would issue one single-byte store per byte, each lane of the wave to a different line.  Instead every
+// wave takes its 64 lines one after the other and all lanes copy the line's `to` strings, consecutive bytes to consecutive lanes
+// (the SAM writer's lanes-per-line copy, cm_sam_post.hip: sp_copy, without its word-wide middle: the strings start anywhere).
+// col: where this lane's line left room for the column (nullptr: no line); every lane of the block calls this
+__device__ __forceinline__ void pp_fill_columns(uint8_t *col, uint64_t bcv, const PpCfg &cfg) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t nseg = cfg.bc_len / cfg.bt.from_len;
+  for (unsigned long long m = __ballot(col != nullptr); m; m &= m - 1) {
+    const int src = __ffsll((long long)m) - 1;
+    uint8_t *d = reinterpret_cast<uint8_t *>(__shfl((unsigned long long)(uintptr_t)col, src, 64));
+    const uint64_t key = __shfl((unsigned long long)bcv, src, 64);
+    for (uint32_t i = 0; i < nseg; ++i) {
+      if (i) { if (lane == 0) *d = '-'; ++d; }
+      const uint64_t v = cm_bt_find(cfg.bt, cm_bt_seed(cfg.bt, key, nseg, i));  // (the same bucket for every lane: one request)
+      if (v == CM_BT_EMPTY) continue;
+      const uint8_t *s = cfg.bt.blob + (v >> 32);
+      const uint32_t l = (uint32_t)v;
+      for (uint32_t t = lane; t < l; t += 64) d[t] = s[t];
+      d += l;
+    }
+  }
 }
 
 __global__ __launch_bounds__(PP_BLOCK) void k_pp_format(const uint8_t *__restrict__ store, const uint64_t *__restrict__ bc,
@@ -447,13 +494,17 @@ __global__ __launch_bounds__(PP_BLOCK) void k_pp_format(const uint8_t *__restric
   const uint32_t jend = j0 + PP_BLOCK < n ? j0 + PP_BLOCK : n;
   const uint64_t base = line_off[j0], total = line_off[jend] - base;
   const bool staged = total <= PP_LDS_BYTES;
+  const bool by_waves = !staged && cfg.bt.tab != nullptr;  // (the whole block's)
+  uint8_t *col = nullptr;
+  uint64_t bcv = 0;
   if (j < n && line_len[j]) {
     PpRec r = pp_load(store, win[j]);
     if (cfg.tn5) pp_tn5(r, cfg.kind);
     const uint64_t off = line_off[j];
-    pp_render(staged ? lds + (off - base) : text + off, r, pp_has_bc(cfg.kind) ? bc[win[j]] : 0, dups[j], cfg, names,
-              name_off);
+    bcv = pp_has_bc(cfg.kind) ? bc[win[j]] : 0;
+    col = pp_render(staged ? lds + (off - base) : text + off, r, bcv, dups[j], cfg, names, name_off, by_waves, (uint32_t)line_len[j]);
   }
+  if (by_waves) pp_fill_columns(col, bcv, cfg);
   if (!staged) return;
   __syncthreads();
   // coalesced copy LDS -> text: bytes up to the first 16-byte boundary, aligned body, tail
@@ -635,6 +686,10 @@ extern "C" int cmgpu_store_format(cmgpu_ctx *c, int kind, const char *const *nam
     for (int r = c->ex.rank + 1; r < c->ex.world; ++r) if (c->ex.owned_by[r]) cfg.last_section = 0;
   cfg.wl = (const uint64_t *)c->wl.p;
   cfg.wl_mask = c->wl_mask;
+  // the translation table belongs to the kinds that print a barcode; every other kind runs as without one
+  const bool translate = c->bt_entries != 0 && pp_prints_bc(kind);
+  cfg.bt = translate ? cm_bt_dev(c) : CmBtDev{nullptr, nullptr, 0, 0};
+  cfg.bt_miss = nullptr;
   if (cfg.bulk && c->wl_size == 0) { cm_set_error(c, "bulk-level duplicate removal needs the whitelist abundances (cmgpu_set_whitelist)"); return CMGPU_EINVAL; }
   CmTextJob job;
   int rc;
@@ -664,6 +719,11 @@ extern "C" int cmgpu_store_format(cmgpu_ctx *c, int kind, const char *const *nam
   if (longs.ensure(((size_t)n / PP_RUN_SERIAL + 2) * 4)) return job.enomem("post-processing");
   uint32_t *long_cnt = (uint32_t *)longs.p, *long_list = long_cnt + 1;
   if (hipMemsetAsync(long_cnt, 0, 4, s) != hipSuccess) { cm_set_error(c, "memset failed"); return CMGPU_EHIP; }
+  // --barcode-translate: the selection counts the printed lines whose barcode the table lacks in the job's spare count word
+  if (translate) {
+    if ((rc = job.zero_counts())) return rc;
+    cfg.bt_miss = job.extra_word();
+  }
   // --summary: the selection credits every run to its survivor's barcode.  The keys are in the table since their reads were counted;
   // a store filled by the multi-GPU exchange also holds records of reads another context counted
   CmSmDev sm;
@@ -673,8 +733,9 @@ extern "C" int cmgpu_store_format(cmgpu_ctx *c, int kind, const char *const *nam
                      (uint32_t *)dups.p, (uint64_t *)job.llen.p, long_list, long_cnt, sm);
   hipLaunchKernelGGL(k_pp_select_long, dim3(1024), dim3(64), 0, s, store, bc, (const uint32_t *)job.idx(), n, cfg, job.seq_off(),
                      (uint32_t *)win.p, (uint32_t *)dups.p, (uint64_t *)job.llen.p, (const uint32_t *)long_list, (const uint32_t *)long_cnt, sm);
-  uint64_t total = 0, lines = 0;
-  if ((rc = job.scan_lines(&total, &lines))) return rc;
+  uint64_t total = 0, lines = 0, misses = 0;
+  if ((rc = job.scan_lines(&total, &lines, translate ? &misses : nullptr))) return rc;
+  if (misses) { cm_set_error(c, CM_BT_MISS_MESSAGE); return CMGPU_EFORMAT; }  // (no text: text_bytes is 0 since the call began)
   if ((rc = job.alloc_text(total))) return rc;
   // ---- format
   hipLaunchKernelGGL(k_pp_format, g, b, 0, s, store, bc, (const uint32_t *)win.p, (const uint32_t *)dups.p, (const uint64_t *)job.llen.p,

@@ -169,6 +169,7 @@ struct SpCfg {
   uint32_t n_seq, bc_len, base;   // sequences of the reference; barcode length (0: bulk); read id of the read store's first read
   uint64_t n_reads;               // reads per mate in the read store
   int mapq_thr, dedup;            // dedup: 0 off, 1 low-memory rule (first record of the run's largest MAPQ), 2 in-memory rule (last of the run)
+  CmBtDev bt;                     // --barcode-translate: the CB:Z: value through the table (bt.tab == nullptr: Seed2Sequence)
 };
 struct SpReads {  // the read store, per mate (cm_ingest.hip)
   const uint8_t *names[2], *bases[2], *quals[2];
@@ -210,7 +211,8 @@ __device__ __forceinline__ uint32_t sp_seq_len(const SpRec &r, const uint32_t *_
 __global__ __launch_bounds__(SP_BLOCK) void k_sp_len(const uint8_t *__restrict__ rec, const uint64_t *__restrict__ bc, const uint8_t *__restrict__ var,
                                                        const uint64_t *__restrict__ var_offs, const uint32_t *__restrict__ idx, uint32_t n, SpCfg cfg,
                                                        SpReads rs, const uint32_t *__restrict__ name_off, uint64_t *__restrict__ line_len,
-                                                       unsigned long long *__restrict__ n_foreign, CmSmDev sm) {
+                                                       unsigned long long *__restrict__ counts, CmSmDev sm) {
+  // counts[0]: records that belong to no read of the read store; counts[1]: lines whose barcode the translation table does not have
   const uint32_t j = blockIdx.x * SP_BLOCK + threadIdx.x;
   if (j >= n) return;
   const uint32_t i = idx[j];
@@ -218,7 +220,7 @@ __global__ __launch_bounds__(SP_BLOCK) void k_sp_len(const uint8_t *__restrict__
   const uint64_t q = (uint64_t)(r.read_id - cfg.base);
   // a record whose read is not in the read store, or whose mate lies on a sequence the reference does not have: the stores are not of one
   // run -- counted, and the call fails (no line is written for it: the kernels never index past a store)
-  if (q >= cfg.n_reads || (r.mrid >= 0 && (uint32_t)r.mrid >= cfg.n_seq)) { atomicAdd(n_foreign, 1ull); line_len[j] = 0; return; }
+  if (q >= cfg.n_reads || (r.mrid >= 0 && (uint32_t)r.mrid >= cfg.n_seq)) { atomicAdd(counts, 1ull); line_len[j] = 0; return; }
   if (sm.keys && r.rid < cfg.n_seq) {
     // --summary (mapping_writer.h:281-301, 420-432): the first record of an operator== run (every record without duplicate removal) counts
     // the run under its barcode; the run's last record has its largest MAPQ, the survivor's under either rule.  Both mates of a pair are
@@ -259,6 +261,10 @@ __global__ __launch_bounds__(SP_BLOCK) void k_sp_len(const uint8_t *__restrict__
     }
     if (!win) { line_len[j] = 0; return; }
   }
+  // the record is printed: only now does a barcode the translation table lacks count (the reference exits in Translate, which it
+  // calls for a mapping it is about to print)
+  uint32_t cb_len = cfg.bc_len;
+  if (cfg.bc_len && cfg.bt.tab && !cm_bt_length(cfg.bt, bc[i], cfg.bc_len, &cb_len)) { atomicAdd(counts + 1, 1ull); line_len[j] = 0; return; }
   const uint32_t mate = r.valid - 1u;
   uint32_t cig_text;
   const uint32_t sl = sp_seq_len(r, reinterpret_cast<const uint32_t *>(var + var_offs[i]), &cig_text);
@@ -267,7 +273,7 @@ __global__ __launch_bounds__(SP_BLOCK) void k_sp_len(const uint8_t *__restrict__
   const uint32_t tl = r.tlen < 0 ? 1u + cm_digits10((uint32_t)(-(int64_t)r.tlen)) : cm_digits10((uint32_t)r.tlen);
   line_len[j] = (uint64_t)nm_len + 1 + cm_digits10(r.flag) + 1 + (name_off[r.rid + 1] - name_off[r.rid]) + 1 + cm_digits10(r.pos + 1) + 1 + cm_digits10(r.mapq) + 1 +
                 cig_text + 1 + rnext + 1 + cm_digits10(r.mrid < 0 ? 0u : r.mpos + 1) + 1 + tl + 1 + sl + 1 + sl + 6 + cm_digits10(r.nm) + 6 + r.md_len +
-                (cfg.bc_len ? 6 + cfg.bc_len : 0) + 1;
+                (cfg.bc_len ? 6 + cb_len : 0) + 1;
 }
 
 // the group's lanes copy len bytes to dst: single bytes up to dst's next 4-byte boundary, then whole words, a word per lane and step (the
@@ -341,6 +347,18 @@ __global__ __launch_bounds__(SP_BLOCK) void k_sp_format(const uint8_t *__restric
   uint8_t *rname_at = mid + 1 + cm_digits10(r.flag) + 1;
   sp_copy<0, G>(rname_at, names + rn0, rn1 - rn0, lane);
   if (other) sp_copy<0, G>(rname_at + (rn1 - rn0) + 1 + cm_digits10(r.pos + 1) + 1 + cm_digits10(r.mapq) + 1 + cig_text + 1, names + mn0, mn1 - mn0, lane);
+  if (cfg.bc_len && cfg.bt.tab) {  // the translated CB:Z: value: the group copies the `to` strings, lane 0 puts the dashes between them
+    uint8_t *d = tail + 6 + cm_digits10(r.nm) + 6 + r.md_len + 6;
+    const uint64_t key = bc[i];
+    const uint32_t nseg = cfg.bc_len / cfg.bt.from_len;
+    for (uint32_t sg = 0; sg < nseg; ++sg) {
+      if (sg) { if (lane == 0) *d = '-'; ++d; }
+      const uint64_t v = cm_bt_find(cfg.bt, cm_bt_seed(cfg.bt, key, nseg, sg));
+      if (v == CM_BT_EMPTY) continue;
+      sp_copy<0, G>(d, cfg.bt.blob + (v >> 32), (uint32_t)v, lane);
+      d += (uint32_t)v;
+    }
+  }
   if (lane == 0) {
     uint8_t *p = mid;
     *p++ = '\t';
@@ -371,8 +389,11 @@ __global__ __launch_bounds__(SP_BLOCK) void k_sp_format(const uint8_t *__restric
     p += r.md_len;
     if (cfg.bc_len) {
       *p++ = '\t'; *p++ = 'C'; *p++ = 'B'; *p++ = ':'; *p++ = 'Z'; *p++ = ':';
-      const uint64_t key = bc[i];
-      for (uint32_t b = 0; b < cfg.bc_len; ++b) *p++ = "ACGT"[(key >> ((cfg.bc_len - 1 - b) * 2)) & 3];  // Seed2Sequence
+      if (cfg.bt.tab) p = line + line_len[j] - 1;  // (the value: the group's copy above)
+      else {
+        const uint64_t key = bc[i];
+        for (uint32_t b = 0; b < cfg.bc_len; ++b) *p++ = "ACGT"[(key >> ((cfg.bc_len - 1 - b) * 2)) & 3];  // Seed2Sequence
+      }
     }
     *p = '\n';
   }
@@ -412,25 +433,27 @@ extern "C" int cmgpu_store_format_sam(cmgpu_ctx *c, const char *const *ref_names
   SpCfg cfg;
   cfg.n_seq = n_sequences; cfg.bc_len = st.has_bc ? barcode_length : 0; cfg.base = c->rd_base; cfg.n_reads = c->rd_n;
   cfg.mapq_thr = p->mapq_threshold; cfg.dedup = p->remove_pcr_duplicates ? (p->low_memory_mode ? 1 : 2) : 0;
+  cfg.bt = st.has_bc ? cm_bt_dev(c) : CmBtDev{nullptr, nullptr, 0, 0};
   SpReads rs;
   for (int m = 0; m < 2; ++m) {
     const CmReadMate &r = c->rd[st.paired ? m : 0];
     rs.names[m] = (const uint8_t *)r.names.p; rs.bases[m] = (const uint8_t *)r.bases.p; rs.quals[m] = (const uint8_t *)r.quals.p;
     rs.name_offs[m] = (const uint64_t *)r.name_offs.p; rs.offs[m] = (const uint64_t *)r.offs.p;
   }
-  // the job's second count word: records that belong to no read of the read store (k_sp_len)
+  // the job's spare count words: records that belong to no read of the read store, and lines whose barcode the translation table lacks (k_sp_len)
   if ((rc = job.zero_counts())) return rc;
   CmSmDev sm;  // --summary: the length kernel credits every run to its barcode (the keys are in the table since their reads were counted)
   if ((rc = cm_summary_dev(c, 0, 0, !st.has_bc, &sm))) return rc;
   hipLaunchKernelGGL(k_sp_len, g, b, 0, s, rec, bc, (const uint8_t *)st.var.p, (const uint64_t *)st.var_offs.p, (const uint32_t *)job.idx(), n, cfg, rs,
                      job.seq_off(), (uint64_t *)job.llen.p, job.extra_word(), sm);
-  uint64_t total = 0, lines = 0, foreign = 0;
-  if ((rc = job.scan_lines(&total, &lines, &foreign))) return rc;
+  uint64_t total = 0, lines = 0, foreign = 0, misses = 0;
+  if ((rc = job.scan_lines(&total, &lines, &foreign, &misses))) return rc;
   if (foreign) {
     cm_set_error(c, std::to_string((unsigned long long)foreign) + " SAM records belong to no read of the read store (reads " + std::to_string(c->rd_base) + " .. " +
                         std::to_string((unsigned long long)c->rd_base + c->rd_n) + ") or to a mate sequence the reference does not have: the record store and the read store are not of one run");
     return CMGPU_EINVAL;
   }
+  if (misses) { cm_set_error(c, CM_BT_MISS_MESSAGE); return CMGPU_EFORMAT; }  // (no text: text_bytes is 0 since the call began)
   // (the sort's buffers go before the text comes: a realistic run's text is several GB)
   job.release_sort();
   if ((rc = job.alloc_text(total, "SAM text: " + std::to_string((unsigned long long)total) + " bytes"))) return rc;

@@ -12,6 +12,7 @@
 #include <utility>
 #include <vector>
 
+#include "cm_barcode_translate.h"
 #include "cm_ctx.h"
 #include "cm_summary.h"
 
@@ -24,6 +25,18 @@ __device__ __forceinline__ uint8_t *cm_put_u32(uint8_t *p, uint32_t v) {
   for (uint32_t i = d; i-- > 0;) { p[i] = (uint8_t)('0' + v % 10); v /= 10; }
   return p + d;
 }
+
+// the context's barcode translation table as the kernels take it (cm_api.hip: cmgpu_set_barcode_translation); none: tab == nullptr
+static inline CmBtDev cm_bt_dev(const cmgpu_ctx *c) {
+  CmBtDev t;
+  t.tab = c->bt_entries ? (const uint64_t *)c->bt_tab.p : nullptr;
+  t.blob = (const uint8_t *)c->bt_blob.p;
+  t.mask = c->bt_mask;
+  t.from_len = c->bt_from;
+  return t;
+}
+// the message of a barcode the table does not have: the reference's own (barcode_translator.h:87)
+#define CM_BT_MISS_MESSAGE "Barcode does not exist in the translation table."
 
 struct CmLinesOp {  // a line length -> 1 line, or none
   __host__ __device__ uint64_t operator()(uint64_t l) const { return l ? 1 : 0; }
@@ -51,7 +64,7 @@ struct CmTextJob {
   std::vector<uint32_t> noff;
   CmTmpBuf names, name_off;        // the sequence names back to back, their n_sequences + 1 offsets
   CmTmpBuf k0, k1, v0, v1, tmp;    // sort: keys in / out, index in / out, work area (the scan's and the reduction's too)
-  CmTmpBuf llen, loff, count;      // n + 1 line lengths, their offsets; two 64-bit words: lines, and one for the writer
+  CmTmpBuf llen, loff, count;      // n + 1 line lengths, their offsets; three 64-bit words: lines, and two for the writer
   uint64_t *ka = nullptr, *kb = nullptr;
   uint32_t *va = nullptr, *vb = nullptr;
 
@@ -73,14 +86,15 @@ struct CmTextJob {
     while (rid_bits < 32 && (1ull << rid_bits) < (uint64_t)n_sequences + rid_extra) ++rid_bits;
     return CMGPU_OK;
   }
-  // the line arrays and the two count words (a writer that frees the sort's buffers before its selection asks for them only then)
+  // the line arrays and the three count words (a writer that frees the sort's buffers before its selection asks for them only then)
   int alloc_lengths() {
-    return llen.ensure(((size_t)n + 1) * 8) || loff.ensure(((size_t)n + 1) * 8) || count.ensure(16) ? enomem("post-processing") : CMGPU_OK;
+    return llen.ensure(((size_t)n + 1) * 8) || loff.ensure(((size_t)n + 1) * 8) || count.ensure(24) ? enomem("post-processing") : CMGPU_OK;
   }
-  // the second count word is the writer's: zero_counts before its kernels count in *extra_word(), scan_lines brings the value back
+  // the second and third count words are the writer's: zero_counts before its kernels count in extra_word()[0] and [1], scan_lines
+  // brings the values back
   unsigned long long *extra_word() const { return (unsigned long long *)count.p + 1; }
   int zero_counts() {
-    if (hipMemsetAsync(count.p, 0, 16, s) != hipSuccess) { cm_set_error(c, "memset failed"); return CMGPU_EHIP; }
+    if (hipMemsetAsync(count.p, 0, 24, s) != hipSuccess) { cm_set_error(c, "memset failed"); return CMGPU_EHIP; }
     return CMGPU_OK;
   }
 
@@ -103,8 +117,8 @@ struct CmTextJob {
   }
 
   // line lengths -> offsets, bytes and lines of the text; waits for the stream, after which the count words are released.
-  // word1: receives the second count word (extra_word)
-  int scan_lines(uint64_t *total, uint64_t *lines, uint64_t *word1 = nullptr) {
+  // word1, word2: receive the second and third count words (extra_word)
+  int scan_lines(uint64_t *total, uint64_t *lines, uint64_t *word1 = nullptr, uint64_t *word2 = nullptr) {
     const uint64_t *len = (const uint64_t *)llen.p;
     if (hipMemsetAsync((uint64_t *)llen.p + n, 0, 8, s) != hipSuccess) { cm_set_error(c, "memset failed"); return CMGPU_EHIP; }
     size_t tb2 = 0;
@@ -115,6 +129,7 @@ struct CmTextJob {
     if (e == hipSuccess) e = hipMemcpyAsync(total, (uint64_t *)loff.p + n, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(lines, count.p, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && word1) e = hipMemcpyAsync(word1, (uint64_t *)count.p + 1, 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && word2) e = hipMemcpyAsync(word2, (uint64_t *)count.p + 2, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = cm_stream_sync(s);
     count.release();
     if (e != hipSuccess) { cm_set_error(c, std::string("post-processing scan: ") + hipGetErrorString(e)); return CMGPU_EHIP; }

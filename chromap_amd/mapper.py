@@ -362,6 +362,30 @@ class ChromapGPU:
         C.CDLL(None).free(keys)
         self.barcode_length = barcode_length
 
+    def set_barcode_translation(self, text_or_path):
+        """--barcode-translate on the device: from now on store_format (the barcoded BED kinds) and store_format_sam (CB:Z:) print
+        the table's names.  bytes: the table's text (lines "to<TAB or ,>from"); str: the path of the file, gzip-compressed or plain;
+        None clears the table.  A printed barcode the table lacks makes the format call raise ChromapError (CMGPU_EFORMAT,
+        "Barcode does not exist in the translation table.")"""
+        text = text_or_path
+        if isinstance(text_or_path, str):
+            with open(text_or_path, "rb") as f:
+                text = f.read()
+            if text[:2] == b"\x1f\x8b":
+                import gzip
+                text = gzip.decompress(text)
+        if text is None:
+            self._check(self.L.cmgpu_set_barcode_translation(self.ctx, None, 0), self.ctx)
+        else:
+            text = bytes(text)
+            self._check(self.L.cmgpu_set_barcode_translation(self.ctx, text, len(text)), self.ctx)
+
+    def barcode_translation_info(self):
+        """(entries, length of a `from` segment, bytes of HBM the table takes); (0, 0, 0) without a table"""
+        n, fl, nb = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+        self._check(self.L.cmgpu_barcode_translation_info(self.ctx, C.byref(n), C.byref(fl), C.byref(nb)), self.ctx)
+        return int(n.value), int(fl.value), int(nb.value)
+
     def compute_barcode_abundance(self, bc, bco):
         bc = np.ascontiguousarray(bc, dtype=np.uint8)
         bco = np.ascontiguousarray(bco, dtype=np.uint32)

@@ -473,6 +473,42 @@ int cmgpu_store_format_sam(cmgpu_ctx *ctx, const char *const *ref_names, const u
                            const cmgpu_params *params, uint32_t barcode_length, uint64_t *n_lines, uint64_t *n_bytes);
 int cmgpu_write_sam_header(const char *const *ref_names, const uint32_t *ref_lengths, uint32_t n_sequences, const char *out_path);
 
+/* ---- --barcode-translate on the device (src/barcode_translator.h:42-101) -----------------------
+ * A translation table per context, held in HBM: with one set, cmgpu_store_format writes column 4 of CMGPU_TEXT_BED_PE_BC /
+ * CMGPU_TEXT_BED_SE_BC, and cmgpu_store_format_sam the CB:Z: value, as the table's names instead of ACGT (TagAlign and pairs
+ * print no barcode; every other kind gives the bytes it gives without a table).  n_bytes and n_lines are the translated text's.
+ *   table_text   the inflated text of the file (the caller does the gzopen): lines "to<TAB or ,>from".  The key is the 2-bit
+ *                packing of `from` (other letters count as A); the last line of a repeated key wins; the LAST line's `from`
+ *                length is the segment length; a line without a separator is skipped; `to` may be empty.  No usable line:
+ *                CMGPU_EINVAL.  NULL / 0 clears the table.
+ *   segments     a barcode of L bases is translated as L / from_length segments joined by '-', cut with the reference's shifts
+ *                seed_i = ((key << (2 * i * from)) >> (2 * (n - 1) * from)) & mask on 64-bit values (:80-83) -- also where L is
+ *                no multiple of from_length.  from_length > L: the column is empty.
+ *   a miss       a line that would be printed (after duplicate removal, the MAPQ filter and the sequence check) whose barcode
+ *                has a segment the table lacks: the format call returns CMGPU_EFORMAT, cmgpu_last_error is the reference's
+ *                "Barcode does not exist in the translation table." and no text is published (cmgpu_store_info: 0 bytes).
+ *   HBM          16 bytes per bucket, a power of two of buckets >= 2 x entries (>= 16), + the bytes of the `to` names.
+ * cmgpu_copy_barcode_translation: the table of another context (one context per GPU, like cmgpu_copy_whitelist); a source
+ * without a table clears the destination's. */
+int cmgpu_set_barcode_translation(cmgpu_ctx *ctx, const char *table_text, uint64_t n_bytes);
+int cmgpu_barcode_translation_info(const cmgpu_ctx *ctx, uint32_t *n_entries, uint32_t *from_length, uint64_t *n_bytes_hbm);
+int cmgpu_copy_barcode_translation(cmgpu_ctx *dst, cmgpu_ctx *src);
+/* The image cmgpu_set_barcode_translation uploads, made without a device (a pure host function):
+ *   buckets   2 x uint64 each, {key, to_offset << 32 | to_length}; a VALUE word of all ones marks an empty bucket (all ones is a
+ *             legal key: 32 T's).  *n_buckets is a power of two >= 2 x entries (>= 16).  A key is in the first free bucket from
+ *             ((key * 0x9E3779B97F4A7C15) >> 32) & (n_buckets - 1) onwards, wrapping at the table's end; keys are inserted in
+ *             increasing order.
+ *   blob      the `to` names back to back (no terminators), *blob_bytes of them
+ * buckets == NULL (or blob == NULL with names to store): sizes only.  bucket_capacity (in buckets) or blob_capacity too small:
+ * CMGPU_ECAPACITY with the sizes reported.  No usable line: CMGPU_EINVAL. */
+int cmgpu_barcode_translation_pack(const char *table_text, uint64_t n_bytes, uint64_t *buckets, uint64_t bucket_capacity, char *blob,
+                                   uint64_t blob_capacity, uint64_t *n_buckets, uint64_t *blob_bytes, uint32_t *from_length);
+/* One barcode key through a packed image on the host, with the lookup, segment and render functions the device writers use:
+ * out receives the translated column (*n_out bytes, no terminator).  A segment the table lacks: CMGPU_EFORMAT; capacity < *n_out:
+ * CMGPU_ECAPACITY with *n_out set. */
+int cmgpu_barcode_translate_host(const uint64_t *buckets, uint64_t n_buckets, const char *blob, uint32_t from_length, uint64_t barcode_key,
+                                 uint32_t barcode_length, char *out, uint64_t capacity, uint64_t *n_out);
+
 /* ---- device-side post-processing -------------------------------------
  * Replaces, for BED output: MappingProcessor::SortOutputMappings / RemovePCRDuplicate
  * (src/mapping_processor.h:100-202), the low-memory merge's duplicate handling
