@@ -791,13 +791,14 @@ __device__ __forceinline__ bool cm_rescue_is_wave(const CmDev &d, uint32_t r, ui
 // The list is kept in CM_RS_SEGS segments, each with a counter on a cache line of its own: same-address device atomics
 // retire at ~90 per microsecond (one per wave of an 8 M-read batch on ONE counter measured 1.4 ms); a block appends with
 // one atomic to segment blockIdx % CM_RS_SEGS.  Segment g starts at rs_list + g * seg_cap.
+template <class M>
 __global__ __launch_bounds__(CM_BLOCK) void k_s4a_rescue_count(CmDev d, uint32_t n, uint32_t seg_cap, uint32_t coop) {
   __shared__ uint32_t sh_cnt, sh_base;
   if (threadIdx.x == 0) sh_cnt = 0;
   __syncthreads();
   const uint32_t i0 = blockIdx.x * CM_BLOCK + threadIdx.x;
   const uint32_t i = i0 < n && d.perm_reads ? d.perm_reads[i0] : i0;
-  const bool aug0 = i0 < n && cm_s4a_decide(d, i);
+  const bool aug0 = i0 < n && cm_s4a_decide<M>(d, i);
   // a read whose mate has many candidates goes to list 23 instead: a wave each (k_s4a_rescue_wave / k_s4b_rescue_wave)
   const bool wv = aug0 && cm_rescue_is_wave(d, i, coop);
   cm_wave_append(d.hv_list + (size_t)CM_L_SEARCH_WAVE * d.hv_stride, d.hv_cnt + CM_L_SEARCH_WAVE, wv, i);
@@ -1100,11 +1101,12 @@ __global__ __launch_bounds__(G < CM_BLOCK ? CM_BLOCK : G) void k_s4b_coop(CmDev 
 #define CM_S5C_P_SMALL 512u   // most reads of the wave class: work arrays of this size (more waves per CU)
 #define CM_S5C_P_WAVE 2048u   // candidates of a strand the wave's work arrays hold
 #define CM_S5C_P_BLOCK 16384u // ... a block's (longer lists: the acceptance loop by one lane)
+template <class M = CmModeAny>
 __device__ __forceinline__ void cm_s4c_queue_sort(const CmDev &d, uint32_t pair, bool live, uint32_t coop) {
   for (uint32_t q = 0; q < 4; ++q) {  // (read, strand) lists of the pair
     const uint32_t r = 2 * pair + (q >> 1);
     uint32_t cnt = live ? ((q & 1u) ? d.fcn[r] : d.fcp[r]) : 0u;
-    if ((coop & 8u) && !d.p.split && live && d.fcp[r] + d.fcn[r] > CM_S5C_COOP_MIN) cnt = 0;  // the S5 waves sort this read's lists themselves
+    if ((coop & 8u) && !M::split(d) && live && d.fcp[r] + d.fcn[r] > CM_S5C_COOP_MIN) cnt = 0;  // the S5 waves sort this read's lists themselves
     cm_wave_append(d.srt_list, &d.srt_cnt[0], cnt > CM_SORT_SERIAL_MAX && cnt <= CM_SORT_WAVE_MAX, (r << 1) | (q & 1u));
   }
 }
@@ -1113,12 +1115,13 @@ __device__ __forceinline__ void cm_s4c_queue_sort(const CmDev &d, uint32_t pair,
 #define CM_S4C_P_BLOCK 4096u  // ... of a block
 #define CM_S4C_P_BIG 15360u   // ... of a block of 1024 lanes that leaves the position lists in global memory (a lane walking such a
                               // pair's two-pointer loop at global latency was the whole 16 ms of k_s4c_reduce on the mosaic genome)
+template <class M>
 __global__ __launch_bounds__(CM_BLOCK) void k_s4c_reduce(CmDev d, uint32_t n, uint32_t coop) {
   if (d.abort && *d.abort) return;
   const uint32_t i = blockIdx.x * CM_BLOCK + threadIdx.x;
   const uint32_t pair = i < n ? (d.perm_pairs ? d.perm_pairs[i] : i) : 0u;
   uint32_t cls = 0;
-  if (i < n && cm_s4c_pre(d, pair)) {
+  if (i < n && cm_s4c_pre<M>(d, pair)) {
     const uint32_t r1 = 2 * pair, r2 = r1 + 1;
     uint32_t big = d.mcp[r1] > d.mcn[r1] ? d.mcp[r1] : d.mcn[r1];
     big = d.mcp[r2] > big ? d.mcp[r2] : big;
@@ -1133,7 +1136,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_s4c_reduce(CmDev d, uint32_t n, ui
     cm_wave_append(d.hv_list + CM_L_PF_HUGE * (size_t)d.hv_stride, d.hv_cnt + CM_L_PF_HUGE, cls == CM_L_PF_HUGE, pair);
   }
   if (!d.perm_pairs) return;  // the queue is only served in a batch with heavy reads
-  cm_s4c_queue_sort(d, pair, i < n && !cls && d.alive[pair], coop);
+  cm_s4c_queue_sort<M>(d, pair, i < n && !cls && d.alive[pair], coop);
 }
 // the pairs of list 9 / 14: the filter's two directions by a wave / a block each (cm_coop_s4c); the list's length is on the device
 template <int G, bool STAGED>
@@ -1165,11 +1168,12 @@ __global__ __launch_bounds__(G < CM_BLOCK ? CM_BLOCK : G) void k_s4c_coop(CmDev 
   }
 }
 // S5a.  coop: a read with more than CM_S5C_COOP_MIN candidates is left to a wave -- alignments and acceptance loop (k_s5c_coop, list 12)
+template <class M>
 __global__ __launch_bounds__(CM_BLOCK) void k_s5a_prepare(CmDev d, uint32_t n, uint32_t coop) {
   if (d.abort && *d.abort) return;
   const uint32_t i = blockIdx.x * CM_BLOCK + threadIdx.x;
   const uint32_t r = i < n ? (d.perm_reads ? d.perm_reads[i] : i) : 0u;
-  const bool to_wave = i < n && cm_s5a_prepare(d, r, coop ? CM_S5C_COOP_MIN : 0u);
+  const bool to_wave = i < n && cm_s5a_prepare<M>(d, r, coop ? CM_S5C_COOP_MIN : 0u);
   // list 12: a wave per read; list 22: a block per read -- a strand's list is longer than the wave's work arrays
   const bool big = to_wave && (d.fcp[r] > CM_S5C_P_WAVE || d.fcn[r] > CM_S5C_P_WAVE);
   const bool small = to_wave && d.fcp[r] <= CM_S5C_P_SMALL && d.fcn[r] <= CM_S5C_P_SMALL;  // list 28: a quarter of the work arrays
@@ -1180,13 +1184,14 @@ __global__ __launch_bounds__(CM_BLOCK) void k_s5a_prepare(CmDev d, uint32_t n, u
   }
 }
 // S5c; long draft-mapping lists are queued for k_sort_lists (S6a sorts them by position; split alignment keeps emission order)
+template <class M>
 __global__ __launch_bounds__(CM_BLOCK) void k_s5c_finalize(CmDev d, uint32_t n, uint32_t coop) {
   if (d.abort && *d.abort) return;
   const uint32_t i = blockIdx.x * CM_BLOCK + threadIdx.x;
   const uint32_t r = i < n ? (d.perm_reads ? d.perm_reads[i] : i) : 0u;
   const uint32_t cmin = coop ? CM_S5C_COOP_MIN : 0u;
   if (i < n) cm_s5c_finalize(d, r, cmin);
-  if (!d.perm_reads || d.p.split || d.p.single) return;  // the queue is only served in a batch with heavy reads
+  if (!d.perm_reads || M::split(d) || M::single(d)) return;  // the queue is only served in a batch with heavy reads
   const bool live = i < n && !(cmin && d.nv[r] > cmin) && d.alive[r >> 1];  // (a wave's reads: sorted there)
   const uint32_t a = live ? d.ndp[r] : 0u, b = live ? d.ndn[r] : 0u;
   cm_wave_append(d.srt_list, &d.srt_cnt[0], a > CM_SORT_SERIAL_MAX && a <= CM_SORT_WAVE_MAX, r << 1);
@@ -1322,15 +1327,20 @@ __device__ __forceinline__ uint32_t cm_s6_class(const CmDev &d, uint32_t pair, u
   if (big <= CM_S6A_COOP_MIN) return 0;
   return big2 <= CM_S6A_P_SMALL ? small_list : big2 <= CM_S6A_P_WAVE ? wave_list : block_list;
 }
+// The paired-end instance also lists the pairs S6c has to look at (list 24): those it found more than one best pairing for, and
+// those it leaves to a group, whose n_best is not known yet.  k_s6c_list then visits these few instead of every pair.
+template <class M>
 __global__ __launch_bounds__(CM_BLOCK) void k_s6a_pair(CmDev d, uint32_t n, uint32_t coop) {
   if (d.abort && *d.abort) return;
   const uint32_t i = blockIdx.x * CM_BLOCK + threadIdx.x;
   const uint32_t pair = i < n ? (d.perm_pairs ? d.perm_pairs[i] : i) : 0u;
   uint32_t cls = 0;
-  if (i < n && cm_s6a_pre<false>(d, pair)) {
+  bool multi = false;
+  if (i < n && cm_s6a_pre<false, M>(d, pair)) {
     cls = coop ? cm_s6_class(d, pair, CM_L_S6A_SMALL, CM_L_S6A_WAVE, CM_L_S6A_BLOCK) : 0u;
-    if (!cls) cm_s6a_sweeps<false>(d, pair);
+    multi = cls != 0 || cm_s6a_sweeps<false>(d, pair) > 1;  // (the count in a register: no load behind the store to pe_nbest)
   }
+  if constexpr (M::kPe) cm_wave_append(d.hv_list + (size_t)CM_L_S6C_MULTI * d.hv_stride, d.hv_cnt + CM_L_S6C_MULTI, multi, pair);
   if (coop) {
     cm_wave_append(d.hv_list + (size_t)CM_L_S6A_SMALL * d.hv_stride, d.hv_cnt + CM_L_S6A_SMALL, cls == CM_L_S6A_SMALL, pair);
     cm_wave_append(d.hv_list + (size_t)CM_L_S6A_WAVE * d.hv_stride, d.hv_cnt + CM_L_S6A_WAVE, cls == CM_L_S6A_WAVE, pair);
@@ -1354,19 +1364,34 @@ __global__ __launch_bounds__(CM_BLOCK, 6) void k_s6a_coop(CmDev d, uint32_t P, u
 // S6c.  coop: a multi-mapped pair with a draft-mapping list longer than CM_S6A_COOP_MIN goes to list 17 (a wave) / 20 (a block),
 // where the group finds the sampled pairings (cm_coop_s6c) -- one lane repeating both pairing sweeps over lists of hundreds of
 // entries held its wave for the whole kernel (k_s6c_multi 1.6 ms for 28 k multi-mapped pairs of the repeat workload)
-__global__ __launch_bounds__(CM_BLOCK) void k_s6c_multi(CmDev d, uint32_t n, uint32_t coop) {
-  if (d.abort && *d.abort) return;
-  const uint32_t i = blockIdx.x * CM_BLOCK + threadIdx.x;
-  const uint32_t pair = i < n ? (d.perm_pairs ? d.perm_pairs[i] : i) : 0u;
+// one pair of S6c: to its class's list, or the records of its sampled pairings by this lane (called by whole waves)
+template <class M>
+__device__ __forceinline__ void cm_s6c_item(const CmDev &d, bool mine, uint32_t pair, uint32_t coop) {
   uint32_t cls = 0;
-  if (i < n) {
-    if (coop && !d.p.single && !d.p.split && d.pe_nbest[pair] > 1) cls = cm_s6_class(d, pair, CM_L_S6C_SMALL, CM_L_S6C_WAVE, CM_L_S6C_BLOCK);
-    if (!cls) cm_s6c_multi<false>(d, pair);
+  if (mine) {
+    if (coop && !M::single(d) && !M::split(d) && d.pe_nbest[pair] > 1) cls = cm_s6_class(d, pair, CM_L_S6C_SMALL, CM_L_S6C_WAVE, CM_L_S6C_BLOCK);
+    if (!cls) cm_s6c_multi<false, M>(d, pair);
   }
   if (coop) {
     cm_wave_append(d.hv_list + (size_t)CM_L_S6C_SMALL * d.hv_stride, d.hv_cnt + CM_L_S6C_SMALL, cls == CM_L_S6C_SMALL, pair);
     cm_wave_append(d.hv_list + (size_t)CM_L_S6C_WAVE * d.hv_stride, d.hv_cnt + CM_L_S6C_WAVE, cls == CM_L_S6C_WAVE, pair);
     cm_wave_append(d.hv_list + (size_t)CM_L_S6C_BLOCK * d.hv_stride, d.hv_cnt + CM_L_S6C_BLOCK, cls == CM_L_S6C_BLOCK, pair);
+  }
+}
+__global__ __launch_bounds__(CM_BLOCK) void k_s6c_multi(CmDev d, uint32_t n, uint32_t coop) {
+  if (d.abort && *d.abort) return;
+  const uint32_t i = blockIdx.x * CM_BLOCK + threadIdx.x;
+  cm_s6c_item<CmModeAny>(d, i < n, i < n ? (d.perm_pairs ? d.perm_pairs[i] : i) : 0u, coop);
+}
+// the paired-end instance: over list 24 (k_s6a_pair), whose length is on the device -- the grid strides by whole blocks.  A pair of
+// the list takes one slot of list 24 and at most one of a class's list: never more than the pairs of the range
+__global__ __launch_bounds__(CM_BLOCK) void k_s6c_list(CmDev d, uint32_t coop) {
+  if (d.abort && *d.abort) return;
+  const uint32_t cnt = d.hv_cnt[CM_L_S6C_MULTI];
+  const uint32_t *list = d.hv_list + (size_t)CM_L_S6C_MULTI * d.hv_stride;
+  for (uint32_t j0 = blockIdx.x * CM_BLOCK; j0 < cnt; j0 += gridDim.x * CM_BLOCK) {
+    const uint32_t j = j0 + threadIdx.x;
+    cm_s6c_item<CmModePe>(d, j < cnt, j < cnt ? list[j] : 0u, coop);
   }
 }
 template <int G>
@@ -1963,8 +1988,11 @@ void cm_launch_k_s3b_candidates(const CmDev &d, uint32_t n, uint32_t max_read_le
 }
 // capacity of one list segment: the reads of every CM_RS_SEGS-th block
 uint32_t cm_rescue_seg_cap(uint32_t n_reads) { return ((n_reads + CM_BLOCK - 1) / CM_BLOCK / CM_RS_SEGS + 1) * CM_BLOCK; }
+// The paired-end instances serve a batch that is neither single-end nor split-aligned (cmgpu_set_option "generic_kernels": never)
+static inline bool cm_mode_pe(const CmDev &d) { return !d.p.split && !d.p.single && !d.generic_kernels; }
+#define CM_LAUNCH_MODE(kname, ...) do { if (cm_mode_pe(d)) hipLaunchKernelGGL(kname<CmModePe>, __VA_ARGS__); else hipLaunchKernelGGL(kname<CmModeAny>, __VA_ARGS__); } while (0)
 void cm_launch_k_s4a_rescue_count(const CmDev &d, uint32_t n, hipStream_t s, bool coop) {
-  if (n) hipLaunchKernelGGL(k_s4a_rescue_count, grid_for(n), dim3(CM_BLOCK), 0, s, d, n, cm_rescue_seg_cap(n), coop ? 1u : 0u);
+  if (n) CM_LAUNCH_MODE(k_s4a_rescue_count, grid_for(n), dim3(CM_BLOCK), 0, s, d, n, cm_rescue_seg_cap(n), coop ? 1u : 0u);
 }
 // list kernels: enough waves for every listed read of a typical batch to get a lane at once, grid-stride beyond that
 static inline uint32_t rescue_wave_blocks(uint32_t n_reads) {  // waves for list 23: a few per CU and more for large batches
@@ -2046,7 +2074,7 @@ void cm_launch_k_s4c_reduce(const CmDev &d, uint32_t n, hipStream_t s, uint32_t 
   if (!cm_lds_optin(&k_s4c_coop<CM_BLOCK, true>, gbk)) coop &= ~4u;
   CmDev d2 = d;
   d2.s4c_pbig = pbig > CM_S4C_P_BLOCK ? pbig : 0;
-  hipLaunchKernelGGL(k_s4c_reduce, grid_for(n), dim3(CM_BLOCK), 0, s, d2, n, coop);
+  CM_LAUNCH_MODE(k_s4c_reduce, grid_for(n), dim3(CM_BLOCK), 0, s, d2, n, coop);
   if (!(coop & 4u)) return;
   uint32_t blocks = n / 2048 + 64;
   if (blocks > 4096) blocks = 4096;
@@ -2059,7 +2087,7 @@ void cm_launch_k_s4c_reduce(const CmDev &d, uint32_t n, hipStream_t s, uint32_t 
 }
 void cm_launch_k_s5a_prepare(const CmDev &d, uint32_t n, hipStream_t s, bool coop) {
   if (!n) return;
-  hipLaunchKernelGGL(k_s5a_prepare, grid_for(n), dim3(CM_BLOCK), 0, s, d, n, coop ? 1u : 0u);
+  CM_LAUNCH_MODE(k_s5a_prepare, grid_for(n), dim3(CM_BLOCK), 0, s, d, n, coop ? 1u : 0u);
   if (coop) {  // the lists it left unsorted: a wave per read
     if (cm_cls_on(d, CM_L_S5_SMALL)) hipLaunchKernelGGL(k_s5_sort_coop, dim3(4096), dim3(CM_BLOCK), 0, s, d, CM_L_S5_SMALL);
     if (cm_cls_on(d, CM_L_S5_WAVE)) hipLaunchKernelGGL(k_s5_sort_coop, dim3(2048), dim3(CM_BLOCK), 0, s, d, CM_L_S5_WAVE);
@@ -2068,7 +2096,7 @@ void cm_launch_k_s5a_prepare(const CmDev &d, uint32_t n, hipStream_t s, bool coo
 }
 void cm_launch_k_s5c_finalize(const CmDev &d, uint32_t n, hipStream_t s, bool coop) {
   if (!n) return;
-  hipLaunchKernelGGL(k_s5c_finalize, grid_for(n), dim3(CM_BLOCK), 0, s, d, n, coop ? 1u : 0u);
+  CM_LAUNCH_MODE(k_s5c_finalize, grid_for(n), dim3(CM_BLOCK), 0, s, d, n, coop ? 1u : 0u);
   if (!coop) return;
   auto gbytes = [](uint32_t P) {
     const size_t b1 = cm_coop_ver_mem_bytes(P), b2 = cm_coop_sort_mem_bytes(CM_S5C_SORT_P, CM_S5C_SORT_RB);
@@ -2099,7 +2127,7 @@ void cm_launch_k_s6a_pair(const CmDev &d, uint32_t n, hipStream_t s, bool coop) 
   if (!n) return;
   const size_t lw = (CM_BLOCK / 64) * cm_s6_group_bytes(CM_S6A_P_WAVE), lb = cm_s6_group_bytes(CM_S6A_P_BLOCK);
   if (coop && !(cm_lds_optin(&k_s6a_coop<64>, lw) && cm_lds_optin(&k_s6a_coop<CM_BLOCK>, lb))) coop = false;
-  hipLaunchKernelGGL(k_s6a_pair, grid_for(n), dim3(CM_BLOCK), 0, s, d, n, coop ? 1u : 0u);
+  CM_LAUNCH_MODE(k_s6a_pair, grid_for(n), dim3(CM_BLOCK), 0, s, d, n, coop ? 1u : 0u);
   if (!coop) return;
   uint32_t blocks = n / 4096 + 64;
   if (blocks > 2048) blocks = 2048;
@@ -2111,10 +2139,11 @@ void cm_launch_k_s6c_multi(const CmDev &d, uint32_t n, hipStream_t s, bool coop)
   if (!n) return;
   const size_t lw = (CM_BLOCK / 64) * cm_s6_group_bytes(CM_S6A_P_WAVE), lb = cm_s6_group_bytes(CM_S6A_P_BLOCK);
   if (coop && !(cm_lds_optin(&k_s6c_coop<64>, lw) && cm_lds_optin(&k_s6c_coop<CM_BLOCK>, lb))) coop = false;
-  hipLaunchKernelGGL(k_s6c_multi, grid_for(n), dim3(CM_BLOCK), 0, s, d, n, coop ? 1u : 0u);
-  if (!coop) return;
   uint32_t blocks = n / 4096 + 64;
   if (blocks > 2048) blocks = 2048;
+  if (!cm_mode_pe(d)) hipLaunchKernelGGL(k_s6c_multi, grid_for(n), dim3(CM_BLOCK), 0, s, d, n, coop ? 1u : 0u);
+  else if (cm_cls_on(d, CM_L_S6C_MULTI)) hipLaunchKernelGGL(k_s6c_list, dim3(blocks), dim3(CM_BLOCK), 0, s, d, coop ? 1u : 0u);
+  if (!coop) return;
   if (cm_cls_on(d, CM_L_S6C_SMALL)) hipLaunchKernelGGL(k_s6c_coop<64>, dim3(blocks), dim3(CM_BLOCK), (CM_BLOCK / 64) * cm_s6_group_bytes(CM_S6A_P_SMALL), s, d, CM_S6A_P_SMALL, CM_L_S6C_SMALL);
   if (cm_cls_on(d, CM_L_S6C_WAVE)) hipLaunchKernelGGL(k_s6c_coop<64>, dim3(blocks), dim3(CM_BLOCK), lw, s, d, CM_S6A_P_WAVE, CM_L_S6C_WAVE);
   if (cm_cls_on(d, CM_L_S6C_BLOCK)) hipLaunchKernelGGL(k_s6c_coop<CM_BLOCK>, dim3(256), dim3(CM_BLOCK), lb, s, d, CM_S6A_P_BLOCK, CM_L_S6C_BLOCK);

@@ -11,6 +11,24 @@
 #include "cm_types.h"
 
 // ---------------------------------------------------------------------------------------
+// The mapping mode as a compile-time parameter of the S4-S6 stage functions.  split_alignment and single-end are uniform
+// run-time flags, but a kernel that carries every mode gets the registers of its worst branch (the split drop-off
+// verification inlined into S5a, the split pairing and the single-end emitters in S6) and with them the occupancy of all.
+//   CmModeAny: reads d.p as before -- the default of every template, so callers that name no mode are unchanged.
+//   CmModePe:  paired-end without split alignment (the atac / chip / BED presets): both flags are constant false.
+// ---------------------------------------------------------------------------------------
+struct CmModeAny {
+  static constexpr bool kPe = false;
+  static CM_HD bool split(const CmDev &d) { return d.p.split != 0; }
+  static CM_HD bool single(const CmDev &d) { return d.p.single != 0; }
+};
+struct CmModePe {
+  static constexpr bool kPe = true;
+  static CM_HD bool split(const CmDev &) { return false; }
+  static CM_HD bool single(const CmDev &) { return false; }
+};
+
+// ---------------------------------------------------------------------------------------
 // small helpers
 // ---------------------------------------------------------------------------------------
 // CharToUint8 (utils.h:87-104)
@@ -1479,15 +1497,16 @@ CM_HD const uint8_t *cm_c0_ncnt(const CmDev &d, uint32_t r) { return d.hcnt + d.
 // S4a in two parts so that a block can run the (rare, long) rescue searches on packed lanes:
 // cm_s4a_decide: does this read supplement its candidates from its mate (candidate_processor.cc:
 // 75-146)?  cm_s4a_rescue: the counting pass of the two rescue searches for a read that does.
+template <class M = CmModeAny>
 CM_HD bool cm_s4a_decide(const CmDev &d, uint32_t r) {
   const uint32_t pair = r >> 1;
   d.aug[r] = 0; d.res_neg[r] = 0; d.res_pos[r] = 0; d.resc_n[r] = 0; d.resc_p[r] = 0;
-  const bool live = d.p.single ? ((r & 1) == 0 && d.mm_cnt[r] > 0) : (d.mm_cnt[2 * pair] > 0 && d.mm_cnt[2 * pair + 1] > 0);
+  const bool live = M::single(d) ? ((r & 1) == 0 && d.mm_cnt[r] > 0) : (d.mm_cnt[2 * pair] > 0 && d.mm_cnt[2 * pair + 1] > 0);
   const uint32_t ncp = d.ncp[r], ncn = d.ncn[r];
   d.m_tot[r] = live ? ncp + ncn : 0;
   if (!live) return false;
   const uint32_t mm_count = d.mm_cnt[r];
-  bool augment = !d.p.split && !d.p.single;  // split alignment / single-end never supplement (chromap.h:1021)
+  bool augment = !M::split(d) && !M::single(d);  // split alignment / single-end never supplement (chromap.h:1021)
   const uint8_t *pc = cm_c0_pcnt(d, r), *nc = cm_c0_ncnt(d, r);
   for (uint32_t i = 0; augment && i < ncp; ++i) if (pc[i] >= mm_count / 2) { augment = false; break; }
   if (augment) for (uint32_t i = 0; i < ncn; ++i) if (nc[i] >= mm_count / 2) { augment = false; break; }
@@ -1675,12 +1694,13 @@ CM_HD void cm_rerank(const CmDev &d, uint32_t r) {
 // cm_s4c_reduce in three parts so that a group of lanes can run the filter of a pair with long candidate lists
 // (cm_coop_s4c, cm_coop.h): cm_s4c_pre does everything up to the filter and says whether it has to run, cm_s4c_filter is
 // the two directions, cm_s4c_post the pair's fate and the re-ranking.
+template <class M = CmModeAny>
 CM_HD bool cm_s4c_pre(const CmDev &d, uint32_t pair) {
   const uint32_t r1 = 2 * pair, r2 = r1 + 1;
   d.fcp[r1] = d.fcn[r1] = d.fcp[r2] = d.fcn[r2] = 0;
   d.alive[pair] = 0;
   d.force0[pair] = 0;
-  if (d.p.single) {  // chromap.h:442-445: candidates go straight to verification (split alignment or not: the single side)
+  if (M::single(d)) {  // chromap.h:442-445: candidates go straight to verification (split alignment or not: the single side)
     if (d.mm_cnt[r1] == 0 || d.mcp[r1] + d.mcn[r1] == 0) return false;
     const uint64_t *mp = cm_m_pos(d, r1), *mn = cm_m_neg(d, r1);
     const uint8_t *mpc = cm_m_pcnt(d, r1), *mnc = cm_m_ncnt(d, r1);
@@ -1703,7 +1723,7 @@ CM_HD bool cm_s4c_pre(const CmDev &d, uint32_t pair) {
   d.force0[pair] = (uint8_t)ret;
   const uint32_t nc1 = d.mcp[r1] + d.mcn[r1], nc2 = d.mcp[r2] + d.mcn[r2];
   if (!(nc1 > 0 && nc2 > 0)) return false;
-  if (d.p.split) {  // no paired-end filter (chromap.h:1036-1038): candidates pass through unchanged
+  if (M::split(d)) {  // no paired-end filter (chromap.h:1036-1038): candidates pass through unchanged
     for (uint32_t r = r1; r <= r2; ++r) {
       const uint64_t *mp = cm_m_pos(d, r), *mn = cm_m_neg(d, r);
       const uint8_t *mpc = cm_m_pcnt(d, r), *mnc = cm_m_ncnt(d, r);
@@ -1735,8 +1755,9 @@ CM_HD void cm_s4c_post(const CmDev &d, uint32_t pair) {
   d.alive[pair] = (f1 > 0 && f2 > 0) ? 1 : 0;
   if (d.alive[pair]) { cm_rerank(d, r1); cm_rerank(d, r2); }
 }
+template <class M = CmModeAny>
 CM_HD void cm_s4c_reduce(const CmDev &d, uint32_t pair) {
-  if (!cm_s4c_pre(d, pair)) return;
+  if (!cm_s4c_pre<M>(d, pair)) return;
   cm_s4c_filter(d, pair);
   cm_s4c_post(d, pair);
 }
@@ -2393,14 +2414,16 @@ CM_HD int cm_verify_compute(const CmDev &d, const uint8_t *read, uint32_t L, int
 }
 
 // pre_err/pre_end (may be null): results computed beforehand by the per-candidate kernel for
-// candidate index ci of this strand's list
+// candidate index ci of this strand's list.  PRE: they are there -- the caller's code then holds no alignment at all (a kernel
+// that only runs the acceptance loop would otherwise carry the banded alignment's registers for a branch it never takes)
+template <bool PRE = false>
 CM_HD bool cm_verify_one(const CmDev &d, const uint8_t *read, uint32_t L, int strand, uint64_t cpos, CmBest &bst,
                          uint64_t *dp, int16_t *de, uint32_t *nd, const int16_t *pre_err, const int16_t *pre_end,
                          uint32_t ci) {
   const int e = d.p.e;
   int end_pos = (int)L;
   int ne;
-  if (pre_err) { ne = pre_err[ci]; end_pos = pre_end[ci]; }
+  if (PRE || pre_err) { ne = pre_err[ci]; end_pos = pre_end[ci]; }
   else ne = cm_verify_compute(d, read, L, strand, cpos, &end_pos);
   if (ne <= e) {
     cm_update_best(bst, ne);
@@ -2415,6 +2438,7 @@ CM_HD bool cm_verify_one(const CmDev &d, const uint8_t *read, uint32_t L, int st
 
 // one strand of GenerateDraftMappings: scalar loop (draft_mapping_generator.cc:359-557, non-split)
 // or the lane-grouped loop with the candidate_count_threshold break (:159-357)
+template <bool PRE = false>
 CM_HD uint32_t cm_draft_strand(const CmDev &d, const uint8_t *read, uint32_t L, int strand, const uint64_t *cp,
                                const uint8_t *cc, uint32_t nc, CmBest &bst, uint64_t *dp, int16_t *de,
                                const int16_t *pre_err = nullptr, const int16_t *pre_end = nullptr) {
@@ -2426,13 +2450,11 @@ CM_HD uint32_t cm_draft_strand(const CmDev &d, const uint8_t *read, uint32_t L, 
       uint32_t position = (uint32_t)cp[ci];
       if (strand == 1) position = position - L + 1;
       if (!cm_valid_candidate(d, rid, position, L)) continue;
-      cm_verify_one(d, read, L, strand, cp[ci], bst, dp, de, &nd, pre_err, pre_end, ci);
+      cm_verify_one<PRE>(d, read, L, strand, cp[ci], bst, dp, de, &nd, pre_err, pre_end, ci);
     }
     return nd;
   }
-  uint64_t vpos[8];
-  uint8_t vcnt[8];
-  uint32_t vidx[8];
+  uint32_t vidx[8];  // (the valid candidates' indices only: positions and counts are read again where they are used -- 24 registers less)
   uint32_t nvalid = 0, thr = 0, ci = 0;
   while (ci < nc) {
     if (cc[ci] < thr) break;
@@ -2440,17 +2462,15 @@ CM_HD uint32_t cm_draft_strand(const CmDev &d, const uint8_t *read, uint32_t L, 
     uint32_t position = (uint32_t)cp[ci];
     if (strand == 1) position = position - L + 1;
     if (!cm_valid_candidate(d, rid, position, L)) { ++ci; continue; }
-    vpos[nvalid] = cp[ci];
-    vcnt[nvalid] = cc[ci];
     vidx[nvalid] = ci;
     ++nvalid;
     ++ci;
     if (nvalid < (uint32_t)lanes) continue;
     for (int mi = 0; mi < lanes; ++mi)
-      if (!cm_verify_one(d, read, L, strand, vpos[mi], bst, dp, de, &nd, pre_err, pre_end, vidx[mi])) thr = vcnt[mi];
+      if (!cm_verify_one<PRE>(d, read, L, strand, cp[vidx[mi]], bst, dp, de, &nd, pre_err, pre_end, vidx[mi])) thr = cc[vidx[mi]];
     nvalid = 0;
   }
-  for (uint32_t i = 0; i < nvalid; ++i) cm_verify_one(d, read, L, strand, vpos[i], bst, dp, de, &nd, pre_err, pre_end, vidx[i]);
+  for (uint32_t i = 0; i < nvalid; ++i) cm_verify_one<PRE>(d, read, L, strand, cp[vidx[i]], bst, dp, de, &nd, pre_err, pre_end, vidx[i]);
   return nd;
 }
 
@@ -2528,6 +2548,7 @@ CM_HD uint32_t cm_draft_strand_split(const CmDev &d, const uint8_t *read, uint32
 //      incl. the all-minimizer shortcut (:72-157).  Draft mappings go to dpos/derr at the
 //      same offsets as the filtered candidate lists.
 // ---------------------------------------------------------------------------------------
+template <class M = CmModeAny>
 CM_HD void cm_s5_verify(const CmDev &d, uint32_t r) {
   const uint32_t pair = r >> 1;
   d.ndp[r] = 0; d.ndn[r] = 0;
@@ -2542,7 +2563,7 @@ CM_HD void cm_s5_verify(const CmDev &d, uint32_t r) {
     uint64_t *dpp = d.dpos + d.m_off[r], *dpn = d.dpos + d.m_off[r] + d.ncp[r] + d.resc_p[r];
     int16_t *dep = d.derr + d.m_off[r], *den = d.derr + d.m_off[r] + d.ncp[r] + d.resc_p[r];
     bool done = false;
-    if (d.p.split) {  // draft_mapping_generator.cc:31-39: no shortcut, scalar drop-off verification (single-end reads too: the split
+    if (M::split(d)) {  // draft_mapping_generator.cc:31-39: no shortcut, scalar drop-off verification (single-end reads too: the split
                       // side; the empty second mate of a single-end pair has no candidates and leaves no draft mapping)
       uint32_t *dsp = d.dsplit + d.m_off[r], *dsn = d.dsplit + d.m_off[r] + d.ncp[r] + d.resc_p[r];
       cm_sort_cand(pp, pc, ncp);
@@ -2587,12 +2608,24 @@ CM_HD void cm_s5_verify(const CmDev &d, uint32_t r) {
 // ---------------------------------------------------------------------------------------
 // coop_min > 0: a read with more candidates than that gets its lists sorted and its acceptance loop run by a group of lanes
 // (cm_coop_s5_sort / cm_coop_s5c, cm_coop.h; the alignments stay with the per-candidate kernel): the function returns true
+template <class M = CmModeAny>
 CM_HD bool cm_s5a_prepare(const CmDev &d, uint32_t r, uint32_t coop_min = 0) {
   const uint32_t pair = r >> 1;
   d.nv[r] = 0;
-  if (d.p.split || !d.alive[pair]) { cm_s5_verify(d, r); return false; }  // split alignment keeps the in-place path
-  d.ndp[r] = 0; d.ndn[r] = 0;
   const int e = d.p.e;
+  if constexpr (M::kPe) {
+    // a dead pair: what cm_s5_verify leaves for one (no draft mappings, CmBest's start values), without that function's
+    // verification -- which a paired-end kernel would otherwise carry in its registers for nothing
+    if (!d.alive[pair]) {
+      d.ndp[r] = 0; d.ndn[r] = 0;
+      d.min_err[r] = e + 1; d.second_err[r] = e + 1;
+      d.n_best[r] = 0; d.n_second[r] = 0;
+      return false;
+    }
+  } else {
+    if (M::split(d) || !d.alive[pair]) { cm_s5_verify<M>(d, r); return false; }  // split alignment keeps the in-place path
+  }
+  d.ndp[r] = 0; d.ndn[r] = 0;
   CmBest bst = {e + 1, e + 1, 0, 0};
   const uint32_t L = d.rlen[r];
   uint64_t *pp = cm_f_pos(d, r), *np = cm_f_neg(d, r);
@@ -2672,8 +2705,8 @@ CM_HD void cm_s5c_accept(const CmDev &d, uint32_t r) {
   const uint32_t L = d.rlen[r];
   const uint8_t *read = cm_read_ptr(d, r);
   const uint32_t op = d.m_off[r], on = d.m_off[r] + d.ncp[r] + d.resc_p[r];
-  d.ndp[r] = cm_draft_strand(d, read, L, 0, d.fbuf + op, d.fcnt + op, d.fcp[r], bst, d.dpos + op, d.derr + op, d.v_err + op, d.v_end + op);
-  d.ndn[r] = cm_draft_strand(d, read, L, 1, d.fbuf + on, d.fcnt + on, d.fcn[r], bst, d.dpos + on, d.derr + on, d.v_err + on, d.v_end + on);
+  d.ndp[r] = cm_draft_strand<true>(d, read, L, 0, d.fbuf + op, d.fcnt + op, d.fcp[r], bst, d.dpos + op, d.derr + op, d.v_err + op, d.v_end + op);
+  d.ndn[r] = cm_draft_strand<true>(d, read, L, 1, d.fbuf + on, d.fcnt + on, d.fcn[r], bst, d.dpos + on, d.derr + on, d.v_err + on, d.v_end + on);
   d.min_err[r] = bst.min_err; d.second_err[r] = bst.second_err;
   d.n_best[r] = bst.n_best; d.n_second[r] = bst.n_second;
 }
@@ -3417,14 +3450,14 @@ CM_HD void cm_emit_single_record(const CmDev &d, uint32_t pair, uint32_t choice,
 // ---------------------------------------------------------------------------------------
 // in two parts so that a group of lanes can run the sweeps of a pair with many draft mappings (cm_coop_s6a, cm_coop.h):
 // cm_s6a_pre does everything else and says whether the paired-end sweeps have to run
-template <bool SAM = false>
+template <bool SAM = false, class M = CmModeAny>
 CM_HD bool cm_s6a_pre(const CmDev &d, uint32_t pair) {
   const uint32_t r1 = 2 * pair, r2 = r1 + 1;
   for (uint32_t t = 0; t < (uint32_t)d.p.max_best; ++t) d.rec_ok[(uint64_t)pair * (uint32_t)d.p.max_best + t] = 0;
   d.pe_nbest[pair] = 0;
   if (!d.alive[pair]) return false;
   const uint32_t nd1 = d.ndp[r1] + d.ndn[r1], nd2 = d.ndp[r2] + d.ndn[r2];
-  if (d.p.single) {  // GenerateBestMappingsForSingleEndRead (mapping_generator.h:115-157); with split alignment too: the single side
+  if (M::single(d)) {  // GenerateBestMappingsForSingleEndRead (mapping_generator.h:115-157); with split alignment too: the single side
                      // (one read's best mappings, no pairing) -- cm_emit_single_record takes the split side for the record itself
     if (nd1 == 0) return false;
     d.pe_nbest[pair] = d.n_best[r1];
@@ -3433,7 +3466,7 @@ CM_HD bool cm_s6a_pre(const CmDev &d, uint32_t pair) {
     return false;
   }
   if (!(nd1 > 0 && nd2 > 0)) return false;  // chromap.h:1092-1093
-  if (d.p.split) {  // drafts stay in emission order (chromap.h:1099-1106)
+  if (M::split(d)) {  // drafts stay in emission order (chromap.h:1099-1106)
     CmPe sp;
     cm_split_pairing(d, pair, 0, sp);
     d.pe_min[pair] = sp.min_sum; d.pe_second[pair] = sp.second_sum;
@@ -3444,8 +3477,9 @@ CM_HD bool cm_s6a_pre(const CmDev &d, uint32_t pair) {
   }
   return true;
 }
+// returns the number of best pairings (what it leaves in pe_nbest)
 template <bool SAM = false>
-CM_HD void cm_s6a_sweeps(const CmDev &d, uint32_t pair) {
+CM_HD int cm_s6a_sweeps(const CmDev &d, uint32_t pair) {
   const uint32_t r1 = 2 * pair, r2 = r1 + 1;
   for (uint32_t r = r1; r <= r2; ++r) {
     cm_sort_draft(const_cast<uint64_t *>(cm_d_pos(d, r, 0)), const_cast<int16_t *>(cm_d_err(d, r, 0)), d.ndp[r]);
@@ -3464,10 +3498,11 @@ CM_HD void cm_s6a_sweeps(const CmDev &d, uint32_t pair) {
   d.pe_nbest[pair] = pe.n_best; d.pe_nsecond[pair] = pe.n_second;
   d.pe_first[pair] = pe.f_dir; d.pe_i1[pair] = pe.f_i1; d.pe_i2[pair] = pe.f_i2;
   if (pe.n_best == 1) cm_emit_record<SAM>(d, pair, pe);
+  return pe.n_best;
 }
-template <bool SAM = false>
+template <bool SAM = false, class M = CmModeAny>
 CM_HD void cm_s6a_pair(const CmDev &d, uint32_t pair) {
-  if (cm_s6a_pre<SAM>(d, pair)) cm_s6a_sweeps<SAM>(d, pair);
+  if (cm_s6a_pre<SAM, M>(d, pair)) cm_s6a_sweeps<SAM>(d, pair);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -3574,10 +3609,10 @@ CM_HD void cm_s6b_sample(const CmDev &d, uint32_t chunk, CmMt &g) {
 // ---------------------------------------------------------------------------------------
 // S6c: per pair -- record for multi-mappers (re-runs the sweeps to find the chosen pair)
 // ---------------------------------------------------------------------------------------
-template <bool SAM = false>
+template <bool SAM = false, class M = CmModeAny>
 CM_HD void cm_s6c_multi(const CmDev &d, uint32_t pair) {
   const int nb = d.pe_nbest[pair];
-  if (nb <= 1 || (!d.p.single && nb > d.p.drop_rep)) return;  // --drop-repetitive-reads applies to pairs only
+  if (nb <= 1 || (!M::single(d) && nb > d.p.drop_rep)) return;  // --drop-repetitive-reads applies to pairs only
   const uint32_t r1 = 2 * pair, r2 = r1 + 1;
   CmPe pe;
   pe.min_sum = d.pe_min[pair]; pe.second_sum = d.pe_second[pair]; pe.n_best = nb; pe.n_second = d.pe_nsecond[pair];
@@ -3586,8 +3621,8 @@ CM_HD void cm_s6c_multi(const CmDev &d, uint32_t pair) {
   const uint32_t to_report = (uint32_t)nb < K ? (uint32_t)nb : K;
   for (uint32_t t = 0; t < to_report; ++t) {  // the chosen indices are increasing, so are the records of a pair
     const int64_t want = (int64_t)d.pe_choice[(uint64_t)pair * K + t];
-    if (d.p.single) { cm_emit_single_record<SAM>(d, pair, (uint32_t)want, t); continue; }  // (single-end split alignment: here, not below)
-    if (d.p.split) {
+    if (M::single(d)) { cm_emit_single_record<SAM>(d, pair, (uint32_t)want, t); continue; }  // (single-end split alignment: here, not below)
+    if (M::split(d)) {
       CmPe sp;
       cm_split_pairing(d, pair, want, sp);
       cm_emit_pairs_record<SAM>(d, pair, sp, t);

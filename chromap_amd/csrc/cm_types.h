@@ -56,12 +56,13 @@
 //   13  CM_L_S6A_WAVE         pairs, draft mappings <= 1024          k_s6a_coop<64>                       CM_S6A_P_WAVE
 //   18  CM_L_S6A_BLOCK        pairs with more                        k_s6a_coop<256>                      CM_S6A_P_BLOCK
 //   30 / 17 / 20  CM_L_S6C_SMALL / WAVE / BLOCK   multi-mapped pairs, the same classes   k_s6c_coop<64> / <64> / <256>
-// (24: free.)  A class's kernels are launched when the class had items lately (CmDev::cls_mask, cm_kernels.hip).
+//   24  CM_L_S6C_MULTI        pairs S6c looks at (paired-end instance)  k_s6c_list (a lane per pair)       --: n_best > 1, or S6a left the pair to a group
+// A class's kernels are launched when the class had items lately (CmDev::cls_mask, cm_kernels.hip).
 enum CmList : uint32_t {
   CM_L_HIT_WAVE = 0, CM_L_HIT_B256A = 1, CM_L_HIT_B256B = 2, CM_L_HIT_SLAB = 3, CM_L_HIT_G16 = 4, CM_L_HIT_DECLINED = 5, CM_L_RS_WAVE = 6, CM_L_RS_B256A = 7,
   CM_L_RS_B256B = 8, CM_L_PF_BLOCK = 9, CM_L_HIT_B512 = 10, CM_L_RS_B512 = 11, CM_L_S5_WAVE = 12, CM_L_S6A_WAVE = 13, CM_L_PF_BLOCK_BIG = 14, CM_L_RS_SLAB = 15,
   CM_L_HIT_SERIAL = 16, CM_L_S6C_WAVE = 17, CM_L_S6A_BLOCK = 18, CM_L_PF_HUGE = 19, CM_L_S6C_BLOCK = 20, CM_L_HIT_WAVE_SMALL = 21, CM_L_S5_BLOCK = 22,
-  CM_L_SEARCH_WAVE = 23, CM_L_HIT_B1024 = 25, CM_L_RS_B1024 = 26, CM_L_PF_WAVE = 27, CM_L_S5_SMALL = 28, CM_L_S6A_SMALL = 29, CM_L_S6C_SMALL = 30,
+  CM_L_SEARCH_WAVE = 23, CM_L_S6C_MULTI = 24, CM_L_HIT_B1024 = 25, CM_L_RS_B1024 = 26, CM_L_PF_WAVE = 27, CM_L_S5_SMALL = 28, CM_L_S6A_SMALL = 29, CM_L_S6C_SMALL = 30,
   CM_L_SEARCH_WAVE_BIG = 31
 };
 #define CM_HV_LISTS 32
@@ -202,6 +203,7 @@ struct CmDev {
   uint32_t mm_cap;  // capacity of the dense minimizer arrays (0: not checked): S3a leaves a read whose range passes it idle
   uint32_t coop_rb; // tests: run-table size of the cooperative sorters (0: two per minimizer of the longest read)
   uint32_t hv_sub;  // class 21: lists of hv_mid < hits <= hv_sub go to waves with a quarter of the wave class's work area (0: no such class)
+  uint32_t generic_kernels;  // cmgpu_set_option "generic_kernels": the S4-S6 kernels' CmModeAny instances whatever the mode (A/B runs, tests)
   uint32_t hv_mid;  // class 4: lists of s3b_cap < hits <= hv_mid go to groups of 16 lanes (k_s3b_heavy<16>); 0 = no such class
   // ---- rescue / merged candidates
   uint8_t *aug;         // [2n] augment flag

@@ -99,7 +99,9 @@ int cmgpu_gather_sweep(cmgpu_ctx *ctx, uint64_t n, int repeat, int loads_per_lan
  * kernels of the long-list classes launched for the classes the previous range used, one re-run when another class has items; -1: on,
  * starting from an empty launch set -- the tests' way to force that re-run),
  * "verify_planes" 0/1 (alignments of the verification on bit planes of the reference and the reads instead of their bytes),
- * "long_read_fused" 0/1 (reads longer than 69 bases: trimming + minimizers in one pass instead of count / scan / fill).
+ * "long_read_fused" 0/1 (reads longer than 69 bases: trimming + minimizers in one pass instead of count / scan / fill),
+ * "generic_kernels" 0/1 (1: paired-end batches without split alignment run the S4-S6 kernels that carry every mode instead of
+ * their own instances; tests/test_gpu_mode_instances.py compares the two).
  * Every setting gives the same records (tests/test_gpu_parity.py runs the fuzz data under each). */
 int cmgpu_set_option(cmgpu_ctx *ctx, const char *name, int64_t value);
 int cmgpu_get_option(const cmgpu_ctx *ctx, const char *name, int64_t *value);
