@@ -26,7 +26,8 @@ PARAM_FIELDS = ("error_threshold", "min_num_seeds", "max_seed_frequency0", "max_
                 "min_read_length", "max_num_best_mappings", "drop_repetitive_reads", "trim_adapters",
                 "split_alignment", "mapq_threshold", "remove_pcr_duplicates", "tn5_shift", "low_memory_mode",
                 "read_batch_size", "taskloop_grain_size", "bc_error_threshold", "output_mappings_not_in_whitelist",
-                "output_format", "dedup_at_bulk_level", "bc_probability_threshold")
+                "output_format", "dedup_at_bulk_level", "allocate_multi_mappings", "multi_mapping_allocation_distance",
+                "multi_mapping_allocation_seed", "bc_probability_threshold")
 
 
 class Params(C.Structure):
@@ -108,7 +109,7 @@ SYMBOLS = ("cmgpu_default_params", "cmgpu_apply_preset", "cmgpu_create", "cmgpu_
            "cmgpu_export_reference", "cmgpu_reference_lengths", "cmgpu_write_bed_pe", "cmgpu_write_pairs", "cmgpu_map_single", "cmgpu_write_bed_se", "cmgpu_load_whitelist_file", "cmgpu_set_whitelist", "cmgpu_store_format_pairs", "cmgpu_write_pairs_header",
            "cmgpu_compute_barcode_abundance", "cmgpu_map_pairs_barcoded", "cmgpu_map_single_barcoded", "cmgpu_write_bed_pe_bc",
            "cmgpu_store_clear", "cmgpu_store_reserve", "cmgpu_store_append_resident", "cmgpu_store_append", "cmgpu_store_format",
-           "cmgpu_store_text", "cmgpu_store_write_text", "cmgpu_store_info",
+           "cmgpu_store_text", "cmgpu_store_write_text", "cmgpu_store_info", "cmgpu_store_allocation_info",
            "cmgpu_sam_layout", "cmgpu_download_sam", "cmgpu_write_sam", "cmgpu_download_barcode_keys", "cmgpu_set_barcode_check", "cmgpu_write_sam_barcoded", "cmgpu_write_sam_barcoded_translated",
            "cmgpu_warm_up", "cmgpu_fastq_set_format", "cmgpu_fastq_scan", "cmgpu_fastq_scan_bgzf", "cmgpu_fastq_take", "cmgpu_fastq_commit", "cmgpu_barcode_abundance_resident",
            "cmgpu_fastq_keep_names", "cmgpu_names_clear", "cmgpu_names_info", "cmgpu_download_names", "cmgpu_store_format_pairs_resident",
@@ -194,6 +195,7 @@ def declare(L):
     sig("cmgpu_store_text", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64])
     sig("cmgpu_store_write_text", C.c_int, [C.c_void_p, C.c_char_p, C.c_int])
     sig("cmgpu_store_info", C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint64), P(C.c_uint64)])
+    sig("cmgpu_store_allocation_info", C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint64), P(C.c_uint64)])
     sig("cmgpu_sam_layout", C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint32)])
     sig("cmgpu_download_sam", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
     sig("cmgpu_write_sam", C.c_int64, [P(C.c_char_p), C.c_void_p, C.c_uint32, P(Params), C.c_void_p, C.c_uint64, C.c_int, C.c_void_p,

@@ -156,6 +156,8 @@ extern "C" int cmgpu_get_option(const cmgpu_ctx *c, const char *name, int64_t *v
   else if (n == "lanes") *value = c->opt.lanes;
   else if (n == "coop") *value = c->opt.coop;
   else if (n == "generic_kernels") *value = c->opt.generic_kernels;
+  else if (n == "alloc_us") *value = (int64_t)(c->alloc_seconds * 1e6);  // the allocation stage of the last cmgpu_store_format
+  else if (n == "alloc_draw_us") *value = (int64_t)(c->alloc_draw_seconds * 1e6);  // measurement: host share of the last allocation (cm_post.hip)
   else if (n.rfind("coop_profile_", 0) == 0) {
     const int k = atoi(n.c_str() + 13);
     unsigned long long v = 0;

@@ -7,6 +7,7 @@
 #include <chrono>
 #include <functional>
 
+#include "../../include/chromap_amd_debug.h"
 #include "cm_cli_reader.h"
 #include "cm_cli_args.h"
 
@@ -706,6 +707,18 @@ static int64_t write_bed(Run &r) {
     nbytes += nbs[gi];
   }
   const double t1 = now_s();
+  if (a.p.allocate_multi_mappings) {
+    if (a.p.low_memory_mode) {
+      fprintf(stderr, "--allocate-multi-mappings does nothing in low-memory mode (--low-mem, --preset): no multi-mapping is allocated.\n");
+    } else {  // MappingProcessor::AllocateMultiMappings' lines (mapping_processor.h:368, 435-439); one context: validate()
+      uint64_t n_multi = 0, n_allocated = 0, n_without = 0;
+      int64_t us = 0;
+      ck(r.ctx(), cmgpu_store_allocation_info(r.ctx(), &n_multi, &n_allocated, &n_without));
+      (void)cmgpu_get_option(r.ctx(), "alloc_us", &us);
+      fprintf(stderr, "Got all %llu multi-mappings!\nAllocated %llu multi-mappings in %.3fs.\n# multi-mappings that have no uni-mapping overlaps: %llu.\n",
+              (unsigned long long)n_multi, (unsigned long long)n_allocated, (double)us * 1e-6, (unsigned long long)n_without);
+    }
+  }
   // sections in rank order: the owners hold contiguous, increasing chromosome ranges
   for (cmgpu_ctx *cx : r.ctxs) ck(cx, cmgpu_store_write_text(cx, a.out_path.c_str(), 1));  // (emptied at the start)
   r.t_post = now_s() - t0;

@@ -127,6 +127,9 @@ static Args parse(int argc, char **argv) {
     else if (o == "--Tn5-shift") a.p.tn5_shift = 1;
     else if (o == "--split-alignment") a.p.split_alignment = 1;
     else if (o == "--low-mem") a.p.low_memory_mode = 1;
+    else if (o == "--allocate-multi-mappings") a.p.allocate_multi_mappings = 1;
+    else if (o == "--multi-mapping-allocation-distance") a.p.multi_mapping_allocation_distance = atoi(need("--multi-mapping-allocation-distance"));
+    else if (o == "--multi-mapping-allocation-seed") a.p.multi_mapping_allocation_seed = atoi(need("--multi-mapping-allocation-seed"));
     else if (o == "--BED") { a.out_bed = true; a.out_pairs = false; a.out_sam = false; }
     else if (o == "--SAM") { a.out_sam = true; a.out_bed = false; a.out_pairs = false; }
     else if (o == "--TagAlign") { a.out_tagalign = true; a.out_bed = true; a.out_sam = false; a.out_pairs = false; }
@@ -188,6 +191,10 @@ static Args parse(int argc, char **argv) {
              "       [-b barcode.fq --barcode-whitelist wl.txt] -o out [-e -s -f -l -q --min-read-length --trim-adapters\n"
              "       --remove-pcr-duplicates --Tn5-shift --low-mem --BED|--TagAlign|--pairs|--SAM --bc-error-threshold ...]\n"
              "       [--summary FILE [--turn-off-num-uniq-cache-slots] [--frip-est-params a;b;c;d;e]]\n"
+             "  --allocate-multi-mappings  BED / TagAlign without --low-mem and without a preset: every read whose mappings have MAPQ < 4 is given to\n"
+             "                  one of them, drawn by the uniquely mapped fragments around each; reads with none around are dropped\n"
+             "  --multi-mapping-allocation-distance INT  how far around a mapping the uniquely mapped fragments count [0]\n"
+             "  --multi-mapping-allocation-seed INT      seed of the draw [11]\n"
              "  --split-alignment  with -1 alone (single-end reads): BED, --TagAlign or --SAM whose coordinates and MAPQ carry each read's split site;\n"
              "                  with -2 as well the output is --pairs (--preset hic)\n"
              "  --barcode-translate FILE  lines to<TAB or ,>from (gzip or plain): BED column 4 and the SAM CB:Z: value are written as the\n"
@@ -243,4 +250,12 @@ static void validate(Args &a) {
   a.p.dedup_at_bulk_level = barcoded && !a.cell_level_dedup ? 1 : 0;  // remove_pcr_duplicates_at_bulk_level defaults to true (mapping_parameters.h:49)
   if ((a.gpus > 1 || a.force_exchange) && (a.out_pairs || a.out_sam || a.host_ingest))
     die("--gpus > 1 needs BED / TagAlign output and device-side FASTQ ingest (pairs and SAM text is rendered by one context from its own stores)");
+  // the reference allocates in its in-memory flavour only (chromap.h:1305-1353): with --low-mem or a preset the flag does nothing there and here
+  if (a.p.allocate_multi_mappings && !a.p.low_memory_mode) {
+    if (a.out_sam) die("--allocate-multi-mappings with --SAM is outside this build (the SAM writers have no allocation stage)");
+    if (a.out_pairs) die("--allocate-multi-mappings with pairs output is outside this build (the pairs writers have no allocation stage)");
+    if (!a.summary_path.empty()) die("--allocate-multi-mappings with --summary is outside this build (the duplicate and low-MAPQ counts are taken before the allocation)");
+    if (a.gpus > 1 || a.force_exchange)
+      die("--allocate-multi-mappings with --gpus > 1 or --force-exchange is outside this build (a read's positions lie on chromosomes that different GPUs own)");
+  }
 }

@@ -212,6 +212,8 @@ struct cmgpu_ctx {
   // device-side record store + rendered text (cm_post.hip)
   DevBuf store, store_bc, text;
   uint64_t store_n = 0, store_cap = 0, text_bytes = 0, text_lines = 0;
+  uint64_t alloc_multi = 0, alloc_kept = 0, alloc_without_overlap = 0;  // the last cmgpu_store_format's allocation (cmgpu_store_allocation_info)
+  double alloc_seconds = 0, alloc_draw_seconds = 0;                     // the stage's time, and its draw's on the host (cmgpu_get_option alloc_us, alloc_draw_us)
   bool store_has_bc = false;
   bool store_pairs_rec = false;  // the stored records are cmgpu_pairs_record entries (kind of the first append, like store_has_bc)
   CmFqStream fq[3];  // read 1, read 2, barcode

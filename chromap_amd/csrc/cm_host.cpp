@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/chromap_amd.h"
+#include "cm_alloc.h"
 #include "cm_barcode_translate.h"
 
 extern "C" void cmgpu_default_params(cmgpu_params *p) {  // mapping_parameters.h:19-61
@@ -28,6 +29,7 @@ extern "C" void cmgpu_default_params(cmgpu_params *p) {  // mapping_parameters.h
   p->read_batch_size = 500000;
   p->taskloop_grain_size = 5000;
   p->bc_error_threshold = 1;
+  p->multi_mapping_allocation_seed = 11;
   p->bc_probability_threshold = 0.9;
 }
 
@@ -181,6 +183,61 @@ static inline void put_u32(std::string &s, uint32_t v) {
   while (n) s.push_back(buf[--n]);
 }
 
+// --allocate-multi-mappings on the host (MappingProcessor::AllocateMultiMappings, mapping_processor.h:319-440; cm_alloc.h): the weight of
+// a multi-mapping is the number of uni-mappings of its chromosome with start < interval_end and end > interval_start -- counted as
+// #(start < interval_end) - #(end <= interval_start) over the sorted starts and the sorted ends (end <= interval_start implies
+// start < interval_end), which is what the reference's interval tree counts
+CmAllocCounts cm_alloc_host(const std::vector<CmAllocRec> &recs, int32_t distance, int32_t seed, std::vector<uint8_t> &keep) {
+  CmAllocCounts cnt;
+  keep.assign(recs.size(), 1);
+  std::vector<uint64_t> us, ue;
+  std::vector<uint32_t> multi;  // positions in recs, to be ordered by (read_id, position)
+  for (size_t i = 0; i < recs.size(); ++i) {
+    const CmAllocRec &r = recs[i];
+    if (r.mapq < CM_ALLOC_MIN_UNIQUE_MAPQ) { multi.push_back((uint32_t)i); continue; }
+    us.push_back(((uint64_t)r.rid << 32) | r.start);
+    ue.push_back(((uint64_t)r.rid << 32) | r.end);
+  }
+  cnt.n_multi = multi.size();
+  if (multi.empty()) return cnt;  // (the reference asserts here; a run without multi-mappings is left as it is)
+  std::sort(us.begin(), us.end());
+  std::sort(ue.begin(), ue.end());
+  std::stable_sort(multi.begin(), multi.end(), [&](uint32_t a, uint32_t b) { return recs[a].read_id < recs[b].read_id; });
+  std::vector<uint32_t> w(multi.size());
+  for (size_t g = 0; g < multi.size(); ++g) {
+    const CmAllocRec &r = recs[multi[g]];
+    uint32_t qs, qe;
+    cm_alloc_interval(r.start, r.end, distance, &qs, &qe);
+    const uint64_t a = std::lower_bound(us.begin(), us.end(), ((uint64_t)r.rid << 32) | qe) - us.begin();
+    const uint64_t b = std::upper_bound(ue.begin(), ue.end(), ((uint64_t)r.rid << 32) | qs) - ue.begin();
+    w[g] = (uint32_t)(a > b ? a - b : 0);
+    if (g == 0 || recs[multi[g - 1]].read_id != r.read_id) w[g] |= CM_ALLOC_HEAD;
+    keep[multi[g]] = 0;
+  }
+  std::vector<uint32_t> kept;
+  cnt.n_without_overlap = cm_alloc_draw(w.data(), w.size(), seed, kept);
+  cnt.n_allocated = kept.size();
+  for (uint32_t g : kept) keep[multi[g]] = 1;
+  return cnt;
+}
+// a writer's survivors with their duplicate counts, held back until the allocation has seen them all
+template <class Rec>
+struct CmAllocPending {
+  std::vector<Rec> rec;
+  std::vector<uint32_t> dups;
+  std::vector<CmAllocRec> key;
+  void add(const Rec &r, const cmgpu_record &c, uint32_t d) {
+    rec.push_back(r);
+    dups.push_back(d);
+    key.push_back(CmAllocRec{c.rid, c.fragment_start, c.fragment_start + c.fragment_length, c.mapq, c.read_id});
+  }
+};
+static inline bool alloc_on(const cmgpu_params *p) {
+  if (p->allocate_multi_mappings && p->low_memory_mode)
+    fprintf(stderr, "--allocate-multi-mappings does nothing in low-memory mode (--low-mem, --preset): no multi-mapping is allocated\n");
+  return p->allocate_multi_mappings && !p->low_memory_mode;
+}
+
 extern "C" int64_t cmgpu_write_bed_pe(const char *const *names, uint32_t n_sequences, const cmgpu_params *p,
                                       cmgpu_record *rec, uint64_t n, const char *out_path) {
   FILE *f = fopen(out_path, "wb");
@@ -189,6 +246,8 @@ extern "C" int64_t cmgpu_write_bed_pe(const char *const *names, uint32_t n_seque
   // LAST record of a run (mapping_processor.h:160-202); low-memory flavour: see above
   const bool inmem = !p->low_memory_mode;
   const bool shift_late = p->tn5_shift && !inmem;
+  const bool alloc = alloc_on(p);
+  CmAllocPending<cmgpu_record> pend;
   if (inmem && p->tn5_shift)
     for (uint64_t i = 0; i < n; ++i) {
       rec[i].fragment_start += 4; rec[i].positive_alignment_length -= 4; rec[i].fragment_length -= 9; rec[i].negative_alignment_length -= 5;
@@ -232,8 +291,15 @@ extern "C" int64_t cmgpu_write_bed_pe(const char *const *names, uint32_t n_seque
         ++j;
       }
     }
-    if (last.mapq >= p->mapq_threshold) emit(last, dups);
+    if (alloc) { if (last.rid < n_sequences) pend.add(last, last, dups); }
+    else if (last.mapq >= p->mapq_threshold) emit(last, dups);
     i = j;
+  }
+  if (alloc) {
+    std::vector<uint8_t> keep;
+    cm_alloc_host(pend.key, p->multi_mapping_allocation_distance, p->multi_mapping_allocation_seed, keep);
+    for (size_t t = 0; t < pend.rec.size(); ++t)
+      if (keep[t] && pend.rec[t].mapq >= p->mapq_threshold) emit(pend.rec[t], pend.dups[t]);
   }
   if (!buf.empty()) fwrite(buf.data(), 1, buf.size(), f);
   fclose(f);
@@ -280,6 +346,7 @@ extern "C" int64_t cmgpu_write_pairs_ranked(const char *const *names, const uint
                                             const cmgpu_params *p, cmgpu_pairs_record *rec, uint64_t n,
                                             const char *const *read_names, uint32_t read_id_base, const uint32_t *pairs_rank,
                                             const char *out_path) {
+  if (p->allocate_multi_mappings && !p->low_memory_mode) return CMGPU_EINVAL;  // no allocation stage for pairs records
   FILE *f = fopen(out_path, "wb");
   if (!f) return CMGPU_EIO;
   std::sort(rec, rec + n, [](const cmgpu_pairs_record &a, const cmgpu_pairs_record &b) {
@@ -376,6 +443,24 @@ extern "C" int64_t cmgpu_write_bed_pe_bc(const char *const *names, uint32_t n_se
   std::string buf;
   buf.reserve(1 << 20);
   int64_t lines = 0;
+  const bool alloc = alloc_on(p);
+  CmAllocPending<cmgpu_record_bc> pend;
+  auto emit = [&](const cmgpu_record_bc &last, uint32_t dups) {
+    cmgpu_record r = last.r;
+    if (p->tn5_shift && !inmem) { r.fragment_start += 4; r.fragment_length -= 9; }
+    buf.append(names[r.rid]);
+    buf.push_back('\t');
+    put_u32(buf, r.fragment_start);
+    buf.push_back('\t');
+    put_u32(buf, r.fragment_start + r.fragment_length);
+    buf.push_back('\t');
+    for (uint32_t b = 0; b < barcode_length; ++b) buf.push_back("ACGT"[(last.barcode >> ((barcode_length - 1 - b) * 2)) & 3]);
+    buf.push_back('\t');
+    put_u32(buf, dups > 255 ? 255 : dups);
+    buf.push_back('\n');
+    ++lines;
+    if (buf.size() > (1 << 20) - 256) { fwrite(buf.data(), 1, buf.size(), f); buf.clear(); }
+  };
   uint64_t i = 0;
   while (i < n) {
     cmgpu_record_bc last = rec[i];
@@ -389,23 +474,17 @@ extern "C" int64_t cmgpu_write_bed_pe_bc(const char *const *names, uint32_t n_se
         ++j;
       }
     }
-    if (last.r.mapq >= p->mapq_threshold && last.r.rid < n_sequences) {
-      cmgpu_record r = last.r;
-      if (p->tn5_shift && !inmem) { r.fragment_start += 4; r.fragment_length -= 9; }
-      buf.append(names[r.rid]);
-      buf.push_back('\t');
-      put_u32(buf, r.fragment_start);
-      buf.push_back('\t');
-      put_u32(buf, r.fragment_start + r.fragment_length);
-      buf.push_back('\t');
-      for (uint32_t b = 0; b < barcode_length; ++b) buf.push_back("ACGT"[(last.barcode >> ((barcode_length - 1 - b) * 2)) & 3]);
-      buf.push_back('\t');
-      put_u32(buf, dups > 255 ? 255 : dups);
-      buf.push_back('\n');
-      ++lines;
-      if (buf.size() > (1 << 20) - 256) { fwrite(buf.data(), 1, buf.size(), f); buf.clear(); }
+    if (last.r.rid < n_sequences) {
+      if (alloc) pend.add(last, last.r, dups);
+      else if (last.r.mapq >= p->mapq_threshold) emit(last, dups);
     }
     i = j;
+  }
+  if (alloc) {
+    std::vector<uint8_t> keep;
+    cm_alloc_host(pend.key, p->multi_mapping_allocation_distance, p->multi_mapping_allocation_seed, keep);
+    for (size_t t = 0; t < pend.rec.size(); ++t)
+      if (keep[t] && pend.rec[t].r.mapq >= p->mapq_threshold) emit(pend.rec[t], pend.dups[t]);
   }
   if (!buf.empty()) fwrite(buf.data(), 1, buf.size(), f);
   fclose(f);
@@ -427,6 +506,23 @@ extern "C" int64_t cmgpu_write_bed_se(const char *const *names, uint32_t n_seque
   std::string buf;
   buf.reserve(1 << 20);
   int64_t lines = 0;
+  const bool alloc = alloc_on(p);
+  CmAllocPending<cmgpu_record> pend;
+  auto emit = [&](cmgpu_record last, uint32_t dups) {
+    if (p->tn5_shift && !inmem) { if (last.direction == 1) last.fragment_start += 4; else last.fragment_length -= 5; }
+    buf.append(names[last.rid]);
+    buf.push_back('\t');
+    put_u32(buf, last.fragment_start);
+    buf.push_back('\t');
+    put_u32(buf, last.fragment_start + last.fragment_length);
+    buf.append("\tN\t");
+    put_u32(buf, last.mapq);
+    buf.append(last.direction ? "\t+\t" : "\t-\t");
+    put_u32(buf, dups > 255 ? 255 : dups);
+    buf.push_back('\n');
+    ++lines;
+    if (buf.size() > (1 << 20) - 256) { fwrite(buf.data(), 1, buf.size(), f); buf.clear(); }
+  };
   uint64_t i = 0;
   while (i < n) {
     cmgpu_record last = rec[i];
@@ -439,22 +535,17 @@ extern "C" int64_t cmgpu_write_bed_se(const char *const *names, uint32_t n_seque
         ++j;
       }
     }
-    if (last.mapq >= p->mapq_threshold && last.rid < n_sequences) {
-      if (p->tn5_shift && !inmem) { if (last.direction == 1) last.fragment_start += 4; else last.fragment_length -= 5; }
-      buf.append(names[last.rid]);
-      buf.push_back('\t');
-      put_u32(buf, last.fragment_start);
-      buf.push_back('\t');
-      put_u32(buf, last.fragment_start + last.fragment_length);
-      buf.append("\tN\t");
-      put_u32(buf, last.mapq);
-      buf.append(last.direction ? "\t+\t" : "\t-\t");
-      put_u32(buf, dups > 255 ? 255 : dups);
-      buf.push_back('\n');
-      ++lines;
-      if (buf.size() > (1 << 20) - 256) { fwrite(buf.data(), 1, buf.size(), f); buf.clear(); }
+    if (last.rid < n_sequences) {
+      if (alloc) pend.add(last, last, dups);
+      else if (last.mapq >= p->mapq_threshold) emit(last, dups);
     }
     i = j;
+  }
+  if (alloc) {
+    std::vector<uint8_t> keep;
+    cm_alloc_host(pend.key, p->multi_mapping_allocation_distance, p->multi_mapping_allocation_seed, keep);
+    for (size_t t = 0; t < pend.rec.size(); ++t)
+      if (keep[t] && pend.rec[t].mapq >= p->mapq_threshold) emit(pend.rec[t], pend.dups[t]);
   }
   if (!buf.empty()) fwrite(buf.data(), 1, buf.size(), f);
   fclose(f);
@@ -577,6 +668,7 @@ static int64_t write_sam_impl(const char *const *ref_names, const uint32_t *ref_
                               const char *quals2, const uint32_t *offsets2, const uint64_t *bck, uint32_t bc_len, const char *out_path,
                               const CmBarcodeTable *tr = nullptr) {
   auto bc_of = [&](uint64_t slot) -> uint64_t { return bck ? bck[paired ? slot / 2 : slot] : 0; };
+  if (p->allocate_multi_mappings && !p->low_memory_mode) return CMGPU_EINVAL;  // no allocation stage for SAM records
   FILE *f = fopen(out_path, "wb");
   if (!f) return CMGPU_EIO;
   std::string buf;

@@ -26,6 +26,10 @@
 #include <thread>
 #include <rocprim/rocprim.hpp>
 
+#include <chrono>
+#include <vector>
+
+#include "cm_alloc.h"
 #include "cm_ctx.h"
 #include "cm_kernels.h"
 #include "cm_summary.h"
@@ -34,6 +38,7 @@
 #define PP_RUN_SERIAL 128u  // records of a duplicate run its head walks alone (k_pp_select); longer runs: k_pp_select_long
 #define PP_BLOCK 256
 #define PP_LDS_BYTES 32768
+#define PP_LEN_MISS (~0ull)  // allocation only: a survivor whose barcode the translation table lacks, until k_al_apply knows whether it is printed
 
 struct PpCfg {
   int kind;       // CMGPU_TEXT_BED_PE / _SE / _PE_BC
@@ -49,6 +54,7 @@ struct PpCfg {
   uint32_t wl_mask;
   CmBtDev bt;          // --barcode-translate: column 4 of the barcoded BED kinds through the table (bt.tab == nullptr: Seed2Sequence)
   unsigned long long *bt_miss;  // surviving lines whose barcode the table does not have (the job's spare count word)
+  int alloc;           // --allocate-multi-mappings (in-memory flavour): the selection leaves the MAPQ filter to k_al_apply
 };
 
 struct PpRec {  // cmgpu_record, read with two 8-byte loads + one 8-byte load
@@ -149,7 +155,7 @@ __device__ __forceinline__ void pp_sm_run(const CmSmDev &sm, const PpCfg &cfg, u
 __device__ __forceinline__ void pp_finish(uint32_t j, PpRec r, uint32_t wi, uint64_t bcv, uint32_t dups, bool bulk_done, const PpCfg &cfg,
                                           const uint32_t *__restrict__ name_off, uint32_t *__restrict__ win,
                                           uint32_t *__restrict__ dups_out, uint64_t *__restrict__ line_len) {
-  if ((!bulk_done && (int)r.mapq < cfg.mapq_thr) || r.rid >= cfg.n_seq) { line_len[j] = 0; return; }
+  if ((!bulk_done && !cfg.alloc && (int)r.mapq < cfg.mapq_thr) || r.rid >= cfg.n_seq) { line_len[j] = 0; return; }
   if (cfg.tn5) pp_tn5(r, cfg.kind);
   if (dups > 255) dups = 255;
   const uint32_t nm = name_off[r.rid + 1] - name_off[r.rid];
@@ -164,7 +170,10 @@ __device__ __forceinline__ void pp_finish(uint32_t j, PpRec r, uint32_t wi, uint
     len = nm + 1 + cm_digits10(r.start) + 1 + cm_digits10(r.start + r.len) + 1;
     if (pp_prints_bc(cfg.kind)) {  // chr start end barcode dups
       uint32_t bl = cfg.bc_len;
-      if (cfg.bt.tab && !cm_bt_length(cfg.bt, bcv, cfg.bc_len, &bl)) { atomicAdd(cfg.bt_miss, 1ull); line_len[j] = 0; return; }
+      if (cfg.bt.tab && !cm_bt_length(cfg.bt, bcv, cfg.bc_len, &bl)) {
+        if (cfg.alloc) { win[j] = wi; dups_out[j] = dups; line_len[j] = PP_LEN_MISS; return; }
+        atomicAdd(cfg.bt_miss, 1ull); line_len[j] = 0; return;
+      }
       len += bl + 1 + cm_digits10(dups) + 1;
     }
     else if (cfg.kind == CMGPU_TEXT_TAGALIGN_SE_BC) len += 2 + cm_digits10(r.mapq) + 2 + 1;     // chr start end N mapq strand (mapping_writer.cc:26-34)
@@ -401,6 +410,126 @@ __global__ __launch_bounds__(64) void k_pp_select_long(const uint8_t *__restrict
       pp_finish(j, r, wi, cfg.bt.tab ? bc[wi] : 0, run_end - j, false, cfg, name_off, win, dups_out, line_len);
     }
   }
+}
+
+// ---------------------------------------------------------------------------------------
+// --allocate-multi-mappings (MappingProcessor::AllocateMultiMappings, mapping_processor.h:319-440), between the selection and the
+// line offsets.  In allocation mode the selection keeps every survivor of duplicate removal (line length != 0) whatever its MAPQ:
+//   classify   survivor with MAPQ >= 4: uni-mapping, below: multi-mapping; one 64-bit word per position (uni count low, multi count
+//              high), so that one exclusive scan numbers both
+//   scatter    uni-mappings: (rid << 32 | start) -- ascending already, the positions are sorted by (rid, start, length) -- and
+//              (rid << 32 | end), radix-sorted next; multi-mappings: sorted position and read_id, then stable-sorted by read_id, which
+//              leaves a read's members in (chromosome rank, position) order as std::stable_sort(ReadIdLess) does
+//   weight     one thread per multi-mapping, in group order: #(start < interval_end) - #(end <= interval_start) by two binary searches
+//              over the whole arrays (the chromosomes below the query's cancel out); end <= interval_start implies start <
+//              interval_end, so the difference is the reference's interval-tree count.  No atomics
+//   group      heads from the sorted read_ids; a scan by key gives every read's weight sum at its last member, where the reads
+//              with and without overlaps are counted
+//   draw       on the host (cm_alloc.h) over the downloaded weights; the kept members' numbers come back
+//   apply      every multi-mapping that was not kept, and every survivor below the MAPQ threshold, loses its line
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ PpRec al_survivor(const uint8_t *store, const uint32_t *__restrict__ win, uint32_t j, const PpCfg &cfg) {
+  PpRec r = pp_load(store, win[j]);
+  if (cfg.tn5) pp_tn5(r, cfg.kind);  // (in-memory flavour: the coordinates that were sorted)
+  return r;
+}
+
+__global__ __launch_bounds__(PP_BLOCK) void k_al_classify(const uint8_t *__restrict__ store, const uint32_t *__restrict__ win,
+                                                            const uint64_t *__restrict__ line_len, uint32_t n, uint64_t *__restrict__ cls) {
+  const uint32_t j = blockIdx.x * PP_BLOCK + threadIdx.x;
+  if (j > n) return;
+  uint64_t v = 0;
+  if (j < n && line_len[j]) v = pp_load(store, win[j]).mapq >= CM_ALLOC_MIN_UNIQUE_MAPQ ? 1ull : 1ull << 32;
+  cls[j] = v;  // (cls[n] = 0: the scan's last element is the two totals)
+}
+
+__global__ __launch_bounds__(PP_BLOCK) void k_al_scatter(const uint8_t *__restrict__ store, const uint32_t *__restrict__ win,
+                                                           const uint64_t *__restrict__ cls, const uint64_t *__restrict__ cls_off, uint32_t n,
+                                                           PpCfg cfg, uint64_t *__restrict__ uni_start, uint64_t *__restrict__ uni_end,
+                                                           uint32_t *__restrict__ multi_pos, uint32_t *__restrict__ multi_read,
+                                                           uint32_t *__restrict__ multi_num) {
+  const uint32_t j = blockIdx.x * PP_BLOCK + threadIdx.x;
+  if (j >= n) return;
+  const uint64_t v = cls[j];
+  if (!v) return;
+  const PpRec r = al_survivor(store, win, j, cfg);
+  const uint64_t off = cls_off[j];
+  if (v == 1ull) {
+    const uint32_t u = (uint32_t)off;
+    uni_start[u] = ((uint64_t)r.rid << 32) | r.start;
+    uni_end[u] = ((uint64_t)r.rid << 32) | (uint32_t)(r.start + r.len);
+  } else {
+    const uint32_t m = (uint32_t)(off >> 32);
+    multi_pos[m] = j;
+    multi_read[m] = r.read_id;
+    multi_num[m] = m;
+  }
+}
+
+// first index in a[0 .. n) whose element is >= key (upper: > key)
+__device__ __forceinline__ uint32_t al_bound(const uint64_t *__restrict__ a, uint32_t n, uint64_t key, bool upper) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    const uint64_t v = a[mid];
+    if (upper ? v <= key : v < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(PP_BLOCK) void k_al_weight(const uint8_t *__restrict__ store, const uint32_t *__restrict__ win, PpCfg cfg,
+                                                          const uint64_t *__restrict__ uni_start, const uint64_t *__restrict__ uni_end,
+                                                          uint32_t n_uni, const uint32_t *__restrict__ multi_pos,
+                                                          const uint32_t *__restrict__ group_read, const uint32_t *__restrict__ group_num,
+                                                          uint32_t n_multi, int distance, uint32_t *__restrict__ weight,
+                                                          uint32_t *__restrict__ weight_head) {
+  const uint32_t g = blockIdx.x * PP_BLOCK + threadIdx.x;
+  if (g >= n_multi) return;
+  const PpRec r = al_survivor(store, win, multi_pos[group_num[g]], cfg);
+  const uint32_t start = r.start, end = r.start + r.len;
+  const uint32_t qs = start > (uint32_t)distance ? start - (uint32_t)distance : 0;  // mapping_processor.h:270-275
+  const uint32_t qe = end + (uint32_t)distance;
+  const uint32_t a = al_bound(uni_start, n_uni, ((uint64_t)r.rid << 32) | qe, false);
+  const uint32_t b = al_bound(uni_end, n_uni, ((uint64_t)r.rid << 32) | qs, true);
+  const uint32_t w = a > b ? a - b : 0;
+  const bool head = g == 0 || group_read[g - 1] != group_read[g];
+  weight[g] = w;
+  weight_head[g] = w | (head ? CM_ALLOC_HEAD : 0u);
+}
+
+// sum[g]: inclusive sum of the weights of g's read up to g.  cnt[0]: reads whose weights sum to more than 0, cnt[1]: to 0
+__global__ __launch_bounds__(PP_BLOCK) void k_al_count(const uint32_t *__restrict__ group_read, const uint32_t *__restrict__ sum,
+                                                         uint32_t n_multi, unsigned long long *__restrict__ cnt) {
+  const uint32_t g = blockIdx.x * PP_BLOCK + threadIdx.x;
+  const bool tail = g < n_multi && (g + 1 == n_multi || group_read[g + 1] != group_read[g]);
+  const bool some = tail && sum[g] != 0;
+  const unsigned long long ms = __ballot(some), mz = __ballot(tail && !some);
+  if ((threadIdx.x & 63u) == 0) {
+    if (ms) atomicAdd(cnt, (unsigned long long)__popcll(ms));
+    if (mz) atomicAdd(cnt + 1, (unsigned long long)__popcll(mz));
+  }
+}
+
+__global__ __launch_bounds__(PP_BLOCK) void k_al_mark(const uint32_t *__restrict__ kept, uint32_t n_kept, const uint32_t *__restrict__ group_num,
+                                                        const uint32_t *__restrict__ multi_pos, uint32_t n_multi, uint32_t n,
+                                                        uint8_t *__restrict__ keep) {
+  const uint32_t k = blockIdx.x * PP_BLOCK + threadIdx.x;
+  if (k >= n_kept) return;
+  const uint32_t g = kept[k];
+  if (g >= n_multi) return;
+  const uint32_t j = multi_pos[group_num[g]];
+  if (j < n) keep[j] = 1;
+}
+
+__global__ __launch_bounds__(PP_BLOCK) void k_al_apply(const uint8_t *__restrict__ store, const uint32_t *__restrict__ win,
+                                                         const uint8_t *__restrict__ keep, uint32_t n, PpCfg cfg, uint64_t *__restrict__ line_len) {
+  const uint32_t j = blockIdx.x * PP_BLOCK + threadIdx.x;
+  if (j >= n) return;
+  const uint64_t ll = line_len[j];
+  if (!ll) return;
+  const uint32_t mapq = pp_load(store, win[j]).mapq;
+  if ((mapq < CM_ALLOC_MIN_UNIQUE_MAPQ && !keep[j]) || (int)mapq < cfg.mapq_thr) { line_len[j] = 0; return; }
+  if (ll == PP_LEN_MISS) { atomicAdd(cfg.bt_miss, 1ull); line_len[j] = 0; }  // a printed line whose barcode the table lacks
 }
 
 // leave_bc (translated barcodes only): room is left for column 4 instead of writing it, and the column's place is returned -- the
@@ -654,6 +783,88 @@ extern "C" int cmgpu_store_append(cmgpu_ctx *c, const void *records, uint64_t n,
   return CMGPU_OK;
 }
 
+// the allocation stage of cmgpu_store_format: after the selection kernels, before the line offsets.  job.loff is free until scan_lines and
+// takes the classification's scan
+static int pp_allocate(cmgpu_ctx *c, CmTextJob &job, const PpCfg &cfg, const cmgpu_params *p, const uint8_t *store, const uint32_t *win, uint32_t n) {
+  hipStream_t s = c->stream;
+  const dim3 b(PP_BLOCK), g((n + PP_BLOCK - 1) / PP_BLOCK), g1(n / PP_BLOCK + 1);
+  CmTmpBuf cls, keep, tmp;
+  if (cls.ensure(((size_t)n + 1) * 8) || keep.ensure((size_t)n)) return job.enomem("allocation");
+  CM_HIPCHECK(c, hipMemsetAsync(keep.p, 0, (size_t)n, s));
+  uint64_t *cls_off = (uint64_t *)job.loff.p;
+  hipLaunchKernelGGL(k_al_classify, g1, b, 0, s, store, win, (const uint64_t *)job.llen.p, n, (uint64_t *)cls.p);
+  { const int rc = cm_scan_u64(c, (const uint64_t *)cls.p, cls_off, (size_t)n + 1, tmp, s, "allocation scan"); if (rc) return rc; }
+  uint64_t totals = 0;
+  CM_HIPCHECK(c, hipMemcpyAsync(&totals, cls_off + n, 8, hipMemcpyDeviceToHost, s));
+  CM_HIPCHECK(c, cm_stream_sync(s));
+  const uint32_t n_uni = (uint32_t)totals, n_multi = (uint32_t)(totals >> 32);
+  c->alloc_multi = n_multi;
+  if (n_uni >= CM_ALLOC_HEAD) { cm_set_error(c, "allocation is limited to 2^31 uni-mappings"); return CMGPU_ECAPACITY; }
+  if (n_multi) {  // (none: the reference asserts; here the text is the plain one)
+    const dim3 gm((n_multi + PP_BLOCK - 1) / PP_BLOCK);
+    CmTmpBuf us, ue0, ue1, mpos, mread0, mread1, mnum0, mnum1, wt, wh, sum, cnt, kept_d;
+    const size_t ub = ((size_t)n_uni + 1) * 8, mb = (size_t)n_multi * 4;
+    if (us.ensure(ub) || ue0.ensure(ub) || ue1.ensure(ub) || mpos.ensure(mb) || mread0.ensure(mb) || mread1.ensure(mb) || mnum0.ensure(mb) ||
+        mnum1.ensure(mb) || wt.ensure(mb) || wh.ensure(mb) || sum.ensure(mb) || cnt.ensure(16)) return job.enomem("allocation");
+    CM_HIPCHECK(c, hipMemsetAsync(cnt.p, 0, 16, s));
+    hipLaunchKernelGGL(k_al_scatter, g, b, 0, s, store, win, (const uint64_t *)cls.p, (const uint64_t *)cls_off, n, cfg, (uint64_t *)us.p,
+                       (uint64_t *)ue0.p, (uint32_t *)mpos.p, (uint32_t *)mread0.p, (uint32_t *)mnum0.p);
+    size_t tb = 0;
+    if (n_uni) {
+      const unsigned bits = 32 + job.rid_bits;
+      CM_HIPCHECK(c, rocprim::radix_sort_keys(nullptr, tb, (uint64_t *)ue0.p, (uint64_t *)ue1.p, (size_t)n_uni, 0, bits, s));
+      if (tmp.ensure(tb + 256)) return job.enomem("allocation sort");
+      CM_HIPCHECK(c, rocprim::radix_sort_keys(tmp.p, tb, (uint64_t *)ue0.p, (uint64_t *)ue1.p, (size_t)n_uni, 0, bits, s));
+    }
+    CM_HIPCHECK(c, rocprim::radix_sort_pairs(nullptr, tb, (uint32_t *)mread0.p, (uint32_t *)mread1.p, (uint32_t *)mnum0.p, (uint32_t *)mnum1.p,
+                                             (size_t)n_multi, 0, 32, s));
+    if (tmp.ensure(tb + 256)) return job.enomem("allocation sort");
+    CM_HIPCHECK(c, rocprim::radix_sort_pairs(tmp.p, tb, (uint32_t *)mread0.p, (uint32_t *)mread1.p, (uint32_t *)mnum0.p, (uint32_t *)mnum1.p,
+                                             (size_t)n_multi, 0, 32, s));
+    const uint32_t *group_read = (const uint32_t *)mread1.p, *group_num = (const uint32_t *)mnum1.p;
+    hipLaunchKernelGGL(k_al_weight, gm, b, 0, s, store, win, cfg, (const uint64_t *)us.p, (const uint64_t *)ue1.p, n_uni, (const uint32_t *)mpos.p,
+                       group_read, group_num, n_multi, (int)p->multi_mapping_allocation_distance, (uint32_t *)wt.p, (uint32_t *)wh.p);
+    CM_HIPCHECK(c, rocprim::inclusive_scan_by_key(nullptr, tb, group_read, (const uint32_t *)wt.p, (uint32_t *)sum.p, (size_t)n_multi,
+                                                  rocprim::plus<uint32_t>(), rocprim::equal_to<uint32_t>(), s));
+    if (tmp.ensure(tb + 256)) return job.enomem("allocation scan");
+    CM_HIPCHECK(c, rocprim::inclusive_scan_by_key(tmp.p, tb, group_read, (const uint32_t *)wt.p, (uint32_t *)sum.p, (size_t)n_multi,
+                                                  rocprim::plus<uint32_t>(), rocprim::equal_to<uint32_t>(), s));
+    hipLaunchKernelGGL(k_al_count, gm, b, 0, s, group_read, (const uint32_t *)sum.p, n_multi, (unsigned long long *)cnt.p);
+    // ---- the draw: one generator for the run, on the host
+    std::vector<uint32_t> w(n_multi), kept;
+    uint64_t counts[2] = {0, 0};
+    CM_HIPCHECK(c, hipMemcpyAsync(counts, cnt.p, 16, hipMemcpyDeviceToHost, s));
+    CM_HIPCHECK(c, hipMemcpyAsync(w.data(), wh.p, mb, hipMemcpyDeviceToHost, s));
+    CM_HIPCHECK(c, cm_stream_sync(s));
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t without = cm_alloc_draw(w.data(), n_multi, p->multi_mapping_allocation_seed, kept);
+    c->alloc_draw_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (kept.size() != counts[0] || without != counts[1]) { cm_set_error(c, "allocation: the device's group counts and the draw's disagree"); return CMGPU_EHIP; }
+    c->alloc_kept = counts[0];
+    c->alloc_without_overlap = counts[1];
+    if (!kept.empty()) {
+      if (kept_d.ensure(kept.size() * 4)) return job.enomem("allocation");
+      CM_HIPCHECK(c, hipMemcpyAsync(kept_d.p, kept.data(), kept.size() * 4, hipMemcpyHostToDevice, s));
+      hipLaunchKernelGGL(k_al_mark, dim3((unsigned)((kept.size() + PP_BLOCK - 1) / PP_BLOCK)), b, 0, s, (const uint32_t *)kept_d.p, (uint32_t)kept.size(),
+                         group_num, (const uint32_t *)mpos.p, n_multi, n, (uint8_t *)keep.p);
+    }
+    hipLaunchKernelGGL(k_al_apply, g, b, 0, s, store, win, (const uint8_t *)keep.p, n, cfg, (uint64_t *)job.llen.p);
+    CM_HIPCHECK(c, cm_stream_sync(s));  // (kept, and the buffers of this scope, are in use until here)
+    return CMGPU_OK;
+  }
+  hipLaunchKernelGGL(k_al_apply, g, b, 0, s, store, win, (const uint8_t *)keep.p, n, cfg, (uint64_t *)job.llen.p);
+  CM_HIPCHECK(c, cm_stream_sync(s));
+  return CMGPU_OK;
+}
+
+extern "C" int cmgpu_store_allocation_info(const cmgpu_ctx *c, uint64_t *n_multi, uint64_t *n_allocated, uint64_t *n_without_overlap) {
+  if (!c) return CMGPU_EINVAL;
+  if (n_multi) *n_multi = c->alloc_multi;
+  if (n_allocated) *n_allocated = c->alloc_kept;
+  if (n_without_overlap) *n_without_overlap = c->alloc_without_overlap;
+  return CMGPU_OK;
+}
+
 // ---------------------------------------------------------------------------------------
 // sort + select + format
 // ---------------------------------------------------------------------------------------
@@ -670,6 +881,8 @@ extern "C" int cmgpu_store_format(cmgpu_ctx *c, int kind, const char *const *nam
   *n_bytes = 0;
   c->text_bytes = 0;
   c->text_lines = 0;
+  c->alloc_multi = c->alloc_kept = c->alloc_without_overlap = 0;
+  c->alloc_seconds = c->alloc_draw_seconds = 0;
   const uint32_t n = (uint32_t)c->store_n;
   if (n == 0) return CMGPU_OK;
   PpCfg cfg;
@@ -690,6 +903,9 @@ extern "C" int cmgpu_store_format(cmgpu_ctx *c, int kind, const char *const *nam
   const bool translate = c->bt_entries != 0 && pp_prints_bc(kind);
   cfg.bt = translate ? cm_bt_dev(c) : CmBtDev{nullptr, nullptr, 0, 0};
   cfg.bt_miss = nullptr;
+  // the reference allocates in its in-memory flavour only (chromap.h:1305-1353); with low_memory_mode the flag does nothing
+  cfg.alloc = p->allocate_multi_mappings && !p->low_memory_mode;
+  if (cfg.alloc && c->ex.transport) { cm_set_error(c, "allocate_multi_mappings: a read's positions lie on chromosomes of several ranks"); return CMGPU_EINVAL; }
   if (cfg.bulk && c->wl_size == 0) { cm_set_error(c, "bulk-level duplicate removal needs the whitelist abundances (cmgpu_set_whitelist)"); return CMGPU_EINVAL; }
   CmTextJob job;
   int rc;
@@ -729,10 +945,16 @@ extern "C" int cmgpu_store_format(cmgpu_ctx *c, int kind, const char *const *nam
   CmSmDev sm;
   if ((rc = cm_summary_dev(c, c->ex.transport ? n : 0, pp_has_bc(kind) && c->wl_size && !p->output_mappings_not_in_whitelist ? c->wl_size : 0,
                            !pp_has_bc(kind), &sm))) return rc;
+  if (cfg.alloc && sm.keys) { cm_set_error(c, "allocate_multi_mappings: the summary's duplicate and low-MAPQ counts are taken before the allocation"); return CMGPU_EINVAL; }
   hipLaunchKernelGGL(k_pp_select, g, b, 0, s, store, bc, (const uint32_t *)job.idx(), n, cfg, job.seq_off(), (uint32_t *)win.p,
                      (uint32_t *)dups.p, (uint64_t *)job.llen.p, long_list, long_cnt, sm);
   hipLaunchKernelGGL(k_pp_select_long, dim3(1024), dim3(64), 0, s, store, bc, (const uint32_t *)job.idx(), n, cfg, job.seq_off(),
                      (uint32_t *)win.p, (uint32_t *)dups.p, (uint64_t *)job.llen.p, (const uint32_t *)long_list, (const uint32_t *)long_cnt, sm);
+  if (cfg.alloc) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((rc = pp_allocate(c, job, cfg, p, store, (const uint32_t *)win.p, n))) return rc;
+    c->alloc_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();  // (pp_allocate ends with the stream waited for)
+  }
   uint64_t total = 0, lines = 0, misses = 0;
   if ((rc = job.scan_lines(&total, &lines, translate ? &misses : nullptr))) return rc;
   if (misses) { cm_set_error(c, CM_BT_MISS_MESSAGE); return CMGPU_EFORMAT; }  // (no text: text_bytes is 0 since the call began)
@@ -850,6 +1072,7 @@ __global__ __launch_bounds__(PP_BLOCK) void k_pp_pairs_format(const uint8_t *__r
 static int pp_format_pairs(cmgpu_ctx *c, const char *const *names, uint32_t n_sequences, const cmgpu_params *p, bool resident,
                            const char *read_names, const uint64_t *read_name_offsets, uint32_t n_read_names,
                            uint32_t read_id_base, uint64_t *n_lines, uint64_t *n_bytes) {
+  if (p->allocate_multi_mappings && !p->low_memory_mode) { cm_set_error(c, "allocate_multi_mappings: pairs records have no allocation stage"); return CMGPU_EINVAL; }
   if (!cm_store_pairs_records(c)) { cm_set_error(c, "pairs text needs pairs records (split alignment, or output_format = CMGPU_FORMAT_PAIRS)"); return CMGPU_EINVAL; }
   // (cell barcodes: they decided which pairs were mapped -- CorrectBarcodeAt, chromap.h:896-906 -- and go no further: a PairsMapping's barcode is
   //  neither printed nor part of its order or equality, pairs_mapping.h:40-50, GetBarcode() == 0; the store's key array is left alone)

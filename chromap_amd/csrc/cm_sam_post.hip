@@ -403,6 +403,7 @@ extern "C" int cmgpu_store_format_sam(cmgpu_ctx *c, const char *const *ref_names
                                       uint32_t barcode_length, uint64_t *n_lines, uint64_t *n_bytes) {
   (void)ref_lengths;  // (the @SQ lines are the caller's: cmgpu_write_sam_header)
   if (!c || !ref_names || !p || !n_lines || !n_bytes) return CMGPU_EINVAL;
+  if (p->allocate_multi_mappings && !p->low_memory_mode) { cm_set_error(c, "allocate_multi_mappings: SAM records have no allocation stage"); return CMGPU_EINVAL; }
   CM_HIPCHECK(c, cm_enter(c));
   CmSamStore &st = c->ss;
   if (st.has_bc && (barcode_length == 0 || barcode_length > 32)) { cm_set_error(c, "the SAM record store holds barcodes: barcode_length must be 1..32"); return CMGPU_EINVAL; }

@@ -644,6 +644,13 @@ class ChromapGPU:
                                               C.byref(nl), C.byref(nb)), self.ctx)
         return nl.value, nb.value
 
+    def store_allocation_info(self):
+        """(multi-mappings, allocated reads, reads without uni-mapping overlaps) of the last store_format with allocate_multi_mappings;
+        zeros when no allocation ran (flag off, low_memory_mode, empty store)"""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.cmgpu_store_allocation_info(self.ctx, C.byref(a), C.byref(b), C.byref(c)), self.ctx)
+        return int(a.value), int(b.value), int(c.value)
+
     def store_text(self):
         nb = C.c_uint64(0)
         self.L.cmgpu_store_info(self.ctx, None, C.byref(nb), None)

@@ -87,6 +87,10 @@ typedef struct cmgpu_params {
                                    * NM, MD); CMGPU_FORMAT_PAIRS: pairs records from the ordinary (non-split) pairing */
   int32_t dedup_at_bulk_level;    /* single-cell BED, low-memory flavour: --remove-pcr-duplicates-at-bulk-level (the reference's
                                    * default without --preset atac); applied by cmgpu_store_format only */
+  int32_t allocate_multi_mappings; /* --allocate-multi-mappings: in-memory flavour only (low_memory_mode == 0); cmgpu_store_format of the BED /
+                                    * TagAlign kinds, cmgpu_write_bed_pe / _se / _pe_bc */
+  int32_t multi_mapping_allocation_distance; /* --multi-mapping-allocation-distance (0) */
+  int32_t multi_mapping_allocation_seed;     /* --multi-mapping-allocation-seed (11) */
   double bc_probability_threshold; /* --bc-probability-threshold */
 } cmgpu_params;
 
@@ -556,6 +560,14 @@ int cmgpu_write_pairs_header(const char *const *names, const uint32_t *lengths, 
 int cmgpu_store_text(cmgpu_ctx *ctx, char *out, uint64_t capacity);
 int cmgpu_store_write_text(cmgpu_ctx *ctx, const char *path, int append);
 int cmgpu_store_info(const cmgpu_ctx *ctx, uint64_t *n_records, uint64_t *text_bytes, uint64_t *text_lines);
+/* --allocate-multi-mappings (MappingProcessor::AllocateMultiMappings, src/mapping_processor.h:319-440): with
+ * params->allocate_multi_mappings and without low_memory_mode, cmgpu_store_format gives every read whose surviving records have
+ * MAPQ < 4 to one of them, drawn with probability proportional to the uni-mappings (MAPQ >= 4) within
+ * multi_mapping_allocation_distance of it, and drops the reads that have none; then the MAPQ filter and the text as usual.  The
+ * counts of the last cmgpu_store_format, the reference's "Got all N multi-mappings", "Allocated K multi-mappings" and "# multi-mappings
+ * that have no uni-mapping overlaps: M"; zeros when no allocation ran.  Not with --summary counting, nor on a store filled by the
+ * multi-GPU exchange (CMGPU_EINVAL); cmgpu_store_format_pairs* and cmgpu_store_format_sam refuse the flag. */
+int cmgpu_store_allocation_info(const cmgpu_ctx *ctx, uint64_t *n_multi, uint64_t *n_allocated, uint64_t *n_without_overlap);
 
 /* ---- FASTQ ingest on the device ---------------------------------------
  * Replaces, for 4-line FASTQ text, kseq_read + SequenceBatch::LoadOneSequenceAndSaveAt
