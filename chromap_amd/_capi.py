@@ -124,6 +124,24 @@ SYMBOLS = ("cmgpu_default_params", "cmgpu_apply_preset", "cmgpu_create", "cmgpu_
            "cmgpu_host_alloc", "cmgpu_host_free", "cmgpu_host_register", "cmgpu_host_unregister", "cmgpu_submit_pairs", "cmgpu_map_submitted", "cmgpu_map_submitted_async", "cmgpu_records_wait",
            "cmgpu_debug_trace", "cmgpu_debug_minimizers", "cmgpu_debug_minimizers_all", "cmgpu_debug_array")
 
+# names cmgpu_debug_array knows (include/chromap_amd_debug.h): per read, per pair, and the 64 counters of the device work lists
+DEBUG_ARRAYS_PER_READ = ("rlen", "mm_cnt", "hit_tot", "ncp", "ncn", "resc_p", "resc_n", "mcp", "mcn", "fcp", "fcn", "ndp", "ndn", "nv")
+DEBUG_ARRAYS_PER_PAIR = ("pe_nbest",)
+DEBUG_LIST_COUNTERS = "hv_cnt"
+HV_LISTS = 32  # CM_HV_LISTS: words of "hv_cnt" that count items (the other 32 are work cursors)
+
+
+def debug_array(L, ctx, name, n_pairs):
+    """one array of the last mapped batch by name, as numpy uint32"""
+    import numpy as np
+    cap = 64 if name == DEBUG_LIST_COUNTERS else max(1, 2 * n_pairs)
+    out = np.zeros(cap, np.uint32)
+    n = C.c_uint64(0)
+    if L.cmgpu_debug_array(ctx, name.encode(), out.ctypes.data, cap, C.byref(n)) != 0:
+        raise RuntimeError(L.cmgpu_last_error(ctx).decode())
+    return out[:n.value]
+
+
 UNIQUE_ID_BYTES = 128
 ALLGATHER_COUNTS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint32)
 ALLTOALLV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32)

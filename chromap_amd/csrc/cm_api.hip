@@ -1584,6 +1584,12 @@ extern "C" int cmgpu_debug_array(cmgpu_ctx *c, const char *name, uint32_t *out, 
   if (!c || !name || !out) return CMGPU_EINVAL;
   CM_HIPCHECK(c, cm_enter(c));
   const std::string nm(name);
+  if (nm == "hv_cnt") {  // the device work lists' counters of the last mapped range (words 0 .. CM_HV_LISTS - 1: items per CmList id; the rest: work cursors)
+    if (n_out) *n_out = 64;
+    if (capacity < 64 || !c->hv_cnt.p || c->hv_cnt.cap < 256) { cm_set_error(c, "debug array: buffer too small or array not resident"); return CMGPU_ECAPACITY; }
+    CM_HIPCHECK(c, hipMemcpy(out, c->hv_cnt.p, 256, hipMemcpyDeviceToHost));
+    return CMGPU_OK;
+  }
   struct { const char *n; DevBuf *b; int per_pair; } tab[] = {
     {"rlen", &c->rlen, 0}, {"mm_cnt", &c->mm_cnt, 0}, {"hit_tot", &c->hit_tot, 0}, {"ncp", &c->ncp, 0}, {"ncn", &c->ncn, 0},
     {"resc_p", &c->resc_p, 0}, {"resc_n", &c->resc_n, 0}, {"mcp", &c->mcp, 0}, {"mcn", &c->mcn, 0}, {"fcp", &c->fcp, 0},

@@ -134,7 +134,9 @@ int cmgpu_reference_lengths(cmgpu_ctx *ctx, uint32_t *lengths, uint32_t capacity
 
 /* A per-read (2 n entries: "rlen", "mm_cnt", "hit_tot", "ncp", "ncn", "resc_p", "resc_n", "mcp", "mcn", "fcp", "fcn", "ndp",
  * "ndn", "nv") or per-pair (n entries: "pe_nbest") 32-bit array of the last mapped batch -- the list lengths the stages saw
- * (tools/list_hist.py).  *n_out = entries. */
+ * (tools/list_hist.py).  *n_out = entries.
+ * "hv_cnt": the 64 counters of the device work lists of the last mapped range -- word l < 32 = the reads / pairs that went to
+ * long-list class l (the CmList ids of cm_types.h), the words above are the lists' work cursors.  A read-only copy. */
 int cmgpu_debug_array(cmgpu_ctx *ctx, const char *name, uint32_t *out, uint64_t capacity, uint64_t *n_out);
 
 #ifdef __cplusplus

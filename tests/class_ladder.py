@@ -1,0 +1,434 @@
+"""Genomes with element families of EXACT copy numbers, one case per tier of the long-list size classes (the table at the top
+of chromap_amd/csrc/cm_types.h; the policy in cm_classes.h): every list length a class boundary B names is met at B - 1, B and
+B + 1 by a read the generator planned for it.  Seeded, plain numpy; the oracle (tests/oracle_lib.py) supplies minimizers and the
+index, nothing here looks at the device code.
+
+Three kinds of family:
+
+  cand    a unit of CAND_UNIT bases copied cp times on the + strand and cn times on the - strand, exact copies, apart from each
+          other by more than the insert-size limit.  Read 1 is the unit's head, read 2 the reverse complement of its tail: cp / cn
+          candidates per read and strand, as many after the pair filter, as many draft mappings, cp + cn co-best pairings.
+  hit     a short unit of c copies; read 1 straddles the left edge of copy 0, so j of its minimizers lie in the unit (c occurrences
+          each) and u in copy 0's own flank (one each): j * c + u hits.  Read 2 lies in the flank behind copy 0.
+  rescue  read 1 lies in element A (cp + cn copies, under the first seed-frequency cap), read 2 in element R, which stands beside
+          every copy of A and is more frequent than the second cap: read 2 has no candidates of its own, the rescue search finds
+          its m2 minimizers beside each of read 1's cp candidates -- m2 * cp rescue hits.  R-bearing blocks alternate in
+          orientation along the genome: the reference's search starts its scan at the last probe of its binary search, which may
+          be the occurrence BEFORE the window, and takes it when it has the searched orientation; with alternating neighbours it
+          never has.
+
+A case's `plan` says which pair is meant to produce which length in which array; `model_hit_tot` and `model_rescue` are the two
+lengths the oracle's trace does not carry, from the oracle's index and minimizers (the hits of a read are the
+index occurrences of its minimizers under the cap of the round that is used; the rescue hits the occurrences of its minimizers
+inside the search windows around the mate's best candidates).  tests/test_class_ladder_cpu.py holds the plan to both."""
+import atexit
+import ctypes as C
+import os
+import shutil
+import tempfile
+
+import numpy as np
+
+import oracle_lib as ol
+
+ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
+COMP = np.zeros(256, dtype=np.uint8)
+for _a, _b in zip(b"ACGTN", b"TGCAN"):
+    COMP[_a] = _b
+K, W = 17, 7
+CAND_UNIT = 120
+INSERT = {50: 240, 100: 320}   # max_insert_size of the cand / hit cases by read length: a fragment fits, a cand unit's next copy (>= 140 further) does not
+RESCUE_INSERT = 300
+RESCUE_A, RESCUE_R = 60, 200
+CAND_ARRAYS = (("ncp", "ncn"), ("mcp", "mcn"), ("fcp", "fcn"), ("ndp", "ndn"))
+
+# boundaries of the size-class table, by the kind of list they cut
+HIT_B = {50: (16, 64, 256, 512, 1024, 2048, 4096, 7040, 8192, 65535), 100: (16, 96)}
+CAND_B = (256, 512, 1024, 2048, 4096, 8192, 15360, 16384)   # pair filter 256 / 1024 / 4096 / 15360, verification 512 / 2048 / 16384, pairing 256 / 1024 / 8192
+NBEST_B = (256, 1024, 8192)
+RESCUE_B = (512, 1024, 2048, 3968, 7680)                    # the issue's 3968 and 7680, and the classes below them
+
+# name -> (read length, hit boundaries, cand boundaries, co-best boundaries, rescue boundaries, first / second seed-frequency cap)
+TIERS = {
+    "lane_50": (50, (16, 64, 256, 512), (256, 512), (256,), (), 1000, 2000),
+    "lane_100": (100, (16, 96), (), (), (), 500, 1000),
+    "block_1k_2k": (50, (1024, 2048), (1024, 2048), (1024,), (), 3000, 6000),
+    "hits_4k_8k": (50, (4096, 7040, 8192), (), (), (), 12000, 24000),
+    "slab_64k": (50, (65535,), (), (), (), 70000, 140000),
+    "cand_4096": (50, (), (4096,), (), (), 5000, 10000),
+    "pair_8192": (50, (), (8192,), (8192,), (), 9000, 18000),
+    "pf_15360": (50, (), (15360,), (), (), 16000, 32000),
+    "verif_16384": (50, (), (16384,), (), (), 17000, 34000),
+    "rescue": (50, (), (), (), RESCUE_B, 300, 400),
+}
+SMALL_TIERS = ("lane_50", "lane_100")   # every planned length <= 513: cheap enough for the host emulation
+LARGEST_TIERS = ("pf_15360", "verif_16384")
+HIT_KEY64_TIER = "hits_4k_8k"
+
+
+def rc(a):
+    return COMP[a[::-1]]
+
+
+def _rand(rng, n):
+    return ACGT[rng.integers(0, 4, size=int(n))]
+
+
+def minimizers(read):
+    """(hashes, hits) of ora_minimizers; a hit is position of the k-mer's last base << 1 | strand"""
+    L = ol.lib()
+    read = np.frombuffer(bytes(read), np.uint8) if not isinstance(read, np.ndarray) else read
+    s = np.concatenate([read, np.zeros(8, np.uint8)])
+    oh, ot = np.zeros(1024, np.uint64), np.zeros(1024, np.uint64)
+    n = L.ora_minimizers(s.ctypes.data_as(C.c_char_p), len(read), 0, K, W, oh.ctypes.data, ot.ctypes.data)
+    return [int(x) for x in oh[:n]], [int(x) for x in ot[:n]]
+
+
+class IndexLookup:
+    """the oracle's index by minimizer hash: None (absent), a one-entry array (singleton), or the occurrence run"""
+    def __init__(self, o):
+        self.o = o
+        n = int(o.idx.n_occ)
+        self.occ = np.ctypeslib.as_array(o.idx.occ, shape=(n,)) if n else np.zeros(0, np.uint64)
+
+    def get(self, h):
+        steps = C.c_uint64(0)
+        it = self.o.L.ora_kh_get(C.byref(self.o.idx), (h << 1) & 0xFFFFFFFFFFFFFFFF, C.byref(steps))
+        if it == self.o.idx.n_buckets:
+            return None, False
+        key, val = int(self.o.idx.keys[it]), int(self.o.idx.vals[it])
+        if key & 1:
+            return np.array([val], np.uint64), True
+        off, n = val >> 32, val & 0xFFFFFFFF
+        return self.occ[off:off + n], False
+
+
+def model_hit_tot(ix, read, f0, f1):
+    """hits of the round that is used: the occurrences of the read's minimizers that are less frequent than the cap, first with
+    the first cap; a read without a hit tries again under the second"""
+    hs, _ = minimizers(read)
+    runs = [ix.get(h) for h in hs]
+
+    def under(cap):
+        return sum(1 if single else (len(run) if len(run) < cap else 0) for run, single in runs if run is not None)
+    tot = under(f0)
+    return tot if tot else under(f1)
+
+
+def model_rescue(ix, read, mate_candidates, negative, search_range):
+    """rescue hits of `read` on one strand (negative: the read maps to the - strand there) around the mate's candidates of the
+    other strand -- (position, count) in ascending position, position = sequence << 32 | coordinate.  Windows of search_range on
+    both sides of the candidates with the highest count, overlapping ones joined; per minimizer and window a binary search for
+    the window's start among the sorted occurrences, the scan starts at its LAST PROBE and runs to the window's end; an occurrence
+    counts when its orientation is the searched one.  Singletons count without a look at the windows."""
+    top = max(c for _, c in mate_candidates)
+    win = []
+    for p, c in mate_candidates:
+        if c != top:
+            continue
+        lo, hi = (0 if p < search_range else p - search_range), p + search_range
+        if win and not win[-1][1] < lo:
+            win[-1][1] = hi
+        else:
+            win.append([lo, hi])
+    hs, ps = minimizers(read)
+    tot = 0
+    for h, hit in zip(hs, ps):
+        run, single = ix.get(h)
+        if run is None:
+            continue
+        want_same = 0 if negative else 1
+        if single:
+            tot += int(int((int(run[0]) & 1) == (hit & 1)) == want_same)
+            continue
+        keys = (run >> np.uint64(1)).tolist()
+        same = ((run & np.uint64(1)) == np.uint64(hit & 1)).tolist()
+        n = len(keys)
+        prev_l = 0
+        for lo, hi in win:
+            l, r, m = prev_l, n - 1, 0
+            while l <= r:
+                m = (l + r) // 2
+                if keys[m] < lo:
+                    l = m + 1
+                elif keys[m] > lo:
+                    r = m - 1
+                else:
+                    break
+            prev_l = m
+            oi = m
+            while oi < n and keys[oi] <= hi:
+                tot += int(int(same[oi]) == want_same)
+                oi += 1
+    return tot
+
+
+class Case:
+    pass
+
+
+def _plan_hit_family(rng, T, L, f0):
+    """a unit, copy 0's flanks and the read offset t (flank bases in front) with j * c + u == T; j as large as the reads offer"""
+    U = L + 10
+    min_j = 5 if T > 4096 else 1
+    for _ in range(400):
+        unit, fl, fr = _rand(rng, U), _rand(rng, 40), _rand(rng, L + 30)   # read 2 lies in fr alone
+        D = np.concatenate([fl, unit, fr])
+        core = set(minimizers(unit)[0])
+        best = None
+        for t in range(1, L - K + 1):
+            hs, ps = minimizers(D[40 - t:40 - t + L])
+            j = u = 0
+            certain = len(set(hs)) == len(hs)
+            for h, hit in zip(hs, ps):
+                if ((hit >> 1) & 0xFFFFFFFF) - K + 1 >= t:   # the k-mer lies in the unit: a minimizer of every copy if it is one of the unit alone
+                    j += 1
+                    certain = certain and h in core
+                else:
+                    u += 1
+                    certain = certain and h not in core
+            if not certain or j < min_j or (T - u) % j:
+                continue
+            c = (T - u) // j
+            if 2 <= c < f0 and (best is None or j > best[1]):
+                best = (t, j, u, c)
+        if best:
+            return D, unit, best
+    raise RuntimeError("no straddling read gives %d hits" % T)
+
+
+def _factor(x, menu, lo=2, hi=295):
+    """(m2, cp) with m2 * cp == x, m2 among the minimizer counts the reads offer, the most copies first"""
+    for m2 in sorted(menu):
+        if x % m2 == 0 and lo <= x // m2 <= hi:
+            return m2, x // m2
+    return None
+
+
+def _build(name, d):
+    L, hit_b, cand_b, nbest_b, resc_b, f0, f1 = TIERS[name]
+    rng = np.random.default_rng([sum(name.encode()), len(name), 20251])
+    rescue = bool(resc_b)
+    insert = RESCUE_INSERT if rescue else INSERT[L]
+    blocks = []    # {"seq", "fam", "strand", "chr", "pos"}; a family: {"kind", "copies": its blocks, ...}
+    fams = []
+
+    def copies(fam, seq, n_plus, n_minus, first=None):
+        for i in range(n_plus + n_minus):
+            s = 0 if i < n_plus else 1
+            b = {"seq": first if (i == 0 and first is not None) else (seq if s == 0 else rc(seq)), "fam": fam, "strand": s}
+            fam["copies"].append(b)
+            blocks.append(b)
+
+    for B in cand_b:
+        for d_ in (-1, 0, 1):
+            minor = 3 + d_
+            cp, cn = (B + d_, minor) if d_ else (minor, B)
+            fam = {"kind": "cand", "B": B, "cp": cp, "cn": cn, "unit": _rand(rng, CAND_UNIT), "copies": [], "planned": ("cand",)}
+            copies(fam, fam["unit"], cp, cn)
+            fams.append(fam)
+    for B in nbest_b:
+        for d_ in (-1, 0, 1):
+            cp, cn = (B + d_ - 3, 3) if d_ else (4, B - 4)
+            fam = {"kind": "cand", "B": B, "cp": cp, "cn": cn, "unit": _rand(rng, CAND_UNIT), "copies": [], "planned": ("nbest",)}
+            copies(fam, fam["unit"], cp, cn)
+            fams.append(fam)
+    for B in hit_b:
+        for T in (B - 1, B, B + 1):
+            Lh = min(L, 50) if T <= 17 else L   # (a read of 100 bases has more minimizers than that; the classes follow the batch's longest read)
+            D, unit, (t, j, u, c) = _plan_hit_family(rng, T, Lh, f0)
+            fam = {"kind": "hit", "B": B, "T": T, "t": t, "j": j, "u": u, "c": c, "D": D, "L": Lh, "copies": []}
+            # the other copies' neighbouring bases differ from copy 0's: no k-mer across copy 0's edges occurs a second time
+            guarded = np.concatenate([ACGT[[(b"ACGT".index(bytes([D[39]])) + 1) % 4]], unit, ACGT[[(b"ACGT".index(bytes([D[40 + len(unit)]])) + 1) % 4]]])
+            copies(fam, guarded, (c + 1) // 2, c // 2, first=D)
+            fams.append(fam)
+    unmet = []
+    if rescue:
+        R, menu = _rand(rng, RESCUE_R), {}
+        for ln in range(60, RESCUE_R + 1, 2):
+            for a in range(0, RESCUE_R - ln + 1, 7):
+                m2 = len(minimizers(rc(R[a:a + ln]))[0])
+                menu.setdefault(m2, (a, ln))
+        i = 0
+        for B in resc_b:
+            for d_ in (-1, 0, 1):
+                x, step = B + d_, (d_ or 1)
+                while _factor(x, menu) is None:   # the nearest length the reads can give on this side
+                    x += step
+                m2, cp = _factor(x, menu)
+                if x != B + d_:
+                    assert abs(x - (B + d_)) <= m2 - 1, (B, d_, x, m2)
+                    unmet.append({"array": "resc_p/resc_n", "boundary": B, "want": B + d_, "nearest": x})
+                minor = 2 + i % 3
+                fam = {"kind": "rescue", "B": B, "T": x, "m2": m2, "sub": menu[m2], "major": i % 2, "cp": cp if i % 2 == 0 else minor,
+                       "cn": minor if i % 2 == 0 else cp, "A": _rand(rng, RESCUE_A), "copies": []}
+                copies(fam, np.concatenate([fam["A"], R]), fam["cp"], fam["cn"])
+                fams.append(fam)
+                i += 1
+        lone = {"kind": "lone", "copies": []}
+        n_plus = sum(b["strand"] == 0 for b in blocks)
+        n_minus = len(blocks) - n_plus
+        total = max(f1 + 50, 2 * max(n_plus, n_minus))   # R is more frequent than the second cap
+        copies(lone, R, total // 2 - n_plus, total - total // 2 - n_minus)
+        plus = [b for b in blocks if b["strand"] == 0]
+        minus = [b for b in blocks if b["strand"] == 1]
+        rng.shuffle(plus)
+        rng.shuffle(minus)
+        order = [x for pair in zip(plus, minus) for x in pair] + plus[len(minus):] + minus[len(plus):]
+        assert abs(len(plus) - len(minus)) <= 1
+    else:
+        order = list(blocks)
+        rng.shuffle(order)
+    n_chr = 3
+    uniq = [{"seq": _rand(rng, 2500), "fam": None, "strand": 0} for _ in range(n_chr)]
+    chroms = []
+    per = (len(order) + n_chr - 1) // n_chr
+    lo_sp, hi_sp = (900, 960) if rescue else (20, 41)
+    for ci in range(n_chr):
+        mine = [uniq[ci]] + order[ci * per:(ci + 1) * per]
+        parts, pos = [_rand(rng, 300)], 300
+        sp = rng.integers(lo_sp, hi_sp, size=len(mine))
+        for b, s in zip(mine, sp):
+            parts.append(_rand(rng, s))
+            pos += int(s)
+            b["chr"], b["pos"] = ci, pos
+            parts.append(b["seq"])
+            pos += len(b["seq"])
+        parts.append(_rand(rng, 300 + (lo_sp if rescue else 0)))
+        chroms.append(np.concatenate(parts))
+
+    # ---- pairs and plan
+    r1, r2, plan, trace = [], [], [], {}
+
+    def add(a, b):
+        r1.append(np.ascontiguousarray(a).tobytes())
+        r2.append(np.ascontiguousarray(b).tobytes())
+        return len(r1) - 1
+
+    def unique_pairs(n):
+        for _ in range(n):
+            u = uniq[int(rng.integers(0, n_chr))]["seq"]
+            fl = int(rng.integers(L + 60, insert + 1))
+            st = int(rng.integers(0, len(u) - fl))
+            a, b = u[st:st + L], rc(u[st + fl - L:st + fl])
+            i = add(a, b) if rng.random() < 0.5 else add(b, a)
+            trace[i] = {"n_cand1": 1, "n_cand2": 1, "n_draft1": 1, "n_draft2": 1, "nbest": 1}
+    unique_pairs(12)
+    for fi, fam in enumerate(fams):
+        if fam["kind"] == "cand":
+            cp, cn, unit = fam["cp"], fam["cn"], fam["unit"]
+            for o in (0, 3, 7):
+                i = add(unit[o:o + L], rc(unit[CAND_UNIT - L - o:CAND_UNIT - o]))
+                trace[i] = {"n_cand1": cp + cn, "n_cand2": cp + cn, "n_draft1": cp + cn, "n_draft2": cp + cn, "nbest": cp + cn}
+                if "cand" in fam["planned"]:
+                    for ap, an in CAND_ARRAYS:
+                        plan += [{"pair": i, "mate": 0, "array": ap, "want": cp, "boundary": fam["B"], "kind": "cand", "fam": fi},
+                                 {"pair": i, "mate": 0, "array": an, "want": cn, "boundary": fam["B"], "kind": "cand", "fam": fi},
+                                 {"pair": i, "mate": 1, "array": ap, "want": cn, "boundary": fam["B"], "kind": "cand", "fam": fi},
+                                 {"pair": i, "mate": 1, "array": an, "want": cp, "boundary": fam["B"], "kind": "cand", "fam": fi}]
+                else:
+                    plan.append({"pair": i, "mate": None, "array": "pe_nbest", "want": cp + cn, "boundary": fam["B"], "kind": "nbest"})
+        elif fam["kind"] == "hit":
+            D, t, Lh = fam["D"], fam["t"], fam["L"]
+            i = add(D[40 - t:40 - t + Lh], rc(D[len(D) - Lh:]))
+            plan.append({"pair": i, "mate": 0, "array": "hit_tot", "want": fam["T"], "boundary": fam["B"], "kind": "hit"})
+            i = add(rc(D[len(D) - Lh:]), D[40 - t:40 - t + Lh])   # the same fragment with the mates exchanged
+            plan.append({"pair": i, "mate": 1, "array": "hit_tot", "want": fam["T"], "boundary": fam["B"], "kind": "hit"})
+        elif fam["kind"] == "rescue":
+            a, ln = fam["sub"]
+            for o in (3, 6):
+                i = add(fam["A"][o:o + L], rc(R[a:a + ln]))
+                cands = {0: [], 1: []}   # read 1's candidates by strand: the read's first base on the + strand, its last on the -
+                for b in fam["copies"]:
+                    p = b["pos"] + o if b["strand"] == 0 else b["pos"] + RESCUE_A + RESCUE_R - o - 1
+                    cands[b["strand"]].append(((b["chr"] << 32) | p, 1))
+                major = fam["major"]
+                # read 1's + candidates drive the search on read 2's - strand, its - candidates the one on the + strand
+                plan.append({"pair": i, "mate": 1, "array": "resc_n" if major == 0 else "resc_p", "want": fam["T"], "boundary": fam["B"],
+                             "kind": "rescue", "mate_candidates": sorted(cands[major]), "negative": major == 0})
+                trace[i] = {"rep2_nonzero": 1, "n_cand1": fam["cp"] + fam["cn"]}
+    unique_pairs(12)
+
+    def pack(rs):
+        off = np.zeros(len(rs) + 1, np.uint32)
+        off[1:] = np.cumsum([len(r) for r in rs])
+        return np.frombuffer(b"".join(rs), np.uint8).copy(), off
+    c = Case()
+    c.name, c.dir, c.read_len = name, d, L
+    c.fa = os.path.join(d, name + ".fa")
+    with open(c.fa, "wb") as f:
+        for i, ch in enumerate(chroms):
+            f.write(b">c%d\n" % i + ch.tobytes() + b"\n")
+    c.genome = sum(len(ch) for ch in chroms)
+    c.preset = "chip"
+    c.kw = {"mapq_threshold": 0, "max_seed_freq0": f0, "max_seed_freq1": f1, "max_insert_size": insert}
+    c.b1, c.o1 = pack(r1)
+    c.b2, c.o2 = pack(r2)
+    c.n_pairs = len(r1)
+    c.max_read_len = max(max(len(x) for x in r1), max(len(x) for x in r2))
+    c.plan, c.trace, c.unmet, c.families = plan, trace, unmet, fams
+    c.search_range = 2 * insert
+    c.idx = os.path.join(d, name + ".idx")
+    return c
+
+
+_CASES = {}
+_TMP = []
+
+
+def _cleanup():
+    for d in _TMP:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+atexit.register(_cleanup)
+
+
+def get_case(name):
+    """the case of a tier, generated once per process; its index file is written by oracle_for()"""
+    if name not in _CASES:
+        d = tempfile.mkdtemp(prefix="class_ladder_")
+        _TMP.append(d)
+        _CASES[name] = _build(name, d)
+    return _CASES[name]
+
+
+def read_of(case, pair, mate):
+    b, o = (case.b1, case.o1) if mate == 0 else (case.b2, case.o2)
+    return b[o[pair]:o[pair + 1]]
+
+
+def oracle_for(case):
+    """a fresh oracle over the case (it builds the index; the index file is written on the first call)"""
+    o = ol.Oracle(None, case.fa, ol.params(case.preset, **case.kw))
+    if not os.path.exists(case.idx):
+        assert o.L.ora_index_save(case.idx.encode(), C.byref(o.idx)) == 0
+    return o
+
+
+def model_lengths(case, o):
+    """plan entry -> the Python model's length, for the two arrays the oracle's trace does not carry"""
+    ix = IndexLookup(o)
+    out = {}
+    for n, e in enumerate(case.plan):
+        if e["kind"] == "hit":
+            out[n] = model_hit_tot(ix, read_of(case, e["pair"], e["mate"]), case.kw["max_seed_freq0"], case.kw["max_seed_freq1"])
+        elif e["kind"] == "rescue":
+            out[n] = model_rescue(ix, read_of(case, e["pair"], e["mate"]), e["mate_candidates"], e["negative"], case.search_range)
+    return out
+
+
+def required_lengths(name):
+    """the coverage condition of a tier: (array group, boundary, length) that some planned read must show exactly"""
+    L, hit_b, cand_b, nbest_b, resc_b, _, _ = TIERS[name]
+    req = []
+    for B in hit_b:
+        req += [(("hit_tot",), B, B + d) for d in (-1, 0, 1)]
+    for B in cand_b:
+        for grp in CAND_ARRAYS:
+            req += [(grp, B, B + d) for d in (-1, 0, 1)]
+    for B in nbest_b:
+        req += [(("pe_nbest",), B, B + d) for d in (-1, 0, 1)]
+    for B in resc_b:
+        req += [(("resc_p", "resc_n"), B, B + d) for d in (-1, 0, 1)]
+    return req

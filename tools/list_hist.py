@@ -69,6 +69,10 @@ def main():
                           ths=(10**3, 10**4, 10**5, 10**6, 10**7, 10**8)))
     lists.append(describe("pe_nbest per pair", A["pe_nbest"]))
     res["lists"] = lists
+    # items per device work list of the last range (CmList ids, cm_types.h): which classes' kernels had work
+    from chromap_amd import _capi
+    hv = _capi.debug_array(g.L, g.ctx, _capi.DEBUG_LIST_COUNTERS, a.pairs)[:_capi.HV_LISTS]
+    res["list_items_last_range"] = {str(l): int(hv[l]) for l in range(len(hv)) if hv[l]}
     print(json.dumps(res))
     for o in lists:
         print("%-60s nonzero %9d sum %12d max %9d  p50 %s p99 %s p99.9 %s" % (o["name"], o["nonzero"], o["sum"], o["max"], o.get("p50"), o.get("p99"), o.get("p99.9")), file=sys.stderr)
