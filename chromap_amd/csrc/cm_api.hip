@@ -785,6 +785,7 @@ static void cm_set_classes(const cmgpu_ctx *c, CmDev &d) {
   in.lane_cap = cm_s3b_lane_cap(c->max_read_len);
   cm_s3b_heavy_classes(in.hv_max, &in.hv_big);
   cm_size_classes(in, d);
+  cm_granted_classes(d);
 }
 // the context's buffers and counters as the stage kernels see them: per-pair inputs and outputs are offset views, the
 // intermediates (indexed from 0) are reused by every sub-batch.  Fields a stage sets (mm_cap, read_pl, sam_*) and the size
@@ -1203,7 +1204,7 @@ static int stage_finish(RangeRun &r, uint64_t *k_out, cmgpu_stats *stats) {
   const bool aborted = r.spec && hst[CM_ST_ABORT];  // this batch needs more room than the previous one left
   if (!aborted) {  // speculative launch set: a class with items whose kernels were not launched -> the range again with every class on
     unsigned long long seen = 0, keep = 0;
-    for (uint32_t l = 6; l < CM_HV_LISTS; ++l) if (h_cls[l]) seen |= 1ull << (l == 31 ? 23 : l);  // (list 31's kernels are launched with list 23's)
+    for (uint32_t l = CM_L_RS_WAVE; l < CM_HV_LISTS; ++l) if (h_cls[l]) seen |= 1ull << (l == CM_L_SEARCH_WAVE_BIG ? CM_L_SEARCH_WAVE : l);  // (the lists from CM_L_RS_WAVE on; CM_L_SEARCH_WAVE_BIG is launched with CM_L_SEARCH_WAVE)
     if (seen & ~r.d.cls_mask) return CM_RC_AGAIN_ALL_CLASSES;
     for (uint32_t l = 0; l < 64; ++l) {
       if ((seen >> l) & 1ull) c->cls_age[l] = 32; else if (c->cls_age[l]) --c->cls_age[l];

@@ -7,11 +7,13 @@
 #include <atomic>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 #include <rocprim/rocprim.hpp>
 
 #include "cm_kernels.h"
 #include "cm_stages.h"
+#include "cm_classes.h"
 #include "cm_coop.h"
 
 #define CM_BLOCK 256
@@ -388,8 +390,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_s3a_count(CmDev d, uint32_t n) {
   // batch from a repeat-bearing genome, where nearly every wave holds a read of some class (k_s3a_count 1.4 ms against 0.45 ms
   // on the uniform genome with one atomic per wave).  The order inside a list is of no consequence.
   // (class 21: the lists of the wave class that fit a quarter of its work area -- four reads per CU where the full-size area has one)
-  const uint32_t cls = tot <= d.s3b_cap ? 5u /* (none: the lane's own slots) */ : tot <= d.hv_mid ? CM_L_HIT_G16 : tot <= d.hv_sub ? CM_L_HIT_WAVE_SMALL : tot <= d.hv_max[0] ? CM_L_HIT_WAVE : tot <= d.hv_max[1] ? CM_L_HIT_B256A
-                       : tot <= d.hv_max[2] ? CM_L_HIT_B256B : tot <= d.hv_max[3] ? CM_L_HIT_B512 : tot <= d.hv_big ? CM_L_HIT_B1024 : CM_L_HIT_SLAB;
+  const uint32_t cls = cm_hit_class(d, tot);
   __shared__ uint32_t sh_cnt[8], sh_base[8];
   if (threadIdx.x < 8) sh_cnt[threadIdx.x] = 0;
   __syncthreads();
@@ -406,9 +407,9 @@ __global__ __launch_bounds__(CM_BLOCK) void k_s3a_count(CmDev d, uint32_t n) {
     if (cls == ids[q]) { slot = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)); mine = q; }
   }
   __syncthreads();
-  if (threadIdx.x < 8 && sh_cnt[threadIdx.x]) sh_base[threadIdx.x] = atomicAdd(&d.hv_cnt[ids[threadIdx.x]], sh_cnt[threadIdx.x]);
+  if (threadIdx.x < 8 && sh_cnt[threadIdx.x]) sh_base[threadIdx.x] = atomicAdd(cm_list_cnt(d, ids[threadIdx.x]), sh_cnt[threadIdx.x]);
   __syncthreads();
-  if (mine < 8) d.hv_list[(size_t)ids[mine] * d.hv_stride + sh_base[mine] + slot] = i;
+  if (mine < 8) cm_list(d, ids[mine])[sh_base[mine] + slot] = i;
 }
 // S3b with the per-read hit list staged in LDS ([entry][thread] layout: 16 x 8-byte entries and
 // 16 count bytes per thread = 36 KB per block).  The first version sorted every list in its
@@ -686,7 +687,8 @@ struct CmDevGroup {
 };
 // per-group LDS: the cooperative work area, then the group's cross-wave words
 #define CM_XW_BYTES 256
-__host__ __device__ inline size_t cm_coop_group_bytes(uint32_t P, uint32_t MM, uint32_t RB, bool own_oc, bool key32 = false) { return ((cm_coop_mem_bytes(P, MM, RB, own_oc, key32) + 15) & ~(size_t)15) + CM_XW_BYTES; }
+__host__ __device__ inline size_t cm_group_bytes(size_t area_bytes) { return ((area_bytes + 15) & ~(size_t)15) + CM_XW_BYTES; }
+__host__ __device__ inline size_t cm_coop_group_bytes(uint32_t P, uint32_t MM, uint32_t RB, bool own_oc, bool key32 = false) { return cm_group_bytes(cm_coop_mem_bytes(P, MM, RB, own_oc, key32)); }
 
 // S3b for long hit lists, merge-sort form (cm_coop_s3b): blockDim.x / G groups per block, one listed read each.  What the
 // function declines (more occurrence runs than its tables hold) is appended to fb_list for the bitonic kernel above.
@@ -728,6 +730,14 @@ __device__ __forceinline__ void cm_wave_append(uint32_t *__restrict__ list, uint
   if (lane == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
   base = __shfl(base, (int)leader, 64);
   if (pred) list[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = value;
+}
+// ... to the device work list `id` (called by all lanes of the wave)
+__device__ __forceinline__ void cm_list_append(const CmDev &d, uint32_t id, bool pred, uint32_t value) { cm_wave_append(cm_list(d, id), cm_list_cnt(d, id), pred, value); }
+// the lists `ids` are a class function's answers: the lane's item goes to the one that equals `cls`, if any
+template <int N>
+__device__ __forceinline__ void cm_list_append_class(const CmDev &d, const uint32_t (&ids)[N], uint32_t cls, bool pred, uint32_t value) {
+#pragma unroll
+  for (int q = 0; q < N; ++q) cm_list_append(d, ids[q], pred && cls == ids[q], value);
 }
 
 // Dynamic distribution of a device work list over the waves of a launch (round 6; cmgpu_set_option "coop" bit 16, NOT the default).
@@ -801,7 +811,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_s4a_rescue_count(CmDev d, uint32_t
   const bool aug0 = i0 < n && cm_s4a_decide<M>(d, i);
   // a read whose mate has many candidates goes to list 23 instead: a wave each (k_s4a_rescue_wave / k_s4b_rescue_wave)
   const bool wv = aug0 && cm_rescue_is_wave(d, i, coop);
-  cm_wave_append(d.hv_list + (size_t)CM_L_SEARCH_WAVE * d.hv_stride, d.hv_cnt + CM_L_SEARCH_WAVE, wv, i);
+  cm_list_append(d, CM_L_SEARCH_WAVE, wv, i);
   const bool aug = aug0 && !wv;
   // slot inside the block: wave-aggregated LDS atomic
   const unsigned long long m = __ballot(aug);
@@ -925,7 +935,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_s4b_rescue_merge(CmDev d, uint32_t
   const bool to_wave = mine && coop && d.m_tot[i] > CM_S4B_COPY_MIN;
   if (mine && !to_wave) cm_s4b_rescue_merge(d, i);
   if (to_wave) { d.mcp[i] = 0; d.mcn[i] = 0; }  // (until list 6's wave has copied the lists)
-  if (coop) cm_wave_append(d.hv_list + (size_t)CM_L_RS_WAVE * d.hv_stride, d.hv_cnt + CM_L_RS_WAVE, to_wave, i);
+  if (coop) cm_list_append(d, CM_L_RS_WAVE, to_wave, i);
 }
 // fill pass of one direction by a group: per-minimizer counts to LDS, lane 0 turns them into offsets (minimizer order = the
 // order cm_rescue writes in), the lanes write their minimizers' hits there
@@ -947,17 +957,11 @@ __device__ __forceinline__ void cm_group_rescue_fill(const CmDev &d, uint32_t r,
   cm_group_sync<CM_RS_G>();
 }
 // Reads with many rescue hits (more than CM_RS_COOP_MIN on a strand) only get their hits written here; sorting, clustering and
-// merging them is the work of a group of lanes (k_s4b_coop), by size class: list 6 up to hv_max[0] hits (a wave each), 7 / 8 / 11
-// up to hv_max[1] / [2] / [3] (a block of 256 / 512 / 1024 lanes each).  coop == 0: everything by one lane, as before.
-#define CM_RS_COOP_MIN 32u
-#define CM_S4B_PMAX 7680u  // rescue hits the largest shared work area holds (20 bytes per hit: 8192 would pass the CU's 160 KB)
-__host__ __device__ inline uint32_t cm_s4b_pmax(const CmDev &d) { return d.rs_big; }
+// merging them is the work of a group of lanes (k_s4b_coop), by size class (cm_rescue_class).  coop == 0: everything by one lane, as before.
 __device__ __forceinline__ uint32_t cm_rescue_coop_class(const CmDev &d, uint32_t r, uint32_t coop) {
-  const uint32_t big = d.resc_p[r] > d.resc_n[r] ? d.resc_p[r] : d.resc_n[r];
-  if (!coop || big <= CM_RS_COOP_MIN || d.hv_max[0] == 0) return 0;
-  return big <= d.hv_max[0] ? CM_L_RS_WAVE : big <= d.hv_max[1] ? CM_L_RS_B256A : big <= d.hv_max[2] ? CM_L_RS_B256B : big <= d.rs_max3 ? CM_L_RS_B512 : big <= d.rs_big ? CM_L_RS_B1024
-         : (d.coop_slab && big <= d.coop_slab_cap) ? CM_L_RS_SLAB : 0u;
+  return coop ? cm_rescue_class(d, d.resc_p[r] > d.resc_n[r] ? d.resc_p[r] : d.resc_n[r]) : CM_L_NONE;
 }
+__device__ static const uint32_t cm_rs_lists[6] = {CM_L_RS_WAVE, CM_L_RS_B256A, CM_L_RS_B256B, CM_L_RS_B512, CM_L_RS_B1024, CM_L_RS_SLAB};
 __global__ __launch_bounds__(64) void k_s4b_rescue_list(CmDev d, uint32_t seg_cap, uint32_t coop) {
   if (d.abort && *d.abort) return;
   __shared__ uint32_t sh_cnt[64 / CM_RS_G][CM_RS_MAXMM];
@@ -968,12 +972,9 @@ __global__ __launch_bounds__(64) void k_s4b_rescue_list(CmDev d, uint32_t seg_ca
     const uint32_t j = j0 + threadIdx.x;
     const uint32_t r = j < cnt ? list[j] : 0u;
     const bool mine = j < cnt && d.resc_n[r] + d.resc_p[r] > 0 && !cm_rescue_is_heavy(d, r, coop);
-    const uint32_t cls = mine ? cm_rescue_coop_class(d, r, coop) : 0u;
-    if (mine) cm_s4b_rescue_merge(d, r, cls ? CM_S4B_FILL_ONLY : CM_S4B_ALL);
-    for (uint32_t c = 6; c <= 8; ++c) cm_wave_append(d.hv_list + (size_t)c * d.hv_stride, d.hv_cnt + c, cls == c, r);
-    cm_wave_append(d.hv_list + (size_t)CM_L_RS_B512 * d.hv_stride, d.hv_cnt + CM_L_RS_B512, cls == CM_L_RS_B512, r);
-    cm_wave_append(d.hv_list + (size_t)CM_L_RS_B1024 * d.hv_stride, d.hv_cnt + CM_L_RS_B1024, cls == CM_L_RS_B1024, r);
-    cm_wave_append(d.hv_list + (size_t)CM_L_RS_SLAB * d.hv_stride, d.hv_cnt + CM_L_RS_SLAB, cls == CM_L_RS_SLAB, r);
+    const uint32_t cls = mine ? cm_rescue_coop_class(d, r, coop) : CM_L_NONE;
+    if (mine) cm_s4b_rescue_merge(d, r, cls != CM_L_NONE ? CM_S4B_FILL_ONLY : CM_S4B_ALL);
+    cm_list_append_class(d, cm_rs_lists, cls, true, r);
   }
   const long long tg0 = d.prof ? clock64() : 0;
   if (d.prof && threadIdx.x == 0) { const unsigned long long dt = (unsigned long long)(tg0 - tl0); atomicAdd(&d.prof[34], dt); atomicMax(&d.prof[35], dt); }
@@ -982,7 +983,7 @@ __global__ __launch_bounds__(64) void k_s4b_rescue_list(CmDev d, uint32_t seg_ca
     const uint32_t j = j0 + grp;
     const uint32_t r = j < cnt ? list[j] : 0u;
     const bool mine = j < cnt && cm_rescue_is_heavy(d, r, coop) && d.resc_n[r] + d.resc_p[r] > 0;  // uniform in the group
-    uint32_t cls = 0;
+    uint32_t cls = CM_L_NONE;
     if (mine) {
       const uint32_t o = r ^ 1u;
       const uint32_t ncp = d.ncp[r], ncn = d.ncn[r], rp = d.resc_p[r], rn = d.resc_n[r];
@@ -996,12 +997,9 @@ __global__ __launch_bounds__(64) void k_s4b_rescue_list(CmDev d, uint32_t seg_ca
       if (t == 0) { d.mcp[r] = 0; d.mcn[r] = 0; }  // (until the hits are sorted and merged: here, or by the class's group)
       __threadfence_block();
       cls = cm_rescue_coop_class(d, r, coop);
-      if (t == 0 && !cls) cm_s4b_rescue_merge(d, r, CM_S4B_PREFILLED);  // sort, cluster, merge of the hits the group wrote
+      if (t == 0 && cls == CM_L_NONE) cm_s4b_rescue_merge(d, r, CM_S4B_PREFILLED);  // sort, cluster, merge of the hits the group wrote
     }
-    for (uint32_t c = 6; c <= 8; ++c) cm_wave_append(d.hv_list + (size_t)c * d.hv_stride, d.hv_cnt + c, t == 0 && cls == c, r);
-    cm_wave_append(d.hv_list + (size_t)CM_L_RS_B512 * d.hv_stride, d.hv_cnt + CM_L_RS_B512, t == 0 && cls == CM_L_RS_B512, r);
-    cm_wave_append(d.hv_list + (size_t)CM_L_RS_B1024 * d.hv_stride, d.hv_cnt + CM_L_RS_B1024, t == 0 && cls == CM_L_RS_B1024, r);
-    cm_wave_append(d.hv_list + (size_t)CM_L_RS_SLAB * d.hv_stride, d.hv_cnt + CM_L_RS_SLAB, t == 0 && cls == CM_L_RS_SLAB, r);
+    cm_list_append_class(d, cm_rs_lists, cls, t == 0, r);
   }
   if (d.prof && threadIdx.x == 0) { const unsigned long long dt = (unsigned long long)(clock64() - tg0); atomicAdd(&d.prof[36], dt); atomicMax(&d.prof[37], dt); }
 }
@@ -1014,9 +1012,9 @@ template <bool SMALL>
 __global__ __launch_bounds__(64) void k_s4a_rescue_wave(CmDev d) {
   __shared__ __attribute__((aligned(16))) uint8_t rmem[SMALL ? CM_RESCUE_MEM_BYTES_S : CM_RESCUE_MEM_BYTES];
   const uint32_t li = SMALL ? CM_L_SEARCH_WAVE : CM_L_SEARCH_WAVE_BIG;
-  const uint32_t cnt = d.hv_cnt[li];
+  const uint32_t cnt = *cm_list_cnt(d, li);
   if (blockIdx.x >= cnt) return;
-  const uint32_t *list = d.hv_list + (size_t)li * d.hv_stride;
+  const uint32_t *list = cm_list(d, li);
   const CmCoopRescueMem m = SMALL ? cm_coop_rescue_mem_at(rmem, CM_RESCUE_WMAX_S, CM_RESCUE_PAIRS_S) : cm_coop_rescue_mem_at(rmem);
   CmDevGroup<64> g;
   g.t = threadIdx.x;
@@ -1033,7 +1031,7 @@ __global__ __launch_bounds__(64) void k_s4a_rescue_wave(CmDev d) {
       if (threadIdx.x == 0) atomicAdd(&d.prof[mx < 16 ? 40 : mx < 32 ? 41 : mx < 64 ? 42 : mx < 128 ? 43 : mx < 200 ? 44 : mx < 300 ? 45 : 46], 1ull);
     }
     if (SMALL && !cm_coop_rescue_fits(d, r, g, CM_RESCUE_WMAX_S)) {
-      if (threadIdx.x == 0) d.hv_list[(size_t)CM_L_SEARCH_WAVE_BIG * d.hv_stride + atomicAdd(d.hv_cnt + CM_L_SEARCH_WAVE_BIG, 1u)] = r;
+      if (threadIdx.x == 0) cm_list(d, CM_L_SEARCH_WAVE_BIG)[atomicAdd(cm_list_cnt(d, CM_L_SEARCH_WAVE_BIG), 1u)] = r;
       continue;
     }
     const long long ti = d.prof ? clock64() : 0;
@@ -1051,9 +1049,9 @@ __global__ __launch_bounds__(64) void k_s4b_rescue_wave(CmDev d, uint32_t coop) 
   if (d.abort && *d.abort) return;
   __shared__ __attribute__((aligned(16))) uint8_t rmem[SMALL ? CM_RESCUE_MEM_BYTES_S : CM_RESCUE_MEM_BYTES];
   const uint32_t li = SMALL ? CM_L_SEARCH_WAVE : CM_L_SEARCH_WAVE_BIG;
-  const uint32_t cnt = d.hv_cnt[li];
+  const uint32_t cnt = *cm_list_cnt(d, li);
   if (blockIdx.x >= cnt) return;
-  const uint32_t *list = d.hv_list + (size_t)li * d.hv_stride;
+  const uint32_t *list = cm_list(d, li);
   const CmCoopRescueMem m = SMALL ? cm_coop_rescue_mem_at(rmem, CM_RESCUE_WMAX_S, CM_RESCUE_PAIRS_S) : cm_coop_rescue_mem_at(rmem);
   CmDevGroup<64> g;
   g.t = threadIdx.x;
@@ -1068,7 +1066,7 @@ __global__ __launch_bounds__(64) void k_s4b_rescue_wave(CmDev d, uint32_t coop) 
     g.sync();
     const uint32_t cls = cm_rescue_coop_class(d, r, coop);
     if (threadIdx.x == 0) {
-      if (cls) d.hv_list[(size_t)cls * d.hv_stride + atomicAdd(d.hv_cnt + cls, 1u)] = r;
+      if (cls != CM_L_NONE) cm_list(d, cls)[atomicAdd(cm_list_cnt(d, cls), 1u)] = r;
       else cm_s4b_rescue_merge(d, r, CM_S4B_PREFILLED);
     }
   }
@@ -1076,31 +1074,44 @@ __global__ __launch_bounds__(64) void k_s4b_rescue_wave(CmDev d, uint32_t coop) 
 }
 // S4b for the reads listed above: a group per read sorts its rescue hits, clusters them and merges them with the read's
 // candidates (cm_coop_rescue_merge).  The list's length is only known on the device: the grid strides over it.
+// The frame of the kernels that give every item of a device work list to a group of G lanes (blockDim.x / G groups per block): no items
+// when the range is being abandoned; `base`: the group's slice of the block's shared memory -- `area_bytes` of work area, which the kernel
+// lays out and reuses from item to item, then the group's cross-wave words; next(): the grid's groups stride over the list, whose length is on the device
+template <int G>
+struct CmListGroups {
+  CmDevGroup<G> g;
+  uint8_t *base;
+  const uint32_t *list;
+  uint32_t n_list, j;
+  __device__ __forceinline__ CmListGroups(const CmDev &d, const uint32_t *list_, const uint32_t *n_list_dev, size_t area_bytes) : list(list_) {
+    const uint32_t gpb = blockDim.x / G, grp = threadIdx.x / G;
+    n_list = d.abort && *d.abort ? 0u : *n_list_dev;
+    const size_t gb = cm_group_bytes(area_bytes);
+    base = cm_lds + (size_t)grp * gb;
+    g.t = threadIdx.x % G;
+    g.xw = reinterpret_cast<uint32_t *>(base + gb - CM_XW_BYTES);
+    j = blockIdx.x * gpb + grp;
+  }
+  __device__ __forceinline__ bool next(uint32_t *item) {
+    if (j >= n_list) return false;
+    *item = list[j];
+    j += gridDim.x * (blockDim.x / G);
+    return true;
+  }
+};
 template <int G>
 __global__ __launch_bounds__(G < CM_BLOCK ? CM_BLOCK : G) void k_s4b_coop(CmDev d, const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_list_dev, uint32_t P, uint32_t RB,
                                                                       uint32_t use_slab) {
-  if (d.abort && *d.abort) return;
-  const uint32_t gpb = blockDim.x / G, grp = threadIdx.x / G;
-  const uint32_t n_list = *n_list_dev;
-  const size_t gb = cm_coop_group_bytes(P, 1, RB, true);
-  uint8_t *base = cm_lds + (size_t)grp * gb;
-  CmCoopMem m = cm_coop_mem_at(base, P, 1, RB, true);
+  CmListGroups<G> L(d, list, n_list_dev, cm_coop_mem_bytes(P, 1, RB, true));
+  CmCoopMem m = cm_coop_mem_at(L.base, P, 1, RB, true);
   if (use_slab) cm_coop_slab_at(m, d.coop_slab + (size_t)blockIdx.x * cm_coop_slab_bytes(d.coop_slab_cap), d.coop_slab_cap);
-  CmDevGroup<G> g;
-  g.t = threadIdx.x % G;
-  g.xw = reinterpret_cast<uint32_t *>(base + gb - CM_XW_BYTES);
-  for (uint32_t gid = blockIdx.x * gpb + grp; gid < n_list; gid += gridDim.x * gpb) {
-    if (use_slab) cm_coop_rescue_merge<true>(d, list[gid], g, m); else cm_coop_rescue_merge<false>(d, list[gid], g, m);
-    g.sync();  // the work area is reused
+  for (uint32_t r; L.next(&r);) {
+    if (use_slab) cm_coop_rescue_merge<true>(d, r, L.g, m); else cm_coop_rescue_merge<false>(d, r, L.g, m);
+    L.g.sync();  // the work area is reused
   }
 }
 // S4c; long filtered candidate lists are queued for k_sort_lists.  coop: a pair with a merged candidate list longer than
 // CM_S4C_COOP_MIN entries only gets the part before the filter here and goes to list 9 for k_s4c_coop (a wave per pair).
-#define CM_S4C_COOP_MIN 48u
-#define CM_S5C_COOP_MIN 48u  // candidates of a read above which S5 (sorting the lists, alignments, acceptance) is a wave's work
-#define CM_S5C_P_SMALL 512u   // most reads of the wave class: work arrays of this size (more waves per CU)
-#define CM_S5C_P_WAVE 2048u   // candidates of a strand the wave's work arrays hold
-#define CM_S5C_P_BLOCK 16384u // ... a block's (longer lists: the acceptance loop by one lane)
 template <class M = CmModeAny>
 __device__ __forceinline__ void cm_s4c_queue_sort(const CmDev &d, uint32_t pair, bool live, uint32_t coop) {
   for (uint32_t q = 0; q < 4; ++q) {  // (read, strand) lists of the pair
@@ -1110,60 +1121,39 @@ __device__ __forceinline__ void cm_s4c_queue_sort(const CmDev &d, uint32_t pair,
     cm_wave_append(d.srt_list, &d.srt_cnt[0], cnt > CM_SORT_SERIAL_MAX && cnt <= CM_SORT_WAVE_MAX, (r << 1) | (q & 1u));
   }
 }
-#define CM_S4C_P_SMALL 256u   // most pairs with long lists: a wave each (the classes above take a block of 256 lanes per pair)
-#define CM_S4C_P_WAVE 1024u   // entries of a candidate list the work arrays of a wave hold
-#define CM_S4C_P_BLOCK 4096u  // ... of a block
-#define CM_S4C_P_BIG 15360u   // ... of a block of 1024 lanes that leaves the position lists in global memory (a lane walking such a
-                              // pair's two-pointer loop at global latency was the whole 16 ms of k_s4c_reduce on the mosaic genome)
+__device__ static const uint32_t cm_pf_lists[4] = {CM_L_PF_BLOCK, CM_L_PF_WAVE, CM_L_PF_BLOCK_BIG, CM_L_PF_HUGE};
 template <class M>
 __global__ __launch_bounds__(CM_BLOCK) void k_s4c_reduce(CmDev d, uint32_t n, uint32_t coop) {
   if (d.abort && *d.abort) return;
   const uint32_t i = blockIdx.x * CM_BLOCK + threadIdx.x;
   const uint32_t pair = i < n ? (d.perm_pairs ? d.perm_pairs[i] : i) : 0u;
-  uint32_t cls = 0;
+  uint32_t cls = CM_L_NONE;
   if (i < n && cm_s4c_pre<M>(d, pair)) {
     const uint32_t r1 = 2 * pair, r2 = r1 + 1;
     uint32_t big = d.mcp[r1] > d.mcn[r1] ? d.mcp[r1] : d.mcn[r1];
     big = d.mcp[r2] > big ? d.mcp[r2] : big;
     big = d.mcn[r2] > big ? d.mcn[r2] : big;
-    if ((coop & 4u) && big > CM_S4C_COOP_MIN) cls = big <= CM_S4C_P_SMALL ? CM_L_PF_WAVE : big <= CM_S4C_P_WAVE ? CM_L_PF_BLOCK : big <= CM_S4C_P_BLOCK ? CM_L_PF_BLOCK_BIG : big <= d.s4c_pbig ? CM_L_PF_HUGE : 0u;
-    if (!cls) { cm_s4c_filter(d, pair); cm_s4c_post(d, pair); }
+    if (coop & 4u) cls = cm_pf_class(d, big);
+    if (cls == CM_L_NONE) { cm_s4c_filter(d, pair); cm_s4c_post(d, pair); }
   }
-  if (coop & 4u) {
-    cm_wave_append(d.hv_list + CM_L_PF_BLOCK * (size_t)d.hv_stride, d.hv_cnt + CM_L_PF_BLOCK, cls == CM_L_PF_BLOCK, pair);
-    cm_wave_append(d.hv_list + CM_L_PF_WAVE * (size_t)d.hv_stride, d.hv_cnt + CM_L_PF_WAVE, cls == CM_L_PF_WAVE, pair);
-    cm_wave_append(d.hv_list + CM_L_PF_BLOCK_BIG * (size_t)d.hv_stride, d.hv_cnt + CM_L_PF_BLOCK_BIG, cls == CM_L_PF_BLOCK_BIG, pair);
-    cm_wave_append(d.hv_list + CM_L_PF_HUGE * (size_t)d.hv_stride, d.hv_cnt + CM_L_PF_HUGE, cls == CM_L_PF_HUGE, pair);
-  }
+  if (coop & 4u) cm_list_append_class(d, cm_pf_lists, cls, true, pair);
   if (!d.perm_pairs) return;  // the queue is only served in a batch with heavy reads
-  cm_s4c_queue_sort<M>(d, pair, i < n && !cls && d.alive[pair], coop);
+  cm_s4c_queue_sort<M>(d, pair, i < n && cls == CM_L_NONE && d.alive[pair], coop);
 }
 // the pairs of list 9 / 14: the filter's two directions by a wave / a block each (cm_coop_s4c); the list's length is on the device
 template <int G, bool STAGED>
 __global__ __launch_bounds__(G < CM_BLOCK ? CM_BLOCK : G) void k_s4c_coop(CmDev d, uint32_t P, uint32_t lid, uint32_t coop) {
-  if (d.abort && *d.abort) return;
-  const uint32_t gpb = blockDim.x / G, grp = threadIdx.x / G;
-  const uint32_t n_list = d.hv_cnt[lid];
-  const uint32_t *list = d.hv_list + (size_t)lid * d.hv_stride;
-  const size_t gb = ((cm_coop_pair_mem_bytes(P, STAGED) + 15) & ~(size_t)15) + CM_XW_BYTES;
-  uint8_t *base = cm_lds + (size_t)grp * gb;
-  const CmCoopPairMem m = cm_coop_pair_mem_at(base, P, STAGED);
-  CmDevGroup<G> g;
-  g.t = threadIdx.x % G;
-  g.xw = reinterpret_cast<uint32_t *>(base + gb - CM_XW_BYTES);
-  for (uint32_t j0 = blockIdx.x * gpb; j0 < n_list; j0 += gridDim.x * gpb) {
-    const uint32_t j = j0 + grp;
-    const uint32_t pair = j < n_list ? list[j] : 0u;
-    if (j < n_list) cm_coop_s4c<STAGED>(d, pair, g, m);
-    g.sync();
-    if (d.perm_pairs) {  // long filtered lists: queued for the sorting waves
-      const bool live = j < n_list && d.alive[pair];
-      for (uint32_t q = 0; q < 4; ++q) {
-        const uint32_t r = 2 * pair + (q >> 1);
-        uint32_t cnt = live ? ((q & 1u) ? d.fcn[r] : d.fcp[r]) : 0u;
-        if ((coop & 8u) && live && d.fcp[r] + d.fcn[r] > CM_S5C_COOP_MIN) cnt = 0;  // sorted by the S5 waves
-        if (g.t == 0 && cnt > CM_SORT_SERIAL_MAX && cnt <= CM_SORT_WAVE_MAX) d.srt_list[atomicAdd(&d.srt_cnt[0], 1u)] = (r << 1) | (q & 1u);
-      }
+  CmListGroups<G> L(d, cm_list(d, lid), cm_list_cnt(d, lid), cm_coop_pair_mem_bytes(P, STAGED));
+  const CmCoopPairMem m = cm_coop_pair_mem_at(L.base, P, STAGED);
+  for (uint32_t pair; L.next(&pair);) {
+    cm_coop_s4c<STAGED>(d, pair, L.g, m);
+    L.g.sync();
+    if (!d.perm_pairs || !d.alive[pair]) continue;
+    for (uint32_t q = 0; q < 4; ++q) {  // long filtered lists: queued for the sorting waves
+      const uint32_t r = 2 * pair + (q >> 1);
+      uint32_t cnt = (q & 1u) ? d.fcn[r] : d.fcp[r];
+      if ((coop & 8u) && d.fcp[r] + d.fcn[r] > CM_S5C_COOP_MIN) cnt = 0;  // sorted by the S5 waves
+      if (L.g.t == 0 && cnt > CM_SORT_SERIAL_MAX && cnt <= CM_SORT_WAVE_MAX) d.srt_list[atomicAdd(&d.srt_cnt[0], 1u)] = (r << 1) | (q & 1u);
     }
   }
 }
@@ -1174,14 +1164,8 @@ __global__ __launch_bounds__(CM_BLOCK) void k_s5a_prepare(CmDev d, uint32_t n, u
   const uint32_t i = blockIdx.x * CM_BLOCK + threadIdx.x;
   const uint32_t r = i < n ? (d.perm_reads ? d.perm_reads[i] : i) : 0u;
   const bool to_wave = i < n && cm_s5a_prepare<M>(d, r, coop ? CM_S5C_COOP_MIN : 0u);
-  // list 12: a wave per read; list 22: a block per read -- a strand's list is longer than the wave's work arrays
-  const bool big = to_wave && (d.fcp[r] > CM_S5C_P_WAVE || d.fcn[r] > CM_S5C_P_WAVE);
-  const bool small = to_wave && d.fcp[r] <= CM_S5C_P_SMALL && d.fcn[r] <= CM_S5C_P_SMALL;  // list 28: a quarter of the work arrays
-  if (coop) {
-    cm_wave_append(d.hv_list + (size_t)CM_L_S5_SMALL * d.hv_stride, d.hv_cnt + CM_L_S5_SMALL, small, r);
-    cm_wave_append(d.hv_list + (size_t)CM_L_S5_WAVE * d.hv_stride, d.hv_cnt + CM_L_S5_WAVE, to_wave && !big && !small, r);
-    cm_wave_append(d.hv_list + (size_t)CM_L_S5_BLOCK * d.hv_stride, d.hv_cnt + CM_L_S5_BLOCK, big, r);
-  }
+  const uint32_t lists[3] = {CM_L_S5_SMALL, CM_L_S5_WAVE, CM_L_S5_BLOCK};
+  if (coop) cm_list_append_class(d, lists, to_wave ? cm_s5_class(d.fcp[r], d.fcn[r]) : CM_L_NONE, true, r);
 }
 // S5c; long draft-mapping lists are queued for k_sort_lists (S6a sorts them by position; split alignment keeps emission order)
 template <class M>
@@ -1207,8 +1191,8 @@ __global__ __launch_bounds__(CM_BLOCK, 8) void k_s5_sort_coop(CmDev d, uint32_t 
   __shared__ uint64_t stage_p[(CM_BLOCK / 64) * CM_SORT_STAGE];  // a list of up to CM_SORT_STAGE candidates is staged here once
   __shared__ uint8_t stage_c[(CM_BLOCK / 64) * CM_SORT_STAGE];
   const uint32_t grp = threadIdx.x / 64;
-  const uint32_t n_list = d.hv_cnt[lid];
-  const uint32_t *list = d.hv_list + (size_t)lid * d.hv_stride;
+  const uint32_t n_list = *cm_list_cnt(d, lid);
+  const uint32_t *list = cm_list(d, lid);
   CmDevGroup<64> g;
   g.t = threadIdx.x % 64;
   g.xw = nullptr;
@@ -1224,23 +1208,18 @@ __global__ __launch_bounds__(CM_BLOCK, 8) void k_s5_sort_coop(CmDev d, uint32_t 
 }
 #define CM_S5C_SORT_P 1024u  // draft mappings a wave sorts in shared memory (longer lists: in global memory)
 #define CM_S5C_SORT_RB 130u
+__host__ __device__ inline size_t cm_s5c_area_bytes(uint32_t P) {
+  const size_t b1 = cm_coop_ver_mem_bytes(P), b2 = cm_coop_sort_mem_bytes(CM_S5C_SORT_P, CM_S5C_SORT_RB);
+  return b1 > b2 ? b1 : b2;
+}
 template <int G>
 __global__ __launch_bounds__(CM_BLOCK) void k_s5c_coop(CmDev d, uint32_t P, uint32_t lid) {
-  if (d.abort && *d.abort) return;
-  const uint32_t gpb = blockDim.x / G, grp = threadIdx.x / G;
-  const uint32_t n_list = d.hv_cnt[lid];
-  const uint32_t *list = d.hv_list + (size_t)lid * d.hv_stride;
-  const size_t b1 = cm_coop_ver_mem_bytes(P), b2 = cm_coop_sort_mem_bytes(CM_S5C_SORT_P, CM_S5C_SORT_RB);
-  const size_t gb = (((b1 > b2 ? b1 : b2) + 15) & ~(size_t)15) + CM_XW_BYTES;  // the sort's buffers overlay the acceptance loop's arrays
-  uint8_t *base = cm_lds + (size_t)grp * gb;
-  const CmCoopVerMem m = cm_coop_ver_mem_at(base, P);
-  const CmCoopSortMem sm = cm_coop_sort_mem_at(base, CM_S5C_SORT_P, CM_S5C_SORT_RB);
-  CmDevGroup<G> g;
-  g.t = threadIdx.x % G;
-  g.xw = reinterpret_cast<uint32_t *>(base + gb - CM_XW_BYTES);
-  for (uint32_t j = blockIdx.x * gpb + grp; j < n_list; j += gridDim.x * gpb) {
-    cm_coop_s5c(d, list[j], g, m, sm);
-    g.sync();
+  CmListGroups<G> L(d, cm_list(d, lid), cm_list_cnt(d, lid), cm_s5c_area_bytes(P));
+  const CmCoopVerMem m = cm_coop_ver_mem_at(L.base, P);
+  const CmCoopSortMem sm = cm_coop_sort_mem_at(L.base, CM_S5C_SORT_P, CM_S5C_SORT_RB);  // the sort's buffers overlay the acceptance loop's arrays
+  for (uint32_t r; L.next(&r);) {
+    cm_coop_s5c(d, r, L.g, m, sm);
+    L.g.sync();
   }
 }
 
@@ -1315,17 +1294,13 @@ __global__ __launch_bounds__(CM_BLOCK) void k_s5b_verify(CmDev d, uint32_t n_rea
 // S6a.  coop: a pair with a draft-mapping list longer than CM_S6A_COOP_MIN goes to list 13, where a wave runs its two sweeps with
 // the second list of each direction staged in shared memory -- or, when read 2 has a list longer than CM_S6A_P_WAVE, to list 18,
 // where a block does (lists up to CM_S6A_P_BLOCK staged, longer ones read where they are)
-#define CM_S6A_COOP_MIN 48u
-#define CM_S6A_P_SMALL 256u
-#define CM_S6A_P_WAVE 1024u
-#define CM_S6A_P_BLOCK 8192u
-__device__ __forceinline__ uint32_t cm_s6_class(const CmDev &d, uint32_t pair, uint32_t small_list, uint32_t wave_list, uint32_t block_list) {
+__device__ static const uint32_t cm_s6a_lists[3] = {CM_L_S6A_SMALL, CM_L_S6A_WAVE, CM_L_S6A_BLOCK}, cm_s6c_lists[3] = {CM_L_S6C_SMALL, CM_L_S6C_WAVE, CM_L_S6C_BLOCK};
+__device__ __forceinline__ uint32_t cm_s6_pair_class(const CmDev &d, uint32_t pair, const uint32_t (&lists)[3]) {
   const uint32_t r1 = 2 * pair, r2 = r1 + 1;
   uint32_t big2 = d.ndp[r2] > d.ndn[r2] ? d.ndp[r2] : d.ndn[r2], big = big2;
   big = d.ndp[r1] > big ? d.ndp[r1] : big;
   big = d.ndn[r1] > big ? d.ndn[r1] : big;
-  if (big <= CM_S6A_COOP_MIN) return 0;
-  return big2 <= CM_S6A_P_SMALL ? small_list : big2 <= CM_S6A_P_WAVE ? wave_list : block_list;
+  return cm_s6_class(big, big2, lists[0], lists[1], lists[2]);
 }
 // The paired-end instance also lists the pairs S6c has to look at (list 24): those it found more than one best pairing for, and
 // those it leaves to a group, whose n_best is not known yet.  k_s6c_list then visits these few instead of every pair.
@@ -1334,32 +1309,20 @@ __global__ __launch_bounds__(CM_BLOCK) void k_s6a_pair(CmDev d, uint32_t n, uint
   if (d.abort && *d.abort) return;
   const uint32_t i = blockIdx.x * CM_BLOCK + threadIdx.x;
   const uint32_t pair = i < n ? (d.perm_pairs ? d.perm_pairs[i] : i) : 0u;
-  uint32_t cls = 0;
+  uint32_t cls = CM_L_NONE;
   bool multi = false;
   if (i < n && cm_s6a_pre<false, M>(d, pair)) {
-    cls = coop ? cm_s6_class(d, pair, CM_L_S6A_SMALL, CM_L_S6A_WAVE, CM_L_S6A_BLOCK) : 0u;
-    multi = cls != 0 || cm_s6a_sweeps<false>(d, pair) > 1;  // (the count in a register: no load behind the store to pe_nbest)
+    if (coop) cls = cm_s6_pair_class(d, pair, cm_s6a_lists);
+    multi = cls != CM_L_NONE || cm_s6a_sweeps<false>(d, pair) > 1;  // (the count in a register: no load behind the store to pe_nbest)
   }
-  if constexpr (M::kPe) cm_wave_append(d.hv_list + (size_t)CM_L_S6C_MULTI * d.hv_stride, d.hv_cnt + CM_L_S6C_MULTI, multi, pair);
-  if (coop) {
-    cm_wave_append(d.hv_list + (size_t)CM_L_S6A_SMALL * d.hv_stride, d.hv_cnt + CM_L_S6A_SMALL, cls == CM_L_S6A_SMALL, pair);
-    cm_wave_append(d.hv_list + (size_t)CM_L_S6A_WAVE * d.hv_stride, d.hv_cnt + CM_L_S6A_WAVE, cls == CM_L_S6A_WAVE, pair);
-    cm_wave_append(d.hv_list + (size_t)CM_L_S6A_BLOCK * d.hv_stride, d.hv_cnt + CM_L_S6A_BLOCK, cls == CM_L_S6A_BLOCK, pair);
-  }
+  if constexpr (M::kPe) cm_list_append(d, CM_L_S6C_MULTI, multi, pair);
+  if (coop) cm_list_append_class(d, cm_s6a_lists, cls, true, pair);
 }
 template <int G>
 __global__ __launch_bounds__(CM_BLOCK, 6) void k_s6a_coop(CmDev d, uint32_t P, uint32_t lid) {
-  if (d.abort && *d.abort) return;
-  const uint32_t gpb = blockDim.x / G, grp = threadIdx.x / G;
-  const uint32_t n_list = d.hv_cnt[lid];
-  const uint32_t *list = d.hv_list + (size_t)lid * d.hv_stride;
-  const size_t gb = ((cm_coop_pe_mem_bytes(P) + 15) & ~(size_t)15) + CM_XW_BYTES;
-  uint8_t *base = cm_lds + (size_t)grp * gb;
-  const CmCoopPeMem m = cm_coop_pe_mem_at(base, P);
-  CmDevGroup<G> g;
-  g.t = threadIdx.x % G;
-  g.xw = reinterpret_cast<uint32_t *>(base + gb - CM_XW_BYTES);
-  for (uint32_t j = blockIdx.x * gpb + grp; j < n_list; j += gridDim.x * gpb) cm_coop_s6a<false>(d, list[j], g, m);
+  CmListGroups<G> L(d, cm_list(d, lid), cm_list_cnt(d, lid), cm_coop_pe_mem_bytes(P));
+  const CmCoopPeMem m = cm_coop_pe_mem_at(L.base, P);
+  for (uint32_t pair; L.next(&pair);) cm_coop_s6a<false>(d, pair, L.g, m);
 }
 // S6c.  coop: a multi-mapped pair with a draft-mapping list longer than CM_S6A_COOP_MIN goes to list 17 (a wave) / 20 (a block),
 // where the group finds the sampled pairings (cm_coop_s6c) -- one lane repeating both pairing sweeps over lists of hundreds of
@@ -1367,16 +1330,12 @@ __global__ __launch_bounds__(CM_BLOCK, 6) void k_s6a_coop(CmDev d, uint32_t P, u
 // one pair of S6c: to its class's list, or the records of its sampled pairings by this lane (called by whole waves)
 template <class M>
 __device__ __forceinline__ void cm_s6c_item(const CmDev &d, bool mine, uint32_t pair, uint32_t coop) {
-  uint32_t cls = 0;
+  uint32_t cls = CM_L_NONE;
   if (mine) {
-    if (coop && !M::single(d) && !M::split(d) && d.pe_nbest[pair] > 1) cls = cm_s6_class(d, pair, CM_L_S6C_SMALL, CM_L_S6C_WAVE, CM_L_S6C_BLOCK);
-    if (!cls) cm_s6c_multi<false, M>(d, pair);
+    if (coop && !M::single(d) && !M::split(d) && d.pe_nbest[pair] > 1) cls = cm_s6_pair_class(d, pair, cm_s6c_lists);
+    if (cls == CM_L_NONE) cm_s6c_multi<false, M>(d, pair);
   }
-  if (coop) {
-    cm_wave_append(d.hv_list + (size_t)CM_L_S6C_SMALL * d.hv_stride, d.hv_cnt + CM_L_S6C_SMALL, cls == CM_L_S6C_SMALL, pair);
-    cm_wave_append(d.hv_list + (size_t)CM_L_S6C_WAVE * d.hv_stride, d.hv_cnt + CM_L_S6C_WAVE, cls == CM_L_S6C_WAVE, pair);
-    cm_wave_append(d.hv_list + (size_t)CM_L_S6C_BLOCK * d.hv_stride, d.hv_cnt + CM_L_S6C_BLOCK, cls == CM_L_S6C_BLOCK, pair);
-  }
+  if (coop) cm_list_append_class(d, cm_s6c_lists, cls, true, pair);
 }
 __global__ __launch_bounds__(CM_BLOCK) void k_s6c_multi(CmDev d, uint32_t n, uint32_t coop) {
   if (d.abort && *d.abort) return;
@@ -1387,8 +1346,8 @@ __global__ __launch_bounds__(CM_BLOCK) void k_s6c_multi(CmDev d, uint32_t n, uin
 // the list takes one slot of list 24 and at most one of a class's list: never more than the pairs of the range
 __global__ __launch_bounds__(CM_BLOCK) void k_s6c_list(CmDev d, uint32_t coop) {
   if (d.abort && *d.abort) return;
-  const uint32_t cnt = d.hv_cnt[CM_L_S6C_MULTI];
-  const uint32_t *list = d.hv_list + (size_t)CM_L_S6C_MULTI * d.hv_stride;
+  const uint32_t cnt = *cm_list_cnt(d, CM_L_S6C_MULTI);
+  const uint32_t *list = cm_list(d, CM_L_S6C_MULTI);
   for (uint32_t j0 = blockIdx.x * CM_BLOCK; j0 < cnt; j0 += gridDim.x * CM_BLOCK) {
     const uint32_t j = j0 + threadIdx.x;
     cm_s6c_item<CmModePe>(d, j < cnt, j < cnt ? list[j] : 0u, coop);
@@ -1396,17 +1355,9 @@ __global__ __launch_bounds__(CM_BLOCK) void k_s6c_list(CmDev d, uint32_t coop) {
 }
 template <int G>
 __global__ __launch_bounds__(CM_BLOCK) void k_s6c_coop(CmDev d, uint32_t P, uint32_t lid) {
-  if (d.abort && *d.abort) return;
-  const uint32_t gpb = blockDim.x / G, grp = threadIdx.x / G;
-  const uint32_t n_list = d.hv_cnt[lid];
-  const uint32_t *list = d.hv_list + (size_t)lid * d.hv_stride;
-  const size_t gb = ((cm_coop_pe_mem_bytes(P) + 15) & ~(size_t)15) + CM_XW_BYTES;
-  uint8_t *base = cm_lds + (size_t)grp * gb;
-  const CmCoopPeMem m = cm_coop_pe_mem_at(base, P);
-  CmDevGroup<G> g;
-  g.t = threadIdx.x % G;
-  g.xw = reinterpret_cast<uint32_t *>(base + gb - CM_XW_BYTES);
-  for (uint32_t j = blockIdx.x * gpb + grp; j < n_list; j += gridDim.x * gpb) cm_coop_s6c<false>(d, list[j], g, m);
+  CmListGroups<G> L(d, cm_list(d, lid), cm_list_cnt(d, lid), cm_coop_pe_mem_bytes(P));
+  const CmCoopPeMem m = cm_coop_pe_mem_at(L.base, P);
+  for (uint32_t pair; L.next(&pair);) cm_coop_s6c<false>(d, pair, L.g, m);
 }
 CM_ITEM_KERNEL(k_s6a_pair_sam, cm_s6a_pair<true>, perm_pairs)
 CM_ITEM_KERNEL(k_s6c_multi_sam, cm_s6c_multi<true>, perm_pairs)
@@ -1832,117 +1783,142 @@ uint32_t cm_s3b_lane_cap(uint32_t max_read_len) {
   uint32_t cap = max_read_len / 3;
   return cap < 16 ? 16 : (cap > 64 ? 64 : cap);
 }
-// the cooperative kernel's size classes: hits per wave-group, per block, per block with a large LDS allocation
-// Round 4: finer classes (a wave up to 256 / 512 hits, 256 lanes up to 1024 / 2048, 512 up to 4096, 1024 up to 8192 with the large
-// allocation): the stages are chains of shared-memory round trips, a group's work area is what limits the waves a CU holds, and a
-// work area of the list's own size class was worth 20 % of the stage on the mosaic genome.
-void cm_s3b_heavy_classes(uint32_t *hv_max, uint32_t *hv_big) {
-  // HIP function attributes belong to the device the call is made on (one process may drive several: chromap-amd --gpus N),
-  // so the large-LDS opt-in is made -- and remembered -- per device; lane threads of one device may race here, hence atomics
-  static std::atomic<int> big_ok[64];  // 0 unknown, 1 granted, 2 refused
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const int slot = dev >= 0 && dev < 64 ? dev : 0;
-  int st = big_ok[slot].load(std::memory_order_acquire);
-  if (st == 0 || dev != slot) {
-    st = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_s3b_heavy<CM_BLOCK>), hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 10 + (CM_BLOCK + 8) * 4) == hipSuccess ? 1 : 2;
-    (void)hipGetLastError();
-    if (dev == slot) big_ok[slot].store(st, std::memory_order_release);
-  }
-  hv_max[0] = 512; hv_max[1] = 1024; hv_max[2] = 2048; hv_max[3] = 4096;
-  *hv_big = st == 1 ? 8192 : 0;
-}
 // Speculative launch set (CmDev::cls_mask): the kernels of a long-list class are launched when the class had items in the context's
 // previous range (or always: the first range, a re-run).  An empty launch is not free -- a class kernel asks for up to 150 KB of shared
 // memory and waits for a CU that has it, under three lanes' other kernels: 0.2-0.5 ms each, 8 % of a step of the hic workload
 // (profiles/r04p_hic_kernel_stats.csv: k_s4c_coop<1024, false> 0.49 ms with no pair to work on).  The host compares the lists' counts
 // with the mask at the end of the range and maps the range again with every class on if an unlaunched one had items.
 static inline bool cm_cls_on(const CmDev &d, uint32_t list) { return (d.cls_mask >> list) & 1ull; }
-// the largest dynamic LDS allocation a kernel of this device may ask for, opted in once per device and kernel
+// the largest dynamic LDS allocation a kernel of this device may ask for, opted in per device and kernel -- on demand: the bytes follow the class sizes
 template <class K>
 static bool cm_lds_optin(K kernel, size_t bytes) {
   if (bytes <= 64 * 1024) return true;
   if (bytes > 160 * 1024) return false;
-  // function attributes belong to the device the call is made on; remember the largest size granted (or refused) per device
+  // function attributes belong to the device the call is made on (one process may drive several); lane threads of one device may race here
   static std::mutex mu;
   static std::map<std::pair<int, const void *>, std::pair<size_t, size_t>> seen;  // -> (granted up to, refused from)
   int dev = 0;
   (void)hipGetDevice(&dev);
-  const std::pair<int, const void *> key(dev, reinterpret_cast<const void *>(kernel));
   std::lock_guard<std::mutex> lk(mu);
-  auto it = seen.find(key);
-  if (it != seen.end()) {
-    if (bytes <= it->second.first) return true;
-    if (it->second.second && bytes >= it->second.second) return false;
-  }
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  std::pair<size_t, size_t> &v = seen[std::make_pair(dev, reinterpret_cast<const void *>(kernel))];
+  if (bytes <= v.first) return true;
+  if (v.second && bytes >= v.second) return false;
+  const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
   (void)hipGetLastError();
-  std::pair<size_t, size_t> &v = seen[key];
-  if (e == hipSuccess) { if (bytes > v.first) v.first = bytes; } else if (!v.second || bytes < v.second) v.second = bytes;
-  return e == hipSuccess;
+  (ok ? v.first : v.second) = bytes;  // (more than was granted, less than was refused: the two answers above)
+  return ok;
 }
-// n_cls[c]: reads of list c (k_s3a_count; 11 entries).  coop: lists 0, 1, 2, 10 go through the merge-sort kernel (tables sized for
-// reads of up to max_read_len bases) with a wave / 256 / 512 / 1024 lanes per read; what it declines -- hv_cnt[CM_L_HIT_DECLINED] reads at list 5 --
-// is taken by the bitonic kernel.
+// the cooperative kernel's size classes: hits per wave-group, per block, per block with a large LDS allocation
+// Round 4: finer classes (a wave up to 256 / 512 hits, 256 lanes up to 1024 / 2048, 512 up to 4096, 1024 up to 8192 with the large
+// allocation): the stages are chains of shared-memory round trips, a group's work area is what limits the waves a CU holds, and a
+// work area of the list's own size class was worth 20 % of the stage on the mosaic genome.
+void cm_s3b_heavy_classes(uint32_t *hv_max, uint32_t *hv_big) {
+  hv_max[0] = 512; hv_max[1] = 1024; hv_max[2] = 2048; hv_max[3] = 4096;
+  *hv_big = cm_lds_optin(&k_s3b_heavy<CM_BLOCK>, 8192 * 10 + (CM_BLOCK + 8) * 4) ? 8192 : 0;
+}
+// the classes whose work area is what the device grants: the pair filter's largest takes as many entries as the shared memory a block
+// may have holds at 10 bytes each, verification's as many candidates as fit (what even its arrays cannot hold: lane 0's acceptance
+// loop, the group's sort).  Once per range, so that the launches take `d` as it is
+void cm_granted_classes(CmDev &d) {
+  uint32_t pbig = CM_S4C_P_BIG, pb = CM_S5C_P_BLOCK;
+  while (pbig > CM_S4C_P_BLOCK && !cm_lds_optin(&k_s4c_coop<1024, false>, cm_group_bytes(cm_coop_pair_mem_bytes(pbig, false)))) pbig >>= 1;
+  while (pb > CM_S5C_P_WAVE && !cm_lds_optin(&k_s5c_coop<CM_BLOCK>, cm_group_bytes(cm_s5c_area_bytes(pb)))) pb >>= 1;
+  d.s4c_pbig = pbig > CM_S4C_P_BLOCK ? pbig : 0;
+  d.s5c_pblock = pb;
+}
+// ---- The launches of the long-list classes: a table per stage, a row per class (the functions of cm_classes.h send the items there).
+// Where a row's size comes from: a constant of cm_classes.h as it stands, or one of the range's sizes in CmDev
+enum : uint32_t { CM_P_HV0 = 0x80000000u, CM_P_HV1, CM_P_HV2, CM_P_HV3, CM_P_HV_SUB, CM_P_HV_BIG, CM_P_RS_MAX3, CM_P_RS_BIG, CM_P_RS_TOP, CM_P_S4C_BIG, CM_P_S5C_BLOCK };
+static uint32_t cm_class_size(const CmDev &d, uint32_t v) {
+  switch (v) {
+    case CM_P_HV0: case CM_P_HV1: case CM_P_HV2: case CM_P_HV3: return d.hv_max[v - CM_P_HV0];
+    case CM_P_HV_SUB: return d.hv_sub;          case CM_P_HV_BIG: return d.hv_big;
+    case CM_P_RS_MAX3: return d.rs_max3;        case CM_P_RS_BIG: return d.rs_big;
+    case CM_P_S4C_BIG: return d.s4c_pbig;       case CM_P_S5C_BLOCK: return d.s5c_pblock;
+    case CM_P_RS_TOP: return d.rs_big > d.rs_max3 ? d.rs_big : d.rs_max3;  // the rescue lists' largest work area
+    default: return v;
+  }
+}
+struct CmClassRow {
+  uint32_t list;        // CmList id
+  int G;                // lanes per item: the kernel's instance
+  uint32_t block, gpb;  // threads per block; items (groups) per block
+  uint32_t div, cap;    // blocks: n / div + 64, at most cap -- the lists are a few per cent of the n items, surplus blocks leave at once;
+                        // div 0: cap blocks.  (Hit lists, whose lengths the host knows: a block per gpb items)
+  uint32_t P, above;    // entries of the work area; the class exists when they are more than `above`, the class below it
+  bool slab;            // lists beyond the work area, on the blocks' slabs of global memory (d.coop_slab)
+};
+// the kernel instance by lanes per item: f(std::integral_constant<int, G>) for the G among Gs, its answer
+template <int... Gs, class F>
+static bool cm_by_lanes(int G, F f) {
+  bool r = false;
+  (void)((G == Gs && ((r = f(std::integral_constant<int, Gs>{})), true)) || ...);
+  return r;
+}
+// The one loop over a stage's classes.  For every class that exists: the grid, the shared memory (area_bytes(row, P): a group's work
+// area) and its opt-in -- false: it does not fit this device, the caller keeps the stage's lists with the lanes -- and, `launch`, the
+// launch if the class is on.  inst(g, row, P, go) names the kernel's instance of g lanes and its arguments after d: go(kernel, args...)
+template <int... Gs, int N, class Bytes, class Inst>
+static bool cm_classes(const CmDev &d, hipStream_t s, const CmClassRow (&rows)[N], uint32_t n, bool launch, Bytes area_bytes, Inst inst) {
+  for (const CmClassRow &c : rows) {
+    const uint32_t P = cm_class_size(d, c.P);
+    if (P <= cm_class_size(d, c.above) || (c.slab && !d.coop_slab)) continue;
+    uint32_t blocks = c.div ? n / c.div + 64 : c.cap;
+    if (blocks > c.cap) blocks = c.cap;
+    const size_t lds = c.gpb * cm_group_bytes(area_bytes(c, P));
+    auto go = [&](auto kernel, auto... args) {
+      if (!cm_lds_optin(kernel, lds)) return false;
+      if (launch && cm_cls_on(d, c.list)) hipLaunchKernelGGL(kernel, dim3(blocks), dim3(c.block), lds, s, d, args...);
+      return true;
+    };
+    if (!cm_by_lanes<Gs...>(c.G, [&](auto g) { return inst(g, c, P, go); })) return false;
+  }
+  return true;
+}
+
+// n_cls[c]: reads of list c (k_s3a_count).  coop: the lists of cm_s3b_rows go through the merge-sort kernel (tables sized for reads of up
+// to max_read_len bases); what it declines -- *cm_list_cnt(d, CM_L_HIT_DECLINED) reads -- is taken by the bitonic kernel.
 static inline uint32_t cm_coop_mm(const CmDev &d, uint32_t max_read_len) {
   // a read of L bases has at most L - k + 1 minimizers; the tables hold that many (capped)
   uint32_t MM = max_read_len > (uint32_t)d.p.k ? max_read_len - (uint32_t)d.p.k + 1 : 1;
   return MM > 256 ? 256 : MM;
 }
+// (a block per read: blocks that stride over the list -- 2048 / 8192 of them -- were measured 3-17 % slower, the reads differ too much in size)
+static const CmClassRow cm_s3b_rows[] = {
+  {CM_L_HIT_WAVE, 64, 128, 2, 0, 0, CM_P_HV0, 0},            // a wave per read, two reads per block
+  {CM_L_HIT_WAVE_SMALL, 64, 256, 4, 0, 0, CM_P_HV_SUB, 0},   // the wave class's short lists: a quarter of the work area each
+  {CM_L_HIT_B256A, 256, 256, 1, 0, 0, CM_P_HV1, CM_P_HV0},
+  {CM_L_HIT_B256B, 256, 256, 1, 0, 0, CM_P_HV2, CM_P_HV1},   // (512 lanes for 1024 .. 2048 hits and 1024 for 2048 .. 4096 were measured slower: more lanes
+  {CM_L_HIT_B512, 512, 512, 1, 0, 0, CM_P_HV3, CM_P_HV2},    //  per hit cost more in barriers than the shorter chunks save; ~8 hits per lane it is)
+  {CM_L_HIT_B1024, 1024, 1024, 1, 0, 0, CM_P_HV_BIG, CM_P_HV3},  // the largest work area: one block per CU (two with 32-bit keys)
+};
 void cm_launch_k_s3b_heavy(const CmDev &d, const uint32_t *n_cls, hipStream_t s, bool coop, uint32_t max_read_len) {
   auto pow2 = [](uint32_t x) { uint32_t p = 2; while (p < x) p <<= 1; return p; };  // the sort network's size: a power of two
-  auto lst = [&](uint32_t c) { return (const uint32_t *)(d.hv_list + (size_t)c * d.hv_stride); };
+  auto lst = [&](uint32_t c) { return (const uint32_t *)cm_list(d, c); };
   uint32_t rest[CM_HV_LISTS];
   for (int c = 0; c < CM_HV_LISTS; ++c) rest[c] = n_cls[c];
   if (coop && d.hv_max[0]) {
     const uint32_t MM = cm_coop_mm(d, max_read_len);
     const uint32_t RB = d.coop_rb ? d.coop_rb : 3 * MM + 2;  // a run per minimizer and strand, the + list's table padded to a power of two (cm_coop_s3b_expand)
-    uint32_t *fb_list = d.hv_list + CM_L_HIT_DECLINED * (size_t)d.hv_stride, *fb_cnt = d.hv_cnt + CM_L_HIT_DECLINED;
+    uint32_t *fb_list = cm_list(d, CM_L_HIT_DECLINED), *fb_cnt = cm_list_cnt(d, CM_L_HIT_DECLINED);
     bool any_coop = false;
     const bool k32 = d.goff != nullptr;  // (the reference fits 32-bit hit keys: every class's work area shrinks from 19 to 11 bytes per hit)
-    // (a block per read: blocks that stride over the list -- 2048 / 8192 of them -- were measured 3-17 % slower, the reads differ too much in size)
-#define CM_S3B_LAUNCH(G_, GRID_, BLOCK_, LDS_, ...)                                                                         \
-    do { if (k32) hipLaunchKernelGGL((k_s3b_coop<G_, true>), GRID_, BLOCK_, LDS_, s, __VA_ARGS__);                          \
-         else hipLaunchKernelGGL((k_s3b_coop<G_, false>), GRID_, BLOCK_, LDS_, s, __VA_ARGS__); } while (0)
-#define CM_S3B_OPTIN(G_, LDS_) (k32 ? cm_lds_optin(&k_s3b_coop<G_, true>, LDS_) : cm_lds_optin(&k_s3b_coop<G_, false>, LDS_))
-    if (n_cls[CM_L_HIT_WAVE]) {  // a wave per read, two reads per block
-      const size_t lds = 2 * cm_coop_group_bytes(d.hv_max[0], MM, RB, false, k32);
-      if (CM_S3B_OPTIN(64, lds)) {
-        CM_S3B_LAUNCH(64, dim3((n_cls[CM_L_HIT_WAVE] + 1) / 2), dim3(128), lds, d, lst(CM_L_HIT_WAVE), n_cls[CM_L_HIT_WAVE], d.hv_max[0], MM, RB, fb_list, fb_cnt, 0u);
-        rest[CM_L_HIT_WAVE] = 0; any_coop = true;
-      }
-    }
-    if (n_cls[CM_L_HIT_WAVE_SMALL] && d.hv_sub) {  // the wave class's short lists: four reads per block of 256 lanes, a quarter of the work area each
-      const size_t lds = 4 * cm_coop_group_bytes(d.hv_sub, MM, RB, false, k32);
-      if (CM_S3B_OPTIN(64, lds)) {
-        CM_S3B_LAUNCH(64, dim3((n_cls[CM_L_HIT_WAVE_SMALL] + 3) / 4), dim3(256), lds, d, lst(CM_L_HIT_WAVE_SMALL), n_cls[CM_L_HIT_WAVE_SMALL], d.hv_sub, MM, RB, fb_list, fb_cnt, 0u);
-        rest[CM_L_HIT_WAVE_SMALL] = 0; any_coop = true;
-      }
-    }
-#define CM_S3B_COOP_CLASS(C_, Q_, G_)                                                                                                              \
-    if (n_cls[C_] && d.hv_max[Q_] > d.hv_max[Q_ - 1]) {                                                                                            \
-      const size_t lds = cm_coop_group_bytes(d.hv_max[Q_], MM, RB, false, k32);                                                                    \
-      if (CM_S3B_OPTIN(G_, lds)) {                                                                                                                 \
-        CM_S3B_LAUNCH(G_, dim3(n_cls[C_]), dim3(G_), lds, d, lst(C_), n_cls[C_], d.hv_max[Q_], MM, RB, fb_list, fb_cnt, 0u);                      \
-        rest[C_] = 0; any_coop = true;                                                                                                             \
-      }                                                                                                                                            \
-    }
-    CM_S3B_COOP_CLASS(CM_L_HIT_B256A, 1, 256)
-    CM_S3B_COOP_CLASS(CM_L_HIT_B256B, 2, 256)   // (512 lanes for 1024 .. 2048 hits and 1024 for 2048 .. 4096 were measured slower: more lanes
-    CM_S3B_COOP_CLASS(CM_L_HIT_B512, 3, 512)  //  per hit cost more in barriers than the shorter chunks save; ~8 hits per lane it is)
-#undef CM_S3B_COOP_CLASS
-    if (n_cls[CM_L_HIT_B1024] && d.hv_big > d.hv_max[3]) {  // the largest work area: one block per CU
-      const size_t lds = cm_coop_group_bytes(d.hv_big, MM, RB, false, k32);
-      if (CM_S3B_OPTIN(1024, lds)) {
-        CM_S3B_LAUNCH(1024, dim3(n_cls[CM_L_HIT_B1024]), dim3(1024), lds, d, lst(CM_L_HIT_B1024), n_cls[CM_L_HIT_B1024], d.hv_big, MM, RB, fb_list, fb_cnt, 0u);
-        rest[CM_L_HIT_B1024] = 0; any_coop = true;
-      }
+    for (const CmClassRow &c : cm_s3b_rows) {
+      const uint32_t n = n_cls[c.list], P = cm_class_size(d, c.P);
+      if (!n || P <= cm_class_size(d, c.above)) continue;
+      const size_t lds = c.gpb * cm_coop_group_bytes(P, MM, RB, false, k32);
+      auto go = [&](auto kernel) {
+        if (!cm_lds_optin(kernel, lds)) return false;
+        hipLaunchKernelGGL(kernel, dim3((n + c.gpb - 1) / c.gpb), dim3(c.block), lds, s, d, lst(c.list), n, P, MM, RB, fb_list, fb_cnt, 0u);
+        return true;
+      };
+      if (cm_by_lanes<64, 256, 512, 1024>(c.G, [&](auto g) { return k32 ? go(&k_s3b_coop<decltype(g)::value, true>) : go(&k_s3b_coop<decltype(g)::value, false>); })) { rest[c.list] = 0; any_coop = true; }
     }
     if (n_cls[CM_L_HIT_SLAB] && d.coop_slab && d.hv_max[3]) {  // lists beyond the largest class: 1024 lanes on a slab of global memory each
       const size_t lds = cm_coop_group_bytes(d.hv_max[3], MM, RB, false);
       if (cm_lds_optin(&k_s3b_coop<1024, false>, lds)) {
         const uint32_t blocks = n_cls[CM_L_HIT_SLAB] < d.coop_slab_blocks ? n_cls[CM_L_HIT_SLAB] : d.coop_slab_blocks;
-        uint32_t *sl = d.hv_list + CM_L_HIT_SERIAL * (size_t)d.hv_stride, *sc = d.hv_cnt + CM_L_HIT_SERIAL;  // what even that declines: one lane each
+        uint32_t *sl = cm_list(d, CM_L_HIT_SERIAL), *sc = cm_list_cnt(d, CM_L_HIT_SERIAL);  // what even that declines: one lane each
         hipLaunchKernelGGL((k_s3b_coop<1024, false>), dim3(blocks), dim3(1024), lds, s, d, lst(CM_L_HIT_SLAB), n_cls[CM_L_HIT_SLAB], d.hv_max[3], MM, RB, sl, sc, 1u);
         hipLaunchKernelGGL(k_s3b_serial, dim3(64), dim3(64), 0, s, d, (const uint32_t *)sl, 0u, (const uint32_t *)sc);
         rest[CM_L_HIT_SLAB] = 0;
@@ -1953,24 +1929,18 @@ void cm_launch_k_s3b_heavy(const CmDev &d, const uint32_t *n_cls, hipStream_t s,
       hipLaunchKernelGGL(k_s3b_heavy<CM_BLOCK>, dim3(512), dim3(CM_BLOCK), (size_t)P * 10 + (CM_BLOCK + 8) * 4, s, d, (const uint32_t *)fb_list, 0u, P, (const uint32_t *)fb_cnt);
     }
   }
-  if (rest[CM_L_HIT_WAVE_SMALL]) {
+  // what the merge-sort kernel did not take (coop off, or its work area refused): the bitonic kernel, by class
+  for (uint32_t c : {(uint32_t)CM_L_HIT_WAVE_SMALL, (uint32_t)CM_L_HIT_WAVE}) {
+    if (!rest[c]) continue;
     const uint32_t P = pow2(d.hv_max[0]), gpb = CM_BLOCK / 64;
-    hipLaunchKernelGGL(k_s3b_heavy<64>, dim3((rest[CM_L_HIT_WAVE_SMALL] + gpb - 1) / gpb), dim3(CM_BLOCK), (size_t)gpb * P * 10 + gpb * (64 + 8) * 4, s, d, lst(CM_L_HIT_WAVE_SMALL), rest[CM_L_HIT_WAVE_SMALL], P, (const uint32_t *)nullptr);
+    hipLaunchKernelGGL(k_s3b_heavy<64>, dim3((rest[c] + gpb - 1) / gpb), dim3(CM_BLOCK), (size_t)gpb * P * 10 + gpb * (64 + 8) * 4, s, d, lst(c), rest[c], P, (const uint32_t *)nullptr);
   }
-  if (rest[CM_L_HIT_WAVE]) {
-    const uint32_t P = pow2(d.hv_max[0]), gpb = CM_BLOCK / 64;
-    hipLaunchKernelGGL(k_s3b_heavy<64>, dim3((rest[CM_L_HIT_WAVE] + gpb - 1) / gpb), dim3(CM_BLOCK), (size_t)gpb * P * 10 + gpb * (64 + 8) * 4, s, d, lst(CM_L_HIT_WAVE), rest[CM_L_HIT_WAVE], P, (const uint32_t *)nullptr);
-  }
-  const uint32_t blk[3][2] = {{1, 1}, {2, 2}, {10, 3}};  // list, size class
-  for (int q = 0; q < 3; ++q) {
+  const uint32_t blk[4][2] = {{CM_L_HIT_B256A, CM_P_HV1}, {CM_L_HIT_B256B, CM_P_HV2}, {CM_L_HIT_B512, CM_P_HV3}, {CM_L_HIT_B1024, CM_P_HV_BIG}};  // list, size
+  for (int q = 0; q < 4; ++q) {
     const uint32_t c = blk[q][0];
     if (!rest[c]) continue;
-    const uint32_t P = pow2(d.hv_max[blk[q][1]]);
+    const uint32_t P = pow2(cm_class_size(d, blk[q][1]));
     hipLaunchKernelGGL(k_s3b_heavy<CM_BLOCK>, dim3(rest[c]), dim3(CM_BLOCK), (size_t)P * 10 + (CM_BLOCK + 8) * 4, s, d, lst(c), rest[c], P, (const uint32_t *)nullptr);
-  }
-  if (rest[CM_L_HIT_B1024]) {
-    const uint32_t P = pow2(d.hv_big);
-    hipLaunchKernelGGL(k_s3b_heavy<CM_BLOCK>, dim3(rest[CM_L_HIT_B1024]), dim3(CM_BLOCK), (size_t)P * 10 + (CM_BLOCK + 8) * 4, s, d, lst(CM_L_HIT_B1024), rest[CM_L_HIT_B1024], P, (const uint32_t *)nullptr);
   }
   if (rest[CM_L_HIT_SLAB]) hipLaunchKernelGGL(k_s3b_serial, dim3((rest[CM_L_HIT_SLAB] + 63) / 64), dim3(64), 0, s, d, lst(CM_L_HIT_SLAB), rest[CM_L_HIT_SLAB], (const uint32_t *)nullptr);
   if (rest[CM_L_HIT_G16]) {  // groups of 16 lanes, 16 reads per block
@@ -2013,37 +1983,33 @@ void cm_launch_k_s4a_rescue_list(const CmDev &d, uint32_t n_reads, hipStream_t s
     hipLaunchKernelGGL(k_s4a_rescue_wave<false>, dim3(rescue_wave_blocks(n_reads)), dim3(64), 0, s, d);  // (what the small tables do not hold; leaves at once when there is none)
   }
 }
-// the per-read part (reads without rescue hits) and, coop: the reads whose long lists a wave copies
-static bool cm_s4b_coop_ready(const CmDev &d, uint32_t RB, size_t *lds) {
-  if (!d.hv_max[0]) return false;
-  lds[0] = 2 * cm_coop_group_bytes(d.hv_max[0], 1, RB, true);
-  lds[1] = cm_coop_group_bytes(d.hv_max[1], 1, RB, true);
-  lds[2] = cm_coop_group_bytes(d.hv_max[2], 1, RB, true);
-  lds[3] = cm_coop_group_bytes(d.rs_max3, 1, RB, true);
-  lds[4] = cm_coop_group_bytes(d.rs_big > d.rs_max3 ? d.rs_big : d.rs_max3, 1, RB, true);
-  const bool ok = cm_lds_optin(&k_s4b_coop<64>, lds[0]) && cm_lds_optin(&k_s4b_coop<256>, lds[1] > lds[2] ? lds[1] : lds[2]) && cm_lds_optin(&k_s4b_coop<512>, lds[3]) &&
-                  cm_lds_optin(&k_s4b_coop<1024>, lds[4]);
-  if (!ok) {  // not an error (the one-lane forms take over), but never silently: it costs a factor on repeat-rich input
-    static std::atomic<int> told{0};
-    if (!told.exchange(1)) fprintf(stderr, "chromap_amd: the cooperative rescue kernels do not fit this device's shared memory (%zu / %zu / %zu / %zu bytes); using the one-lane forms\n", lds[0], lds[1], lds[2], lds[4]);
-  }
+// S4b's groups (k_s4b_coop); launch == false: the opt-ins alone
+static const CmClassRow cm_s4b_rows[] = {
+  {CM_L_RS_WAVE, 64, 128, 2, 2048, 2048, CM_P_HV0, 0},
+  {CM_L_RS_B256A, 256, 256, 1, 2048, 2048, CM_P_HV1, CM_P_HV0},
+  {CM_L_RS_B256B, 256, 256, 1, 2048, 2048, CM_P_HV2, CM_P_HV1},
+  {CM_L_RS_B512, 512, 512, 1, 2048, 512, CM_P_RS_MAX3, CM_P_HV2},
+  {CM_L_RS_B1024, 1024, 1024, 1, 2048, 256, CM_P_RS_BIG, CM_P_RS_MAX3},
+  {CM_L_RS_SLAB, 1024, 1024, 1, 0, CM_SLAB_BLOCKS, CM_P_RS_TOP, 0, true},
+};
+static bool cm_s4b_classes(const CmDev &d, uint32_t n_reads, uint32_t max_read_len, hipStream_t s, bool launch) {
+  const uint32_t RB = d.coop_rb ? d.coop_rb : 2 * cm_coop_mm(d, max_read_len) + 2;  // ascending runs the sorter's tables hold: one per minimizer unless a diagonal wraps
+  const bool ok = d.hv_max[0] && cm_classes<64, 256, 512, 1024>(d, s, cm_s4b_rows, n_reads, launch, [&](const CmClassRow &, uint32_t P) { return cm_coop_mem_bytes(P, 1, RB, true); },
+    [&](auto g, const CmClassRow &c, uint32_t P, auto go) { return go(&k_s4b_coop<decltype(g)::value>, (const uint32_t *)cm_list(d, c.list), (const uint32_t *)cm_list_cnt(d, c.list), P, RB, c.slab ? 1u : 0u); });
+  static std::atomic<int> told{0};  // not an error (the one-lane forms take over), but never silently: it costs a factor on repeat-rich input
+  if (!ok && d.hv_max[0] && !told.exchange(1)) fprintf(stderr, "chromap_amd: the cooperative rescue kernels do not fit this device's shared memory; using the one-lane forms\n");
   return ok;
 }
-static inline uint32_t cm_s4b_rb(const CmDev &d, uint32_t max_read_len) {
-  return d.coop_rb ? d.coop_rb : 2 * cm_coop_mm(d, max_read_len) + 2;  // ascending runs the sorter's tables hold: one per minimizer unless a diagonal wraps
-}
+// the per-read part (reads without rescue hits) and, coop: the reads whose long lists a wave copies
 void cm_launch_k_s4b_rescue_merge(const CmDev &d, uint32_t n, hipStream_t s, bool coop, uint32_t max_read_len) {
   if (!n) return;
-  size_t lds[5];
-  const bool all = coop && cm_s4b_coop_ready(d, cm_s4b_rb(d, max_read_len), lds);
+  const bool all = coop && cm_s4b_classes(d, n, max_read_len, s, false);
   hipLaunchKernelGGL(k_s4b_rescue_merge, grid_for(n), dim3(CM_BLOCK), 0, s, d, n, all ? 1u : 0u);
 }
 // coop: reads with many rescue hits are only filled by the list kernel and finished by groups of lanes (k_s4b_coop)
 void cm_launch_k_s4b_rescue_list(const CmDev &d, uint32_t n_reads, hipStream_t s, bool coop, uint32_t max_read_len) {
   if (!n_reads) return;
-  const uint32_t RB = cm_s4b_rb(d, max_read_len);
-  size_t lds[5];
-  const bool all = coop && cm_s4b_coop_ready(d, RB, lds);
+  const bool all = coop && cm_s4b_classes(d, n_reads, max_read_len, s, false);
   hipLaunchKernelGGL(k_s4b_rescue_list, rescue_list_grid(n_reads), dim3(64), 0, s, d, cm_rescue_seg_cap(n_reads), all ? 1u : 0u);
   // list 23's reads were counted by waves whenever the option is on: they are filled by waves too (all == false: the groups that
   // would sort long lists do not fit this device -- every list is then finished by the wave's lane 0)
@@ -2051,65 +2017,45 @@ void cm_launch_k_s4b_rescue_list(const CmDev &d, uint32_t n_reads, hipStream_t s
     hipLaunchKernelGGL(k_s4b_rescue_wave<true>, dim3(rescue_wave_blocks(n_reads)), dim3(64), 0, s, d, all ? 1u : 0u);
     hipLaunchKernelGGL(k_s4b_rescue_wave<false>, dim3(rescue_wave_blocks(n_reads)), dim3(64), 0, s, d, all ? 1u : 0u);
   }
-  if (!all) return;
-  uint32_t blocks = n_reads / 2048 + 64;  // the listed reads are a few per cent of the batch; surplus blocks leave at once
-  if (blocks > 2048) blocks = 2048;
-  auto lst = [&](uint32_t c) { return (const uint32_t *)(d.hv_list + (size_t)c * d.hv_stride); };
-  if (cm_cls_on(d, CM_L_RS_WAVE)) hipLaunchKernelGGL(k_s4b_coop<64>, dim3(blocks), dim3(128), lds[0], s, d, lst(CM_L_RS_WAVE), (const uint32_t *)(d.hv_cnt + CM_L_RS_WAVE), d.hv_max[0], RB, 0u);
-  if ((d.hv_max[1] > d.hv_max[0]) && cm_cls_on(d, CM_L_RS_B256A)) hipLaunchKernelGGL(k_s4b_coop<256>, dim3(blocks), dim3(256), lds[1], s, d, lst(CM_L_RS_B256A), (const uint32_t *)(d.hv_cnt + CM_L_RS_B256A), d.hv_max[1], RB, 0u);
-  if ((d.hv_max[2] > d.hv_max[1]) && cm_cls_on(d, CM_L_RS_B256B)) hipLaunchKernelGGL(k_s4b_coop<256>, dim3(blocks), dim3(256), lds[2], s, d, lst(CM_L_RS_B256B), (const uint32_t *)(d.hv_cnt + CM_L_RS_B256B), d.hv_max[2], RB, 0u);
-  if ((d.rs_max3 > d.hv_max[2]) && cm_cls_on(d, CM_L_RS_B512)) hipLaunchKernelGGL(k_s4b_coop<512>, dim3(blocks > 512 ? 512 : blocks), dim3(512), lds[3], s, d, lst(CM_L_RS_B512), (const uint32_t *)(d.hv_cnt + CM_L_RS_B512), d.rs_max3, RB, 0u);
-  if ((d.rs_big > d.rs_max3) && cm_cls_on(d, CM_L_RS_B1024)) hipLaunchKernelGGL(k_s4b_coop<1024>, dim3(blocks > 256 ? 256 : blocks), dim3(1024), lds[4], s, d, lst(CM_L_RS_B1024), (const uint32_t *)(d.hv_cnt + CM_L_RS_B1024), d.rs_big, RB, 0u);
-  if (d.coop_slab && cm_cls_on(d, CM_L_RS_SLAB))  // lists beyond the largest class: on the blocks' slabs of global memory
-    hipLaunchKernelGGL(k_s4b_coop<1024>, dim3(d.coop_slab_blocks), dim3(1024), lds[4], s, d, lst(CM_L_RS_SLAB), (const uint32_t *)(d.hv_cnt + CM_L_RS_SLAB), d.rs_big > d.rs_max3 ? d.rs_big : d.rs_max3, RB, 1u);
+  if (all) cm_s4b_classes(d, n_reads, max_read_len, s, true);
+}
+// S4c's groups (k_s4c_coop): a wave per pair, a block, a block of 1024 lanes
+static const CmClassRow cm_s4c_rows[] = {
+  {CM_L_PF_WAVE, 64, CM_BLOCK, CM_BLOCK / 64, 2048, 4096, CM_S4C_P_SMALL, 0},
+  {CM_L_PF_BLOCK, CM_BLOCK, CM_BLOCK, 1, 2048, 4096, CM_S4C_P_WAVE, 0},
+  {CM_L_PF_BLOCK_BIG, CM_BLOCK, CM_BLOCK, 1, 0, 256, CM_S4C_P_BLOCK, 0},
+  {CM_L_PF_HUGE, 1024, 1024, 1, 0, 128, CM_P_S4C_BIG, 0},  // (the lists stay in global memory)
+};
+static bool cm_s4c_classes(const CmDev &d, uint32_t n, uint32_t coop, hipStream_t s, bool launch) {
+  return cm_classes<64, CM_BLOCK, 1024>(d, s, cm_s4c_rows, n, launch, [](const CmClassRow &c, uint32_t P) { return cm_coop_pair_mem_bytes(P, c.G != 1024); },
+    [&](auto g, const CmClassRow &c, uint32_t P, auto go) { return go(&k_s4c_coop<decltype(g)::value, decltype(g)::value != 1024>, P, c.list, coop); });
 }
 // coop: the cmgpu_set_option "coop" bit mask (bit 2: pairs with long lists to groups; bit 3: the S5 waves sort the heavy reads' lists)
 void cm_launch_k_s4c_reduce(const CmDev &d, uint32_t n, hipStream_t s, uint32_t coop) {
   if (!n) return;
-  const size_t gw = ((cm_coop_pair_mem_bytes(CM_S4C_P_WAVE) + 15) & ~(size_t)15) + CM_XW_BYTES;
-  const size_t gbk = ((cm_coop_pair_mem_bytes(CM_S4C_P_BLOCK) + 15) & ~(size_t)15) + CM_XW_BYTES;
-  // the lists beyond that: as many entries as the shared memory a block may have holds at 10 bytes each
-  uint32_t pbig = CM_S4C_P_BIG;
-  while (pbig > CM_S4C_P_BLOCK && !cm_lds_optin(&k_s4c_coop<1024, false>, ((cm_coop_pair_mem_bytes(pbig, false) + 15) & ~(size_t)15) + CM_XW_BYTES)) pbig >>= 1;
-  if (!cm_lds_optin(&k_s4c_coop<CM_BLOCK, true>, gbk)) coop &= ~4u;
-  CmDev d2 = d;
-  d2.s4c_pbig = pbig > CM_S4C_P_BLOCK ? pbig : 0;
-  CM_LAUNCH_MODE(k_s4c_reduce, grid_for(n), dim3(CM_BLOCK), 0, s, d2, n, coop);
-  if (!(coop & 4u)) return;
-  uint32_t blocks = n / 2048 + 64;
-  if (blocks > 4096) blocks = 4096;
-  const size_t gs = ((cm_coop_pair_mem_bytes(CM_S4C_P_SMALL) + 15) & ~(size_t)15) + CM_XW_BYTES;
-  if (cm_cls_on(d, CM_L_PF_WAVE)) hipLaunchKernelGGL((k_s4c_coop<64, true>), dim3(blocks), dim3(CM_BLOCK), (CM_BLOCK / 64) * gs, s, d, CM_S4C_P_SMALL, CM_L_PF_WAVE, coop);  // a wave per pair
-  if (cm_cls_on(d, CM_L_PF_BLOCK)) hipLaunchKernelGGL((k_s4c_coop<CM_BLOCK, true>), dim3(blocks), dim3(CM_BLOCK), gw, s, d, CM_S4C_P_WAVE, CM_L_PF_BLOCK, coop);
-  if (cm_cls_on(d, CM_L_PF_BLOCK_BIG)) hipLaunchKernelGGL((k_s4c_coop<CM_BLOCK, true>), dim3(256), dim3(CM_BLOCK), gbk, s, d, CM_S4C_P_BLOCK, CM_L_PF_BLOCK_BIG, coop);
-  if (d2.s4c_pbig && cm_cls_on(d, CM_L_PF_HUGE))
-    hipLaunchKernelGGL((k_s4c_coop<1024, false>), dim3(128), dim3(1024), ((cm_coop_pair_mem_bytes(pbig, false) + 15) & ~(size_t)15) + CM_XW_BYTES, s, d, pbig, 19u, coop);
+  if (!cm_s4c_classes(d, n, coop, s, false)) coop &= ~4u;
+  CM_LAUNCH_MODE(k_s4c_reduce, grid_for(n), dim3(CM_BLOCK), 0, s, d, n, coop);
+  if (coop & 4u) cm_s4c_classes(d, n, coop, s, true);
 }
 void cm_launch_k_s5a_prepare(const CmDev &d, uint32_t n, hipStream_t s, bool coop) {
   if (!n) return;
   CM_LAUNCH_MODE(k_s5a_prepare, grid_for(n), dim3(CM_BLOCK), 0, s, d, n, coop ? 1u : 0u);
-  if (coop) {  // the lists it left unsorted: a wave per read
-    if (cm_cls_on(d, CM_L_S5_SMALL)) hipLaunchKernelGGL(k_s5_sort_coop, dim3(4096), dim3(CM_BLOCK), 0, s, d, CM_L_S5_SMALL);
-    if (cm_cls_on(d, CM_L_S5_WAVE)) hipLaunchKernelGGL(k_s5_sort_coop, dim3(2048), dim3(CM_BLOCK), 0, s, d, CM_L_S5_WAVE);
-    if (cm_cls_on(d, CM_L_S5_BLOCK)) hipLaunchKernelGGL(k_s5_sort_coop, dim3(64), dim3(CM_BLOCK), 0, s, d, CM_L_S5_BLOCK);
-  }
+  const uint32_t sort[3][2] = {{CM_L_S5_SMALL, 4096}, {CM_L_S5_WAVE, 2048}, {CM_L_S5_BLOCK, 64}};  // the lists it left unsorted: a wave per read
+  for (int q = 0; coop && q < 3; ++q)
+    if (cm_cls_on(d, sort[q][0])) hipLaunchKernelGGL(k_s5_sort_coop, dim3(sort[q][1]), dim3(CM_BLOCK), 0, s, d, sort[q][0]);
 }
+// S5c's groups (k_s5c_coop)
+static const CmClassRow cm_s5c_rows[] = {
+  {CM_L_S5_SMALL, 64, CM_BLOCK, CM_BLOCK / 64, 4096, 2048, CM_S5C_P_SMALL, 0},
+  {CM_L_S5_WAVE, 64, 192, 3, 4096, 2048, CM_S5C_P_WAVE, 0},  // three waves per block: under the 64 KB a launch gets without asking
+  {CM_L_S5_BLOCK, CM_BLOCK, CM_BLOCK, 1, 0, 128, CM_P_S5C_BLOCK, 0},  // the reads with a longer list: a block each
+};
 void cm_launch_k_s5c_finalize(const CmDev &d, uint32_t n, hipStream_t s, bool coop) {
   if (!n) return;
   CM_LAUNCH_MODE(k_s5c_finalize, grid_for(n), dim3(CM_BLOCK), 0, s, d, n, coop ? 1u : 0u);
   if (!coop) return;
-  auto gbytes = [](uint32_t P) {
-    const size_t b1 = cm_coop_ver_mem_bytes(P), b2 = cm_coop_sort_mem_bytes(CM_S5C_SORT_P, CM_S5C_SORT_RB);
-    return (((b1 > b2 ? b1 : b2) + 15) & ~(size_t)15) + CM_XW_BYTES;
-  };
-  uint32_t blocks = n / 4096 + 64;
-  if (blocks > 2048) blocks = 2048;
-  if (cm_cls_on(d, CM_L_S5_SMALL)) hipLaunchKernelGGL(k_s5c_coop<64>, dim3(blocks), dim3(CM_BLOCK), (CM_BLOCK / 64) * gbytes(CM_S5C_P_SMALL), s, d, CM_S5C_P_SMALL, CM_L_S5_SMALL);
-  if (cm_cls_on(d, CM_L_S5_WAVE)) hipLaunchKernelGGL(k_s5c_coop<64>, dim3(blocks), dim3(192), 3 * gbytes(CM_S5C_P_WAVE), s, d, CM_S5C_P_WAVE, CM_L_S5_WAVE);  // three waves per block: under the 64 KB a launch gets without asking
-  // the reads with a longer list: a block each (what even its work arrays cannot hold: lane 0's acceptance loop, the group's sort)
-  uint32_t pb = CM_S5C_P_BLOCK;
-  while (pb > CM_S5C_P_WAVE && !cm_lds_optin(&k_s5c_coop<CM_BLOCK>, gbytes(pb))) pb >>= 1;
-  if (cm_cls_on(d, CM_L_S5_BLOCK)) hipLaunchKernelGGL(k_s5c_coop<CM_BLOCK>, dim3(128), dim3(CM_BLOCK), gbytes(pb), s, d, pb, CM_L_S5_BLOCK);
+  cm_classes<64, CM_BLOCK>(d, s, cm_s5c_rows, n, true, [](const CmClassRow &, uint32_t P) { return cm_s5c_area_bytes(P); },
+    [&](auto g, const CmClassRow &c, uint32_t P, auto go) { return go(&k_s5c_coop<decltype(g)::value>, P, c.list); });
 }
 CM_LAUNCH(k_s6a_pair_sam)
 CM_LAUNCH(k_s6c_multi_sam)
@@ -2121,32 +2067,36 @@ void cm_launch_k_s5b_verify(const CmDev &d, uint32_t max_items, uint32_t n_reads
   hipLaunchKernelGGL(k_s5b_verify, dim3(blocks), dim3(CM_BLOCK), 0, s, d, n_reads);
 }
 // the pairing stages' groups: a wave per pair with the second list staged (4 waves x 10 KB per block), a block per pair for the
-// few pairs whose read 2 has a list beyond CM_S6A_P_WAVE (80 KB)
-static inline size_t cm_s6_group_bytes(uint32_t P) { return ((cm_coop_pe_mem_bytes(P) + 15) & ~(size_t)15) + CM_XW_BYTES; }
+// few pairs whose read 2 has a list beyond CM_S6A_P_WAVE (80 KB).  S6a and S6c: the same classes, their own lists and kernels
+static const CmClassRow cm_s6a_rows[] = {
+  {CM_L_S6A_SMALL, 64, CM_BLOCK, CM_BLOCK / 64, 4096, 2048, CM_S6A_P_SMALL, 0},
+  {CM_L_S6A_WAVE, 64, CM_BLOCK, CM_BLOCK / 64, 4096, 2048, CM_S6A_P_WAVE, 0},
+  {CM_L_S6A_BLOCK, CM_BLOCK, CM_BLOCK, 1, 0, 256, CM_S6A_P_BLOCK, 0},
+};
+static const CmClassRow cm_s6c_rows[] = {
+  {CM_L_S6C_SMALL, 64, CM_BLOCK, CM_BLOCK / 64, 4096, 2048, CM_S6A_P_SMALL, 0},
+  {CM_L_S6C_WAVE, 64, CM_BLOCK, CM_BLOCK / 64, 4096, 2048, CM_S6A_P_WAVE, 0},
+  {CM_L_S6C_BLOCK, CM_BLOCK, CM_BLOCK, 1, 0, 256, CM_S6A_P_BLOCK, 0},
+};
+template <bool S6C>
+static bool cm_s6_classes(const CmDev &d, uint32_t n, hipStream_t s, bool launch) {
+  return cm_classes<64, CM_BLOCK>(d, s, S6C ? cm_s6c_rows : cm_s6a_rows, n, launch, [](const CmClassRow &, uint32_t P) { return cm_coop_pe_mem_bytes(P); },
+    [&](auto g, const CmClassRow &c, uint32_t P, auto go) { return go(S6C ? &k_s6c_coop<decltype(g)::value> : &k_s6a_coop<decltype(g)::value>, P, c.list); });
+}
 void cm_launch_k_s6a_pair(const CmDev &d, uint32_t n, hipStream_t s, bool coop) {
   if (!n) return;
-  const size_t lw = (CM_BLOCK / 64) * cm_s6_group_bytes(CM_S6A_P_WAVE), lb = cm_s6_group_bytes(CM_S6A_P_BLOCK);
-  if (coop && !(cm_lds_optin(&k_s6a_coop<64>, lw) && cm_lds_optin(&k_s6a_coop<CM_BLOCK>, lb))) coop = false;
+  coop = coop && cm_s6_classes<false>(d, n, s, false);
   CM_LAUNCH_MODE(k_s6a_pair, grid_for(n), dim3(CM_BLOCK), 0, s, d, n, coop ? 1u : 0u);
-  if (!coop) return;
-  uint32_t blocks = n / 4096 + 64;
-  if (blocks > 2048) blocks = 2048;
-  if (cm_cls_on(d, CM_L_S6A_SMALL)) hipLaunchKernelGGL(k_s6a_coop<64>, dim3(blocks), dim3(CM_BLOCK), (CM_BLOCK / 64) * cm_s6_group_bytes(CM_S6A_P_SMALL), s, d, CM_S6A_P_SMALL, CM_L_S6A_SMALL);
-  if (cm_cls_on(d, CM_L_S6A_WAVE)) hipLaunchKernelGGL(k_s6a_coop<64>, dim3(blocks), dim3(CM_BLOCK), lw, s, d, CM_S6A_P_WAVE, CM_L_S6A_WAVE);
-  if (cm_cls_on(d, CM_L_S6A_BLOCK)) hipLaunchKernelGGL(k_s6a_coop<CM_BLOCK>, dim3(256), dim3(CM_BLOCK), lb, s, d, CM_S6A_P_BLOCK, CM_L_S6A_BLOCK);
+  if (coop) cm_s6_classes<false>(d, n, s, true);
 }
 void cm_launch_k_s6c_multi(const CmDev &d, uint32_t n, hipStream_t s, bool coop) {
   if (!n) return;
-  const size_t lw = (CM_BLOCK / 64) * cm_s6_group_bytes(CM_S6A_P_WAVE), lb = cm_s6_group_bytes(CM_S6A_P_BLOCK);
-  if (coop && !(cm_lds_optin(&k_s6c_coop<64>, lw) && cm_lds_optin(&k_s6c_coop<CM_BLOCK>, lb))) coop = false;
+  coop = coop && cm_s6_classes<true>(d, n, s, false);
   uint32_t blocks = n / 4096 + 64;
   if (blocks > 2048) blocks = 2048;
   if (!cm_mode_pe(d)) hipLaunchKernelGGL(k_s6c_multi, grid_for(n), dim3(CM_BLOCK), 0, s, d, n, coop ? 1u : 0u);
   else if (cm_cls_on(d, CM_L_S6C_MULTI)) hipLaunchKernelGGL(k_s6c_list, dim3(blocks), dim3(CM_BLOCK), 0, s, d, coop ? 1u : 0u);
-  if (!coop) return;
-  if (cm_cls_on(d, CM_L_S6C_SMALL)) hipLaunchKernelGGL(k_s6c_coop<64>, dim3(blocks), dim3(CM_BLOCK), (CM_BLOCK / 64) * cm_s6_group_bytes(CM_S6A_P_SMALL), s, d, CM_S6A_P_SMALL, CM_L_S6C_SMALL);
-  if (cm_cls_on(d, CM_L_S6C_WAVE)) hipLaunchKernelGGL(k_s6c_coop<64>, dim3(blocks), dim3(CM_BLOCK), lw, s, d, CM_S6A_P_WAVE, CM_L_S6C_WAVE);
-  if (cm_cls_on(d, CM_L_S6C_BLOCK)) hipLaunchKernelGGL(k_s6c_coop<CM_BLOCK>, dim3(256), dim3(CM_BLOCK), lb, s, d, CM_S6A_P_BLOCK, CM_L_S6C_BLOCK);
+  if (coop) cm_s6_classes<true>(d, n, s, true);
 }
 
 // threads per block / LDS bytes for the read-staging kernels, from the longest read of the batch

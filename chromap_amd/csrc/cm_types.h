@@ -5,6 +5,7 @@
 #ifndef CM_TYPES_H_
 #define CM_TYPES_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -25,8 +26,10 @@
 #define CM_PR_MULTI 2
 #define CM_V_INVALID 0x7fff
 #define CM_MM_CHUNKS 8            // chunks of a batch whose index probe overlaps the next chunk's minimizer pass
-// Device work lists (CmDev::hv_list + id * hv_stride, their lengths at hv_cnt[id]): the reads / pairs whose lists are too long for the
+// Device work lists (cm_list(d, id), their lengths at *cm_list_cnt(d, id)): the reads / pairs whose lists are too long for the
 // one-lane-per-item kernel of a stage, by stage and size class.  P: entries of the class's shared work area; LDS: bytes per block.
+// A class is defined in cm_classes.h: its sizes (the constants and CmDev fields named here) and the function that sends a length
+// to a list id; its launch -- lanes per item, block, grid, where P comes from -- is a row of its stage's table in cm_kernels.hip.
 //   id  name                  items                                  kernel (lanes per item)             P / LDS per block
 //    0  CM_L_HIT_WAVE         reads, hits <= hv_max[0] (512)         k_s3b_coop<64> (two reads a block)   512 / 2 x 6 KB (32-bit keys; 10 KB with 64-bit keys)
 //   21  CM_L_HIT_WAVE_SMALL   reads, hits <= hv_sub (256)            k_s3b_coop<64> (four reads a block)  256 / 4 x 3 KB
@@ -38,21 +41,21 @@
 //    3  CM_L_HIT_SLAB         reads with more hits                   k_s3b_coop<1024, false>, use_slab    global slab (19 B per hit)
 //    5  CM_L_HIT_DECLINED     reads k_s3b_coop declined              k_s3b_heavy<CM_BLOCK> (bitonic)      pow2(hv_big) x 10 B
 //   16  CM_L_HIT_SERIAL       reads the slab launch declined         k_s3b_serial (a lane)                --
-//   23  CM_L_SEARCH_WAVE      reads whose mate has >= 24 candidates  k_s4a/4b_rescue_wave<true> (64)      64 windows / 4.9 KB
+//   23  CM_L_SEARCH_WAVE      reads whose mate has >= CM_RS_WAVE candidates  k_s4a/4b_rescue_wave<true> (64)  64 windows / 4.9 KB
 //   31  CM_L_SEARCH_WAVE_BIG  ... with more than 64 best candidates  k_s4a/4b_rescue_wave<false> (64)     304 windows / 11 KB
-//    6  CM_L_RS_WAVE          reads, rescue hits <= hv_max[0]        k_s4b_coop<64> (two reads a block)   512 / 2 x 11 KB
+//    6  CM_L_RS_WAVE          reads, rescue hits <= hv_max[0]        k_s4b_coop<64> (two reads a block)   512 / 2 x 11 KB (more than CM_RS_COOP_MIN hits)
 //  7/8  CM_L_RS_B256A / B     reads, rescue hits <= hv_max[1] / [2]  k_s4b_coop<256>                      1024 / 21 KB, 2048 / 41 KB
 //   11  CM_L_RS_B512          reads, rescue hits <= rs_max3 (3968)   k_s4b_coop<512>                      3968 / 79 KB
-//   26  CM_L_RS_B1024         reads, rescue hits <= rs_big (7680)    k_s4b_coop<1024>                     7680 / 153 KB
+//   26  CM_L_RS_B1024         reads, rescue hits <= rs_big (CM_S4B_PMAX)  k_s4b_coop<1024>                7680 / 153 KB
 //   15  CM_L_RS_SLAB          reads with more rescue hits            k_s4b_coop<1024>, use_slab           global slab
-//   27  CM_L_PF_WAVE          pairs, candidate lists <= 256          k_s4c_coop<64, true>                 CM_S4C_P_SMALL
+//   27  CM_L_PF_WAVE          pairs, candidate lists <= 256          k_s4c_coop<64, true>                 CM_S4C_P_SMALL (more than CM_S4C_COOP_MIN entries)
 //    9  CM_L_PF_BLOCK         pairs, lists <= 1024                   k_s4c_coop<256, true>                CM_S4C_P_WAVE
 //   14  CM_L_PF_BLOCK_BIG     pairs, lists <= 4096                   k_s4c_coop<256, true>                CM_S4C_P_BLOCK
-//   19  CM_L_PF_HUGE          pairs, lists <= s4c_pbig (15360)       k_s4c_coop<1024, false>              lists stay in global memory, 10 B per entry
-//   28  CM_L_S5_SMALL         reads, candidates <= CM_S5C_P_SMALL    k_s5_sort_coop, k_s5c_coop<64>       a quarter of the wave class's arrays
+//   19  CM_L_PF_HUGE          pairs, lists <= s4c_pbig (CM_S4C_P_BIG) k_s4c_coop<1024, false>             lists stay in global memory, 10 B per entry
+//   28  CM_L_S5_SMALL         reads, candidates <= CM_S5C_P_SMALL    k_s5_sort_coop, k_s5c_coop<64>       a quarter of the wave class's arrays (more than CM_S5C_COOP_MIN candidates)
 //   12  CM_L_S5_WAVE          reads, candidates <= CM_S5C_P_WAVE     k_s5_sort_coop, k_s5c_coop<64>       CM_S5C_P_WAVE
-//   22  CM_L_S5_BLOCK         reads with more candidates             k_s5_sort_coop, k_s5c_coop<256>      16384
-//   29  CM_L_S6A_SMALL        pairs, draft mappings <= 256           k_s6a_coop<64>                       CM_S6A_P_SMALL
+//   22  CM_L_S5_BLOCK         reads with more candidates             k_s5_sort_coop, k_s5c_coop<256>      s5c_pblock (CM_S5C_P_BLOCK)
+//   29  CM_L_S6A_SMALL        pairs, draft mappings <= 256           k_s6a_coop<64>                       CM_S6A_P_SMALL (more than CM_S6A_COOP_MIN mappings)
 //   13  CM_L_S6A_WAVE         pairs, draft mappings <= 1024          k_s6a_coop<64>                       CM_S6A_P_WAVE
 //   18  CM_L_S6A_BLOCK        pairs with more                        k_s6a_coop<256>                      CM_S6A_P_BLOCK
 //   30 / 17 / 20  CM_L_S6C_SMALL / WAVE / BLOCK   multi-mapped pairs, the same classes   k_s6c_coop<64> / <64> / <256>
@@ -66,6 +69,7 @@ enum CmList : uint32_t {
   CM_L_SEARCH_WAVE_BIG = 31
 };
 #define CM_HV_LISTS 32
+#define CM_L_NONE CM_HV_LISTS   // what a class function (cm_classes.h) answers for a list that stays with its lane
 #define CM_RS_SEGS 64           // rescue list segments (one counter each, on its own cache line)
 #define CM_MAX_BEST 8192        // upper bound on max_num_best_mappings (-n): a 500 000-pair batch then has 2^32 record slots, which are addressed with 32 bits
 #define CM_SORT_SERIAL_MAX 24   // cm_sort_cand / cm_sort_draft: insertion sort up to here, heap sort beyond
@@ -169,10 +173,7 @@ struct CmDev {
   uint8_t *hcnt;        // candidate counts (same indexing as hbuf)
   uint32_t *n_pos_hit;  // [2n] boundary P between + and - sub-lists
   uint32_t *ncp, *ncn;  // [2n] candidates after GenerateCandidates
-  // ---- reads whose hit list does not fit a lane's LDS slots, by size class (k_s3a_count fills, k_s3b_heavy consumes):
-  //      hv_cnt[c] reads of class c listed at hv_list + c * hv_stride; class 0: <= hv_max[0] hits (a wave each),
-  //      1: <= hv_max[1] (a block each), 2: <= hv_max[2] (a block, large LDS), 3: longer (one lane, in global memory),
-  //      4: <= hv_mid (a group of 16 lanes each, four reads per wave)
+  // ---- the device work lists (the CmList table above): *cm_list_cnt(d, id) items at cm_list(d, id), hv_stride words per list
   const uint32_t *perm_reads, *perm_pairs;  // heavy-last processing order of reads / pairs, or nullptr (identity)
   uint32_t *hv_cnt, *hv_list;
   // reads that supplement their candidates from the mate (S4a/S4b), packed in CM_RS_SEGS list segments:
@@ -185,7 +186,9 @@ struct CmDev {
   // the rescue lists' two largest classes (lists 11 / 26: their entries take 20 bytes of the work area, not 19) -- 0: no such class
   uint32_t hv_big, rs_max3, rs_big;
   unsigned long long cls_mask;  // bit l: the kernels of long-list class (list) l are launched for this range (speculative launch set, cm_kernels.hip)
-  uint32_t s4c_pbig;  // entries of a candidate list the pair filter's largest class takes (k_s4c_coop<1024, false>; 0: no such class)
+  // entries the largest class of the pair filter (k_s4c_coop<1024, false>; 0: no such class) / of verification (k_s5c_coop<CM_BLOCK>) takes:
+  // what the device grants of CM_S4C_P_BIG / CM_S5C_P_BLOCK, resolved once per range (cm_device_classes, cm_kernels.hip)
+  uint32_t s4c_pbig, s5c_pblock;
   uint32_t hv_stride, s3b_cap, hv_max[4];  // hv_max: hit-list size classes -- a wave, a block of 256 / 512 / 1024 lanes (lists 0, 1, 2, 10)
   uint8_t *coop_slab;      // global work memory of the groups that take lists longer than their shared memory holds:
   uint32_t coop_slab_cap;  // coop_slab_blocks slabs of cm_coop_slab_bytes(coop_slab_cap) bytes, one per block of those launches
@@ -254,6 +257,10 @@ struct CmDev {
   uint32_t sam_md_cap;
   unsigned long long *stats; // device counters (see CM_ST_*)
 };
+
+// the items of a device work list and its counter
+CM_HD uint32_t *cm_list(const CmDev &d, uint32_t id) { return d.hv_list + (size_t)id * d.hv_stride; }
+CM_HD uint32_t *cm_list_cnt(const CmDev &d, uint32_t id) { return d.hv_cnt + id; }
 
 #define CM_ST_CAND 0
 #define CM_ST_MAPPINGS 1

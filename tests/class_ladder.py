@@ -65,6 +65,60 @@ SMALL_TIERS = ("lane_50", "lane_100")   # every planned length <= 513: cheap eno
 LARGEST_TIERS = ("pf_15360", "verif_16384")
 HIT_KEY64_TIER = "hits_4k_8k"
 
+# ---- the class model: which list id a length belongs to.  A second statement of the table in cm_types.h, written from its prose and
+# independent of the C code (cm_classes.h): tests/test_class_dispatch_cpu.py holds the C functions to it, tests/test_gpu_class_boundaries.py
+# the items the device put on every list.  `cls`: the classes of a batch (test_hostemu_classes.classes)
+# CmList (cm_types.h)
+(HIT_WAVE, HIT_B256A, HIT_B256B, HIT_SLAB, HIT_G16, HIT_DECLINED, RS_WAVE, RS_B256A, RS_B256B, PF_BLOCK, HIT_B512, RS_B512, S5_WAVE, S6A_WAVE,
+ PF_BLOCK_BIG, RS_SLAB, HIT_SERIAL, S6C_WAVE, S6A_BLOCK, PF_HUGE, S6C_BLOCK, HIT_WAVE_SMALL, S5_BLOCK, SEARCH_WAVE, S6C_MULTI, HIT_B1024,
+ RS_B1024, PF_WAVE, S5_SMALL, S6A_SMALL, S6C_SMALL, SEARCH_WAVE_BIG) = range(32)
+# the constants of the table that cm_size_classes does not compute
+SLAB_CAP = 65535
+COOP_MIN = 48                                   # candidates / draft mappings above which a list goes to a group at all
+RS_COOP_MIN = 32
+PF_P = ((256, PF_WAVE), (1024, PF_BLOCK), (4096, PF_BLOCK_BIG), (15360, PF_HUGE))
+S5_P_SMALL, S5_P_WAVE = 512, 2048
+S6_P = ((256, 0), (1024, 1))                    # index into (small, wave, block)
+S6A_LISTS = (S6A_SMALL, S6A_WAVE, S6A_BLOCK)
+S6C_LISTS = (S6C_SMALL, S6C_WAVE, S6C_BLOCK)
+
+
+def _hit_class(tot, cls):
+    if tot <= cls["s3b_cap"]:
+        return None  # a lane's own slots
+    for bound, lid in ((cls["hv_mid"], HIT_G16), (cls["hv_sub"], HIT_WAVE_SMALL), (cls["hv_max0"], HIT_WAVE), (cls["hv_max1"], HIT_B256A),
+                       (cls["hv_max2"], HIT_B256B), (cls["hv_max3"], HIT_B512), (cls["hv_big"], HIT_B1024)):
+        if tot <= bound:
+            return lid
+    return HIT_SLAB
+
+
+def _rescue_class(big, cls):
+    if big <= RS_COOP_MIN:
+        return None
+    for bound, lid in ((cls["hv_max0"], RS_WAVE), (cls["hv_max1"], RS_B256A), (cls["hv_max2"], RS_B256B), (cls["rs_max3"], RS_B512),
+                       (cls["rs_big"], RS_B1024), (SLAB_CAP, RS_SLAB)):
+        if big <= bound:
+            return lid
+    return None
+
+
+def _pf_class(big):
+    """the pair filter's list of a pair whose longest merged candidate list has `big` entries"""
+    return next((l for p, l in PF_P if big <= p), None) if big > COOP_MIN else None
+
+
+def _s5_class(p_, n_):
+    """verification's list of a read with p_ / n_ filtered candidates on the + / - strand"""
+    if not p_ + n_ > COOP_MIN:
+        return None
+    return S5_SMALL if max(p_, n_) <= S5_P_SMALL else S5_WAVE if max(p_, n_) <= S5_P_WAVE else S5_BLOCK
+
+
+def _s6_class(big, big2):
+    """pairing: index into (small, wave, block) for a pair whose longest list of draft mappings has `big` entries, by read 2's longer list"""
+    return next((x for p, x in S6_P if big2 <= p), 2) if big > COOP_MIN else None
+
 
 def rc(a):
     return COMP[a[::-1]]

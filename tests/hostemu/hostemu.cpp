@@ -1241,19 +1241,44 @@ extern "C" int hostemu_bgzf_resolve(uint8_t *win_io, uint32_t isize, const uint3
 // the size-class policy (cm_classes.h) on plain integers.  opts: heavy_wave_max, heavy_block_max, heavy_big_max, heavy_mid_max,
 // s3b_lane_cap; lane_cap: cm_s3b_lane_cap(max_read_len); hv_max_in / hv_big_in: what cm_s3b_heavy_classes reports.
 // out: hv_max[0..3], hv_big, rs_max3, rs_big, hv_mid, hv_sub, s3b_cap
-extern "C" void hostemu_size_classes(const int *opts, uint32_t max_read_len, uint32_t lane_cap, uint32_t n_seq, int has_goff,
-                                     const uint32_t *hv_max_in, uint32_t hv_big_in, uint32_t *out) {
+static void emu_size_classes(const int *opts, uint32_t max_read_len, uint32_t lane_cap, uint32_t n_seq, int has_goff, const uint32_t *hv_max_in,
+                             uint32_t hv_big_in, CmDev &d) {
   CmClassIn in = {};
   for (int q = 0; q < 3; ++q) in.heavy_max[q] = opts[q];
   in.heavy_mid = opts[3]; in.s3b_cap = opts[4];
   in.max_read_len = max_read_len; in.lane_cap = lane_cap; in.n_seq = n_seq; in.has_goff = has_goff != 0;
   for (int q = 0; q < 4; ++q) in.hv_max[q] = hv_max_in[q];
   in.hv_big = hv_big_in;
-  CmDev d;
   memset(&d, 0xa5, sizeof(d));  // (every class field is written, whatever the struct held)
   cm_size_classes(in, d);
+}
+extern "C" void hostemu_size_classes(const int *opts, uint32_t max_read_len, uint32_t lane_cap, uint32_t n_seq, int has_goff,
+                                     const uint32_t *hv_max_in, uint32_t hv_big_in, uint32_t *out) {
+  CmDev d;
+  emu_size_classes(opts, max_read_len, lane_cap, n_seq, has_goff, hv_max_in, hv_big_in, d);
   for (int q = 0; q < 4; ++q) out[q] = d.hv_max[q];
   out[4] = d.hv_big; out[5] = d.rs_max3; out[6] = d.rs_big; out[7] = d.hv_mid; out[8] = d.hv_sub; out[9] = d.s3b_cap;
+}
+// the class functions of cm_classes.h over those classes: the CmList id (CM_L_NONE = CM_HV_LISTS: none) of a list of length a (and b).
+// which: 0 hit lists (a hits), 1 rescue lists (a: the longer list), 2 pair filter (a: the longest list), 3 verification (a, b: the
+// candidates of the two strands), 4 / 5 pairing with S6a's / S6c's lists (a: the longest of the pair's lists, b: the longer of read 2's).
+// s4c_pbig: the pair filter's largest class as the device grants it; slab_cap: entries of a slab of global memory (0: no slabs)
+extern "C" uint32_t hostemu_class_of(const int *opts, uint32_t max_read_len, uint32_t lane_cap, uint32_t n_seq, int has_goff, const uint32_t *hv_max_in,
+                                     uint32_t hv_big_in, uint32_t s4c_pbig, uint32_t slab_cap, int which, uint32_t a, uint32_t b) {
+  CmDev d;
+  emu_size_classes(opts, max_read_len, lane_cap, n_seq, has_goff, hv_max_in, hv_big_in, d);
+  d.s4c_pbig = s4c_pbig;
+  d.coop_slab = slab_cap ? reinterpret_cast<uint8_t *>(&d) : nullptr;  // (only compared with nullptr)
+  d.coop_slab_cap = slab_cap;
+  switch (which) {
+    case 0: return cm_hit_class(d, a);
+    case 1: return cm_rescue_class(d, a);
+    case 2: return cm_pf_class(d, a);
+    case 3: return cm_s5_class(a, b);
+    case 4: return cm_s6_class(a, b, CM_L_S6A_SMALL, CM_L_S6A_WAVE, CM_L_S6A_BLOCK);
+    case 5: return cm_s6_class(a, b, CM_L_S6C_SMALL, CM_L_S6C_WAVE, CM_L_S6C_BLOCK);
+  }
+  return ~0u;
 }
 
 // ---------------------------------------------------------------------------------------

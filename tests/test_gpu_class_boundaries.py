@@ -16,17 +16,10 @@ from test_hostemu_classes import classes
 
 pytestmark = pytest.mark.gpu
 
-# CmList (cm_types.h)
-(HIT_WAVE, HIT_B256A, HIT_B256B, HIT_SLAB, HIT_G16, HIT_DECLINED, RS_WAVE, RS_B256A, RS_B256B, PF_BLOCK, HIT_B512, RS_B512, S5_WAVE, S6A_WAVE,
- PF_BLOCK_BIG, RS_SLAB, HIT_SERIAL, S6C_WAVE, S6A_BLOCK, PF_HUGE, S6C_BLOCK, HIT_WAVE_SMALL, S5_BLOCK, SEARCH_WAVE, S6C_MULTI, HIT_B1024,
- RS_B1024, PF_WAVE, S5_SMALL, S6A_SMALL, S6C_SMALL, SEARCH_WAVE_BIG) = range(32)
-# the constants of the table that cm_classes.h does not compute
-SLAB_CAP = 65535
-COOP_MIN = 48                                   # candidates / draft mappings above which a list goes to a group at all
-RS_COOP_MIN = 32
-PF_P = ((256, PF_WAVE), (1024, PF_BLOCK), (4096, PF_BLOCK_BIG), (15360, PF_HUGE))
-S5_P_SMALL, S5_P_WAVE = 512, 2048
-S6_P = ((256, 0), (1024, 1))                    # index into (small, wave, block)
+from class_ladder import (COOP_MIN, HIT_B256A, HIT_B256B, HIT_B512, HIT_B1024, HIT_DECLINED, HIT_G16, HIT_SERIAL, HIT_SLAB, HIT_WAVE,  # noqa: E402
+                          HIT_WAVE_SMALL, PF_BLOCK, PF_BLOCK_BIG, PF_HUGE, PF_WAVE, RS_B256A, RS_B256B, RS_B512, RS_B1024, RS_SLAB, RS_WAVE,
+                          S5_BLOCK, S5_SMALL, S5_WAVE, S6A_BLOCK, S6A_LISTS, S6A_SMALL, S6A_WAVE, S6C_BLOCK, S6C_LISTS, S6C_MULTI, S6C_SMALL,
+                          S6C_WAVE, SLAB_CAP, _hit_class, _pf_class, _rescue_class, _s5_class, _s6_class)
 # list ids that cannot have items in these cases, and why
 NEVER = {HIT_DECLINED: "k_s3b_coop declines a read only when a hit's diagonal lies before its sequence's start or its run table overflows: "
                        "the ladder's copies stand clear of the chromosome ends (tests/test_gpu_stages.py has the wrapped diagonal)"}
@@ -86,26 +79,6 @@ def _compare_trace(g, case, label):
                 raise AssertionError("%s pair %d: %s = %d on the device, %d in the oracle (stage: %s)" % (label, i, f, getattr(gt[i], f), trace[i][f], stage))
 
 
-def _hit_class(tot, cls):
-    if tot <= cls["s3b_cap"]:
-        return None  # a lane's own slots
-    for bound, lid in ((cls["hv_mid"], HIT_G16), (cls["hv_sub"], HIT_WAVE_SMALL), (cls["hv_max0"], HIT_WAVE), (cls["hv_max1"], HIT_B256A),
-                       (cls["hv_max2"], HIT_B256B), (cls["hv_max3"], HIT_B512), (cls["hv_big"], HIT_B1024)):
-        if tot <= bound:
-            return lid
-    return HIT_SLAB
-
-
-def _rescue_class(big, cls):
-    if big <= RS_COOP_MIN:
-        return None
-    for bound, lid in ((cls["hv_max0"], RS_WAVE), (cls["hv_max1"], RS_B256A), (cls["hv_max2"], RS_B256B), (cls["rs_max3"], RS_B512),
-                       (cls["rs_big"], RS_B1024), (SLAB_CAP, RS_SLAB)):
-        if big <= bound:
-            return lid
-    return None
-
-
 def _expected_lists(case, arrays, cls):
     """list id -> the planned (pair, array, length) that must have put an item there"""
     out = {}
@@ -129,15 +102,15 @@ def _expected_lists(case, arrays, cls):
             if e["want"] != big or big <= COOP_MIN:
                 continue
             if e["array"][0] == "m":
-                lid = next((l for p, l in PF_P if big <= p), None)
+                lid = _pf_class(big)
                 if lid is not None:
                     out.setdefault(lid, why)
             elif e["array"][0] == "f":
-                out.setdefault(S5_SMALL if big <= S5_P_SMALL else S5_WAVE if big <= S5_P_WAVE else S5_BLOCK, why)
+                out.setdefault(_s5_class(big, 0), why)
             else:
-                q = next((x for p, x in S6_P if big <= p), 2)
-                out.setdefault((S6A_SMALL, S6A_WAVE, S6A_BLOCK)[q], why)
-                out.setdefault((S6C_SMALL, S6C_WAVE, S6C_BLOCK)[q], why)  # cp + cn co-best pairings: a multi-mapped pair
+                q = _s6_class(big, big)
+                out.setdefault(S6A_LISTS[q], why)
+                out.setdefault(S6C_LISTS[q], why)  # cp + cn co-best pairings: a multi-mapped pair
                 out.setdefault(S6C_MULTI, why)
     return out
 
@@ -162,26 +135,25 @@ def _expected_counts(case, arrays, cls):
         m = [int(a["mcp"][i, 0]), int(a["mcn"][i, 0]), int(a["mcp"][i, 1]), int(a["mcn"][i, 1])]
         if m[0] + m[1] == 0 or m[2] + m[3] == 0:
             continue  # a pair one of whose reads has no candidate ends before the pair filter
-        lid = next((l for p, l in PF_P if max(m) <= p), None)
-        if max(m) > COOP_MIN and lid is not None:
+        lid = _pf_class(max(m))
+        if lid is not None:
             out[lid] += 1
         f = [int(a["fcp"][i, 0]), int(a["fcn"][i, 0]), int(a["fcp"][i, 1]), int(a["fcn"][i, 1])]
         if f[0] + f[1] == 0 or f[2] + f[3] == 0:
             continue
         for p_, n_ in ((f[0], f[1]), (f[2], f[3])):
-            if p_ + n_ > COOP_MIN:
-                out[S5_SMALL if max(p_, n_) <= S5_P_SMALL else S5_WAVE if max(p_, n_) <= S5_P_WAVE else S5_BLOCK] += 1
+            if _s5_class(p_, n_) is not None:
+                out[_s5_class(p_, n_)] += 1
         d = [int(a["ndp"][i, 0]), int(a["ndn"][i, 0]), int(a["ndp"][i, 1]), int(a["ndn"][i, 1])]
         if d[0] + d[1] == 0 or d[2] + d[3] == 0:
             continue
-        q = None
-        if max(d) > COOP_MIN:  # the class by read 2's longer list
-            q = next((x for p, x in S6_P if max(d[2], d[3]) <= p), 2)
-            out[(S6A_SMALL, S6A_WAVE, S6A_BLOCK)[q]] += 1
+        q = _s6_class(max(d), max(d[2], d[3]))  # the class by read 2's longer list
+        if q is not None:
+            out[S6A_LISTS[q]] += 1
         if q is not None or arrays["pe_nbest"][i] > 1:
             out[S6C_MULTI] += 1
         if q is not None and arrays["pe_nbest"][i] > 1:
-            out[(S6C_SMALL, S6C_WAVE, S6C_BLOCK)[q]] += 1
+            out[S6C_LISTS[q]] += 1
     return out
 
 
