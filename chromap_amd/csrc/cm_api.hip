@@ -131,6 +131,8 @@ extern "C" int cmgpu_set_option(cmgpu_ctx *c, const char *name, int64_t value) {
     c->opt.coop_rb = (int)value;
   } else if (n == "coop") {  // bit mask of the stages whose long lists go to groups of lanes (cm_coop.h)
     c->opt.coop = (int)value;
+  } else if (n == "s3b_short") {  // 0: lists of at most 16 hits at a lane cap of 16 go through k_s3b_candidates like every other cap's (the A/B of k_s3b_short)
+    c->opt.s3b_short = value ? 1 : 0;
   } else if (n == "generic_kernels") {  // 1: no per-mode kernel instances (cm_stages.h: CmModeAny everywhere) -- the A/B of the paired-end instances
     c->opt.generic_kernels = value ? 1 : 0;
   } else if (n == "item_limit") {  // forces the sub-batch path (tests): largest dense intermediate the pipeline may allocate
@@ -156,6 +158,7 @@ extern "C" int cmgpu_get_option(const cmgpu_ctx *c, const char *name, int64_t *v
   else if (n == "lanes") *value = c->opt.lanes;
   else if (n == "coop") *value = c->opt.coop;
   else if (n == "generic_kernels") *value = c->opt.generic_kernels;
+  else if (n == "s3b_short") *value = c->opt.s3b_short;
   else if (n == "alloc_us") *value = (int64_t)(c->alloc_seconds * 1e6);  // the allocation stage of the last cmgpu_store_format
   else if (n == "alloc_draw_us") *value = (int64_t)(c->alloc_draw_seconds * 1e6);  // measurement: host share of the last allocation (cm_post.hip)
   else if (n.rfind("coop_profile_", 0) == 0) {
@@ -826,6 +829,7 @@ static void cm_bind_dev(cmgpu_ctx *c, CmDev &d, uint32_t lo, uint32_t hi) {
   d.coop_rb = c->opt.coop_rb > 0 ? (uint32_t)c->opt.coop_rb : 0u;
   d.wq_dynamic = ((uint32_t)c->opt.coop >> 16) & 1u;
   d.generic_kernels = c->opt.generic_kernels ? 1u : 0u;
+  d.s3b_short = c->opt.s3b_short ? 1u : 0u;
   if (c->has_rank) {  // stages from verification on address the reference by rank
     d.rid_rank = (const uint32_t *)c->rid_rank.p;
     d.ref_off = (const uint64_t *)c->ref_off_r.p;

@@ -425,6 +425,17 @@ __global__ __launch_bounds__(CM_BLOCK) void k_s3b_candidates(CmDev d, uint32_t n
   if (i < n && d.hit_tot[i] <= cap) cm_s3b_candidates_lds(d, i, sh_h + threadIdx.x, sh_c + threadIdx.x, cap, blockDim.x);
 }
 
+// The short-list instance for cap == 16 (what reads of up to 50 bases get, and every read while the 16-lane groups take the lists
+// beyond -- cm_size_classes; cm_s3b_short, cm_stages.h): the lane's 16 slots are all that stays in
+// LDS (32 KB per block: five blocks per CU), the width of the block is a constant so that a slot's address is a shift, and the list is
+// sorted and clustered in registers.  cmgpu_set_option "s3b_short" 0 sends these reads through k_s3b_candidates instead.
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_s3b_short(CmDev d, uint32_t n) {
+  __shared__ uint64_t sh_h[CM_S3S_CAP * BLOCK];
+  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  if (i < n && d.hit_tot[i] <= CM_S3S_CAP) cm_s3b_short<BLOCK>(d, i, sh_h, threadIdx.x);
+}
+
 // ---------------------------------------------------------------------------------------
 // S3b for long hit lists (reads from repeats: hundreds to thousands of hits).  One lane sorting such a list
 // in its global segment took ~28 ms and held its whole wave for that long (a genome with 2 % of its bases in
@@ -1571,7 +1582,11 @@ __global__ __launch_bounds__(CM_BLOCK) void k_probe_range(const uint64_t *__rest
   if (hi > cap) hi = cap;  // overflow of the dense arrays: the host reruns with larger ones
   uint32_t steps = 0, hit = 0;
   const unsigned long long tile0 = lo + (unsigned long long)blockIdx.x * (U * CM_BLOCK);
-  if (tile0 < hi) cm_probe_lanes<U, PAIR>(bkt, bmask, hash, val, kind, lo, hi, tile0, &steps, &hit);
+  if (tile0 >= hi) {  // a surplus block (block-uniform): its zero partial from one lane, no reduction (k_probe_reduce reads every partial)
+    if (threadIdx.x == 0) block_partials[blockIdx.x] = make_uint2(0u, 0u);
+    return;
+  }
+  cm_probe_lanes<U, PAIR>(bkt, bmask, hash, val, kind, lo, hi, tile0, &steps, &hit);
   cm_probe_account(steps, hit, block_partials);
 }
 
@@ -1952,6 +1967,11 @@ void cm_launch_k_s3b_candidates(const CmDev &d, uint32_t n, uint32_t max_read_le
   if (!n) return;
   const uint32_t cap = d.s3b_cap;  // cm_s3b_lane_cap(max_read_len) unless overridden (cmgpu_set_option "s3b_lane_cap")
   (void)max_read_len;
+  // (the strand travels in bit 63 of the key there: a sequence id needs bit 31 free, as for the group kernels -- cm_size_classes)
+  if (cap == CM_S3S_CAP && d.s3b_short && d.n_seq < 0x80000000u) {
+    hipLaunchKernelGGL(k_s3b_short<CM_BLOCK>, dim3((n + CM_BLOCK - 1) / CM_BLOCK), dim3(CM_BLOCK), 0, s, d, n);
+    return;
+  }
   uint32_t threads = 256;
   while (threads > 64 && (size_t)cap * threads * 9 > 36 * 1024 + 1024) threads >>= 1;
   hipLaunchKernelGGL(k_s3b_candidates, dim3((n + threads - 1) / threads), dim3(threads), (size_t)cap * threads * 9, s, d, n, cap);

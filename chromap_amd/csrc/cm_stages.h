@@ -1359,6 +1359,149 @@ CM_HD void cm_s3b_candidates_lds(const CmDev &d, uint32_t r, uint64_t *lds_h, ui
 CM_HD void cm_s3b_candidates(const CmDev &d, uint32_t r) { cm_s3b_candidates_lds(d, r, nullptr, nullptr, 0, 1); }
 
 // ---------------------------------------------------------------------------------------
+// S3b for reads of at most CM_S3S_CAP hits (the lane cap of reads up to 50 bases, and of every read by default -- cm_size_classes): what cm_s3b_candidates_lds leaves in hbuf / hcnt,
+// n_pos_hit, ncp and ncn, element for element, in a form without data-dependent loops behind the expansion.
+//   expand   as cm_s3b_core, but into consecutive slots of the lane's column of S (slot i of lane t at S[i * BLOCK + t], BLOCK a
+//            compile-time power of two: the index is a shift) with the strand in bit 63 of the key, as k_s3b_heavy keeps it: the
+//            caller sees to sequence ids below 2^31, so the largest key of a - hit is 0xFFFFFFFE'FFFFFFFF and all ones is free to pad with;
+//   sort     the slots go to registers once, unused ones all ones, through Batcher's odd-even merge network: 63 compare-exchanges in
+//            10 layers, no branch, no memory.  The + hits come out first, each strand's in cm_sort_u64's order (bit 63 is equal within
+//            a strand), the padding last;
+//   cluster  ONE sweep over the registers.  cm_sweep_strided runs over each strand's list with an all-ones sentinel behind it.  Its
+//            state is (mcount, equal, best_equal, best_local, prev_hit); a break resets it to (1, 1, 1, x, x) -- exactly the state a
+//            sweep that starts at x begins with.  In the joined list the first - hit follows the last + hit where the sentinel stood:
+//            its high word has bit 31 set, the + hit's does not, so the sequence ids differ and the first break condition holds, as
+//            it did for the sentinel (whose id, all ones, differs from every real one, with or without bit 31).  The candidate that
+//            leaves at that break is therefore the same, and the sweep continues over the - hits from a fresh start's state.  Within a
+//            strand every comparison sees both keys with the same bit 63: ids and whole keys compare equal exactly when they did,
+//            positions are the low words.  Behind the last hit stands the padding (or, with 16 hits, the constant), the - list's sentinel.
+//   store    a candidate goes straight to its slot in the read's global segment, + from hit_off[r], - from hit_off[r] + np, by bit 63
+//            of best_local, which is then cleared.
+// Steps behind the list's end are predicated off (pi <= tot), so a wave runs the 16 unrolled steps once whatever its reads' lengths.
+// ---------------------------------------------------------------------------------------
+#define CM_S3S_CAP 16
+CM_HD void cm_cmpx_u64(uint64_t &a, uint64_t &b) {
+  const bool sw = b < a;
+  const uint64_t lo = sw ? b : a, hi = sw ? a : b;
+  a = lo; b = hi;
+}
+// Batcher's odd-even merge sort of 16 keys (Knuth 5.2.2 M; every index is a constant once the loops are unrolled)
+CM_HD void cm_sort16_network(uint64_t (&a)[CM_S3S_CAP]) {
+#pragma unroll
+  for (int p = 1; p < CM_S3S_CAP; p <<= 1) {
+#pragma unroll
+    for (int k = p; k >= 1; k >>= 1) {
+#pragma unroll
+      for (int j = k % p; j + k < CM_S3S_CAP; j += 2 * k) {
+#pragma unroll
+        for (int i = 0; i < k; ++i) {
+          if (i + j + k < CM_S3S_CAP && (i + j) / (2 * p) == (i + j + k) / (2 * p)) cm_cmpx_u64(a[i + j], a[i + j + k]);
+        }
+      }
+    }
+  }
+}
+// one hit into the lane's next slot, the strand in bit 63
+template <int BLOCK>
+CM_HD void cm_s3b_short_put(uint64_t *col, uint32_t *cnt, uint32_t *np, uint64_t ref_hit, uint32_t ps, int k) {
+  bool same;
+  const uint64_t cp = cm_cand_from_hit(ref_hit, ps, k, &same);
+  col[((*cnt)++) * (uint32_t)BLOCK] = same ? cp : cp | (1ull << 63);
+  *np += same ? 1u : 0u;
+}
+// the lists of a read with 1 .. CM_S3S_CAP hits
+template <int BLOCK>
+CM_HD void cm_s3b_short_lists(const CmDev &d, uint32_t r, uint32_t tot, uint64_t *S, uint32_t t, uint32_t *np_out, uint32_t *ncp_out,
+                              uint32_t *ncn_out) {
+  static_assert(BLOCK > 0 && (BLOCK & (BLOCK - 1)) == 0, "the slot index is a shift");
+  const uint32_t b = d.mm_off[r], n = d.mm_cnt[r];
+  const uint32_t maxf = d.round2[r] ? (uint32_t)d.p.f1 : (uint32_t)d.p.f0;
+  const uint64_t SB = 1ull << 63;
+  uint64_t *col = S + t;
+  uint32_t cnt = 0, np = 0;
+  for (uint32_t i0 = 0; i0 < n; i0 += CM_S3B_GROUP) {  // (the gathers four at a time, as in cm_s3b_core)
+    uint8_t kind[CM_S3B_GROUP];
+    uint64_t val[CM_S3B_GROUP], first[CM_S3B_GROUP];
+    uint32_t ps[CM_S3B_GROUP];
+#pragma unroll
+    for (int q = 0; q < CM_S3B_GROUP; ++q) {
+      const bool in = i0 + q < n;
+      kind[q] = in ? d.pr_kind[b + i0 + q] : (uint8_t)CM_PR_MISS;
+      val[q] = in ? d.pr_val[b + i0 + q] : 0;
+      ps[q] = in ? d.mm_ps[b + i0 + q] : 0;
+    }
+    // a singleton is a run of one whose occurrence is the value itself: one path for both kinds, the first occurrence of every run
+    // without a wait inside the loop, the loop for the second occurrence on only
+    uint32_t len[CM_S3B_GROUP];
+#pragma unroll
+    for (int q = 0; q < CM_S3B_GROUP; ++q) {
+      const uint32_t nocc = (uint32_t)val[q];
+      const bool single = kind[q] == CM_PR_SINGLE;
+      const bool run = kind[q] != CM_PR_MISS && !single && nocc < maxf && nocc > 0;
+      len[q] = single ? 1u : run ? nocc : 0u;
+      first[q] = run ? d.occ[(uint32_t)(val[q] >> 32)] : val[q];
+    }
+#pragma unroll
+    for (int q = 0; q < CM_S3B_GROUP; ++q) {
+      if (len[q] == 0) continue;
+      cm_s3b_short_put<BLOCK>(col, &cnt, &np, first[q], ps[q], d.p.k);
+      const uint64_t *o = d.occ + (uint32_t)(val[q] >> 32);
+      for (uint32_t oi = 1; oi < len[q]; ++oi) cm_s3b_short_put<BLOCK>(col, &cnt, &np, o[oi], ps[q], d.p.k);
+    }
+  }
+  uint64_t a[CM_S3S_CAP];
+#pragma unroll
+  for (int i = 0; i < CM_S3S_CAP; ++i) a[i] = (uint32_t)i < tot ? col[(uint32_t)i * (uint32_t)BLOCK] : ~0ull;
+  cm_sort16_network(a);
+  const bool use_high = d.round2[r] && np > 0 && np < tot;
+  int req = (int)n - (int)d.rep_cnt[r];
+  req = req > 1 ? req : 1;
+  req = req > d.p.min_seeds ? d.p.min_seeds : req;
+  if (use_high) req = d.p.min_seeds;
+  const uint32_t e = (uint32_t)d.p.e;
+  uint64_t *h = d.hbuf + d.hit_off[r];
+  uint8_t *hc = d.hcnt + d.hit_off[r];
+  uint32_t out_p = 0, out_n = 0;
+  int mcount = 1, equal = 1, best_equal = 1;
+  uint64_t prev_hit = a[0], best_local = a[0];
+#pragma unroll
+  for (int pi = 1; pi <= CM_S3S_CAP; ++pi) {
+    if ((uint32_t)pi <= tot) {
+      // (step 16 sees the sentinel; the inner test only keeps the constant index of that dead arm inside the array)
+      const uint64_t x = pi < CM_S3S_CAP ? a[pi < CM_S3S_CAP ? pi : 0] : ~0ull;
+      const bool brk = (uint32_t)(x >> 32) != (uint32_t)(prev_hit >> 32) || (uint32_t)x > (uint32_t)prev_hit + e ||
+                       ((uint32_t)mcount >= n && (uint32_t)x > (uint32_t)best_local + e);
+      if (brk && mcount >= req) {
+        const bool neg = (best_local >> 63) != 0;
+        const uint32_t at = neg ? np + out_n : out_p;
+        h[at] = best_local & ~SB;
+        hc[at] = (uint8_t)best_equal;
+        out_n += neg ? 1u : 0u; out_p += neg ? 0u : 1u;
+      }
+      // cm_sweep_strided's two arms as selects (the lanes of a wave take both anyway)
+      const bool eq_best = x == best_local, eq_prev = x == prev_hit;
+      const int equal1 = eq_best || eq_prev ? equal + 1 : 1;
+      const bool take_prev = !eq_best && eq_prev && equal1 > best_equal;
+      best_equal = brk ? 1 : eq_best ? best_equal + 1 : take_prev ? equal1 : best_equal;
+      best_local = brk ? x : take_prev ? prev_hit : best_local;
+      equal = brk ? 1 : equal1;
+      mcount = brk ? 1 : mcount + 1;
+      prev_hit = x;
+    }
+  }
+  *np_out = np; *ncp_out = out_p; *ncn_out = out_n;
+}
+template <int BLOCK>
+CM_HD void cm_s3b_short(const CmDev &d, uint32_t r, uint64_t *S, uint32_t t) {
+  const uint32_t tot = d.hit_tot[r];
+  uint32_t np = 0, ncp = 0, ncn = 0;
+  if (tot) cm_s3b_short_lists<BLOCK>(d, r, tot, S, t, &np, &ncp, &ncn);
+  d.n_pos_hit[r] = np;
+  d.ncp[r] = ncp;
+  d.ncn[r] = ncn;
+}
+
+// ---------------------------------------------------------------------------------------
 // Mate rescue (Index::GenerateCandidatePositionsFromRepetitiveReadWithMateInfoOnOneStrand,
 // index.cc:351-489).  One function does both the counting pass (out == nullptr) and the
 // fill pass.  strand: 0 = kPositive, 1 = kNegative.  Mate candidates are (mp, mc, mn),
@@ -2119,6 +2262,28 @@ CM_HD void cm_pack_read_planes_any(const CmDev &d, uint32_t r) {
     v[w] = ~cm_brev32(F[0]); v[W + w] = ~cm_brev32(F[1]); v[2 * W + w] = cm_brev32(F[2]);
   }
 }
+// Eight bases (two 4-byte words, a the lower) -> eight bits of each plane, as cm_c2u sees them except that p0 / p1 are not yet cleared
+// where pn is set.  Per byte, as in cm_mmf_pack4: bits 1-2 of a letter Gray-decode to its code (A C G T: 00 01 11 10 -> 0 1 2 3); the
+// byte is one of the eight letters when, the case bit and bits 1-2 aside, it equals 0x41 (A C G) or 0x50 (T).  Each plane's bit sits
+// at bit 0 of its byte; the second word's go to bit 4, and two shift-ors bring the eight of them together.
+CM_HD void cm_pack4_bits(uint32_t w, uint32_t *b0, uint32_t *b1, uint32_t *bn) {
+  const uint32_t x = (w >> 1) & 0x03030303u;
+  const uint32_t code = x ^ ((x >> 1) & 0x01010101u);
+  const uint32_t is_t = (x >> 1) & ~x & 0x01010101u;
+  const uint32_t diff = ((w & 0xD9D9D9D9u) ^ 0x41414141u) ^ (is_t | (is_t << 4));
+  const uint32_t nz = ((diff & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | diff;  // bit 7 of a byte: the byte of diff is not zero
+  *b0 = code & 0x01010101u; *b1 = (code >> 1) & 0x01010101u; *bn = (nz >> 7) & 0x01010101u;
+}
+CM_HD uint32_t cm_fold8(uint32_t u) {  // bits 0 8 16 24 (bases 0-3) and 4 12 20 28 (bases 4-7) -> bits 0..7
+  u |= u >> 7;
+  return (u | (u >> 14)) & 0xFFu;
+}
+CM_HD void cm_pack8_planes(uint32_t a, uint32_t b, uint32_t *p0, uint32_t *p1, uint32_t *pn) {
+  uint32_t a0, a1, an, c0, c1, cn;
+  cm_pack4_bits(a, &a0, &a1, &an);
+  cm_pack4_bits(b, &c0, &c1, &cn);
+  *p0 = cm_fold8(a0 | (c0 << 4)); *p1 = cm_fold8(a1 | (c1 << 4)); *pn = cm_fold8(an | (cn << 4));
+}
 // W words per plane known at compile time: everything in registers -- the reversed planes are the forward words bit-reversed in
 // reverse order, moved down by 32 W - L bits -- and the read's 6 W words leave in 16-byte stores (k_pack_reads: the reads of a
 // wave are neighbours in the batch, so are their planes)
@@ -2141,14 +2306,15 @@ CM_HD void cm_pack_read_planes_w(const CmDev &d, uint32_t r) {
     uint32_t q0 = 0, q1 = 0, qn = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      uint64_t v = sh8 ? (wv[4 * w + k] >> sh8) | (wv[4 * w + k + 1] << (64u - sh8)) : wv[4 * w + k];
-#pragma unroll
-      for (int b = 0; b < 8; ++b, v >>= 8) {
-        const uint32_t j = (uint32_t)(8 * k + b);
-        const uint32_t u = 32u * (uint32_t)w + j < L ? cm_c2u((uint8_t)v) : 4u;
-        q0 |= (u & 1u) << j; q1 |= ((u >> 1) & 1u) << j; qn |= (u >> 2) << j;
-      }
+      const uint64_t v = sh8 ? (wv[4 * w + k] >> sh8) | (wv[4 * w + k + 1] << (64u - sh8)) : wv[4 * w + k];
+      uint32_t p0, p1, pn;
+      cm_pack8_planes((uint32_t)v, (uint32_t)(v >> 32), &p0, &p1, &pn);
+      q0 |= p0 << (8 * k); q1 |= p1 << (8 * k); qn |= pn << (8 * k);
     }
+    // once per word: the bases at and beyond L count as code 4, like those that are no letter -- pn set, p0 and p1 clear
+    const uint32_t left = L > 32u * (uint32_t)w ? L - 32u * (uint32_t)w : 0u;
+    if (left < 32u) qn |= ~0u << left;
+    q0 &= ~qn; q1 &= ~qn;
     o[w] = q0; o[W + w] = q1; o[2 * W + w] = qn;
   }
 #pragma unroll

@@ -207,6 +207,7 @@ struct CmDev {
   uint32_t coop_rb; // tests: run-table size of the cooperative sorters (0: two per minimizer of the longest read)
   uint32_t hv_sub;  // class 21: lists of hv_mid < hits <= hv_sub go to waves with a quarter of the wave class's work area (0: no such class)
   uint32_t generic_kernels;  // cmgpu_set_option "generic_kernels": the S4-S6 kernels' CmModeAny instances whatever the mode (A/B runs, tests)
+  uint32_t s3b_short;  // cmgpu_set_option "s3b_short": lists of at most 16 hits at lane cap 16 go through k_s3b_short (0: k_s3b_candidates, the A/B)
   uint32_t hv_mid;  // class 4: lists of s3b_cap < hits <= hv_mid go to groups of 16 lanes (k_s3b_heavy<16>); 0 = no such class
   // ---- rescue / merged candidates
   uint8_t *aug;         // [2n] augment flag

@@ -101,8 +101,11 @@ int cmgpu_gather_sweep(cmgpu_ctx *ctx, uint64_t n, int repeat, int loads_per_lan
  * "verify_planes" 0/1 (alignments of the verification on bit planes of the reference and the reads instead of their bytes),
  * "long_read_fused" 0/1 (reads longer than 69 bases: trimming + minimizers in one pass instead of count / scan / fill),
  * "generic_kernels" 0/1 (1: paired-end batches without split alignment run the S4-S6 kernels that carry every mode instead of
- * their own instances; tests/test_gpu_mode_instances.py compares the two).
- * Every setting gives the same records (tests/test_gpu_parity.py runs the fuzz data under each). */
+ * their own instances; tests/test_gpu_mode_instances.py compares the two),
+ * "s3b_short" 1/0 (0: hit lists of at most 16 hits at a lane cap of 16 go through the general per-lane kernel, k_s3b_candidates,
+ * instead of the short-list instance k_s3b_short; tests/test_gpu_s3b_short.py compares the two).
+ * Every setting gives the same records (tests/test_gpu_parity.py runs the fuzz data under each; "s3b_short" 1 and 0:
+ * tests/test_gpu_s3b_short.py, on its own data and on one fuzz configuration). */
 int cmgpu_set_option(cmgpu_ctx *ctx, const char *name, int64_t value);
 int cmgpu_get_option(const cmgpu_ctx *ctx, const char *name, int64_t *value);
 
