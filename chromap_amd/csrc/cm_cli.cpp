@@ -86,6 +86,8 @@ struct Run {
   uint64_t num_reads = 0;
   cmgpu_stats st;
   double t_begin = 0, t_read = 0, t_parse = 0, t_map = 0, t_post = 0;
+  double t_compress = 0;       // --output-bgzf: the contexts' compress calls
+  uint64_t bgzf_bytes = 0, bgzf_text_bytes = 0;  // --output-bgzf: bytes written (header blocks and the end-of-file block included) for that many bytes of text
   std::vector<std::string> read_names;  // pairs output needs read-1 names by read_id (host parser only: the device ingest keeps them in HBM)
   HostSam sam;
   cmgpu_ctx *ctx() const { return ctxs[0]; }
@@ -618,14 +620,56 @@ static std::string read_translation_table(const Args &a) {
   gzclose(tf);
   return table;
 }
+// ---- --output-bgzf: what the plain writers append to the output file goes there as BGZF blocks
+// The header lines start the output file: write_to(path) is the library call that writes them.  With --output-bgzf they are rendered
+// into a file of their own beside the output, which goes away again, and become stored BGZF blocks: the output never holds plain text.
+template <class F>
+static void write_header(Run &r, F write_to) {
+  const std::string &path = r.a.out_path;
+  if (!r.a.output_bgzf) {
+    if (write_to(path.c_str()) != CMGPU_OK) die("Cannot write " + path);
+    return;
+  }
+  const std::string tmp = path + ".header.tmp";
+  if (write_to(tmp.c_str()) != CMGPU_OK) { remove(tmp.c_str()); die("Cannot write " + tmp); }
+  std::string text;
+  FILE *f = fopen(tmp.c_str(), "rb");
+  if (!f) die("Cannot read " + tmp);
+  char buf[1 << 16];
+  for (size_t got; (got = fread(buf, 1, sizeof(buf), f)) > 0;) text.append(buf, got);
+  fclose(f);
+  remove(tmp.c_str());
+  if (cmgpu_bgzf_write_host_text(path.c_str(), text.data(), text.size(), 0) != CMGPU_OK) die("Cannot write " + path);
+  r.bgzf_text_bytes += text.size();
+  r.bgzf_bytes += text.size() + 31 * ((text.size() + 0xff00 - 1) / 0xff00);
+}
+// a context's text store: plain, or compressed on the device
+static void write_section(Run &r, cmgpu_ctx *cx) {
+  const char *path = r.a.out_path.c_str();
+  if (!r.a.output_bgzf) { ck(cx, cmgpu_store_write_text(cx, path, 1)); return; }
+  const double t0 = now_s();
+  uint64_t nb = 0, nout = 0, ntext = 0;
+  ck(cx, cmgpu_store_compress_text(cx, &nb, &nout));
+  r.t_compress += now_s() - t0;
+  ck(cx, cmgpu_bgzf_info(cx, nullptr, nullptr, &ntext));
+  ck(cx, cmgpu_bgzf_write(cx, path, 1));
+  r.bgzf_bytes += nout;
+  r.bgzf_text_bytes += ntext;
+}
+static void bgzf_finish(Run &r) {
+  if (!r.a.output_bgzf) return;
+  if (cmgpu_bgzf_write_eof(r.a.out_path.c_str()) != CMGPU_OK) die("Cannot write " + r.a.out_path);
+  r.bgzf_bytes += 28;
+}
 // ---- the writers: each returns the number of lines written (negative: the file could not be written)
 // sort + duplicate removal + MAPQ filter + SAM lines on the device, from the reads and records in HBM
 static int64_t write_sam_device(Run &r) {
   cmgpu_ctx *ctx = r.ctx();
   uint64_t nl = 0, nbytes = 0;
   ck(ctx, cmgpu_store_format_sam(ctx, r.out_names.data(), r.out_lengths.data(), r.ref.n_sequences, &r.a.p, r.barcoded ? r.bc_len : 0, &nl, &nbytes));
-  if (cmgpu_write_sam_header(r.out_names.data(), r.out_lengths.data(), r.ref.n_sequences, r.a.out_path.c_str()) != CMGPU_OK) die("Cannot write " + r.a.out_path);
-  ck(ctx, cmgpu_store_write_text(ctx, r.a.out_path.c_str(), 1));
+  write_header(r, [&](const char *path) { return cmgpu_write_sam_header(r.out_names.data(), r.out_lengths.data(), r.ref.n_sequences, path); });
+  write_section(r, ctx);
+  bgzf_finish(r);
   return (int64_t)nl;
 }
 // the host writers: sort, duplicate removal and text from the records and reads collected by map_host_ingest
@@ -670,9 +714,11 @@ static int64_t write_pairs(Run &r) {
     for (size_t i = 0; i < r.read_names.size(); ++i) { blob += r.read_names[i]; roff[i + 1] = blob.size(); }
     ck(ctx, cmgpu_store_format_pairs(ctx, r.out_names.data(), r.ref.n_sequences, &r.a.p, blob.data(), roff.data(), (uint32_t)r.read_names.size(), 0, &nl, &nbytes));
   }
-  if (cmgpu_write_pairs_header(r.out_names.data(), r.out_lengths.data(), r.ref.n_sequences, r.pairs_rank.empty() ? nullptr : r.pairs_rank.data(), r.a.out_path.c_str()) != CMGPU_OK)
-    die("Cannot write " + r.a.out_path);
-  ck(ctx, cmgpu_store_write_text(ctx, r.a.out_path.c_str(), 1));
+  write_header(r, [&](const char *path) {
+    return cmgpu_write_pairs_header(r.out_names.data(), r.out_lengths.data(), r.ref.n_sequences, r.pairs_rank.empty() ? nullptr : r.pairs_rank.data(), path);
+  });
+  write_section(r, ctx);
+  bgzf_finish(r);
   return (int64_t)nl;
 }
 // --barcode-translate for BED (BarcodeTranslator, barcode_translator.h:42-101): the table goes to the first context and is copied to the
@@ -720,7 +766,8 @@ static int64_t write_bed(Run &r) {
     }
   }
   // sections in rank order: the owners hold contiguous, increasing chromosome ranges
-  for (cmgpu_ctx *cx : r.ctxs) ck(cx, cmgpu_store_write_text(cx, a.out_path.c_str(), 1));  // (emptied at the start)
+  for (cmgpu_ctx *cx : r.ctxs) write_section(r, cx);  // (emptied at the start)
+  bgzf_finish(r);
   r.t_post = now_s() - t0;
   fprintf(stderr, "Sorted, deduplicated and formatted %llu bytes on the device in %.3fs, wrote them in %.3fs.\n", (unsigned long long)nbytes,
           t1 - t0, now_s() - t1);
@@ -797,6 +844,9 @@ int main(int argc, char **argv) {
   if (r.device_ingest)
     fprintf(stderr, "Mapped all reads in %.2fs (file read + inflate %.2fs, H2D + device FASTQ parse %.2fs, mapping %.2fs, post-processing + write %.2fs).\n",
             now_s() - r.t_begin, r.t_read, r.t_parse, r.t_map, r.t_post);
+  if (a.output_bgzf)
+    fprintf(stderr, "Compressed %llu bytes of text into %llu bytes of BGZF on the device in %.3fs.\n", (unsigned long long)r.bgzf_text_bytes,
+            (unsigned long long)r.bgzf_bytes, r.t_compress);
   for (cmgpu_ctx *cx : r.ctxs) cmgpu_destroy(cx);
   cmgpu_free_host_ref(&r.ref);
   return 0;

@@ -59,6 +59,7 @@ struct Args {
   ReadFormat fmt[3];  // read 1, read 2, barcode
   int k = 17, w = 7, device = 0, gpus = 1;
   bool force_exchange = false;
+  bool output_bgzf = false;  // --output-bgzf: the output file is BGZF blocks, compressed on the device
   uint32_t batch_pairs = 4000000;  // multiple of the reference's 500000-pair read batch
 };
 
@@ -182,6 +183,7 @@ static Args parse(int argc, char **argv) {
     else if (o == "--device") a.device = atoi(need("--device"));
     else if (o == "--gpus") a.gpus = atoi(need("--gpus"));           // one context + host thread per GPU, records exchanged to chromosome owners
     else if (o == "--force-exchange") a.force_exchange = true;      // the multi-GPU code path with one GPU
+    else if (o == "--output-bgzf") a.output_bgzf = true;
     else if (o == "--host-ingest") a.host_ingest = true;   // kseq-style host parser (the fallback for text the device ingest refuses)
     else if (o == "--ingest-chunk-mb") { a.chunk_bytes = (size_t)atol(need("--ingest-chunk-mb")) << 20; a.chunk_given = true; }
     else if (o == "--batch-pairs") a.batch_pairs = (uint32_t)atol(need("--batch-pairs"));
@@ -199,6 +201,9 @@ static Args parse(int argc, char **argv) {
              "                  with -2 as well the output is --pairs (--preset hic)\n"
              "  --barcode-translate FILE  lines to<TAB or ,>from (gzip or plain): BED column 4 and the SAM CB:Z: value are written as the\n"
              "                  table's names; BED is translated on the device, --SAM on the host\n"
+             "  --output-bgzf   the output file as BGZF blocks (bgzip's format, readable by tabix / pairix / samtools), compressed on the\n"
+             "                  device; nothing is inferred from the output file's name.  Not where the host renders the text:\n"
+             "                  --host-ingest --SAM, --SAM --barcode-translate\n"
              "  --summary FILE  per-barcode CSV (one row for bulk data): barcode,total,duplicate,unmapped,lowmapq counted on the device;\n"
              "                  cachehit, fric, estfrip and numcacheslots are written as 0 (the minimizer cache is not modelled)\n");
       exit(0);
@@ -250,6 +255,10 @@ static void validate(Args &a) {
   a.p.dedup_at_bulk_level = barcoded && !a.cell_level_dedup ? 1 : 0;  // remove_pcr_duplicates_at_bulk_level defaults to true (mapping_parameters.h:49)
   if ((a.gpus > 1 || a.force_exchange) && (a.out_pairs || a.out_sam || a.host_ingest))
     die("--gpus > 1 needs BED / TagAlign output and device-side FASTQ ingest (pairs and SAM text is rendered by one context from its own stores)");
+  // the compressor reads the text store in HBM; the host SAM writers render into a file
+  if (a.output_bgzf && a.out_sam && a.host_ingest) die("--output-bgzf with --host-ingest --SAM is outside this build (the host renders that text; compress the file with bgzip)");
+  if (a.output_bgzf && a.out_sam && !a.translate_path.empty())
+    die("--output-bgzf with --SAM --barcode-translate is outside this build (the host renders that text; compress the file with bgzip)");
   // the reference allocates in its in-memory flavour only (chromap.h:1305-1353): with --low-mem or a preset the flag does nothing there and here
   if (a.p.allocate_multi_mappings && !a.p.low_memory_mode) {
     if (a.out_sam) die("--allocate-multi-mappings with --SAM is outside this build (the SAM writers have no allocation stage)");

@@ -212,6 +212,9 @@ struct cmgpu_ctx {
   bool single = false;        // resident batch is single-end
   // device-side record store + rendered text (cm_post.hip)
   DevBuf store, store_bc, text;
+  // the compressed store (cm_bgzf_out.hip): BGZF blocks back to back; the chunk's slots, the groups' tokens, the blocks' sizes, an uploaded text
+  DevBuf bgzf, bgzf_slots, bgzf_tok, bgzf_sizes, bgzf_in;
+  uint64_t bgzf_bytes = 0, bgzf_blocks = 0, bgzf_text_bytes = 0;
   uint64_t store_n = 0, store_cap = 0, text_bytes = 0, text_lines = 0;
   uint64_t alloc_multi = 0, alloc_kept = 0, alloc_without_overlap = 0;  // the last cmgpu_store_format's allocation (cmgpu_store_allocation_info)
   double alloc_seconds = 0, alloc_draw_seconds = 0;                     // the stage's time, and its draw's on the host (cmgpu_get_option alloc_us, alloc_draw_us)
@@ -308,7 +311,7 @@ struct cmgpu_ctx {
             &hit_off, &round2, &rep_cnt, &rep_len, &hbuf, &hcnt, &n_pos_hit, &ncp, &ncn, &aug, &res_neg, &res_pos,
             &resc_n, &resc_p, &m_tot, &m_off, &mbuf, &mcnt, &mcp, &mcn, &force0, &fbuf, &fcnt, &fcp, &fcn, &alive,
             &dpos, &derr, &dsplit, &nv, &v_off, &v_err, &v_end, &ndp, &ndn, &min_err, &second_err, &n_best, &n_second, &pe_min, &pe_second, &pe_nbest,
-            &pe_nsecond, &pe_first, &pe_i1, &pe_i2, &pe_choice, &rec, &rec_ok, &scan_tmp, &stats, &partials, &wl, &pow10_tab, &bcb, &bcq, &bco, &bc_key, &bc_ok, &wl_num, &bt_tab, &bt_blob, &store, &store_bc, &text, &sam_rec, &sam_cigar, &sam_md, &sam_z, &part_cnt, &mm_cursor, &mm_marks, &rid_rank, &ref_off_r, &ref_len_r, &pairs_rank,
+            &pe_nsecond, &pe_first, &pe_i1, &pe_i2, &pe_choice, &rec, &rec_ok, &scan_tmp, &stats, &partials, &wl, &pow10_tab, &bcb, &bcq, &bco, &bc_key, &bc_ok, &wl_num, &bt_tab, &bt_blob, &store, &store_bc, &text, &bgzf, &bgzf_slots, &bgzf_tok, &bgzf_sizes, &bgzf_in, &sam_rec, &sam_cigar, &sam_md, &sam_z, &part_cnt, &mm_cursor, &mm_marks, &rid_rank, &ref_off_r, &ref_len_r, &pairs_rank,
             &ex.owner, &ex.send, &ex.counts, &ex.stage, &rec_dense, &rec_dense_b, &maxlen_dev, &bkt_fast, &ref_planes, &read_planes, &mm_stage, &coop_prof, &rs_pool, &rs_pool_off, &goff, &coop_slab, &hv_cnt, &hv_list, &perm_reads, &perm_pairs, &hv_tmp, &srt_cnt, &srt_list, &rs_list, &rs_cnt};
   }
 };
@@ -366,6 +369,9 @@ int cm_ensure_slot_scratch(cmgpu_ctx *c, uint64_t slots);
 int cm_compact_records(cmgpu_ctx *c, void *dst, uint64_t *bc_dst, uint64_t cap, hipStream_t s, const uint32_t **n_valid_dev);
 // cm_post.hip: n 32-byte {record, barcode} entries -> the store's record / barcode arrays at position store_n
 void cm_store_split_bc(cmgpu_ctx *c, const void *in32, uint64_t n, hipStream_t s);
+// cm_post.hip: n_bytes at `dev` to a file (append != 0: behind what it holds), copies and writes overlapped in two slabs.  what: the
+// bytes' name for the error message
+int cm_write_device_bytes(cmgpu_ctx *c, const void *dev, uint64_t n_bytes, const char *path, int append, const char *what);
 // cm_ingest.hip: b with room for `need` bytes, its first `used` bytes preserved (geometric growth from `first` bytes; the copy runs on s and
 // is waited for).  what: the store's name for the CMGPU_ENOMEM message
 int cm_grow_buf(cmgpu_ctx *c, DevBuf &b, uint64_t used, uint64_t need, uint64_t first, hipStream_t s, const char *what);

@@ -1149,15 +1149,13 @@ extern "C" int cmgpu_store_text(cmgpu_ctx *c, char *out, uint64_t capacity) {
 //  and more to free, and copies and writes took turns.  Now two ordinary 16 MiB slabs: the runtime's own staging buffers bring a copy into
 //  pageable memory at ~25 GB/s, and a second thread writes one slab while the next is being copied.  Several writing threads gain nothing:
 //  buffered writes to one file are serialised by the kernel -- tools/probes/write_probe.cpp, 1 / 4 / 16 threads 25 / 25 / 32 ms per 256 MB)
-extern "C" int cmgpu_store_write_text(cmgpu_ctx *c, const char *path, int append) {
-  if (!c || !path) return CMGPU_EINVAL;
-  CM_HIPCHECK(c, cm_enter(c));
+int cm_write_device_bytes(cmgpu_ctx *c, const void *dev, uint64_t n_bytes, const char *path, int append, const char *what) {
   FILE *f = fopen(path, append ? "ab" : "wb");
   if (!f) { cm_set_error(c, std::string("cannot open ") + path); return CMGPU_EIO; }
   const size_t slab = 16u << 20;
-  const uint64_t n_slabs = (c->text_bytes + slab - 1) / slab;
+  const uint64_t n_slabs = (n_bytes + slab - 1) / slab;
   std::vector<uint8_t> buf[2];
-  for (int k = 0; k < 2 && (uint64_t)k < n_slabs; ++k) buf[k].resize(n_slabs == 1 ? (size_t)c->text_bytes : slab);
+  for (int k = 0; k < 2 && (uint64_t)k < n_slabs; ++k) buf[k].resize(n_slabs == 1 ? (size_t)n_bytes : slab);
   // slab i is copied into buf[i & 1] once slab i - 2 has been written out of it
   std::mutex mu;
   std::condition_variable cv;
@@ -1171,7 +1169,7 @@ extern "C" int cmgpu_store_write_text(cmgpu_ctx *c, const char *path, int append
         if (!ok) return;
       }
       const uint64_t o = i * slab;
-      const size_t m = c->text_bytes - o < slab ? (size_t)(c->text_bytes - o) : slab;
+      const size_t m = n_bytes - o < slab ? (size_t)(n_bytes - o) : slab;
       const bool w = fwrite(buf[i & 1].data(), 1, m, f) == m;
       std::lock_guard<std::mutex> lk(mu);
       if (!w) ok = false;
@@ -1188,8 +1186,8 @@ extern "C" int cmgpu_store_write_text(cmgpu_ctx *c, const char *path, int append
       if (!ok) break;
     }
     const uint64_t o = i * slab;
-    const size_t m = c->text_bytes - o < slab ? (size_t)(c->text_bytes - o) : slab;
-    const bool cp = hipMemcpy(buf[i & 1].data(), (const uint8_t *)c->text.p + o, m, hipMemcpyDeviceToHost) == hipSuccess;
+    const size_t m = n_bytes - o < slab ? (size_t)(n_bytes - o) : slab;
+    const bool cp = hipMemcpy(buf[i & 1].data(), (const uint8_t *)dev + o, m, hipMemcpyDeviceToHost) == hipSuccess;
     std::lock_guard<std::mutex> lk(mu);
     if (!cp) { ok = false; copy_failed = true; }
     else copied = i + 1;
@@ -1198,9 +1196,14 @@ extern "C" int cmgpu_store_write_text(cmgpu_ctx *c, const char *path, int append
   }
   writer.join();
   ok = fclose(f) == 0 && ok;
-  if (copy_failed) { (void)hipGetLastError(); cm_set_error(c, "copying the rendered text from the device failed"); return CMGPU_EHIP; }
+  if (copy_failed) { (void)hipGetLastError(); cm_set_error(c, std::string("copying ") + what + " from the device failed"); return CMGPU_EHIP; }
   if (!ok) { cm_set_error(c, std::string("short write to ") + path); return CMGPU_EIO; }
   return CMGPU_OK;
+}
+extern "C" int cmgpu_store_write_text(cmgpu_ctx *c, const char *path, int append) {
+  if (!c || !path) return CMGPU_EINVAL;
+  CM_HIPCHECK(c, cm_enter(c));
+  return cm_write_device_bytes(c, c->text.p, c->text_bytes, path, append, "the rendered text");
 }
 
 extern "C" int cmgpu_store_info(const cmgpu_ctx *c, uint64_t *n_records, uint64_t *text_bytes, uint64_t *text_lines) {

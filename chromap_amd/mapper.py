@@ -61,6 +61,19 @@ def read_fastx(path):
     return bases, off, names
 
 
+def bgzf_write_host_text(path, text, append=False):
+    """small host text (header lines) as stored BGZF blocks built on the host"""
+    text = bytes(text)
+    if _capi.lib().cmgpu_bgzf_write_host_text(path.encode(), text, len(text), int(append)) != 0:
+        raise ChromapError("cannot write " + path)
+
+
+def bgzf_write_eof(path):
+    """appends the 28-byte empty block that ends a BGZF file"""
+    if _capi.lib().cmgpu_bgzf_write_eof(path.encode()) != 0:
+        raise ChromapError("cannot write " + path)
+
+
 def read_fastq_pairs(path1, path2):
     b1, o1, _ = read_fastx(path1)
     b2, o2, _ = read_fastx(path2)
@@ -660,6 +673,37 @@ class ChromapGPU:
 
     def store_write_text(self, path, append=False):
         self._check(self.L.cmgpu_store_write_text(self.ctx, path.encode(), int(append)), self.ctx)
+
+    # ---- BGZF output compressed on the device (include/chromap_amd.h; chromap_amd/csrc/cm_deflate.h)
+    def bgzf_compress(self, data):
+        """`data` (bytes) as BGZF blocks, one per 0xff00 bytes, without the end-of-file block; they stay in the compressed store too"""
+        data = bytes(data)
+        nb, no = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.cmgpu_bgzf_compress(self.ctx, data, len(data), 0, C.byref(nb), C.byref(no)), self.ctx)
+        return self.store_bgzf()
+
+    def store_compress_text(self):
+        """the text store (store_format*) into the compressed store; the text stays readable.  Returns (blocks, bytes)"""
+        nb, no = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.cmgpu_store_compress_text(self.ctx, C.byref(nb), C.byref(no)), self.ctx)
+        return int(nb.value), int(no.value)
+
+    def bgzf_info(self):
+        """(blocks, bytes, text bytes) of the compressed store"""
+        nb, no, nt = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.cmgpu_bgzf_info(self.ctx, C.byref(nb), C.byref(no), C.byref(nt)), self.ctx)
+        return int(nb.value), int(no.value), int(nt.value)
+
+    def store_bgzf(self):
+        """the compressed store's blocks"""
+        n = self.bgzf_info()[1]
+        buf = C.create_string_buffer(max(1, n))
+        self._check(self.L.cmgpu_bgzf_download(self.ctx, buf, n), self.ctx)
+        return buf.raw[:n]
+
+    def store_write_bgzf(self, path, append=False):
+        """the compressed store's blocks to a file, without the end-of-file block (bgzf_write_eof, once, last)"""
+        self._check(self.L.cmgpu_bgzf_write(self.ctx, path.encode(), int(append)), self.ctx)
 
     # ---- --summary: per-barcode TOTAL / DUP / LOWMAPQ / MAPPED counted on the device (include/chromap_amd.h)
     def summary_enable(self, on=True):

@@ -560,6 +560,26 @@ int cmgpu_write_pairs_header(const char *const *names, const uint32_t *lengths, 
 int cmgpu_store_text(cmgpu_ctx *ctx, char *out, uint64_t capacity);
 int cmgpu_store_write_text(cmgpu_ctx *ctx, const char *path, int append);
 int cmgpu_store_info(const cmgpu_ctx *ctx, uint64_t *n_records, uint64_t *text_bytes, uint64_t *text_lines);
+/* ---- BGZF output compressed on the device (cm_deflate.h, cm_bgzf_out.hip) -------------------
+ * The reference writes plain text and leaves the compression to bgzip; here the rendered text becomes BGZF blocks (SAM spec 4.1) in
+ * HBM: block i holds the text bytes [i * 0xff00, (i + 1) * 0xff00) as one dynamic-Huffman DEFLATE block, or a stored one where that
+ * would not be smaller.  The blocks are a function of the text alone.  They land in the context's compressed store, which the next
+ * compression replaces.
+ *   cmgpu_bgzf_compress         n_bytes at `text` (on_device != 0: a device pointer); n_bytes == 0: no block
+ *   cmgpu_store_compress_text   the text store left by cmgpu_store_format*; the text store stays as it is
+ *   cmgpu_bgzf_info             blocks and bytes of the compressed store, and the text bytes they hold
+ *   cmgpu_bgzf_download         the blocks to the host (capacity >= the store's bytes, else CMGPU_ECAPACITY)
+ *   cmgpu_bgzf_write            the blocks to a file (append != 0: behind what it holds), WITHOUT the end-of-file block: the
+ *                               sections of several contexts, or header lines and a context's text, follow each other in one file
+ *   cmgpu_bgzf_write_host_text  n bytes of host text (the @SQ lines, the pairs header) as stored BGZF blocks built on the host
+ *   cmgpu_bgzf_write_eof        appends the 28-byte empty block that ends a BGZF file: once, last */
+int cmgpu_bgzf_compress(cmgpu_ctx *ctx, const void *text, uint64_t n_bytes, int on_device, uint64_t *n_blocks, uint64_t *n_out);
+int cmgpu_store_compress_text(cmgpu_ctx *ctx, uint64_t *n_blocks, uint64_t *n_out);
+int cmgpu_bgzf_info(const cmgpu_ctx *ctx, uint64_t *n_blocks, uint64_t *n_bytes, uint64_t *n_text_bytes);
+int cmgpu_bgzf_download(cmgpu_ctx *ctx, void *out, uint64_t capacity);
+int cmgpu_bgzf_write(cmgpu_ctx *ctx, const char *path, int append);
+int cmgpu_bgzf_write_host_text(const char *path, const void *text, uint64_t n, int append);
+int cmgpu_bgzf_write_eof(const char *path);
 /* --allocate-multi-mappings (MappingProcessor::AllocateMultiMappings, src/mapping_processor.h:319-440): with
  * params->allocate_multi_mappings and without low_memory_mode, cmgpu_store_format gives every read whose surviving records have
  * MAPQ < 4 to one of them, drawn with probability proportional to the uni-mappings (MAPQ >= 4) within

@@ -10,6 +10,9 @@ alignment records kept in HBM, text rendered there) and through the host parser 
 `--barcodes N`: a single-cell job -- a whitelist of N random 16-mers, every pair draws one, 10 % of them with one substitution (the
 generator of tools/ref_baseline.py); `--summary` then times the same job without and with `--summary FILE`, `--reps` runs each, and
 `--baseline-cli` the build of an earlier commit on the same files (without `--summary`; with `--gz` on the BGZF files too).
+`--output-bgzf` (with `--preset hic` or `--sam`): the job plain, the job with `--output-bgzf` (BGZF blocks compressed on the device), and what
+a user does without the flag -- the plain run followed by tools/bgzf.py on its output (zlib level 1, 16 threads); `--reps` runs each, whole-process
+wall time, output sizes, and the compressed file inflated and compared with the plain one.  `--baseline-cli`: the plain job with that build too.
 Prints one JSON object; everything is written under --dir (default /tmp/chromap_amd_e2e)."""
 import argparse
 import ctypes as C
@@ -77,6 +80,7 @@ def main():
     ap.add_argument("--sam", action="store_true", help="time --preset chip --SAM through the device route and the host route (and --baseline-cli)")
     ap.add_argument("--barcodes", type=int, default=0, help="--preset atac: a single-cell job with a whitelist of this many 16-mers (scATAC: 737280)")
     ap.add_argument("--summary", action="store_true", help="--preset atac: also time the job with --summary FILE (and --baseline-cli without it)")
+    ap.add_argument("--output-bgzf", action="store_true", help="--preset hic / --sam: time the job plain, with --output-bgzf, and plain + tools/bgzf.py of the output")
     ap.add_argument("--skip-host-ingest", action="store_true", help="a long job: leave the host parser's run out")
     args = ap.parse_args()
     os.makedirs(args.dir, exist_ok=True)
@@ -118,7 +122,7 @@ def main():
     res = {}
     job = write_barcodes(args.dir, args.pairs, args.barcodes) if args.barcodes else []
 
-    def run(label, f1, f2, extra=(), reps=args.reps, cli=cli):
+    def run(label, f1, f2, extra=(), reps=args.reps, cli=cli, after=None):
         """the CLI `reps` times; the run with the shortest 'Mapped all reads' time is the one reported"""
         best = None
         times = []
@@ -132,8 +136,10 @@ def main():
             os.sync()
             t0 = time.time()
             p = subprocess.run([cli, "--preset", args.preset, "-x", idx, "-r", fa, "-1", f1, "-2", f2, "-o", out] + fmt + job + list(extra), stderr=subprocess.PIPE, check=True)
+            if after:  # (what follows the run belongs to the job's wall time)
+                after()
             dt = time.time() - t0
-            tail = [ln for ln in p.stderr.decode().splitlines() if ln.startswith("Mapped all reads") or ln.startswith("Sorted,")]
+            tail = [ln for ln in p.stderr.decode().splitlines() if ln.startswith("Mapped all reads") or ln.startswith("Sorted,") or ln.startswith("Compressed ")]
             mapped = [float(ln.split("in ")[1].split("s")[0]) for ln in tail if ln.startswith("Mapped all reads")]
             mapped = mapped[0] if mapped else None
             times.append(mapped)
@@ -150,6 +156,34 @@ def main():
         res[label] = best
 
     run("device_ingest", r1, r2)
+    if args.output_bgzf and two_routes:
+        import gzip
+        import hashlib
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import bgzf
+
+        def md5_inflated(path):
+            h = hashlib.md5()
+            with gzip.open(path, "rb") as f:
+                for b in iter(lambda: f.read(1 << 24), b""):
+                    h.update(b)
+            return h.hexdigest()
+        run("device_ingest_output_bgzf", r1, r2, ["--output-bgzf"])
+        res["device_ingest_output_bgzf"]["inflates_to_plain_output"] = md5_inflated(out) == res["device_ingest"]["bed_md5"]
+        run("device_ingest_then_bgzf_py", r1, r2, after=lambda: bgzf.compress_file(out, out + ".bgz", level=1, threads=16))
+        res["device_ingest_then_bgzf_py"]["bgzf_py_bytes"] = os.path.getsize(out + ".bgz")
+        os.remove(out + ".bgz")
+        if args.baseline_cli:
+            run("baseline_cli", r1, r2, cli=args.baseline_cli)
+        dev, host = res["device_ingest_output_bgzf"], res["device_ingest_then_bgzf_py"]
+        res["output_bgzf"] = {"plain_bytes": res["device_ingest"]["bed_bytes"], "device_bgzf_bytes": dev["bed_bytes"], "bgzf_py_bytes": host["bgzf_py_bytes"],
+                              "device_over_bgzf_py_bytes": round(dev["bed_bytes"] / host["bgzf_py_bytes"], 4),
+                              "wall_s_plain": res["device_ingest"]["wall_s_runs"], "wall_s_output_bgzf": dev["wall_s_runs"],
+                              "wall_s_plain_then_bgzf_py": host["wall_s_runs"]}
+        res["config"] = {"preset": args.preset, "sam": args.sam, "pairs": args.pairs, "readlen": args.readlen, "genome": args.genome, "reps": args.reps,
+                         "hardware_threads": os.cpu_count(), "cpu_budget": cpu_budget()}
+        print(json.dumps(res))
+        return
     if args.summary and not two_routes:
         sm = os.path.join(args.dir, "out.summary.csv")
         run("device_ingest_summary", r1, r2, ["--summary", sm])
