@@ -131,6 +131,8 @@ extern "C" int cmgpu_set_option(cmgpu_ctx *c, const char *name, int64_t value) {
     c->opt.coop_rb = (int)value;
   } else if (n == "coop") {  // bit mask of the stages whose long lists go to groups of lanes (cm_coop.h)
     c->opt.coop = (int)value;
+  } else if (n == "pack_once") {  // 0: k_prep_mm converts the reads' bytes in the trim and again in the minimizer pass, and k_pack_reads packs S5's planes (the A/B of the planes route)
+    c->opt.pack_once = value ? 1 : 0;
   } else if (n == "s3b_short") {  // 0: lists of at most 16 hits at a lane cap of 16 go through k_s3b_candidates like every other cap's (the A/B of k_s3b_short)
     c->opt.s3b_short = value ? 1 : 0;
   } else if (n == "generic_kernels") {  // 1: no per-mode kernel instances (cm_stages.h: CmModeAny everywhere) -- the A/B of the paired-end instances
@@ -159,6 +161,7 @@ extern "C" int cmgpu_get_option(const cmgpu_ctx *c, const char *name, int64_t *v
   else if (n == "coop") *value = c->opt.coop;
   else if (n == "generic_kernels") *value = c->opt.generic_kernels;
   else if (n == "s3b_short") *value = c->opt.s3b_short;
+  else if (n == "pack_once") *value = c->opt.pack_once;
   else if (n == "alloc_us") *value = (int64_t)(c->alloc_seconds * 1e6);  // the allocation stage of the last cmgpu_store_format
   else if (n == "alloc_draw_us") *value = (int64_t)(c->alloc_draw_seconds * 1e6);  // measurement: host share of the last allocation (cm_post.hip)
   else if (n.rfind("coop_profile_", 0) == 0) {
@@ -882,6 +885,7 @@ struct RangeRun {
   unsigned long long hits_total = 0;
   uint32_t n_hits = 0;
   bool planes = false;                  // S5b aligns on bit planes (the range's reads are packed)
+  bool planes_in_prep = false;          // ... by k_prep_mm's planes instance, on the mapping stream: no k_pack_reads, no event
   bool spec = false;                    // the candidate arrays keep the previous batch's size (nothing waited for)
   uint32_t n_m = 0;                     // capacity of the candidate arrays
   void bind() { cm_bind_dev(c, d, rlo, rhi); }  // after every buffer that may have moved
@@ -935,12 +939,20 @@ static int mm_fill_and_probe(RangeRun &r, const MmChunks &k, uint32_t mm_cap, Fi
   cm_launch_k_probe_reduce(c->partials.p, k.part_off[k.n_chunks], r.d.stats + CM_ST_PROBE_STEPS, r.s);
   return CMGPU_OK;
 }
+static bool range_wants_planes(const cmgpu_ctx *c) { return c->ref_pl_words != 0 && c->opt.planes; }  // (verify_planes 0 keeps the planes for the children but does not use them: no packed reads either)
+static size_t read_planes_bytes(const cmgpu_ctx *c, uint32_t n2) { return (size_t)n2 * cm_read_pl_stride((c->max_read_len + 31) / 32) * 4 + 16; }
 // S0 + S1 + S2 fused: one pass of the minimizer state machine, block-level reservation of the dense arrays.  A chunk's minimizers
 // are the cursor range its launch covered (copied to mm_marks on the device)
 static int stage_minimizers_fused(RangeRun &r, bool flat) {
   cmgpu_ctx *c = r.c; CmDev &d = r.d; hipStream_t s = r.s;
   const uint32_t n = r.n, n2 = r.n2;
   int rc;
+  // reads of at most 64 bases: k_prep_mm converts each read once and leaves S5's planes too (a second attempt writes them again)
+  const bool pl = !flat && c->opt.pack_once && cm_prep_mm_planes_supported(d, c->max_read_len);
+  if (pl && range_wants_planes(c) && !c->read_planes.ensure(read_planes_bytes(c, n2))) {  // (no room: k_pack_reads' turn to find that out)
+    d.read_pl = (uint32_t *)c->read_planes.p; d.read_pl_w = (c->max_read_len + 31) / 32;
+    r.planes_in_prep = true;
+  }
   uint64_t cap = (uint64_t)n2 * (c->max_read_len / 4 + 3);
   const uint64_t bound = (uint64_t)c->bases0 + c->bases1 + 1;  // one emission per k-mer position at most
   if (cap > bound) cap = bound;
@@ -975,7 +987,7 @@ static int stage_minimizers_fused(RangeRun &r, bool flat) {
     unsigned long long *cursor = (unsigned long long *)c->mm_cursor.p, *marks = (unsigned long long *)c->mm_marks.p;
     rc = mm_fill_and_probe(r, k, (uint32_t)cap, [&](uint32_t ch) {
       if (flat) cm_launch_k_prep_flat(d, k.lo[ch], k.lo[ch + 1], c->max_read_len, (uint32_t)c->opt.prep_tile_reads, (uint32_t)cap, cursor, s);
-      else cm_launch_k_prep_mm(d, k.lo[ch], k.lo[ch + 1], c->max_read_len, (uint32_t)cap, cursor, s, c->mm_stage.p);
+      else cm_launch_k_prep_mm(d, k.lo[ch], k.lo[ch + 1], c->max_read_len, (uint32_t)cap, cursor, s, c->mm_stage.p, pl);
       cm_launch_k_copy_u64(cursor, marks + ch + 1, s);
     });
     if (rc) return rc;
@@ -1038,8 +1050,9 @@ static int stage_minimizers_two_pass(RangeRun &r) {
 // S4 -- the trimmed lengths are final
 static int stage_pack_reads(RangeRun &r) {
   cmgpu_ctx *c = r.c;
-  r.planes = c->ref_pl_words != 0 && c->opt.planes;  // (verify_planes 0 keeps the planes for the children but does not use them: no packed reads either)
-  if (r.planes && c->read_planes.ensure((size_t)r.n2 * cm_read_pl_stride((c->max_read_len + 31) / 32) * 4 + 16)) r.planes = false;  // (no room: this range on bytes)
+  r.planes = range_wants_planes(c);
+  if (r.planes_in_prep) return CMGPU_OK;  // (the front end has written them, on the mapping stream)
+  if (r.planes && c->read_planes.ensure(read_planes_bytes(c, r.n2))) r.planes = false;  // (no room: this range on bytes)
   if (!r.planes) return CMGPU_OK;
   // on a stream of the highest priority: at the mapping streams' priority the kernel only got the slots three lanes' S3 / S4 kernels
   // left over and S5 waited for it (2 x 150: 4 ms of a 21 ms step once the empty class launches no longer padded S4)
@@ -1158,7 +1171,7 @@ static int stage_s4_rescue_filter(RangeRun &r) {
 static int stage_s5_verify(RangeRun &r) {
   cmgpu_ctx *c = r.c; const CmDev &d = r.d; hipStream_t s = r.s;
   const bool coop = (c->opt.coop & 8) != 0 && !c->p.split;  // (split alignments are verified in S5a already)
-  if (r.planes) CM_HIPCHECK(c, hipStreamWaitEvent(s, c->chunk_ev[0], 0));  // k_pack_reads (its own stream) is done
+  if (r.planes && !r.planes_in_prep) CM_HIPCHECK(c, hipStreamWaitEvent(s, c->chunk_ev[0], 0));  // k_pack_reads (its own stream) is done
   cm_launch_k_s5a_prepare(d, r.n2, s, coop);
   cm_scan_u32(d.nv, d.v_off, r.n2, (uint32_t *)c->scan_tmp.p, s);  // the items' number stays on the device: never above n_m
   mark(c, "s5a_prepare");
@@ -1593,6 +1606,14 @@ extern "C" int cmgpu_debug_array(cmgpu_ctx *c, const char *name, uint32_t *out, 
     if (n_out) *n_out = 64;
     if (capacity < 64 || !c->hv_cnt.p || c->hv_cnt.cap < 256) { cm_set_error(c, "debug array: buffer too small or array not resident"); return CMGPU_ECAPACITY; }
     CM_HIPCHECK(c, hipMemcpy(out, c->hv_cnt.p, 256, hipMemcpyDeviceToHost));
+    return CMGPU_OK;
+  }
+  if (nm == "read_pl") {  // the reads' bit planes of the last range (CmDev::read_pl): cm_read_pl_stride(W) words per read, W from the batch's longest read
+    const uint64_t n = 2ull * c->n_pairs * cm_read_pl_stride((c->max_read_len + 31) / 32);
+    if (n_out) *n_out = n;
+    if (c->last_range_lo != 0 || c->last_range_hi != c->n_pairs) { cm_set_error(c, "the batch was mapped in sub-batches"); return CMGPU_EINVAL; }
+    if (capacity < n || !c->read_planes.p || c->read_planes.cap < n * 4) { cm_set_error(c, "debug array: buffer too small or array not resident"); return CMGPU_ECAPACITY; }
+    CM_HIPCHECK(c, hipMemcpy(out, c->read_planes.p, n * 4, hipMemcpyDeviceToHost));
     return CMGPU_OK;
   }
   struct { const char *n; DevBuf *b; int per_pair; } tab[] = {

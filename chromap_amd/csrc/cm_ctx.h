@@ -149,6 +149,7 @@ struct CmOptions {
   int heavy_max[3] = {0, 0, 0};  // size classes of the cooperative hit-list kernel (0: the kernel's own)
   int heavy_last = 0;          // heavy-last processing order: 0 auto, 1 always, -1 never
   int spec = 1;                // candidate arrays sized from the previous batch (cmgpu_ctx::pred_m_ok); 0: every batch waits for its totals
+  int pack_once = 1;           // reads of at most 64 bases on the fused front end: one conversion to bit planes serves trim, minimizers and S5 (0: three, and k_pack_reads) -- measurement / tests
   int s3b_short = 1;           // 0: the general per-lane hit-list kernel at a lane cap of 16 too (k_s3b_candidates) -- measurement / tests
   int generic_kernels = 0;     // 1: the S4-S6 kernels that carry every mode (CmModeAny) for paired-end batches too -- measurement / tests
   int coop_rb = 0;             // tests: run-table size of the cooperative sorters (0: their own)

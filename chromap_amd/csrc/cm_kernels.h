@@ -17,8 +17,10 @@ void cm_launch_k_prep_flat(const CmDev &d, uint32_t pair_lo, uint32_t pair_hi, u
                            unsigned long long *cursor, hipStream_t s);
 uint32_t cm_prep_mm_pairs_per_block(const CmDev &d, uint32_t max_read_len);
 size_t cm_prep_mm_stage_bytes(const CmDev &d, uint32_t max_read_len, uint32_t pairs);
+bool cm_prep_mm_planes_supported(const CmDev &d, uint32_t max_read_len);
+// planes: the instance that converts every read to bit planes once (cm_prep_mm_planes_supported; it writes d.read_pl when that is set)
 void cm_launch_k_prep_mm(const CmDev &d, uint32_t pair_lo, uint32_t pair_hi, uint32_t max_read_len, uint32_t mm_cap,
-                         unsigned long long *cursor, hipStream_t s, void *gstage);
+                         unsigned long long *cursor, hipStream_t s, void *gstage, bool planes = false);
 uint32_t cm_probe_range_blocks(uint64_t max_entries, int variant);
 void cm_launch_k_probe_range(const CmDev &d, const unsigned long long *range, uint64_t max_entries, uint32_t cap, void *partials, hipStream_t s, int variant);
 void cm_launch_k_probe_reduce(const void *partials, uint32_t blocks, unsigned long long *counters, hipStream_t s);

@@ -97,14 +97,38 @@ __global__ void k_mm_fill(CmDev d, uint32_t pair_lo, uint32_t n_pairs /* end of 
 // E6 (shared-memory staging only): an emission is staged as 32 + 16 bits (hash | position-strand << 2k fits 48 bits for k <= 20 and
 // reads of up to 127 bases) -- 24 instead of 32 KB of emissions per block of 256 lanes: four blocks per CU instead of three for this
 // VALU-bound kernel (three Hash64 per base are the reference's own: the minimizer hash is the hash of the smaller strand's hash)
-template <bool GSTAGE, bool E6>
-__global__ void k_prep_mm(CmDev d, uint32_t pair_lo, uint32_t n_pairs /* end of this launch's pair range */, uint32_t lds_half, uint32_t stg,
+// PL (shared-memory staging, reads of at most 64 bases; cmgpu_set_option "pack_once"): every read is converted to bit planes ONCE, by
+// its own lane (cm_read_planes64: one 64-bit word per plane), and the three consumers of 2-bit information share them -- the trim
+// (cm_trim_planes64 instead of cm_trim_fast's byte loop over both mates on half the block's lanes; the mates' planes cross through LDS,
+// [word][thread], in the emission area, which nothing uses before the minimizer pass), the minimizer pass (base codes from two registers
+// instead of a byte load at a 50-byte stride and cm_c2u per base), and S5's planes (cm_finish_read_planes from the same registers once
+// the trimmed length is known: k_pack_reads, its stream and its event are not needed for such a batch).
+template <bool GSTAGE, bool E6, bool PL = false>
+__global__ __attribute__((amdgpu_waves_per_eu(PL ? 6 : 1))) void k_prep_mm(CmDev d, uint32_t pair_lo, uint32_t n_pairs /* end of this launch's pair range */, uint32_t lds_half, uint32_t stg,
                           uint32_t mm_cap, unsigned long long *cursor, uint64_t *gstage) {
+  static_assert(!(PL && GSTAGE), "the planes route stages its emissions in shared memory");
   const uint32_t T = blockDim.x, PB = T >> 1;
   const uint32_t p0 = pair_lo + blockIdx.x * PB, p1 = p0 + PB < n_pairs ? p0 + PB : n_pairs;
   const uint32_t t = threadIdx.x, lp = t < PB ? t : t - PB, pair = p0 + lp;
   const CmStaged s = cm_stage_pairs(d, p0, p1, pair, lds_half);
-  if (t < PB && pair < p1) cm_s0_prep_ptr(d, pair, s.m0, s.m1);
+  uint64_t pl0 = 0, pl1 = 0, pln = 0;  // PL: this lane's read
+  if (PL) {
+    uint64_t *xp = reinterpret_cast<uint64_t *>(cm_lds + 2 * lds_half);  // p0 [T], p1 [T], then "upper-case ACGT only" [T]
+    uint32_t *xu = reinterpret_cast<uint32_t *>(xp + 2 * (size_t)T);
+    if (pair < p1) {
+      const uint32_t raw = t < PB ? d.ro0[pair + 1] - d.ro0[pair] : d.ro1[pair + 1] - d.ro1[pair];
+      uint64_t plu;
+      cm_read_planes64(t < PB ? s.m0 : s.m1, raw, &pl0, &pl1, &pln, &plu);
+      xp[t] = pl0; xp[T + t] = pl1; xu[t] = (plu & cm_mask64(raw)) == 0 ? 1u : 0u;
+    }
+    __syncthreads();
+    if (t < PB && pair < p1) {
+      CmPairPlanes pp;
+      pp.p0[0] = pl0; pp.p1[0] = pl1; pp.upper[0] = xu[t] != 0;
+      pp.p0[1] = xp[t + PB]; pp.p1[1] = xp[T + t + PB]; pp.upper[1] = xu[t + PB] != 0;
+      cm_s0_prep_ptr(d, pair, s.m0, s.m1, &pp);
+    }
+  } else if (t < PB && pair < p1) cm_s0_prep_ptr(d, pair, s.m0, s.m1);
   __syncthreads();
   uint64_t *sh_e = GSTAGE ? gstage + (size_t)blockIdx.x * stg * T : reinterpret_cast<uint64_t *>(cm_lds + 2 * lds_half);
   uint32_t *sh_lo = reinterpret_cast<uint32_t *>(cm_lds + 2 * lds_half);  // E6: the emissions' low words, then their bits 32-47
@@ -119,10 +143,14 @@ __global__ void k_prep_mm(CmDev d, uint32_t pair_lo, uint32_t n_pairs /* end of 
   uint32_t cnt = 0, len = 0;
   if (valid) {
     len = d.rlen[r];
-    cnt = cm_minimizers_w7(seq, len, k, [&](uint32_t n, uint64_t h, uint32_t p) {
+    auto put = [&](uint32_t n, uint64_t h, uint32_t p) {
       const uint64_t v = h | ((uint64_t)p << hb);
       if (n < stg) { if (E6) { sh_lo[(size_t)n * T + t] = (uint32_t)v; sh_hi[(size_t)n * T + t] = (uint16_t)(v >> 32); } else sh_e[(size_t)n * T + t] = v; }
-    });
+    };
+    if (PL) {
+      if (d.read_pl) cm_finish_read_planes(d, r, pl0, pl1, pln, len);
+      cnt = cm_minimizers_w7_planes(pl0, pl1, (pln & cm_mask64(len)) != 0, seq, len, k, put);
+    } else cnt = cm_minimizers_w7(seq, len, k, put);
   }
   // block exclusive scan of cnt
   const uint32_t lane = t & 63, wave = t >> 6;
@@ -2191,14 +2219,26 @@ size_t cm_prep_mm_stage_bytes(const CmDev &d, uint32_t max_read_len, uint32_t pa
   return (size_t)((pairs + pb - 1) / pb) * stg * threads * 8;
 }
 // pairs [pair_lo, pair_hi)
+// the planes route of k_prep_mm (PL): shared-memory staging, a read is one word per plane, and the lanes' exchange area (2 x 8 + 4
+// bytes per lane) fits the emission area it aliases
+bool cm_prep_mm_planes_supported(const CmDev &d, uint32_t max_read_len) {
+  uint32_t threads, half, stg;
+  size_t lds;
+  bool g = false, e6 = false;
+  if (max_read_len > 64 || !prep_mm_geometry(d, max_read_len, &threads, &half, &stg, &lds, &g, &e6) || g) return false;
+  return (size_t)stg * (e6 ? 6 : 8) >= 20;
+}
 void cm_launch_k_prep_mm(const CmDev &d, uint32_t pair_lo, uint32_t pair_hi, uint32_t max_read_len, uint32_t mm_cap,
-                         unsigned long long *cursor, hipStream_t s, void *gstage) {
+                         unsigned long long *cursor, hipStream_t s, void *gstage, bool planes) {
   uint32_t threads, half, stg;
   size_t lds;
   bool g = false, e6 = false;
   if (pair_hi <= pair_lo || !prep_mm_geometry(d, max_read_len, &threads, &half, &stg, &lds, &g, &e6)) return;
   const uint32_t pb = threads / 2;
-  if (g) hipLaunchKernelGGL((k_prep_mm<true, false>), dim3((pair_hi - pair_lo + pb - 1) / pb), dim3(threads), lds, s, d, pair_lo, pair_hi, half, stg, mm_cap, cursor, (uint64_t *)gstage);
+  if (planes && cm_prep_mm_planes_supported(d, max_read_len)) {
+    if (e6) hipLaunchKernelGGL((k_prep_mm<false, true, true>), dim3((pair_hi - pair_lo + pb - 1) / pb), dim3(threads), lds, s, d, pair_lo, pair_hi, half, stg, mm_cap, cursor, (uint64_t *)nullptr);
+    else hipLaunchKernelGGL((k_prep_mm<false, false, true>), dim3((pair_hi - pair_lo + pb - 1) / pb), dim3(threads), lds, s, d, pair_lo, pair_hi, half, stg, mm_cap, cursor, (uint64_t *)nullptr);
+  } else if (g) hipLaunchKernelGGL((k_prep_mm<true, false>), dim3((pair_hi - pair_lo + pb - 1) / pb), dim3(threads), lds, s, d, pair_lo, pair_hi, half, stg, mm_cap, cursor, (uint64_t *)gstage);
   else if (e6) hipLaunchKernelGGL((k_prep_mm<false, true>), dim3((pair_hi - pair_lo + pb - 1) / pb), dim3(threads), lds, s, d, pair_lo, pair_hi, half, stg, mm_cap, cursor, (uint64_t *)nullptr);
   else hipLaunchKernelGGL((k_prep_mm<false, false>), dim3((pair_hi - pair_lo + pb - 1) / pb), dim3(threads), lds, s, d, pair_lo, pair_hi, half, stg, mm_cap, cursor, (uint64_t *)nullptr);
 }

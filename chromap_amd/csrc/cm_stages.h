@@ -519,8 +519,40 @@ CM_HD bool cm_trim_fast(const uint8_t *rd1, uint32_t l1, const uint8_t *lng, uin
   return true;
 }
 
-// s1p / s2p: the pair's reads (global memory, or the block's LDS copy of them)
-CM_HD void cm_s0_prep_ptr(const CmDev &d, uint32_t pair, const uint8_t *s1p, const uint8_t *s2p) {
+// The same search on the bit planes of reads of at most 64 bases (cm_read_planes64: one 64-bit word per plane, base i at bit i, codes
+// A0 C1 G2 T3, complement = ^3 = both planes inverted).  a0 / a1: the planes of read1 (l1 bases); b0 / b1: those of read2 (l2 >= l1
+// bases), forward -- its reverse complement is their bit reversal moved down by 64 - l2 and inverted.  One bit per base:
+//   D(s0) = ((a0 ^ (B0 >> s0)) | (a1 ^ (B1 >> s0))) & mask(n),   n = min(l1, l2 - s0),
+// and the seed masks are `seed` bits wide.  Bits of the planes at and beyond a read's length may hold anything: mask(n) drops them.
+// The caller has checked what cm_trim_fast checks: seed in 1..32, 2 * seed <= min_overlap <= l1 <= l2 <= 64, both reads upper-case
+// A/C/G/T only.
+CM_HD uint32_t cm_brev32(uint32_t v);
+CM_HD uint64_t cm_brev64(uint64_t v) { return ((uint64_t)cm_brev32((uint32_t)v) << 32) | cm_brev32((uint32_t)(v >> 32)); }
+CM_HD uint64_t cm_mask64(uint32_t n) { return n >= 64u ? ~0ull : ((1ull << n) - 1ull); }  // bits [0, n)
+CM_HD void cm_trim_planes64(uint64_t a0, uint64_t a1, uint32_t l1, uint64_t b0, uint64_t b1, uint32_t l2, int min_overlap, int seed,
+                            bool *found, uint32_t *s0_out) {
+  const uint32_t down = 64u - l2;  // 0..63
+  uint64_t B0 = ~(cm_brev64(b0) >> down), B1 = ~(cm_brev64(b1) >> down);
+  const uint64_t seedmask = cm_mask64((uint32_t)seed);
+  bool fa = false, fb = false;
+  uint32_t sa = 0, sb = 0;
+  const uint32_t last = l2 - (uint32_t)min_overlap;
+  for (uint32_t s0 = 0; s0 <= last && !fa; ++s0) {
+    const uint32_t n = l1 < l2 - s0 ? l1 : l2 - s0;
+    const uint64_t D = ((a0 ^ B0) | (a1 ^ B1)) & cm_mask64(n);
+    const bool ok = __builtin_popcountll(D) <= 1;
+    if (ok && (D & seedmask) == 0) { fa = true; sa = s0; }
+    if (ok && ((D >> seed) & seedmask) == 0 && !fb) { fb = true; sb = s0; }
+    B0 >>= 1; B1 >>= 1;
+  }
+  *found = fa || fb;
+  *s0_out = fa ? sa : sb;
+}
+// a pair's reads as planes (cm_read_planes64), for the trim: mate 0, mate 1; upper: the read is made of upper-case A/C/G/T only
+struct CmPairPlanes { uint64_t p0[2], p1[2]; bool upper[2]; };
+
+// s1p / s2p: the pair's reads (global memory, or the block's LDS copy of them); pp (optional): their planes, reads of at most 64 bases
+CM_HD void cm_s0_prep_ptr(const CmDev &d, uint32_t pair, const uint8_t *s1p, const uint8_t *s2p, const CmPairPlanes *pp = nullptr) {
   const uint32_t raw1 = d.ro0[pair + 1] - d.ro0[pair], raw2 = d.ro1[pair + 1] - d.ro1[pair];
   uint32_t len1 = raw1, len2 = raw2;
   bool ok = raw1 >= (uint32_t)d.p.min_read_len && (d.p.single || raw2 >= (uint32_t)d.p.min_read_len);
@@ -539,7 +571,11 @@ CM_HD void cm_s0_prep_ptr(const CmDev &d, uint32_t pair, const uint8_t *s1p, con
     bool fast = false, ffound = false;
     uint32_t fs0 = 0;
     if (seed >= 1 && seed <= 32 && 2 * seed <= min_overlap && l1 >= (uint32_t)min_overlap) {
-      if (l2 <= 64) fast = cm_trim_fast<2>(rd1, l1, lng, l2, min_overlap, seed, &ffound, &fs0);
+      if (pp && l2 <= 64) {
+        const int ia = swap ? 1 : 0, ib = swap ? 0 : 1;
+        fast = pp->upper[0] && pp->upper[1];
+        if (fast) cm_trim_planes64(pp->p0[ia], pp->p1[ia], l1, pp->p0[ib], pp->p1[ib], l2, min_overlap, seed, &ffound, &fs0);
+      } else if (l2 <= 64) fast = cm_trim_fast<2>(rd1, l1, lng, l2, min_overlap, seed, &ffound, &fs0);
       else if (l2 <= 160) fast = cm_trim_fast<5>(rd1, l1, lng, l2, min_overlap, seed, &ffound, &fs0);
       else if (l2 <= 256) fast = cm_trim_fast<8>(rd1, l1, lng, l2, min_overlap, seed, &ffound, &fs0);
     }
@@ -706,8 +742,19 @@ CM_HD uint32_t cm_minimizers_window_e(const uint8_t *seq, uint32_t len, int k, E
 // Per base: shift the 7-entry register window, one 7-way minimum, 7 equality tests into a flag mask,
 // and the entry that leaves the window is emitted if flagged.  A read with a base outside ACGT is redone by
 // the state machine (its behaviour across N runs is not a window rule).
-template <class Emit>
-CM_HD uint32_t cm_minimizers_w7_oddk_seq(const uint8_t *seq, uint32_t len, int k, Emit &&emit) {
+// Where the base codes come from: src(i) = code of base i, 0..3, or 4 for a base outside ACGT (the read is then redone by the state
+// machine).  From the read's bytes, or from its bit planes (cm_read_planes64; reads of at most 64 bases) -- the planes carry no "bad
+// base", the caller decides that once from pn and sends such a read to the state machine instead.
+struct CmSrcBytes {
+  const uint8_t *seq;
+  CM_HD uint32_t operator()(uint32_t i) const { return cm_c2u(seq[i]); }
+};
+struct CmSrcPlanes {
+  uint64_t p0, p1;
+  CM_HD uint32_t operator()(uint32_t i) const { return ((uint32_t)(p0 >> i) & 1u) | (((uint32_t)(p1 >> i) & 1u) << 1); }
+};
+template <class Src, class Emit>
+CM_HD uint32_t cm_minimizers_w7_oddk_seq_src(const Src &src, uint32_t len, int k, Emit &&emit) {
   const uint64_t shift = 2 * (uint64_t)(k - 1);
   const uint64_t mask = (((uint64_t)1) << (2 * k)) - 1;
   uint64_t fw = 0, rv = 0;
@@ -716,7 +763,7 @@ CM_HD uint32_t cm_minimizers_w7_oddk_seq(const uint8_t *seq, uint32_t len, int k
   for (int j = 0; j < 7; ++j) H[j] = ~0ull;
   uint32_t sb = 0, fl = 0, bad = 0, n = 0;
   for (uint32_t pos = 0; pos < len; ++pos) {
-    uint32_t c = cm_c2u(seq[pos]);
+    uint32_t c = src(pos);
     bad |= c >> 2;
     c &= 3;
     fw = ((fw << 2) | c) & mask;
@@ -779,14 +826,14 @@ CM_HD uint32_t cm_minimizers_w7_oddk_seq(const uint8_t *seq, uint32_t len, int k
 // 36 minima / maxima and 7 compares per seven k-mers -- 6.1 two-word operations per base instead of 13.  The first window's rule
 // (the reference drops the earlier k-mers that tie with the seventh, see above) strikes those entries out (all ones) before
 // anything else looks at them.  Block c is settled while block c + 1 is hashed; one empty block runs last.
-template <int HV, class Emit>
-CM_HD uint32_t cm_minimizers_w7_oddk_blocks(const uint8_t *seq, uint32_t len, int k, Emit &&emit) {
+template <int HV, class Src, class Emit>
+CM_HD uint32_t cm_minimizers_w7_oddk_blocks_src(const Src &src, uint32_t len, int k, Emit &&emit) {
   const uint64_t shift = 2 * (uint64_t)(k - 1);
   const uint64_t mask = (((uint64_t)1) << (2 * k)) - 1;
   uint64_t fw = 0, rv = 0;
   uint32_t bad = 0, n = 0;
   for (uint32_t pos = 0; pos + 1 < (uint32_t)k; ++pos) {
-    uint32_t c = cm_c2u(seq[pos]);
+    uint32_t c = src(pos);
     bad |= c >> 2;
     c &= 3;
     fw = ((fw << 2) | c) & mask;
@@ -805,7 +852,7 @@ CM_HD uint32_t cm_minimizers_w7_oddk_blocks(const uint8_t *seq, uint32_t len, in
       const uint32_t i = 7 * b + (uint32_t)j;
       e[j] = 0;
       if (i < m) {
-        uint32_t c = cm_c2u(seq[i + (uint32_t)k - 1]);
+        uint32_t c = src(i + (uint32_t)k - 1);
         bad |= c >> 2;
         c &= 3;
         fw = ((fw << 2) | c) & mask;
@@ -860,12 +907,25 @@ CM_HD uint32_t cm_minimizers_w7_oddk_blocks(const uint8_t *seq, uint32_t len, in
   if (bad) return ~0u;
   return n;
 }
+template <class Src, class Emit>
+CM_HD uint32_t cm_minimizers_w7_oddk_src(const Src &src, uint32_t len, int k, Emit &&emit) {
+  if (len < (uint32_t)k + 6) return cm_minimizers_w7_oddk_seq_src(src, len, k, emit);  // fewer than seven k-mers: the flush rule
+  if (2 * k == 34) return cm_minimizers_w7_oddk_blocks_src<0>(src, len, k, emit);      // (which hash arithmetic: chosen once)
+  if (2 * k > 32 && 2 * k <= 52) return cm_minimizers_w7_oddk_blocks_src<1>(src, len, k, emit);
+  return cm_minimizers_w7_oddk_blocks_src<2>(src, len, k, emit);
+}
+// from the read's bytes
+template <class Emit>
+CM_HD uint32_t cm_minimizers_w7_oddk_seq(const uint8_t *seq, uint32_t len, int k, Emit &&emit) {
+  return cm_minimizers_w7_oddk_seq_src(CmSrcBytes{seq}, len, k, emit);
+}
+template <int HV, class Emit>
+CM_HD uint32_t cm_minimizers_w7_oddk_blocks(const uint8_t *seq, uint32_t len, int k, Emit &&emit) {
+  return cm_minimizers_w7_oddk_blocks_src<HV>(CmSrcBytes{seq}, len, k, emit);
+}
 template <class Emit>
 CM_HD uint32_t cm_minimizers_w7_oddk(const uint8_t *seq, uint32_t len, int k, Emit &&emit) {
-  if (len < (uint32_t)k + 6) return cm_minimizers_w7_oddk_seq(seq, len, k, emit);  // fewer than seven k-mers: the flush rule
-  if (2 * k == 34) return cm_minimizers_w7_oddk_blocks<0>(seq, len, k, emit);      // (which hash arithmetic: chosen once)
-  if (2 * k > 32 && 2 * k <= 52) return cm_minimizers_w7_oddk_blocks<1>(seq, len, k, emit);
-  return cm_minimizers_w7_oddk_blocks<2>(seq, len, k, emit);
+  return cm_minimizers_w7_oddk_src(CmSrcBytes{seq}, len, k, emit);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -951,6 +1011,14 @@ CM_HD uint32_t cm_minimizers_w7(const uint8_t *seq, uint32_t len, int k, Emit &&
     const uint32_t n = cm_minimizers_w7_oddk(seq, len, k, emit);
     if (n != ~0u) return n;
   }
+  return cm_minimizers_window_e<7>(seq, len, k, emit);
+}
+
+// the same from the read's planes where they can serve (odd k, no base outside ACGT: `bad` = pn & mask(len) != 0, decided once by the
+// caller), from its bytes otherwise
+template <class Emit>
+CM_HD uint32_t cm_minimizers_w7_planes(uint64_t p0, uint64_t p1, bool bad, const uint8_t *seq, uint32_t len, int k, Emit &&emit) {
+  if ((k & 1) && !bad) return cm_minimizers_w7_oddk_src(CmSrcPlanes{p0, p1}, len, k, emit);
   return cm_minimizers_window_e<7>(seq, len, k, emit);
 }
 
@@ -2358,6 +2426,52 @@ CM_HD void cm_pack_read_planes(const CmDev &d, uint32_t r) {
     case 7: cm_pack_read_planes_w<7>(d, r); break;
     case 8: cm_pack_read_planes_w<8>(d, r); break;
     default: cm_pack_read_planes_any(d, r);
+  }
+}
+
+// A read of at most 64 bases, converted ONCE for the trim, the minimizer pass and the planes S5 aligns on (k_prep_mm's planes route):
+// one 64-bit word per plane, base i at bit i, from aligned 8-byte loads and a funnel shift like cm_pack_read_planes_w (`read` at any
+// byte alignment, in LDS or global memory; nothing beyond the aligned word that holds the last base is read).
+//   p0 / p1: the code's bits (not cleared where pn is set);  pn: the byte is no letter of ACGT / acgt;
+//   pu: the byte is no UPPER-case A/C/G/T (pn, or bit 5 of the byte set) -- what the trim's fast path asks for.
+// Bits at and beyond len hold anything: every consumer applies its own length (the raw one, or the trimmed one).
+CM_HD void cm_read_planes64(const uint8_t *read, uint32_t len, uint64_t *p0, uint64_t *p1, uint64_t *pn, uint64_t *pu) {
+  const uintptr_t ra = reinterpret_cast<uintptr_t>(read);
+  const uint32_t sh8 = (uint32_t)(ra & 7) * 8;
+  const uint64_t *ap = reinterpret_cast<const uint64_t *>(ra & ~(uintptr_t)7);
+  uint64_t wv[9];
+#pragma unroll
+  for (int q = 0; q <= 8; ++q) wv[q] = (uint32_t)q * 8u < (sh8 >> 3) + len ? ap[q] : 0ull;
+  uint64_t q0 = 0, q1 = 0, qn = 0, qu = 0;
+#pragma unroll
+  for (int g = 0; g < 8; ++g) {
+    if (8u * (uint32_t)g >= len) break;
+    const uint64_t v = sh8 ? (wv[g] >> sh8) | (wv[g + 1] << (64u - sh8)) : wv[g];
+    const uint32_t a = (uint32_t)v, b = (uint32_t)(v >> 32);
+    uint32_t b0, b1, bn;
+    cm_pack8_planes(a, b, &b0, &b1, &bn);
+    const uint32_t lc = cm_fold8(((a >> 5) & 0x01010101u) | (((b >> 5) & 0x01010101u) << 4));
+    q0 |= (uint64_t)b0 << (8 * g); q1 |= (uint64_t)b1 << (8 * g); qn |= (uint64_t)bn << (8 * g); qu |= (uint64_t)(bn | lc) << (8 * g);
+  }
+  *p0 = q0; *p1 = q1; *pn = qn; *pu = qu;
+}
+// From those planes and the trimmed length L: exactly the 6 W words cm_pack_read_planes_w<W> writes for read r (W = d.read_pl_w, 1 or
+// 2) -- pn set at and beyond L and p0 / p1 cleared wherever pn is set; the reverse orientation = the bit reversal moved down to bit 0,
+// p0 / p1 inverted; 16-byte stores.  Nothing for L == 0.
+CM_HD void cm_finish_read_planes(const CmDev &d, uint32_t r, uint64_t p0, uint64_t p1, uint64_t pn, uint32_t L) {
+  if (L == 0) return;
+  const uint64_t fn = pn | ~cm_mask64(L), f0 = p0 & ~fn, f1 = p1 & ~fn;
+  const uint32_t down = 64u - (L < 64u ? L : 64u);  // 0..63
+  const uint64_t r0 = ~(cm_brev64(f0) >> down), r1 = ~(cm_brev64(f1) >> down), rn = cm_brev64(fn) >> down;
+  uint32_t *dst = cm_read_pl_of(d, r);
+  struct alignas(16) Q { uint32_t a, b, c, e; };
+  if (d.read_pl_w == 1) {
+    *reinterpret_cast<Q *>(dst) = Q{(uint32_t)f0, (uint32_t)f1, (uint32_t)fn, (uint32_t)r0};
+    *reinterpret_cast<Q *>(dst + 4) = Q{(uint32_t)r1, (uint32_t)rn, 0u, 0u};
+  } else {
+    *reinterpret_cast<Q *>(dst) = Q{(uint32_t)f0, (uint32_t)(f0 >> 32), (uint32_t)f1, (uint32_t)(f1 >> 32)};
+    *reinterpret_cast<Q *>(dst + 4) = Q{(uint32_t)fn, (uint32_t)(fn >> 32), (uint32_t)r0, (uint32_t)(r0 >> 32)};
+    *reinterpret_cast<Q *>(dst + 8) = Q{(uint32_t)r1, (uint32_t)(r1 >> 32), (uint32_t)rn, (uint32_t)(rn >> 32)};
   }
 }
 

@@ -103,7 +103,10 @@ int cmgpu_gather_sweep(cmgpu_ctx *ctx, uint64_t n, int repeat, int loads_per_lan
  * "generic_kernels" 0/1 (1: paired-end batches without split alignment run the S4-S6 kernels that carry every mode instead of
  * their own instances; tests/test_gpu_mode_instances.py compares the two),
  * "s3b_short" 1/0 (0: hit lists of at most 16 hits at a lane cap of 16 go through the general per-lane kernel, k_s3b_candidates,
- * instead of the short-list instance k_s3b_short; tests/test_gpu_s3b_short.py compares the two).
+ * instead of the short-list instance k_s3b_short; tests/test_gpu_s3b_short.py compares the two),
+ * "pack_once" 1/0 (batches whose longest read has at most 64 bases, on the fused trim + minimizer kernel: 1 converts every read to
+ * bit planes once, in that kernel, for the trim, the minimizer pass and the verification's planes; 0 converts the bytes in each of
+ * the three, the last in a kernel of its own, k_pack_reads; tests/test_gpu_pack_once.py compares the two).
  * Every setting gives the same records (tests/test_gpu_parity.py runs the fuzz data under each; "s3b_short" 1 and 0:
  * tests/test_gpu_s3b_short.py, on its own data and on one fuzz configuration). */
 int cmgpu_set_option(cmgpu_ctx *ctx, const char *name, int64_t value);
@@ -139,7 +142,10 @@ int cmgpu_reference_lengths(cmgpu_ctx *ctx, uint32_t *lengths, uint32_t capacity
  * "ndn", "nv") or per-pair (n entries: "pe_nbest") 32-bit array of the last mapped batch -- the list lengths the stages saw
  * (tools/list_hist.py).  *n_out = entries.
  * "hv_cnt": the 64 counters of the device work lists of the last mapped range -- word l < 32 = the reads / pairs that went to
- * long-list class l (the CmList ids of cm_types.h), the words above are the lists' work cursors.  A read-only copy. */
+ * long-list class l (the CmList ids of cm_types.h), the words above are the lists' work cursors.  A read-only copy.
+ * "read_pl": the reads' bit planes as the verification saw them, for a batch mapped in one piece: S = (6 W + 3) & ~3 words per read,
+ * W = (longest read + 31) / 32; read r's forward p0 / p1 / pn (W words each), then the reverse complement's, at r * S.  Defined
+ * for reads with rlen > 0; *n_out = 2 n S. */
 int cmgpu_debug_array(cmgpu_ctx *ctx, const char *name, uint32_t *out, uint64_t capacity, uint64_t *n_out);
 
 #ifdef __cplusplus
