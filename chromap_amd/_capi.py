@@ -123,7 +123,7 @@ SYMBOLS = ("cmgpu_default_params", "cmgpu_apply_preset", "cmgpu_create", "cmgpu_
            "cmgpu_exchange_owner_table", "cmgpu_exchange_step", "cmgpu_exchange_info", "cmgpu_exchange_plan", "cmgpu_exchange_finalize", "cmgpu_memcpy", "cmgpu_copy_whitelist",
            "cmgpu_set_barcode_translation", "cmgpu_barcode_translation_info", "cmgpu_copy_barcode_translation", "cmgpu_barcode_translation_pack", "cmgpu_barcode_translate_host",
            "cmgpu_host_alloc", "cmgpu_host_free", "cmgpu_host_register", "cmgpu_host_unregister", "cmgpu_submit_pairs", "cmgpu_map_submitted", "cmgpu_map_submitted_async", "cmgpu_records_wait",
-           "cmgpu_debug_trace", "cmgpu_debug_minimizers", "cmgpu_debug_minimizers_all", "cmgpu_debug_array")
+           "cmgpu_debug_trace", "cmgpu_debug_minimizers", "cmgpu_debug_minimizers_all", "cmgpu_debug_array", "cmgpu_debug_mapq", "cmgpu_debug_mapq_tables")
 
 # names cmgpu_debug_array knows (include/chromap_amd_debug.h): per read, per pair, and the 64 counters of the device work lists
 DEBUG_ARRAYS_PER_READ = ("rlen", "mm_cnt", "hit_tot", "ncp", "ncn", "resc_p", "resc_n", "mcp", "mcn", "fcp", "fcn", "ndp", "ndn", "nv")
@@ -141,6 +141,37 @@ def debug_array(L, ctx, name, n_pairs):
     if L.cmgpu_debug_array(ctx, name.encode(), out.ctypes.data, cap, C.byref(n)) != 0:
         raise RuntimeError(L.cmgpu_last_error(ctx).decode())
     return out[:n.value]
+
+
+# cmgpu_debug_mapq (include/chromap_amd_debug.h): kinds, and the columns of its two case matrices
+MAPQ_SINGLE, MAPQ_SPLIT, MAPQ_PAIRED, MAPQ_PAIRED_SPLIT = 0, 1, 2, 3
+MAPQ_READ_COLS = ("num_errors", "alignment_length", "read_length", "min_err", "second_err", "n_best", "n_second", "rep_len", "strand_ncand")
+MAPQ_PAIR_COLS = ("max_diff", "min_sum", "second_sum", "n_best", "n_second", "force_mapq")
+
+
+def debug_mapq(L, ctx, kind, error_threshold, reads, pairs):
+    """the MAPQ functions on n cases: reads int32 [9, 2 n], pairs int32 [6, n] (C order) -> numpy uint8 [n]"""
+    import numpy as np
+    reads = np.ascontiguousarray(reads, dtype=np.int32)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+    n = pairs.shape[1]
+    if reads.shape != (len(MAPQ_READ_COLS), 2 * n) or pairs.shape != (len(MAPQ_PAIR_COLS), n):
+        raise ValueError("MAPQ cases: reads must be [9, 2 n] and pairs [6, n]")
+    out = np.zeros(n, np.uint8)
+    if L.cmgpu_debug_mapq(ctx, kind, error_threshold, n, reads.ctypes.data, pairs.ctypes.data, out.ctypes.data) != 0:
+        raise RuntimeError(L.cmgpu_last_error(ctx).decode())
+    return out
+
+
+def debug_mapq_tables(L, ctx):
+    """the context's MAPQ tables as they stand in HBM: (len_coef float64 [65536], nsec_break uint32 [n_break])"""
+    import numpy as np
+    coef = np.zeros(65536, np.float64)
+    brk = np.zeros(256, np.uint32)
+    nb = C.c_uint32(0)
+    if L.cmgpu_debug_mapq_tables(ctx, coef.ctypes.data, brk.ctypes.data, len(brk), C.byref(nb)) != 0:
+        raise RuntimeError(L.cmgpu_last_error(ctx).decode())
+    return coef, brk[:nb.value]
 
 
 UNIQUE_ID_BYTES = 128
@@ -307,6 +338,8 @@ def declare(L):
     sig("cmgpu_records_wait", C.c_int, [C.c_void_p, P(C.c_uint64)])
     sig("cmgpu_debug_trace", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64])
     sig("cmgpu_debug_array", C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)])
+    sig("cmgpu_debug_mapq", C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p])
+    sig("cmgpu_debug_mapq_tables", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, P(C.c_uint32)])
     sig("cmgpu_debug_minimizers", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, P(C.c_uint32)])
     sig("cmgpu_debug_minimizers_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, P(C.c_uint64)])
     sig("cmgpu_copy_whitelist", C.c_int, [C.c_void_p, C.c_void_p])

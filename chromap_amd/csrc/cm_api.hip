@@ -1632,6 +1632,49 @@ extern "C" int cmgpu_debug_array(cmgpu_ctx *c, const char *name, uint32_t *out, 
   return CMGPU_EINVAL;
 }
 
+// The MAPQ functions of cm_stages.h on their own (include/chromap_amd_debug.h; tests/test_gpu_mapq.py): the cases go up as two
+// column-major matrices, a CmDev by value carries the context's two tables, the error threshold and the per-read columns the paired
+// forms read, one lane per case stores its byte.  Nothing of the mapping path is read or written.
+extern "C" int cmgpu_debug_mapq(cmgpu_ctx *c, int kind, int32_t error_threshold, uint64_t n, const int32_t *reads, const int32_t *pairs,
+                                uint8_t *out) {
+  if (!c || kind < CMGPU_MAPQ_SINGLE || kind > CMGPU_MAPQ_PAIRED_SPLIT || n > (1ull << 30) || (n && (!reads || !pairs || !out))) return CMGPU_EINVAL;
+  CM_HIPCHECK(c, cm_enter(c));
+  if (!c->len_coef.p || !c->nsec_break.p) { cm_set_error(c, "the MAPQ tables are not resident"); return CMGPU_EINVAL; }
+  if (n == 0) return CMGPU_OK;
+  const size_t n2 = 2 * (size_t)n, rbytes = (size_t)CM_MQ_READ_COLS * n2 * 4, pbytes = (size_t)CM_MQ_PAIR_COLS * n * 4;
+  CmTmpBuf dr, dp, dq;
+  if (dr.ensure(rbytes) || dp.ensure(pbytes) || dq.ensure(n)) return CMGPU_ENOMEM;
+  CM_HIPCHECK(c, hipMemcpyAsync(dr.p, reads, rbytes, hipMemcpyHostToDevice, c->stream));
+  CM_HIPCHECK(c, hipMemcpyAsync(dp.p, pairs, pbytes, hipMemcpyHostToDevice, c->stream));
+  CmDev d;
+  memset(&d, 0, sizeof d);
+  d.mq.len_coef = (const double *)c->len_coef.p; d.mq.nsec_break = (const uint32_t *)c->nsec_break.p; d.mq.n_break = c->n_break;
+  d.p.e = error_threshold;
+  d.n_pairs = (uint32_t)n;
+  int32_t *col = (int32_t *)dr.p;
+  d.min_err = col + 3 * n2; d.second_err = col + 4 * n2; d.n_best = col + 5 * n2; d.n_second = col + 6 * n2;
+  d.rep_len = (uint32_t *)(col + 7 * n2);
+  cm_launch_k_debug_mapq(d, kind, (uint32_t)n, col, (const int32_t *)dp.p, (uint8_t *)dq.p, c->stream);
+  CM_HIPCHECK(c, hipMemcpyAsync(out, dq.p, n, hipMemcpyDeviceToHost, c->stream));
+  CM_HIPCHECK(c, cm_stream_sync(c->stream));
+  return CMGPU_OK;
+}
+
+// the context's MAPQ tables as they stand in HBM: len_coef (65536 doubles) and nsec_break (*n_break entries, at most capacity)
+extern "C" int cmgpu_debug_mapq_tables(cmgpu_ctx *c, double *len_coef, uint32_t *nsec_break, uint32_t capacity, uint32_t *n_break) {
+  if (!c || !n_break) return CMGPU_EINVAL;
+  CM_HIPCHECK(c, cm_enter(c));
+  if (!c->len_coef.p || !c->nsec_break.p) { cm_set_error(c, "the MAPQ tables are not resident"); return CMGPU_EINVAL; }
+  *n_break = (uint32_t)c->n_break;
+  CM_HIPCHECK(c, cm_stream_sync(c->stream));
+  if (len_coef) CM_HIPCHECK(c, hipMemcpy(len_coef, c->len_coef.p, 65536 * 8, hipMemcpyDeviceToHost));
+  if (nsec_break) {
+    if (capacity < (uint32_t)c->n_break) { cm_set_error(c, "breakpoint buffer too small"); return CMGPU_ECAPACITY; }
+    CM_HIPCHECK(c, hipMemcpy(nsec_break, c->nsec_break.p, (size_t)c->n_break * 4, hipMemcpyDeviceToHost));
+  }
+  return CMGPU_OK;
+}
+
 // one read's minimizers of the last mapped batch: (hash, position << 1 | strand) in emission order
 extern "C" int cmgpu_debug_minimizers(cmgpu_ctx *c, uint32_t read, uint64_t *hash_out, uint32_t *ps_out, uint32_t capacity, uint32_t *n_out) {
   if (!c || !n_out || read >= 2 * c->n_pairs) return CMGPU_EINVAL;

@@ -58,6 +58,12 @@ void cm_build_heavy_last(const CmDev &d, uint32_t n_pairs, uint32_t *fr, uint32_
                          uint32_t *perm_pairs, uint32_t *scan_tmp, hipStream_t s);
 void cm_launch_k_pack_ref(const uint8_t *ref, uint64_t n_bytes, CmPlRec *pl, hipStream_t s);
 void cm_launch_k_pack_reads(const CmDev &d, uint32_t n_reads, hipStream_t s);
+// test hook (cmgpu_debug_mapq, include/chromap_amd_debug.h): n MAPQ cases, one per lane, through cm_mapq_single / _single_split /
+// _paired / _paired_split.  d carries mq, p.e and the per-read arrays the paired forms read (columns of `reads`); reads: CM_MQ_READ_COLS
+// columns of 2 n values, pairs: CM_MQ_PAIR_COLS columns of n values, out: n bytes -- all device memory
+#define CM_MQ_READ_COLS 9  // num_errors, alignment_length, read_length, min_err, second_err, n_best, n_second, rep_len, strand_ncand
+#define CM_MQ_PAIR_COLS 6  // max_diff, min_sum, second_sum, n_best, n_second, force_mapq
+void cm_launch_k_debug_mapq(const CmDev &d, int kind, uint32_t n, const int32_t *reads, const int32_t *pairs, uint8_t *out, hipStream_t s);
 void cm_launch_k_check_cap(const unsigned long long *total, unsigned long long cap, unsigned long long *flag, hipStream_t s);
 void cm_launch_k_copy_u64(const unsigned long long *src, unsigned long long *dst, hipStream_t s);
 void cm_launch_k_sum_u32(const uint32_t *in, uint32_t n, unsigned long long *out, hipStream_t s);

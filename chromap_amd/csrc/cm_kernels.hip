@@ -1785,6 +1785,35 @@ void cm_launch_k_pack_reads(const CmDev &d, uint32_t n_reads, hipStream_t s) {
   }
 #undef CM_PACK_CASE
 }
+// The MAPQ functions on their own (cmgpu_debug_mapq): case i is pair i, reads 2 i and 2 i + 1; the single-read kinds look at read 2 i.
+// kind: 0 cm_mapq_single, 1 cm_mapq_single_split, 2 cm_mapq_paired, 3 cm_mapq_paired_split.  Not on the mapping path.
+__global__ __launch_bounds__(256) void k_debug_mapq(CmDev d, int kind, uint32_t n, const int32_t *__restrict__ reads,
+                                                    const int32_t *__restrict__ pairs, uint8_t *__restrict__ out) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const size_t n2 = 2 * (size_t)n;
+  const uint32_t r1 = 2 * i, r2 = r1 + 1;
+  const int32_t *err = reads, *al = reads + n2, *len = reads + 2 * n2, *nc = reads + 8 * n2;
+  uint8_t q;
+  if (kind == 0) {
+    q = cm_mapq_single(d, err[r1], (uint16_t)al[r1], len[r1], pairs[i], d.second_err[r1], d.n_best[r1], d.n_second[r1], d.rep_len[r1]);
+  } else if (kind == 1) {
+    q = cm_mapq_single_split(d, err[r1], (uint16_t)al[r1], len[r1], pairs[i], d.second_err[r1], d.n_best[r1], d.n_second[r1], d.rep_len[r1],
+                             (uint32_t)nc[r1]);
+  } else if (kind == 2) {
+    CmPe pe;
+    pe.min_sum = pairs[n + i]; pe.second_sum = pairs[2 * (size_t)n + i]; pe.n_best = pairs[3 * (size_t)n + i]; pe.n_second = pairs[4 * (size_t)n + i];
+    pe.f_dir = pe.f_i1 = pe.f_i2 = 0;
+    q = cm_mapq_paired(d, i, err[r1], err[r2], (uint16_t)al[r1], (uint16_t)al[r2], len[r1], len[r2], pairs[5 * (size_t)n + i], pe);
+  } else {
+    q = cm_mapq_paired_split(d, i, err[r1], err[r2], (uint16_t)al[r1], (uint16_t)al[r2], len[r1], len[r2], (uint32_t)nc[r1], (uint32_t)nc[r2]);
+  }
+  out[i] = q;
+}
+void cm_launch_k_debug_mapq(const CmDev &d, int kind, uint32_t n, const int32_t *reads, const int32_t *pairs, uint8_t *out, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_debug_mapq, dim3((n + 255) / 256), dim3(256), 0, s, d, kind, n, reads, pairs, out);
+}
 void cm_launch_k_copy_u64(const unsigned long long *src, unsigned long long *dst, hipStream_t s) {
   hipLaunchKernelGGL(k_copy_u64, dim3(1), dim3(1), 0, s, src, dst);
 }

@@ -3538,6 +3538,20 @@ CM_HD uint8_t cm_mapq_single_split(const CmDev &d, int num_errors, uint16_t alig
   return (uint8_t)mapq;
 }
 
+// GetMAPQForPairedEndRead with split_alignment (mapping_generator.h:1148-1192): the two reads' values, each times 1.2 and cut to 60;
+// mapq_pe is not used by this combination.  ncand1 / ncand2: candidates on each mapping's strand
+CM_HD uint8_t cm_mapq_paired_split(const CmDev &d, uint32_t pair, int err1, int err2, uint16_t al1, uint16_t al2, int len1, int len2,
+                                   uint32_t ncand1, uint32_t ncand2) {
+  const uint32_t r1 = 2 * pair, r2 = r1 + 1;
+  uint8_t mapq1 = cm_mapq_single_split(d, err1, al1, len1, 2, d.second_err[r1], d.n_best[r1], d.n_second[r1], d.rep_len[r1], ncand1);
+  uint8_t mapq2 = cm_mapq_single_split(d, err2, al2, len2, 2, d.second_err[r2], d.n_best[r2], d.n_second[r2], d.rep_len[r2], ncand2);
+  mapq1 = (uint8_t)(mapq1 * 1.2);
+  if (mapq1 > 60) mapq1 = 60;
+  mapq2 = (uint8_t)(mapq2 * 1.2);
+  if (mapq2 > 60) mapq2 = 60;
+  return mapq1 < mapq2 ? mapq1 : mapq2;  // force_mapq is -1: no supplement in split mode
+}
+
 // orientation o of a split pairing: 0 (+,-), 1 (-,+), 2 (+,+), 3 (-,-)  (mapping_generator.h:176-191)
 CM_HD int cm_split_s1(int o) { return o & 1; }
 CM_HD int cm_split_s2(int o) { return o == 0 || o == 3 ? 1 : 0; }
@@ -3581,15 +3595,8 @@ CM_HD void cm_emit_pairs_record(const CmDev &d, uint32_t pair, const CmPe &pe, u
     b = cm_ref_start_end_split(d, dp2, w2, s2, cm_read_ptr(d, r2), (int)len2);
   }
   const uint16_t al1 = (uint16_t)(a.ref_end - a.ref_start + 1), al2 = (uint16_t)(b.ref_end - b.ref_start + 1);
-  uint8_t mapq1 = cm_mapq_single_split(d, e1, al1, (int)len1, 2, d.second_err[r1], d.n_best[r1], d.n_second[r1], d.rep_len[r1],
-                                       s1 == 0 ? d.fcp[r1] : d.fcn[r1]);
-  uint8_t mapq2 = cm_mapq_single_split(d, e2, al2, (int)len2, 2, d.second_err[r2], d.n_best[r2], d.n_second[r2], d.rep_len[r2],
-                                       s2 == 0 ? d.fcp[r2] : d.fcn[r2]);
-  mapq1 = (uint8_t)(mapq1 * 1.2);
-  if (mapq1 > 60) mapq1 = 60;
-  mapq2 = (uint8_t)(mapq2 * 1.2);
-  if (mapq2 > 60) mapq2 = 60;
-  const uint8_t mapq = mapq1 < mapq2 ? mapq1 : mapq2;  // force_mapq is -1: no supplement in split mode
+  const uint8_t mapq = cm_mapq_paired_split(d, pair, e1, e2, al1, al2, (int)len1, (int)len2, s1 == 0 ? d.fcp[r1] : d.fcn[r1],
+                                            s2 == 0 ? d.fcp[r2] : d.fcn[r2]);
   const uint8_t is_unique = (pe.n_best == 1 || d.n_best[r1] == 1 || d.n_best[r2] == 1) ? 1 : 0;
   if constexpr (SAM) {  // flags mapping_generator.h:613-631, EmplaceBackPairedEndMappingRecord<SAMMapping> (mapping_generator.cc:84-108),
                         // PairedEndMappingInMemory::GetFragmentLength (mapping_in_memory.h:83-90) whatever the chromosomes

@@ -620,6 +620,14 @@ class ChromapGPU:
         if self.L.cmgpu_write_sam_header(names, C.cast(self.reference_lengths(), C.c_void_p), len(self.names), path.encode()) != 0:
             raise ChromapError("cannot write %s" % path)
 
+    def debug_mapq(self, kind, error_threshold, reads, pairs):
+        """test hook: the MAPQ stage functions on their own (_capi.debug_mapq)"""
+        return _capi.debug_mapq(self.L, self.ctx, kind, error_threshold, reads, pairs)
+
+    def debug_mapq_tables(self):
+        """test hook: the resident MAPQ tables (_capi.debug_mapq_tables)"""
+        return _capi.debug_mapq_tables(self.L, self.ctx)
+
     def download_batch(self, n):
         """resident batch back on the host: (b1, o1, b2, o2)"""
         o1 = np.zeros(n + 1, np.uint32)

@@ -148,6 +148,27 @@ int cmgpu_reference_lengths(cmgpu_ctx *ctx, uint32_t *lengths, uint32_t capacity
  * for reads with rlen > 0; *n_out = 2 n S. */
 int cmgpu_debug_array(cmgpu_ctx *ctx, const char *name, uint32_t *out, uint64_t capacity, uint64_t *n_out);
 
+/* ---- the MAPQ functions on their own (tests/test_gpu_mapq.py) ----
+ * n cases, one lane each, through the stage functions the mapping path calls (GetMAPQForSingleEndRead / GetMAPQForPairedEndRead,
+ * mapping_generator.h:920-1192), with the context's two lookup tables as they stand in HBM.  Case i is pair i with reads 2 i and
+ * 2 i + 1; the single-read kinds look at read 2 i only.  The cases are two column-major int32 matrices in host memory:
+ *   reads  9 columns of 2 n values: num_errors, alignment_length (< 65536), read_length, min_num_errors, second_min_num_errors,
+ *          num_best_mappings, num_second_best_mappings, repetitive_seed_length, candidates on the mapping's strand (split kinds)
+ *   pairs  6 columns of n values: max_num_error_difference (single-read kinds), then the pair's min_sum_errors,
+ *          second_min_sum_errors, num_best_mappings, num_second_best_mappings and force_mapq (CMGPU_MAPQ_PAIRED)
+ * error_threshold is the -e the split kinds read.  out: n bytes, the MAPQ as the record would carry it.  Arguments for which the
+ * reference's arithmetic is undefined (a length of 0, a division by num_second_best_mappings / diff + 1 == 0) are the caller's to
+ * leave out.  The call reads and writes nothing of the mapped batch and needs none. */
+#define CMGPU_MAPQ_SINGLE 0        /* cm_mapq_single: single-end and paired-end reads without split alignment */
+#define CMGPU_MAPQ_SPLIT 1         /* cm_mapq_single_split */
+#define CMGPU_MAPQ_PAIRED 2        /* cm_mapq_paired */
+#define CMGPU_MAPQ_PAIRED_SPLIT 3  /* cm_mapq_paired_split: the pair's value under --split-alignment */
+int cmgpu_debug_mapq(cmgpu_ctx *ctx, int kind, int32_t error_threshold, uint64_t n, const int32_t *reads, const int32_t *pairs,
+                     uint8_t *out);
+/* The two tables themselves, downloaded: len_coef (65536 doubles: a < 50 ? 1 : 3 / log(a)) and nsec_break (*n_break entries:
+ * nsec_break[v] = the smallest n >= 1 with (int)(4.343 * log(n + 1) + 0.499) >= v).  Either array may be NULL. */
+int cmgpu_debug_mapq_tables(cmgpu_ctx *ctx, double *len_coef, uint32_t *nsec_break, uint32_t capacity, uint32_t *n_break);
+
 #ifdef __cplusplus
 }
 #endif

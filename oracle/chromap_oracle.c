@@ -3230,3 +3230,40 @@ long ora_write_se_bc(const ora_ref *ref, const ora_params *p, ora_record_bc *rec
   fclose(f);
   return lines;
 }
+
+/* The MAPQ functions above on their own, for tests/test_mapq_cpu.py: n cases as two column-major int32 matrices -- reads: 9 columns
+ * of 2 n values (num_errors, alignment_length, read_length, min_num_errors, second_min_num_errors, num_best_mappings,
+ * num_second_best_mappings, repetitive_seed_length, candidates on the mapping's strand), pairs: 6 columns of n values
+ * (max_num_error_difference, then the pair's min_sum_errors, second_min_sum_errors, num_best_mappings, num_second_best_mappings,
+ * force_mapq).  Case i is pair i, reads 2 i and 2 i + 1.  kind: 0 mapq_single, 1 mapq_single_split, 2 mapq_paired, 3 mapq_paired_split
+ * (reads 2 i only for 0 and 1). */
+int ora_mapq_batch(int kind, int error_threshold, uint64_t n, const int32_t *reads, const int32_t *pairs, uint8_t *out) {
+  if (kind < 0 || kind > 3) return -1;
+  ora_ctx *c = (ora_ctx *)calloc(1, sizeof(ora_ctx));
+  if (!c) return -1;
+  c->p.error_threshold = error_threshold;
+  const size_t n2 = 2 * (size_t)n;
+  meta_t m[2];
+  pe_meta_t pe;
+  memset(m, 0, sizeof m);
+  memset(&pe, 0, sizeof pe);
+  for (uint64_t i = 0; i < n; ++i) {
+    int err[2], len[2];
+    uint16_t al[2];
+    for (int k = 0; k < 2; ++k) {
+      const size_t r = 2 * (size_t)i + (size_t)k;
+      err[k] = reads[r]; al[k] = (uint16_t)reads[n2 + r]; len[k] = reads[2 * n2 + r];
+      m[k].min_err = reads[3 * n2 + r]; m[k].second_err = reads[4 * n2 + r]; m[k].n_best = reads[5 * n2 + r];
+      m[k].n_second = reads[6 * n2 + r]; m[k].rep_len = (uint32_t)reads[7 * n2 + r];
+      m[k].pos_cand.n = (size_t)(uint32_t)reads[8 * n2 + r]; /* the mapping is on the + strand */
+    }
+    if (kind == 0) out[i] = mapq_single(c, err[0], al[0], len[0], pairs[i], &m[0]);
+    else if (kind == 1) out[i] = mapq_single_split(c, err[0], al[0], len[0], pairs[i], &m[0], (uint32_t)m[0].pos_cand.n);
+    else if (kind == 2) {
+      pe.min_sum = pairs[n + i]; pe.second_sum = pairs[2 * n + i]; pe.n_best = pairs[3 * n + i]; pe.n_second = pairs[4 * n + i];
+      out[i] = mapq_paired(c, err[0], err[1], al[0], al[1], len[0], len[1], pairs[5 * n + i], &pe, &m[0], &m[1]);
+    } else out[i] = mapq_paired_split(c, 0, 0, err[0], err[1], al[0], al[1], len[0], len[1], -1, &m[0], &m[1]);
+  }
+  free(c);
+  return 0;
+}

@@ -272,6 +272,14 @@ typedef struct ora_trace {
 } ora_trace;
 void ora_set_trace(ora_ctx *c, ora_trace *trace /* n entries, or NULL */);
 
+/* GetMAPQForSingleEndRead / GetMAPQForPairedEndRead (mapping_generator.h:920-1192) on n cases of plain arguments, through the
+ * functions the mapping calls use.  reads: 9 columns of 2 n int32 values (num_errors, alignment_length, read_length,
+ * min_num_errors, second_min_num_errors, num_best_mappings, num_second_best_mappings, repetitive_seed_length, candidates on the
+ * mapping's strand), pairs: 6 columns of n values (max_num_error_difference, the pair's min_sum_errors, second_min_sum_errors,
+ * num_best_mappings, num_second_best_mappings, force_mapq); case i is pair i, reads 2 i and 2 i + 1.  kind 0: single-end form,
+ * 1: the same with split_alignment, 2: paired-end form, 3: paired-end form with split_alignment.  out: n bytes.  0 on success. */
+int ora_mapq_batch(int kind, int error_threshold, uint64_t n, const int32_t *reads, const int32_t *pairs, uint8_t *out);
+
 /* mapping_writer.h:166-376 (low-mem) / chromap.h:1322-1355 (in-memory) + writer
  * mapping_writer.cc:72-117 (PE bulk BED).  Sorts records in place. Returns #lines. */
 long ora_write_bed_pe(const ora_ref *ref, const ora_params *p, ora_record *rec, long n,

@@ -1,7 +1,10 @@
 // Host drivers for two per-read stage functions of chromap_amd/csrc/cm_stages.h, each against the function that defines its result:
 //   cm_s3b_short (the short-list form of S3b: sorting network, one sweep)   against cm_s3b_candidates_lds (cm_s3b_core)
 //   cm_pack_read_planes_w (the read's bit planes, four bytes at a time)    against cm_pack_read_planes_any
-// Built into a library of its own by tests/hostemu_valu_lib.py for tests/test_s3b_short_cpu.py and tests/test_pack_planes_cpu.py.
+// and a driver for the MAPQ functions on plain arguments (hostemu_mapq_batch: what cmgpu_debug_mapq runs on the device), compared in
+// tests/test_mapq_cpu.py with the model of tests/mapq_model.py and the oracle.
+// Built into a library of its own by tests/hostemu_valu_lib.py for tests/test_s3b_short_cpu.py, tests/test_pack_planes_cpu.py and
+// tests/test_mapq_cpu.py; tests/hostemu/mapq_san_main.cpp includes this file for its sanitizer build.
 // Test infrastructure only.
 #include <stdint.h>
 #include <stdlib.h>
@@ -108,4 +111,53 @@ extern "C" long hostemu_pack_planes_check(const uint8_t *pool, uint32_t pool_len
     }
   }
   return cases;
+}
+
+// The MAPQ functions on their own (the device hook cmgpu_debug_mapq, include/chromap_amd_debug.h, on the host): n cases as the same two
+// column-major matrices -- reads: 9 columns of 2 n values (num_errors, alignment_length, read_length, min_err, second_err, n_best,
+// n_second, rep_len, strand_ncand), pairs: 6 columns of n values (max_diff, min_sum, second_sum, n_best, n_second, force_mapq) -- with
+// the tables of cm_build_len_coef / cm_build_nsec_break.  kind: 0 cm_mapq_single, 1 cm_mapq_single_split, 2 cm_mapq_paired,
+// 3 cm_mapq_paired_split.  coef_out (65536) / brk_out (capacity brk_cap) / n_brk_out: the tables themselves, or NULL.
+extern "C" int hostemu_mapq_batch(int kind, int e, uint64_t n, const int32_t *reads, const int32_t *pairs, uint8_t *out, double *coef_out,
+                                  uint32_t *brk_out, uint32_t brk_cap, uint32_t *n_brk_out) {
+  static std::vector<double> coef;
+  static std::vector<uint32_t> brk;
+  if (coef.empty()) { cm_build_len_coef(coef); cm_build_nsec_break(brk); }
+  if (coef_out) memcpy(coef_out, coef.data(), coef.size() * 8);
+  if (n_brk_out) *n_brk_out = (uint32_t)brk.size();
+  if (brk_out) {
+    if (brk_cap < brk.size()) return -1;
+    memcpy(brk_out, brk.data(), brk.size() * 4);
+  }
+  if (kind < 0 || kind > 3 || n > (1ull << 30)) return -1;
+  CmDev d;
+  memset(&d, 0, sizeof d);
+  d.mq.len_coef = coef.data(); d.mq.nsec_break = brk.data(); d.mq.n_break = (int)brk.size();
+  d.p.e = e;
+  d.n_pairs = (uint32_t)n;
+  const size_t n2 = 2 * (size_t)n;
+  int32_t *col = const_cast<int32_t *>(reads);
+  d.min_err = col + 3 * n2; d.second_err = col + 4 * n2; d.n_best = col + 5 * n2; d.n_second = col + 6 * n2;
+  d.rep_len = reinterpret_cast<uint32_t *>(col + 7 * n2);
+  const int32_t *err = reads, *al = reads + n2, *len = reads + 2 * n2, *nc = reads + 8 * n2;
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint32_t r1 = 2 * (uint32_t)i, r2 = r1 + 1;
+    uint8_t q;
+    if (kind == 0) {
+      q = cm_mapq_single(d, err[r1], (uint16_t)al[r1], len[r1], pairs[i], d.second_err[r1], d.n_best[r1], d.n_second[r1], d.rep_len[r1]);
+    } else if (kind == 1) {
+      q = cm_mapq_single_split(d, err[r1], (uint16_t)al[r1], len[r1], pairs[i], d.second_err[r1], d.n_best[r1], d.n_second[r1], d.rep_len[r1],
+                               (uint32_t)nc[r1]);
+    } else if (kind == 2) {
+      CmPe pe;
+      pe.min_sum = pairs[n + i]; pe.second_sum = pairs[2 * n + i]; pe.n_best = pairs[3 * n + i]; pe.n_second = pairs[4 * n + i];
+      pe.f_dir = pe.f_i1 = pe.f_i2 = 0;
+      q = cm_mapq_paired(d, (uint32_t)i, err[r1], err[r2], (uint16_t)al[r1], (uint16_t)al[r2], len[r1], len[r2], pairs[5 * n + i], pe);
+    } else {
+      q = cm_mapq_paired_split(d, (uint32_t)i, err[r1], err[r2], (uint16_t)al[r1], (uint16_t)al[r2], len[r1], len[r2], (uint32_t)nc[r1],
+                               (uint32_t)nc[r2]);
+    }
+    out[i] = q;
+  }
+  return 0;
 }

@@ -102,8 +102,22 @@ def lib():
     L.ora_write_bed_pe.argtypes = [C.POINTER(OraRef), C.POINTER(OraParams), C.c_void_p, C.c_long, C.c_char_p]
     L.ora_read_fastx.restype = C.c_long
     L.ora_read_fastx.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.ora_mapq_batch.restype = C.c_int
+    L.ora_mapq_batch.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     _LIB = L
     return L
+
+
+def mapq_batch(kind, e, reads, pairs):
+    """the oracle's MAPQ functions on plain arguments: reads int32 [9, 2 n], pairs int32 [6, n] -> uint8 [n]"""
+    import numpy as np
+    reads = np.ascontiguousarray(reads, dtype=np.int32)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+    n = pairs.shape[1]
+    assert reads.shape == (9, 2 * n) and pairs.shape == (6, n)
+    out = np.full(n, 0xEE, np.uint8)
+    assert lib().ora_mapq_batch(kind, e, n, reads.ctypes.data, pairs.ctypes.data, out.ctypes.data) == 0
+    return out
 
 
 def params(preset=None, **kw):
