@@ -70,8 +70,10 @@ __global__ __launch_bounds__(BZ_LANES, 2) void k_bgzf_deflate(const uint8_t *__r
     if (g.t == 0) sizes[b] = total;
   }
 }
-// block b of the chunk to out + (the sizes of the blocks before it)
-__global__ __launch_bounds__(BZ_LANES) void k_bgzf_gather(const uint8_t *__restrict__ slots, const uint32_t *__restrict__ sizes, uint8_t *__restrict__ out) {
+// block b of the chunk to out + (the sizes of the blocks before it).  coff (the chunk's part of the store's offset table): block b's
+// offset in the store -- `used` bytes stand before the chunk -- and behind the chunk's last block the offset of whatever follows
+__global__ __launch_bounds__(BZ_LANES) void k_bgzf_gather(const uint8_t *__restrict__ slots, const uint32_t *__restrict__ sizes, uint8_t *__restrict__ out,
+                                                       uint64_t *__restrict__ coff, uint64_t used) {
   __shared__ uint32_t before;
   const uint32_t b = blockIdx.x;
   if (threadIdx.x == 0) before = 0;
@@ -83,6 +85,10 @@ __global__ __launch_bounds__(BZ_LANES) void k_bgzf_gather(const uint8_t *__restr
   const uint8_t *src = slots + (size_t)b * CM_DF_SLOT;
   uint8_t *dst = out + before;
   const uint32_t n = sizes[b];
+  if (threadIdx.x == 0) {
+    coff[b] = used + before;
+    if (b + 1 == gridDim.x) coff[b + 1] = used + before + n;
+  }
   // whole words where the destination is aligned (a slot is), the bytes around them one by one
   const uint32_t head = (uint32_t)((4u - (reinterpret_cast<uintptr_t>(dst) & 3u)) & 3u);
   const uint32_t h = head < n ? head : n;
@@ -103,16 +109,19 @@ static const CmCrcX2n &bz_x2n() {
 }
 
 // n_bytes of device memory at `text` into the compressed store
-static int bz_compress_device(cmgpu_ctx *c, const uint8_t *text, uint64_t n_bytes, uint64_t *n_blocks, uint64_t *n_out) {
+// (src: CM_BZ_SRC_*, what `text` is -- the tabix indexer reads the same text again)
+static int bz_compress_device(cmgpu_ctx *c, const uint8_t *text, uint64_t n_bytes, int src, uint64_t *n_blocks, uint64_t *n_out) {
   hipStream_t s = c->stream;
   c->bgzf_bytes = 0;
   c->bgzf_blocks = 0;
   c->bgzf_text_bytes = 0;
+  c->bgzf_src = CM_BZ_SRC_NONE;
   const uint64_t n_slices = (n_bytes + CM_DF_SLICE - 1) / CM_DF_SLICE;
   if (n_slices) {
     const uint32_t chunk = n_slices < BZ_CHUNK ? (uint32_t)n_slices : BZ_CHUNK;
     const uint32_t groups = chunk < BZ_GROUPS ? chunk : BZ_GROUPS;
-    if (c->bgzf_slots.ensure((size_t)chunk * CM_DF_SLOT) || c->bgzf_tok.ensure((size_t)groups * CM_DF_SLICE * 4) || c->bgzf_sizes.ensure((size_t)chunk * 4)) {
+    if (c->bgzf_slots.ensure((size_t)chunk * CM_DF_SLOT) || c->bgzf_tok.ensure((size_t)groups * CM_DF_SLICE * 4) || c->bgzf_sizes.ensure((size_t)chunk * 4) ||
+        c->bgzf_coff.ensure((size_t)(n_slices + 1) * 8)) {
       cm_set_error(c, "out of device memory (BGZF output: scratch)"); return CMGPU_ENOMEM;
     }
   }
@@ -135,7 +144,8 @@ static int bz_compress_device(cmgpu_ctx *c, const uint8_t *text, uint64_t n_byte
     // (the first guess: a third of the text, which SAM and pairs text stay under; then doubling)
     const int rc = cm_grow_buf(c, c->bgzf, used, used + add + 16, n_bytes / 3 + (1u << 20), s, "BGZF output");
     if (rc) return rc;
-    hipLaunchKernelGGL(k_bgzf_gather, dim3(m), dim3(BZ_LANES), 0, s, (const uint8_t *)c->bgzf_slots.p, (const uint32_t *)c->bgzf_sizes.p, (uint8_t *)c->bgzf.p + used);
+    hipLaunchKernelGGL(k_bgzf_gather, dim3(m), dim3(BZ_LANES), 0, s, (const uint8_t *)c->bgzf_slots.p, (const uint32_t *)c->bgzf_sizes.p, (uint8_t *)c->bgzf.p + used,
+                       (uint64_t *)c->bgzf_coff.p + first, used);
     CM_HIPCHECK(c, hipGetLastError());
     used += add;
   }
@@ -143,6 +153,9 @@ static int bz_compress_device(cmgpu_ctx *c, const uint8_t *text, uint64_t n_byte
   c->bgzf_bytes = used;
   c->bgzf_blocks = n_slices;
   c->bgzf_text_bytes = n_bytes;
+  c->bgzf_src = src;
+  c->bgzf_src_ptr = src == CM_BZ_SRC_DEVICE ? text : nullptr;
+  c->bgzf_text_gen = c->text_gen;
   if (n_blocks) *n_blocks = n_slices;
   if (n_out) *n_out = used;
   return CMGPU_OK;
@@ -157,12 +170,12 @@ extern "C" int cmgpu_bgzf_compress(cmgpu_ctx *c, const void *text, uint64_t n_by
     CM_HIPCHECK(c, hipMemcpyAsync(c->bgzf_in.p, text, n_bytes, hipMemcpyHostToDevice, c->stream));
     dev = static_cast<const uint8_t *>(c->bgzf_in.p);
   }
-  return bz_compress_device(c, dev, n_bytes, n_blocks, n_out);
+  return bz_compress_device(c, dev, n_bytes, on_device ? CM_BZ_SRC_DEVICE : CM_BZ_SRC_UPLOAD, n_blocks, n_out);
 }
 extern "C" int cmgpu_store_compress_text(cmgpu_ctx *c, uint64_t *n_blocks, uint64_t *n_out) {
   if (!c) return CMGPU_EINVAL;
   CM_HIPCHECK(c, cm_enter(c));
-  return bz_compress_device(c, static_cast<const uint8_t *>(c->text.p), c->text_bytes, n_blocks, n_out);
+  return bz_compress_device(c, static_cast<const uint8_t *>(c->text.p), c->text_bytes, CM_BZ_SRC_STORE, n_blocks, n_out);
 }
 extern "C" int cmgpu_bgzf_info(const cmgpu_ctx *c, uint64_t *n_blocks, uint64_t *n_bytes, uint64_t *n_text_bytes) {
   if (!c) return CMGPU_EINVAL;

@@ -661,6 +661,17 @@ static void bgzf_finish(Run &r) {
   if (cmgpu_bgzf_write_eof(r.a.out_path.c_str()) != CMGPU_OK) die("Cannot write " + r.a.out_path);
   r.bgzf_bytes += 28;
 }
+// --output-tbi: the tabix index of the section cx compressed last, whose blocks stand at `base` in the output file.  The output is
+// complete by now: a text the indexer refuses ends the run with the indexer's words, and without an index file
+static void write_tbi(Run &r, cmgpu_ctx *cx, uint64_t base) {
+  const std::string path = r.a.out_path + ".tbi";
+  const double t0 = now_s();
+  uint64_t n = 0;
+  const int rc = cmgpu_bgzf_index_tabix(cx, base, &n);
+  if (rc != CMGPU_OK) { remove(path.c_str()); ck(cx, rc); }
+  ck(cx, cmgpu_tabix_write(cx, path.c_str()));
+  fprintf(stderr, "Built the tabix index on the device and wrote %s (%llu bytes before compression) in %.3fs.\n", path.c_str(), (unsigned long long)n, now_s() - t0);
+}
 // ---- the writers: each returns the number of lines written (negative: the file could not be written)
 // sort + duplicate removal + MAPQ filter + SAM lines on the device, from the reads and records in HBM
 static int64_t write_sam_device(Run &r) {
@@ -766,8 +777,10 @@ static int64_t write_bed(Run &r) {
     }
   }
   // sections in rank order: the owners hold contiguous, increasing chromosome ranges
+  const uint64_t tbi_base = r.bgzf_bytes;
   for (cmgpu_ctx *cx : r.ctxs) write_section(r, cx);  // (emptied at the start)
   bgzf_finish(r);
+  if (a.output_tbi) write_tbi(r, r.ctx(), tbi_base);  // (one context: validate())
   r.t_post = now_s() - t0;
   fprintf(stderr, "Sorted, deduplicated and formatted %llu bytes on the device in %.3fs, wrote them in %.3fs.\n", (unsigned long long)nbytes,
           t1 - t0, now_s() - t1);

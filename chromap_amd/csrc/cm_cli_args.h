@@ -60,6 +60,7 @@ struct Args {
   int k = 17, w = 7, device = 0, gpus = 1;
   bool force_exchange = false;
   bool output_bgzf = false;  // --output-bgzf: the output file is BGZF blocks, compressed on the device
+  bool output_tbi = false;   // --output-tbi: <output>.tbi, the tabix index of the BGZF output, built on the device
   uint32_t batch_pairs = 4000000;  // multiple of the reference's 500000-pair read batch
 };
 
@@ -184,6 +185,7 @@ static Args parse(int argc, char **argv) {
     else if (o == "--gpus") a.gpus = atoi(need("--gpus"));           // one context + host thread per GPU, records exchanged to chromosome owners
     else if (o == "--force-exchange") a.force_exchange = true;      // the multi-GPU code path with one GPU
     else if (o == "--output-bgzf") a.output_bgzf = true;
+    else if (o == "--output-tbi") a.output_tbi = true;
     else if (o == "--host-ingest") a.host_ingest = true;   // kseq-style host parser (the fallback for text the device ingest refuses)
     else if (o == "--ingest-chunk-mb") { a.chunk_bytes = (size_t)atol(need("--ingest-chunk-mb")) << 20; a.chunk_given = true; }
     else if (o == "--batch-pairs") a.batch_pairs = (uint32_t)atol(need("--batch-pairs"));
@@ -204,6 +206,8 @@ static Args parse(int argc, char **argv) {
              "  --output-bgzf   the output file as BGZF blocks (bgzip's format, readable by tabix / pairix / samtools), compressed on the\n"
              "                  device; nothing is inferred from the output file's name.  Not where the host renders the text:\n"
              "                  --host-ingest --SAM, --SAM --barcode-translate\n"
+             "  --output-tbi    with --output-bgzf and BED or single-end --TagAlign output on one GPU: the tabix index of the output file\n"
+             "                  (what `tabix -p bed` would make of it), built on the device and written to <output>.tbi\n"
              "  --summary FILE  per-barcode CSV (one row for bulk data): barcode,total,duplicate,unmapped,lowmapq counted on the device;\n"
              "                  cachehit, fric, estfrip and numcacheslots are written as 0 (the minimizer cache is not modelled)\n");
       exit(0);
@@ -259,6 +263,14 @@ static void validate(Args &a) {
   if (a.output_bgzf && a.out_sam && a.host_ingest) die("--output-bgzf with --host-ingest --SAM is outside this build (the host renders that text; compress the file with bgzip)");
   if (a.output_bgzf && a.out_sam && !a.translate_path.empty())
     die("--output-bgzf with --SAM --barcode-translate is outside this build (the host renders that text; compress the file with bgzip)");
+  // the index is made of one context's sorted BED text and its blocks
+  if (a.output_tbi) {
+    if (!a.output_bgzf) die("--output-tbi needs --output-bgzf (the index is that of the BGZF blocks)");
+    if (a.out_sam) die("--output-tbi with --SAM is outside this build (a tabix index of SAM text; BAM and its index are not written)");
+    if (a.out_pairs) die("--output-tbi with pairs output is outside this build (pairs text takes a .px2 index, which is not built)");
+    if (a.out_tagalign && paired) die("--output-tbi with paired-end --TagAlign is outside this build (two lines per pair: the text is not sorted by start)");
+    if (a.gpus > 1 || a.force_exchange) die("--output-tbi with --gpus > 1 or --force-exchange is outside this build (the output has one section per GPU)");
+  }
   // the reference allocates in its in-memory flavour only (chromap.h:1305-1353): with --low-mem or a preset the flag does nothing there and here
   if (a.p.allocate_multi_mappings && !a.p.low_memory_mode) {
     if (a.out_sam) die("--allocate-multi-mappings with --SAM is outside this build (the SAM writers have no allocation stage)");

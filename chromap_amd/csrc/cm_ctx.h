@@ -13,6 +13,11 @@
 
 #define CM_MAX_EVENTS 32
 #define CM_MAX_W_HOST 32
+// what the compressed store was made of (cmgpu_ctx::bgzf_src)
+#define CM_BZ_SRC_NONE 0
+#define CM_BZ_SRC_STORE 1   // the text store
+#define CM_BZ_SRC_UPLOAD 2  // bytes of the host's, uploaded to bgzf_in
+#define CM_BZ_SRC_DEVICE 3  // the caller's device memory
 
 struct DevBuf {
   void *p = nullptr;
@@ -216,6 +221,14 @@ struct cmgpu_ctx {
   // the compressed store (cm_bgzf_out.hip): BGZF blocks back to back; the chunk's slots, the groups' tokens, the blocks' sizes, an uploaded text
   DevBuf bgzf, bgzf_slots, bgzf_tok, bgzf_sizes, bgzf_in;
   uint64_t bgzf_bytes = 0, bgzf_blocks = 0, bgzf_text_bytes = 0;
+  // for the tabix index (cm_tabix.hip): the blocks' offsets in the store (bgzf_blocks + 1 64-bit words: the exclusive prefix of their
+  // sizes), and the device text the store was made of -- CM_BZ_SRC_*; `bgzf_src_ptr` where the caller's own device memory was compressed
+  DevBuf bgzf_coff;
+  int bgzf_src = 0;
+  const uint8_t *bgzf_src_ptr = nullptr;
+  std::vector<uint8_t> tabix;  // the last index's payload (cmgpu_bgzf_index_tabix)
+  bool tabix_have = false;
+  uint64_t text_gen = 0, bgzf_text_gen = 0;  // text_gen: counts the texts published to the text store; bgzf_text_gen: the one that was compressed
   uint64_t store_n = 0, store_cap = 0, text_bytes = 0, text_lines = 0;
   uint64_t alloc_multi = 0, alloc_kept = 0, alloc_without_overlap = 0;  // the last cmgpu_store_format's allocation (cmgpu_store_allocation_info)
   double alloc_seconds = 0, alloc_draw_seconds = 0;                     // the stage's time, and its draw's on the host (cmgpu_get_option alloc_us, alloc_draw_us)
@@ -312,7 +325,7 @@ struct cmgpu_ctx {
             &hit_off, &round2, &rep_cnt, &rep_len, &hbuf, &hcnt, &n_pos_hit, &ncp, &ncn, &aug, &res_neg, &res_pos,
             &resc_n, &resc_p, &m_tot, &m_off, &mbuf, &mcnt, &mcp, &mcn, &force0, &fbuf, &fcnt, &fcp, &fcn, &alive,
             &dpos, &derr, &dsplit, &nv, &v_off, &v_err, &v_end, &ndp, &ndn, &min_err, &second_err, &n_best, &n_second, &pe_min, &pe_second, &pe_nbest,
-            &pe_nsecond, &pe_first, &pe_i1, &pe_i2, &pe_choice, &rec, &rec_ok, &scan_tmp, &stats, &partials, &wl, &pow10_tab, &bcb, &bcq, &bco, &bc_key, &bc_ok, &wl_num, &bt_tab, &bt_blob, &store, &store_bc, &text, &bgzf, &bgzf_slots, &bgzf_tok, &bgzf_sizes, &bgzf_in, &sam_rec, &sam_cigar, &sam_md, &sam_z, &part_cnt, &mm_cursor, &mm_marks, &rid_rank, &ref_off_r, &ref_len_r, &pairs_rank,
+            &pe_nsecond, &pe_first, &pe_i1, &pe_i2, &pe_choice, &rec, &rec_ok, &scan_tmp, &stats, &partials, &wl, &pow10_tab, &bcb, &bcq, &bco, &bc_key, &bc_ok, &wl_num, &bt_tab, &bt_blob, &store, &store_bc, &text, &bgzf, &bgzf_slots, &bgzf_tok, &bgzf_sizes, &bgzf_in, &bgzf_coff, &sam_rec, &sam_cigar, &sam_md, &sam_z, &part_cnt, &mm_cursor, &mm_marks, &rid_rank, &ref_off_r, &ref_len_r, &pairs_rank,
             &ex.owner, &ex.send, &ex.counts, &ex.stage, &rec_dense, &rec_dense_b, &maxlen_dev, &bkt_fast, &ref_planes, &read_planes, &mm_stage, &coop_prof, &rs_pool, &rs_pool_off, &goff, &coop_slab, &hv_cnt, &hv_list, &perm_reads, &perm_pairs, &hv_tmp, &srt_cnt, &srt_list, &rs_list, &rs_cnt};
   }
 };

@@ -1,0 +1,330 @@
+// cm_tabix.hip -- the tabix index of the compressed store, built where the text and the blocks' offsets lie (cm_tabix.h has the
+// rules and the per-item functions; cm_bgzf_out.hip leaves the text's whereabouts and the offset table).  Everything as long as the text,
+// its lines or its raw chunks is a kernel, a scan or a sort on the context's stream; the host sees the number of lines, of references
+// and of chunks, the references' table and names, and the finished arrays, which it writes out as the payload.
+// Temporary device memory, all of it a CmTmpBuf released when the call returns: 24 bytes per line (start, begin, end, reference,
+// raw chunk), 16 bytes per 4 KiB of text (the tiles' newline counts and their scan), 44 bytes per raw chunk (key and number twice
+// for the sort, two virtual offsets, the merge flag), 24 per merged chunk, 8 per 16 kb window of every reference, 40 per reference
+// and its name, and rocprim's work areas.
+#include <stdio.h>
+#include <string.h>
+
+#include <string>
+#include <unordered_set>
+#include <vector>
+
+#include "cm_ctx.h"
+#include "cm_tabix.h"
+#include "cm_text_job.h"
+
+#define TX_LANES 256
+
+// the group type cm_tabix.h's tile functions ask for: the workgroup
+struct TxGroup {
+  static constexpr int G = TX_LANES;
+  uint32_t t;
+  uint32_t *xw;  // G / 64 words of shared memory: the waves' totals
+  __device__ __forceinline__ uint32_t scan(uint32_t v, uint32_t *total) {
+    const uint32_t wl = t & 63u, wv = t >> 6;
+    uint32_t incl = v;
+#pragma unroll
+    for (int dlt = 1; dlt < 64; dlt <<= 1) {
+      const uint32_t x = __shfl_up(incl, dlt, 64);
+      if (wl >= (uint32_t)dlt) incl += x;
+    }
+    if (wl == 63u) xw[wv] = incl;
+    __syncthreads();
+    uint32_t base = 0, tot = 0;
+#pragma unroll
+    for (int q = 0; q < G / 64; ++q) { const uint32_t x = xw[q]; base += (uint32_t)q < wv ? x : 0u; tot += x; }
+    __syncthreads();
+    *total = tot;
+    return base + incl - v;
+  }
+  __device__ __forceinline__ uint32_t sum(uint32_t v) { uint32_t tot; (void)scan(v, &tot); return tot; }
+};
+struct TxAtomics {
+  static __device__ __forceinline__ void min64(unsigned long long *p, unsigned long long v) { atomicMin(p, v); }
+};
+
+__global__ __launch_bounds__(TX_LANES) void k_tbx_count(const uint8_t *__restrict__ text, uint64_t n, uint64_t *__restrict__ cnt) {
+  __shared__ uint32_t xw[TX_LANES / 64];
+  TxGroup g;
+  g.t = threadIdx.x;
+  g.xw = xw;
+  const uint32_t c = cm_tbx_tile_count(g, text, n, blockIdx.x);
+  if (g.t == 0) cnt[blockIdx.x] = c;
+}
+__global__ __launch_bounds__(TX_LANES) void k_tbx_starts(const uint8_t *__restrict__ text, uint64_t n, const uint64_t *__restrict__ first, uint64_t *__restrict__ lstart) {
+  __shared__ uint32_t xw[TX_LANES / 64];
+  TxGroup g;
+  g.t = threadIdx.x;
+  g.xw = xw;
+  cm_tbx_tile_starts(g, text, n, blockIdx.x, first[blockIdx.x], lstart);
+}
+__global__ __launch_bounds__(TX_LANES) void k_tbx_parse(CmTbxArrays d) {
+  const uint64_t i = (uint64_t)blockIdx.x * TX_LANES + threadIdx.x;
+  if (i < d.n_lines) cm_tbx_line_parse<TxAtomics>(d, i);
+}
+// (no lane leaves early: the wave's lanes meet to raise their reference's n_intv with one atomic where they all have the same one)
+__global__ __launch_bounds__(TX_LANES) void k_tbx_flags(CmTbxArrays d) {
+  const uint64_t i = (uint64_t)blockIdx.x * TX_LANES + threadIdx.x;
+  uint32_t t = ~0u, want = 0;
+  unsigned long long e = CM_TBX_NO_ERROR;
+  if (i < d.n_lines) want = cm_tbx_line_flags_core(d, i, &t, &e);
+  if (e != CM_TBX_NO_ERROR) atomicMin(d.err, e);
+  const uint32_t t0 = __shfl(t, 0, 64);
+  if (__all(t == t0)) {
+#pragma unroll
+    for (int dlt = 32; dlt > 0; dlt >>= 1) { const uint32_t x = __shfl_xor(want, dlt, 64); want = x > want ? x : want; }
+    if ((threadIdx.x & 63u) == 0 && t != ~0u) atomicMax(&d.ref[t].n_intv, want);
+  } else if (t != ~0u) {
+    atomicMax(&d.ref[t].n_intv, want);
+  }
+}
+__global__ __launch_bounds__(TX_LANES) void k_tbx_emit(CmTbxArrays d) {
+  const uint64_t i = (uint64_t)blockIdx.x * TX_LANES + threadIdx.x;
+  if (i < d.n_lines) cm_tbx_line_emit<TxAtomics>(d, i);
+}
+// reference r's name to blob + off[r]
+__global__ __launch_bounds__(TX_LANES) void k_tbx_names(const uint8_t *__restrict__ text, const CmTbxRef *__restrict__ ref, const uint64_t *__restrict__ off, uint32_t n_ref,
+                                                     uint8_t *__restrict__ blob) {
+  const uint32_t r = blockIdx.x * TX_LANES + threadIdx.x;
+  if (r >= n_ref) return;
+  const uint8_t *src = text + ref[r].name_at;
+  uint8_t *dst = blob + off[r];
+  for (uint32_t i = 0; i < ref[r].name_len; ++i) dst[i] = src[i];
+}
+__global__ __launch_bounds__(TX_LANES) void k_tbx_chunk_flags(const uint64_t *__restrict__ key, const uint32_t *__restrict__ perm, const uint64_t *__restrict__ cbeg,
+                                                           const uint64_t *__restrict__ cend, uint64_t n, uint32_t *__restrict__ flag) {
+  const uint64_t j = (uint64_t)blockIdx.x * TX_LANES + threadIdx.x;
+  if (j < n) flag[j] = cm_tbx_chunk_flag(key, perm, cbeg, cend, j);
+}
+__global__ __launch_bounds__(TX_LANES) void k_tbx_chunk_emit(const uint64_t *__restrict__ key, const uint32_t *__restrict__ perm, const uint64_t *__restrict__ cbeg,
+                                                          const uint64_t *__restrict__ cend, const uint32_t *__restrict__ midx, uint64_t n, CmTbxChunk *__restrict__ out) {
+  const uint64_t j = (uint64_t)blockIdx.x * TX_LANES + threadIdx.x;
+  if (j < n) cm_tbx_chunk_emit(key, perm, cbeg, cend, midx, n, j, out);
+}
+
+namespace {
+struct TxJob {
+  cmgpu_ctx *c;
+  hipStream_t s;
+  CmTmpBuf tmp;  // rocprim's work area
+  ~TxJob() { (void)hipStreamSynchronize(s); }
+  int enomem() { cm_set_error(c, "out of device memory (tabix index)"); return CMGPU_ENOMEM; }
+  int fail(const char *what, hipError_t e) { cm_set_error(c, std::string("tabix index, ") + what + ": " + hipGetErrorString(e)); return CMGPU_EHIP; }
+  // flags -> 1 + (number of the run each entry lies in), in place
+  int scan_flags(uint32_t *v, uint64_t n) {
+    size_t tb = 0;
+    (void)rocprim::inclusive_scan(nullptr, tb, v, v, (size_t)n, rocprim::plus<uint32_t>(), s);
+    if (tmp.ensure(tb + 256)) return enomem();
+    const hipError_t e = rocprim::inclusive_scan(tmp.p, tb, v, v, (size_t)n, rocprim::plus<uint32_t>(), s);
+    return e == hipSuccess ? CMGPU_OK : fail("scan", e);
+  }
+  // every window takes the smallest value from itself to the end: an empty one (all ones) that of the next window a line overlaps
+  int back_fill(unsigned long long *lin, uint64_t n) {
+    auto rev = rocprim::make_reverse_iterator(lin + n);
+    size_t tb = 0;
+    (void)rocprim::inclusive_scan(nullptr, tb, rev, rev, (size_t)n, rocprim::minimum<unsigned long long>(), s);
+    if (tmp.ensure(tb + 256)) return enomem();
+    const hipError_t e = rocprim::inclusive_scan(tmp.p, tb, rev, rev, (size_t)n, rocprim::minimum<unsigned long long>(), s);
+    return e == hipSuccess ? CMGPU_OK : fail("back-fill", e);
+  }
+  int format_error(unsigned long long word) {
+    cm_set_error(c, "tabix index: line " + std::to_string((word >> 3) + 1) + " " + cm_tbx_cause((uint32_t)(word & 7u)));
+    return CMGPU_EFORMAT;
+  }
+};
+static inline uint32_t tx_blocks(uint64_t n) { return (uint32_t)((n + TX_LANES - 1) / TX_LANES); }
+}  // namespace
+
+#define TX_CHECK(job, what, call)                                  \
+  do {                                                             \
+    const hipError_t e_ = (call);                                  \
+    if (e_ != hipSuccess) return (job).fail(what, e_);             \
+  } while (0)
+
+static int tx_index(cmgpu_ctx *c, const uint8_t *text, uint64_t n, uint64_t base, std::vector<uint8_t> &payload) {
+  if (n == 0) {
+    cm_tbx_serialize(nullptr, 0, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, payload);
+    return CMGPU_OK;
+  }
+  hipStream_t s = c->stream;
+  CmTmpBuf tcnt, toff, lstart, beg, end, tid, cidx, err, ref, name_off, names, lin_off, lin, ckey, skey, cval, perm, cbeg, cend, mflag, merged;
+  TxJob job;  // (declared behind the buffers: on every return it waits for the stream before they go)
+  job.c = c;
+  job.s = s;
+  CmTbxArrays d = {};
+  d.t.p = text;
+  d.t.n = n;
+  d.t.n_blocks = c->bgzf_blocks;
+  d.t.coff = (const uint64_t *)c->bgzf_coff.p;
+  d.t.base = base;
+  // ---- 1. line starts
+  const uint64_t n_tiles = (n + CM_TBX_TILE - 1) / CM_TBX_TILE;
+  if (n_tiles > 0x7fffffffull) { cm_set_error(c, "tabix index: the text is too long (8 TiB and more)"); return CMGPU_EINVAL; }
+  if (tcnt.ensure((n_tiles + 1) * 8) || toff.ensure((n_tiles + 1) * 8)) return job.enomem();
+  TX_CHECK(job, "memset", hipMemsetAsync((uint64_t *)tcnt.p + n_tiles, 0, 8, s));
+  hipLaunchKernelGGL(k_tbx_count, dim3((uint32_t)n_tiles), dim3(TX_LANES), 0, s, text, n, (uint64_t *)tcnt.p);
+  TX_CHECK(job, "line count", hipGetLastError());
+  { const int rc = cm_scan_u64(c, (const uint64_t *)tcnt.p, (uint64_t *)toff.p, (size_t)n_tiles + 1, job.tmp, s, "tabix index"); if (rc) return rc; }
+  uint64_t n_lines = 0;
+  uint8_t last = 0;
+  TX_CHECK(job, "line count", hipMemcpyAsync(&n_lines, (uint64_t *)toff.p + n_tiles, 8, hipMemcpyDeviceToHost, s));
+  TX_CHECK(job, "line count", hipMemcpyAsync(&last, text + n - 1, 1, hipMemcpyDeviceToHost, s));
+  TX_CHECK(job, "line count", cm_stream_sync(s));
+  if (last != '\n') {
+    cm_set_error(c, "tabix index: the text does not end with a newline (line " + std::to_string(n_lines + 1) + " is not complete)");
+    return CMGPU_EFORMAT;
+  }
+  if (n_lines > CM_TBX_MAX_LINES) { cm_set_error(c, "tabix index: more than 2^32 - 2 lines"); return CMGPU_EINVAL; }
+  if (lstart.ensure((n_lines + 1) * 8) || beg.ensure(n_lines * 4) || end.ensure(n_lines * 4) || tid.ensure(n_lines * 4) || cidx.ensure(n_lines * 4) ||
+      err.ensure(8)) return job.enomem();
+  d.n_lines = n_lines;
+  d.lstart = (const uint64_t *)lstart.p;
+  d.beg = (uint32_t *)beg.p;
+  d.end = (uint32_t *)end.p;
+  d.tid = (uint32_t *)tid.p;
+  d.cidx = (uint32_t *)cidx.p;
+  d.err = (unsigned long long *)err.p;
+  TX_CHECK(job, "memset", hipMemsetAsync(lstart.p, 0, 8, s));
+  TX_CHECK(job, "memset", hipMemsetAsync(err.p, 0xff, 8, s));
+  hipLaunchKernelGGL(k_tbx_starts, dim3((uint32_t)n_tiles), dim3(TX_LANES), 0, s, text, n, (const uint64_t *)toff.p, (uint64_t *)lstart.p);
+  TX_CHECK(job, "line starts", hipGetLastError());
+  // ---- 2. per line: columns, names' runs
+  hipLaunchKernelGGL(k_tbx_parse, dim3(tx_blocks(n_lines)), dim3(TX_LANES), 0, s, d);
+  TX_CHECK(job, "columns", hipGetLastError());
+  { const int rc = job.scan_flags(d.tid, n_lines); if (rc) return rc; }
+  uint32_t n_ref = 0;
+  unsigned long long word = CM_TBX_NO_ERROR;
+  TX_CHECK(job, "columns", hipMemcpyAsync(&n_ref, d.tid + (n_lines - 1), 4, hipMemcpyDeviceToHost, s));
+  TX_CHECK(job, "columns", hipMemcpyAsync(&word, d.err, 8, hipMemcpyDeviceToHost, s));
+  TX_CHECK(job, "columns", cm_stream_sync(s));
+  tcnt.release();
+  toff.release();
+  if (word != CM_TBX_NO_ERROR) return job.format_error(word);
+  // references, sortedness, raw chunks' heads
+  if (ref.ensure((size_t)n_ref * sizeof(CmTbxRef))) return job.enomem();
+  d.ref = (CmTbxRef *)ref.p;
+  TX_CHECK(job, "memset", hipMemsetAsync(ref.p, 0, (size_t)n_ref * sizeof(CmTbxRef), s));
+  hipLaunchKernelGGL(k_tbx_flags, dim3(tx_blocks(n_lines)), dim3(TX_LANES), 0, s, d);
+  TX_CHECK(job, "references", hipGetLastError());
+  { const int rc = job.scan_flags(d.cidx, n_lines); if (rc) return rc; }
+  uint32_t n_raw = 0;
+  std::vector<CmTbxRef> h_ref(n_ref);
+  TX_CHECK(job, "references", hipMemcpyAsync(&n_raw, d.cidx + (n_lines - 1), 4, hipMemcpyDeviceToHost, s));
+  TX_CHECK(job, "references", hipMemcpyAsync(&word, d.err, 8, hipMemcpyDeviceToHost, s));
+  TX_CHECK(job, "references", hipMemcpyAsync(h_ref.data(), ref.p, (size_t)n_ref * sizeof(CmTbxRef), hipMemcpyDeviceToHost, s));
+  TX_CHECK(job, "references", cm_stream_sync(s));
+  if (word != CM_TBX_NO_ERROR) return job.format_error(word);
+  // (host, per reference: where its name and its windows go)
+  std::vector<uint64_t> h_name_off((size_t)n_ref + 1, 0), h_lin_off((size_t)n_ref + 1, 0);
+  for (uint32_t r = 0; r < n_ref; ++r) {
+    h_name_off[r + 1] = h_name_off[r] + h_ref[r].name_len;
+    h_lin_off[r + 1] = h_lin_off[r] + h_ref[r].n_intv;
+  }
+  const uint64_t n_win = h_lin_off[n_ref], name_bytes = h_name_off[n_ref];
+  if (name_off.ensure(((size_t)n_ref + 1) * 8) || names.ensure(name_bytes + 16) || lin_off.ensure(((size_t)n_ref + 1) * 8) || lin.ensure(n_win * 8 + 16) ||
+      ckey.ensure((size_t)n_raw * 8) || skey.ensure((size_t)n_raw * 8) || cval.ensure((size_t)n_raw * 4) || perm.ensure((size_t)n_raw * 4) ||
+      cbeg.ensure((size_t)n_raw * 8) || cend.ensure((size_t)n_raw * 8) || mflag.ensure((size_t)n_raw * 4)) return job.enomem();
+  TX_CHECK(job, "upload", hipMemcpyAsync(name_off.p, h_name_off.data(), h_name_off.size() * 8, hipMemcpyHostToDevice, s));
+  TX_CHECK(job, "upload", hipMemcpyAsync(lin_off.p, h_lin_off.data(), h_lin_off.size() * 8, hipMemcpyHostToDevice, s));
+  TX_CHECK(job, "memset", hipMemsetAsync(lin.p, 0xff, n_win * 8, s));
+  d.lin_off = (const uint64_t *)lin_off.p;
+  d.lin = (unsigned long long *)lin.p;
+  d.ckey = (uint64_t *)ckey.p;
+  d.cbeg = (uint64_t *)cbeg.p;
+  d.cend = (uint64_t *)cend.p;
+  d.cval = (uint32_t *)cval.p;
+  hipLaunchKernelGGL(k_tbx_names, dim3(tx_blocks(n_ref)), dim3(TX_LANES), 0, s, text, (const CmTbxRef *)ref.p, (const uint64_t *)name_off.p, n_ref, (uint8_t *)names.p);
+  TX_CHECK(job, "names", hipGetLastError());
+  hipLaunchKernelGGL(k_tbx_emit, dim3(tx_blocks(n_lines)), dim3(TX_LANES), 0, s, d);
+  TX_CHECK(job, "raw chunks", hipGetLastError());
+  { const int rc = job.back_fill(d.lin, n_win); if (rc) return rc; }
+  // ---- 3. raw chunks by (reference, bin), file order kept; neighbours joined
+  unsigned bits = 16;
+  while (bits < 48 && (1ull << (bits - 16)) < n_ref) ++bits;
+  {
+    size_t tb = 0;
+    TX_CHECK(job, "sort", rocprim::radix_sort_pairs(nullptr, tb, d.ckey, (uint64_t *)skey.p, d.cval, (uint32_t *)perm.p, (size_t)n_raw, 0, bits, s));
+    if (job.tmp.ensure(tb + 256)) return job.enomem();
+    TX_CHECK(job, "sort", rocprim::radix_sort_pairs(job.tmp.p, tb, d.ckey, (uint64_t *)skey.p, d.cval, (uint32_t *)perm.p, (size_t)n_raw, 0, bits, s));
+  }
+  hipLaunchKernelGGL(k_tbx_chunk_flags, dim3(tx_blocks(n_raw)), dim3(TX_LANES), 0, s, (const uint64_t *)skey.p, (const uint32_t *)perm.p, (const uint64_t *)cbeg.p,
+                     (const uint64_t *)cend.p, (uint64_t)n_raw, (uint32_t *)mflag.p);
+  TX_CHECK(job, "merge", hipGetLastError());
+  { const int rc = job.scan_flags((uint32_t *)mflag.p, n_raw); if (rc) return rc; }
+  uint32_t n_merged = 0;
+  std::vector<uint8_t> h_names(name_bytes + 1);
+  std::vector<uint64_t> h_lin(n_win + 1);
+  TX_CHECK(job, "merge", hipMemcpyAsync(&n_merged, (uint32_t *)mflag.p + (n_raw - 1), 4, hipMemcpyDeviceToHost, s));
+  TX_CHECK(job, "merge", hipMemcpyAsync(h_names.data(), names.p, name_bytes, hipMemcpyDeviceToHost, s));
+  TX_CHECK(job, "merge", hipMemcpyAsync(h_lin.data(), lin.p, n_win * 8, hipMemcpyDeviceToHost, s));
+  TX_CHECK(job, "merge", cm_stream_sync(s));
+  // a name twice: its second run's first line is the offender (host: as many steps as there are references)
+  {
+    std::unordered_set<std::string> seen;
+    for (uint32_t r = 0; r < n_ref; ++r)
+      if (!seen.emplace((const char *)h_names.data() + h_name_off[r], (size_t)h_ref[r].name_len).second)
+        return job.format_error((unsigned long long)h_ref[r].first_line << 3 | CM_TBX_E_RECUR);
+  }
+  std::vector<CmTbxChunk> h_ch(n_merged);
+  if (merged.ensure((size_t)n_merged * sizeof(CmTbxChunk))) return job.enomem();
+  hipLaunchKernelGGL(k_tbx_chunk_emit, dim3(tx_blocks(n_raw)), dim3(TX_LANES), 0, s, (const uint64_t *)skey.p, (const uint32_t *)perm.p, (const uint64_t *)cbeg.p,
+                     (const uint64_t *)cend.p, (const uint32_t *)mflag.p, (uint64_t)n_raw, (CmTbxChunk *)merged.p);
+  TX_CHECK(job, "merge", hipGetLastError());
+  TX_CHECK(job, "merge", hipMemcpyAsync(h_ch.data(), merged.p, (size_t)n_merged * sizeof(CmTbxChunk), hipMemcpyDeviceToHost, s));
+  TX_CHECK(job, "merge", cm_stream_sync(s));
+  // ---- 4. the payload
+  cm_tbx_serialize(h_ref.data(), n_ref, n_lines, h_names.data(), h_name_off.data(), h_ch.data(), n_merged, h_lin.data(), h_lin_off.data(), payload);
+  return CMGPU_OK;
+}
+
+extern "C" int cmgpu_bgzf_index_tabix(cmgpu_ctx *c, uint64_t base_offset, uint64_t *n_bytes) {
+  if (!c) return CMGPU_EINVAL;
+  CM_HIPCHECK(c, cm_enter(c));
+  c->tabix.clear();
+  c->tabix_have = false;
+  if (n_bytes) *n_bytes = 0;
+  const uint8_t *text = nullptr;
+  switch (c->bgzf_src) {
+    case CM_BZ_SRC_STORE:
+      if (c->bgzf_text_gen != c->text_gen || c->bgzf_text_bytes != c->text_bytes) {
+        cm_set_error(c, "tabix index: the text store has been rendered anew since it was compressed");
+        return CMGPU_EINVAL;
+      }
+      text = static_cast<const uint8_t *>(c->text.p);
+      break;
+    case CM_BZ_SRC_UPLOAD: text = static_cast<const uint8_t *>(c->bgzf_in.p); break;
+    case CM_BZ_SRC_DEVICE: text = c->bgzf_src_ptr; break;
+    default:
+      cm_set_error(c, "tabix index: no compressed store to index (cmgpu_bgzf_compress or cmgpu_store_compress_text comes first)");
+      return CMGPU_EINVAL;
+  }
+  if (base_offset >> 47) { cm_set_error(c, "tabix index: base offset beyond 2^47"); return CMGPU_EINVAL; }
+  std::vector<uint8_t> payload;
+  const int rc = tx_index(c, text, c->bgzf_text_bytes, base_offset, payload);
+  if (rc != CMGPU_OK) return rc;
+  c->tabix.swap(payload);
+  c->tabix_have = true;
+  if (n_bytes) *n_bytes = c->tabix.size();
+  return CMGPU_OK;
+}
+extern "C" int cmgpu_tabix_download(cmgpu_ctx *c, void *out, uint64_t capacity) {
+  if (!c || !out) return CMGPU_EINVAL;
+  if (!c->tabix_have) { cm_set_error(c, "no tabix index (cmgpu_bgzf_index_tabix comes first)"); return CMGPU_EINVAL; }
+  if (capacity < c->tabix.size()) { cm_set_error(c, "tabix buffer too small"); return CMGPU_ECAPACITY; }
+  memcpy(out, c->tabix.data(), c->tabix.size());
+  return CMGPU_OK;
+}
+extern "C" int cmgpu_tabix_write(cmgpu_ctx *c, const char *path) {
+  if (!c || !path) return CMGPU_EINVAL;
+  if (!c->tabix_have) { cm_set_error(c, "no tabix index (cmgpu_bgzf_index_tabix comes first)"); return CMGPU_EINVAL; }
+  if (cmgpu_bgzf_write_host_text(path, c->tabix.data(), c->tabix.size(), 0) != CMGPU_OK || cmgpu_bgzf_write_eof(path) != CMGPU_OK) {
+    remove(path);
+    cm_set_error(c, std::string("cannot write ") + path);
+    return CMGPU_EIO;
+  }
+  return CMGPU_OK;
+}

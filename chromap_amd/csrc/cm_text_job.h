@@ -141,6 +141,7 @@ struct CmTextJob {
     const hipError_t e = cm_stream_sync(s);
     if (e != hipSuccess) { cm_set_error(c, std::string("text formatting: ") + hipGetErrorString(e)); return CMGPU_EHIP; }
     c->text_bytes = total;
+    ++c->text_gen;
     c->text_lines = lines;
     *n_lines = lines;
     *n_bytes = total;

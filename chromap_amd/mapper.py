@@ -713,6 +713,20 @@ class ChromapGPU:
         """the compressed store's blocks to a file, without the end-of-file block (bgzf_write_eof, once, last)"""
         self._check(self.L.cmgpu_bgzf_write(self.ctx, path.encode(), int(append)), self.ctx)
 
+    # ---- the tabix index of the compressed store, built on the device (include/chromap_amd.h; chromap_amd/csrc/cm_tabix.h)
+    def bgzf_tabix(self, base_offset=0):
+        """the .tbi payload (before compression) of the text of the last bgzf_compress / store_compress_text, whose blocks will stand
+        at file offset `base_offset`; ChromapError for a text that is not sorted BED (the message names the line)"""
+        n = C.c_uint64(0)
+        self._check(self.L.cmgpu_bgzf_index_tabix(self.ctx, int(base_offset), C.byref(n)), self.ctx)
+        buf = C.create_string_buffer(max(1, n.value))
+        self._check(self.L.cmgpu_tabix_download(self.ctx, buf, n.value), self.ctx)
+        return buf.raw[:n.value]
+
+    def store_write_tbi(self, path):
+        """the last bgzf_tabix payload as a .tbi file: BGZF blocks and the end-of-file block"""
+        self._check(self.L.cmgpu_tabix_write(self.ctx, path.encode()), self.ctx)
+
     # ---- --summary: per-barcode TOTAL / DUP / LOWMAPQ / MAPPED counted on the device (include/chromap_amd.h)
     def summary_enable(self, on=True):
         """from now on every map_* call counts its reads per barcode and every store_format* call credits the duplicate runs;

@@ -580,6 +580,23 @@ int cmgpu_bgzf_download(cmgpu_ctx *ctx, void *out, uint64_t capacity);
 int cmgpu_bgzf_write(cmgpu_ctx *ctx, const char *path, int append);
 int cmgpu_bgzf_write_host_text(const char *path, const void *text, uint64_t n, int append);
 int cmgpu_bgzf_write_eof(const char *path);
+/* ---- tabix index of the compressed store, built on the device (cm_tabix.h, cm_tabix.hip) -------
+ * The .tbi a BGZF BED / TagAlign file needs (SAM/tabix spec, preset `bed`: sequence column 1, begin 2, end 3, 0-based half-open,
+ * comment character '#'), made from what is in HBM once the compressor is done: the text it compressed, and the blocks' sizes.
+ * The text must be sorted as the BED writers sort it: every name in one run of lines, starts ascending within a run; it is empty
+ * or ends with a newline; columns 2 and 3 are decimal; no end beyond 2^29 (the format's limit).  A text that is not -- paired
+ * TagAlign, pairs, SAM -- is refused with CMGPU_EFORMAT and a message that names the first offending line; the context stays usable.
+ * Bins are written in ascending number, a bin's chunks in file order, adjacent chunks joined where the second begins in the block
+ * in which the first ends (htslib's rule); every reference ends with the pseudo-bin 37450; the linear index is back-filled.
+ *   cmgpu_bgzf_index_tabix  indexes the text of the last cmgpu_bgzf_compress / cmgpu_store_compress_text against its blocks, which
+ *                           will stand at base_offset in the file (the bytes written before them: header blocks).  The payload
+ *                           (the uncompressed .tbi) stays with the context; *n_bytes its size.  CMGPU_EINVAL: nothing compressed
+ *                           yet, or the text store has been rendered anew since
+ *   cmgpu_tabix_download    the payload (capacity >= its size, else CMGPU_ECAPACITY)
+ *   cmgpu_tabix_write       the payload as a BGZF file: stored blocks written by the host, then the end-of-file block */
+int cmgpu_bgzf_index_tabix(cmgpu_ctx *ctx, uint64_t base_offset, uint64_t *n_bytes);
+int cmgpu_tabix_download(cmgpu_ctx *ctx, void *out, uint64_t capacity);
+int cmgpu_tabix_write(cmgpu_ctx *ctx, const char *path);
 /* --allocate-multi-mappings (MappingProcessor::AllocateMultiMappings, src/mapping_processor.h:319-440): with
  * params->allocate_multi_mappings and without low_memory_mode, cmgpu_store_format gives every read whose surviving records have
  * MAPQ < 4 to one of them, drawn with probability proportional to the uni-mappings (MAPQ >= 4) within

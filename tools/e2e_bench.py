@@ -13,6 +13,9 @@ generator of tools/ref_baseline.py); `--summary` then times the same job without
 `--output-bgzf` (with `--preset hic` or `--sam`): the job plain, the job with `--output-bgzf` (BGZF blocks compressed on the device), and what
 a user does without the flag -- the plain run followed by tools/bgzf.py on its output (zlib level 1, 16 threads); `--reps` runs each, whole-process
 wall time, output sizes, and the compressed file inflated and compared with the plain one.  `--baseline-cli`: the plain job with that build too.
+`--output-tbi` (with `--preset atac`, with or without `--barcodes`): the job with `--output-bgzf`, the job with `--output-bgzf --output-tbi`
+(the tabix index built on the device) and -- with `--baseline-cli` -- that build with `--output-bgzf`; the builds and flags take turns,
+`--reps` rounds, whole-process wall time; the outputs must inflate to the same text, and the index's own line is kept.
 Prints one JSON object; everything is written under --dir (default /tmp/chromap_amd_e2e)."""
 import argparse
 import ctypes as C
@@ -66,6 +69,52 @@ def write_barcodes(d, n_all, n_wl, seed=1000):
     return ["-b", bc_path, "--barcode-whitelist", wl_path]
 
 
+def output_tbi_job(args, cli, job, out):
+    """--output-bgzf with the parent's build (--baseline-cli), with this build, and with this build and --output-tbi: one run of each per
+    round, the order kept, after one untimed round"""
+    import hashlib
+    import zlib
+    variants = ([("parent_output_bgzf", args.baseline_cli, ["--output-bgzf"])] if args.baseline_cli else []) + \
+               [("output_bgzf", cli, ["--output-bgzf"]), ("output_bgzf_output_tbi", cli, ["--output-bgzf", "--output-tbi"])]
+    res = {label: {"wall_s": [], "lines": []} for label, _, _ in variants}
+
+    def md5_inflated(path):
+        h = hashlib.md5()
+        d = zlib.decompressobj(31)
+        with open(path, "rb") as f:
+            for b in iter(lambda: f.read(1 << 24), b""):
+                while b:
+                    h.update(d.decompress(b))
+                    if d.eof:   # the next BGZF block
+                        b = d.unused_data
+                        d = zlib.decompressobj(31)
+                    else:
+                        b = b""
+        return h.hexdigest()
+    for rnd in range(args.reps + 1):
+        for label, exe, extra in variants:
+            for f in (out, out + ".tbi"):
+                if os.path.exists(f):
+                    os.remove(f)
+            os.sync()
+            t0 = time.time()
+            p = subprocess.run([exe] + job + extra, stderr=subprocess.PIPE, check=True)
+            dt = time.time() - t0
+            if rnd == 0:   # untimed: every build's code objects and the files have been read once
+                res[label]["text_md5"] = md5_inflated(out)
+                res[label]["bgzf_bytes"] = os.path.getsize(out)
+                if "--output-tbi" in extra:
+                    res[label]["tbi_bytes"] = os.path.getsize(out + ".tbi")
+                continue
+            res[label]["wall_s"].append(round(dt, 3))
+            res[label]["lines"].append([ln for ln in p.stderr.decode().splitlines()
+                                        if ln.startswith(("Mapped all reads", "Sorted,", "Compressed ", "Built the tabix index", "Number of output mappings"))])
+    res["same_text"] = len({res[label]["text_md5"] for label, _, _ in variants}) == 1
+    res["config"] = {"pairs": args.pairs, "readlen": args.readlen, "genome": args.genome, "barcodes": args.barcodes, "reps": args.reps,
+                     "hardware_threads": os.cpu_count(), "cpu_budget": cpu_budget()}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--genome", type=int, default=200_000_000)
@@ -81,6 +130,7 @@ def main():
     ap.add_argument("--barcodes", type=int, default=0, help="--preset atac: a single-cell job with a whitelist of this many 16-mers (scATAC: 737280)")
     ap.add_argument("--summary", action="store_true", help="--preset atac: also time the job with --summary FILE (and --baseline-cli without it)")
     ap.add_argument("--output-bgzf", action="store_true", help="--preset hic / --sam: time the job plain, with --output-bgzf, and plain + tools/bgzf.py of the output")
+    ap.add_argument("--output-tbi", action="store_true", help="--preset atac: time --output-bgzf without and with --output-tbi (and --baseline-cli with --output-bgzf), taking turns")
     ap.add_argument("--skip-host-ingest", action="store_true", help="a long job: leave the host parser's run out")
     args = ap.parse_args()
     os.makedirs(args.dir, exist_ok=True)
@@ -121,6 +171,10 @@ def main():
     cli = os.path.join(ROOT, "chromap_amd", "chromap-amd")
     res = {}
     job = write_barcodes(args.dir, args.pairs, args.barcodes) if args.barcodes else []
+
+    if args.output_tbi:
+        print(json.dumps(output_tbi_job(args, cli, ["--preset", args.preset, "-x", idx, "-r", fa, "-1", r1, "-2", r2, "-o", out + ".gz"] + job, out + ".gz")))
+        return
 
     def run(label, f1, f2, extra=(), reps=args.reps, cli=cli, after=None):
         """the CLI `reps` times; the run with the shortest 'Mapped all reads' time is the one reported"""
