@@ -123,7 +123,8 @@ SYMBOLS = ("cmgpu_default_params", "cmgpu_apply_preset", "cmgpu_create", "cmgpu_
            "cmgpu_exchange_owner_table", "cmgpu_exchange_step", "cmgpu_exchange_info", "cmgpu_exchange_plan", "cmgpu_exchange_finalize", "cmgpu_memcpy", "cmgpu_copy_whitelist",
            "cmgpu_set_barcode_translation", "cmgpu_barcode_translation_info", "cmgpu_copy_barcode_translation", "cmgpu_barcode_translation_pack", "cmgpu_barcode_translate_host",
            "cmgpu_host_alloc", "cmgpu_host_free", "cmgpu_host_register", "cmgpu_host_unregister", "cmgpu_submit_pairs", "cmgpu_map_submitted", "cmgpu_map_submitted_async", "cmgpu_records_wait",
-           "cmgpu_debug_trace", "cmgpu_debug_minimizers", "cmgpu_debug_minimizers_all", "cmgpu_debug_array", "cmgpu_debug_mapq", "cmgpu_debug_mapq_tables")
+           "cmgpu_debug_trace", "cmgpu_debug_minimizers", "cmgpu_debug_minimizers_all", "cmgpu_debug_array", "cmgpu_debug_mapq", "cmgpu_debug_mapq_tables",
+           "cmgpu_debug_probe")
 
 # names cmgpu_debug_array knows (include/chromap_amd_debug.h): per read, per pair, and the 64 counters of the device work lists
 DEBUG_ARRAYS_PER_READ = ("rlen", "mm_cnt", "hit_tot", "ncp", "ncn", "resc_p", "resc_n", "mcp", "mcn", "fcp", "fcn", "ndp", "ndn", "nv")
@@ -141,6 +142,27 @@ def debug_array(L, ctx, name, n_pairs):
     if L.cmgpu_debug_array(ctx, name.encode(), out.ctypes.data, cap, C.byref(n)) != 0:
         raise RuntimeError(L.cmgpu_last_error(ctx).decode())
     return out[:n.value]
+
+
+# cmgpu_debug_probe (include/chromap_amd_debug.h): what the probe kernel answers per hash
+PROBE_MISS, PROBE_SINGLETON, PROBE_MULTI = 0, 1, 2
+PROBE_POISON = 0xEE  # byte the device result arrays hold where the kernel wrote nothing
+
+
+def debug_probe(L, ctx, hashes, lookups_per_lane=1, pair_prefetch=0, file_table=True, slack=0):
+    """k_probe once over `hashes`: (kind uint8 [n + slack], value uint64 [n + slack], probe steps, hits); the entries past n are
+    the device arrays' poison unless the kernel wrote there"""
+    import numpy as np
+    hashes = np.ascontiguousarray(hashes, dtype=np.uint64)
+    n = len(hashes)
+    cap = n + slack
+    kind = np.full(cap, 0x55, np.uint8)
+    val = np.full(cap, 0x5555555555555555, np.uint64)
+    steps, hits = C.c_uint64(0), C.c_uint64(0)
+    if L.cmgpu_debug_probe(ctx, hashes.ctypes.data, n, lookups_per_lane, pair_prefetch, int(bool(file_table)), cap, kind.ctypes.data,
+                           val.ctypes.data, C.byref(steps), C.byref(hits)) != 0:
+        raise RuntimeError(L.cmgpu_last_error(ctx).decode())
+    return kind, val, steps.value, hits.value
 
 
 # cmgpu_debug_mapq (include/chromap_amd_debug.h): kinds, and the columns of its two case matrices
@@ -342,6 +364,8 @@ def declare(L):
     sig("cmgpu_debug_trace", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64])
     sig("cmgpu_debug_array", C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)])
     sig("cmgpu_debug_mapq", C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p])
+    sig("cmgpu_debug_probe", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p,
+                                       P(C.c_uint64), P(C.c_uint64)])
     sig("cmgpu_debug_mapq_tables", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, P(C.c_uint32)])
     sig("cmgpu_debug_minimizers", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, P(C.c_uint32)])
     sig("cmgpu_debug_minimizers_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, P(C.c_uint64)])

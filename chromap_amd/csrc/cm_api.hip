@@ -1745,9 +1745,11 @@ extern "C" int cmgpu_probe_bench_variant(cmgpu_ctx *c, uint64_t n, int repeat, i
   // pair_prefetch bit 0: second probe step requested with the first; bit 1: the file's table even when a re-hashed one is resident
   return probe_bench_impl(c, nullptr, n, repeat, lookups_per_lane | ((pair_prefetch & 1) ? 16 : 0) | ((pair_prefetch & 2) ? 32 : 0), avg_ms, probe_steps, hits, nullptr);
 }
-static int probe_bench_impl(cmgpu_ctx *c, const uint64_t *hashes, uint64_t n, int repeat, int variant, double *avg_ms,
-                            uint64_t *probe_steps, uint64_t *hits, uint64_t *occurrences) {
-  if (!c || n == 0 || n > 0xffffff00ull || repeat < 1) return CMGPU_EINVAL;
+// One counted launch of k_probe over n hashes (uploaded from `hashes`, or the resident ones): the table and its mask by `variant`
+// (cm_launch_k_probe's, + 32: the file's table even when a re-hashed one is resident), the context's counters in h[].  The result
+// arrays hold `cap` >= n entries; poison != 0 fills them with 0xEE bytes first, so that a store past n would show.
+static int probe_counted_launch(cmgpu_ctx *c, const uint64_t *hashes, uint64_t n, uint64_t cap, int *variant, bool poison, const uint64_t **tab_out,
+                                uint32_t *tmask_out, unsigned long long *h) {
   CM_HIPCHECK(c, cm_enter(c));
   if (hashes) {
     if (c->mm_hash.ensure(n * 8)) { cm_set_error(c, "out of device memory (probe hashes)"); return CMGPU_ENOMEM; }
@@ -1756,21 +1758,38 @@ static int probe_bench_impl(cmgpu_ctx *c, const uint64_t *hashes, uint64_t n, in
     cm_set_error(c, "no resident hashes");
     return CMGPU_EINVAL;
   }
-  if (c->pr_val.ensure(n * 8) || c->pr_kind.ensure(n)) { cm_set_error(c, "out of device memory (probe results)"); return CMGPU_ENOMEM; }
+  if (c->pr_val.ensure(cap * 8) || c->pr_kind.ensure(cap)) { cm_set_error(c, "out of device memory (probe results)"); return CMGPU_ENOMEM; }
   hipStream_t s = c->stream;
   unsigned long long *ctr = (unsigned long long *)c->stats.p;
   CM_HIPCHECK(c, hipMemsetAsync(ctr, 0, CM_ST_N * 8, s));
-  // warm-up + counted launch
+  if (poison) {
+    CM_HIPCHECK(c, hipMemsetAsync(c->pr_val.p, 0xEE, cap * 8, s));
+    CM_HIPCHECK(c, hipMemsetAsync(c->pr_kind.p, 0xEE, cap, s));
+  }
   if (c->partials.ensure(cm_probe_partial_words((uint32_t)n) * 8)) { cm_set_error(c, "out of device memory (partials)"); return CMGPU_ENOMEM; }
-  const bool file_layout = (variant & 32) != 0 || !c->fmask;  // + 32: the file's table even when a re-hashed one is resident
-  variant &= ~32;
+  const bool file_layout = (*variant & 32) != 0 || !c->fmask;  // + 32: the file's table even when a re-hashed one is resident
+  *variant &= ~32;
   const uint64_t *tab = (const uint64_t *)(file_layout ? c->bkt.p : c->bkt_fast.p);
   const uint32_t tmask = file_layout ? c->bmask : c->fmask;
   cm_launch_k_probe(tab, tmask, (const uint64_t *)c->mm_hash.p, (uint64_t *)c->pr_val.p,
-                    (uint8_t *)c->pr_kind.p, (uint32_t)n, c->partials.p, ctr + CM_ST_PROBE_STEPS, s, variant);
-  unsigned long long h[CM_ST_N];
-  CM_HIPCHECK(c, hipMemcpyAsync(h, ctr, sizeof(h), hipMemcpyDeviceToHost, s));
+                    (uint8_t *)c->pr_kind.p, (uint32_t)n, c->partials.p, ctr + CM_ST_PROBE_STEPS, s, *variant);
+  CM_HIPCHECK(c, hipMemcpyAsync(h, ctr, CM_ST_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   CM_HIPCHECK(c, cm_stream_sync(s));
+  *tab_out = tab;
+  *tmask_out = tmask;
+  return CMGPU_OK;
+}
+
+static int probe_bench_impl(cmgpu_ctx *c, const uint64_t *hashes, uint64_t n, int repeat, int variant, double *avg_ms,
+                            uint64_t *probe_steps, uint64_t *hits, uint64_t *occurrences) {
+  if (!c || n == 0 || n > 0xffffff00ull || repeat < 1) return CMGPU_EINVAL;
+  // warm-up + counted launch
+  unsigned long long h[CM_ST_N];
+  const uint64_t *tab = nullptr;
+  uint32_t tmask = 0;
+  const int rc = probe_counted_launch(c, hashes, n, n, &variant, false, &tab, &tmask, h);
+  if (rc) return rc;
+  hipStream_t s = c->stream;
   CM_HIPCHECK(c, hipEventRecord(c->ev[0], s));
   for (int i = 0; i < repeat; ++i)
     cm_launch_k_probe(tab, tmask, (const uint64_t *)c->mm_hash.p, (uint64_t *)c->pr_val.p,
@@ -1783,6 +1802,29 @@ static int probe_bench_impl(cmgpu_ctx *c, const uint64_t *hashes, uint64_t n, in
   if (probe_steps) *probe_steps = h[CM_ST_PROBE_STEPS];
   if (hits) *hits = h[CM_ST_PROBE_HITS];
   if (occurrences) *occurrences = 0;
+  return CMGPU_OK;
+}
+
+// the probe kernel's answer per hash (include/chromap_amd_debug.h)
+static_assert(CMGPU_PROBE_MISS == CM_PR_MISS && CMGPU_PROBE_SINGLETON == CM_PR_SINGLE && CMGPU_PROBE_MULTI == CM_PR_MULTI, "probe kinds");
+extern "C" int cmgpu_debug_probe(cmgpu_ctx *c, const uint64_t *hashes, uint64_t n, int lookups_per_lane, int pair_prefetch, int file_table,
+                                 uint64_t capacity, uint8_t *kind_out, uint64_t *value_out, uint64_t *probe_steps, uint64_t *hits) {
+  if (!c) return CMGPU_EINVAL;
+  if (!hashes || !kind_out || !value_out || n == 0 || n > 0xffffff00ull || capacity < n || capacity > 0xffffff00ull ||
+      (lookups_per_lane != 1 && lookups_per_lane != 2 && lookups_per_lane != 4 && lookups_per_lane != 8) || (pair_prefetch != 0 && pair_prefetch != 1)) {
+    cm_set_error(c, "bad argument");
+    return CMGPU_EINVAL;
+  }
+  int variant = lookups_per_lane | (pair_prefetch ? 16 : 0) | (file_table ? 32 : 0);
+  unsigned long long h[CM_ST_N];
+  const uint64_t *tab = nullptr;
+  uint32_t tmask = 0;
+  const int rc = probe_counted_launch(c, hashes, n, capacity, &variant, true, &tab, &tmask, h);
+  if (rc) return rc;
+  CM_HIPCHECK(c, hipMemcpy(kind_out, c->pr_kind.p, capacity, hipMemcpyDeviceToHost));
+  CM_HIPCHECK(c, hipMemcpy(value_out, c->pr_val.p, capacity * 8, hipMemcpyDeviceToHost));
+  if (probe_steps) *probe_steps = h[CM_ST_PROBE_STEPS];
+  if (hits) *hits = h[CM_ST_PROBE_HITS];
   return CMGPU_OK;
 }
 

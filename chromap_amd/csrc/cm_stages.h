@@ -653,8 +653,12 @@ CM_HD void cm_s0_prep(const CmDev &d, uint32_t pair) {
 //   WT == 0: runtime w <= CM_MAX_W (private memory; the rare non-default index).
 // Positions [begin, end) of seq are run; `flush` performs the final emission (:136-138).
 // emit(n, hash, pos_strand) -> bool: n = emissions counted so far, return value = whether this one counts.
-template <int WT, class Emit>
-CM_HD uint32_t cm_minimizers_core(const uint8_t *seq, uint32_t begin, uint32_t end, bool flush, int k, int w, Emit &&emit) {
+// ctl(pos, kind) -> bool is told about every position after it has been run (kind 0: ambiguous base, 1: palindromic
+// k-mer, the window did not advance, 2: any other k-mer) and may end the run there, without the final emission.
+struct CmMmNoCtl { CM_HD bool operator()(uint32_t, int) const { return false; } };
+template <int WT, class Emit, class Ctl = CmMmNoCtl>
+CM_HD uint32_t cm_minimizers_core(const uint8_t *seq, uint32_t begin, uint32_t end, bool flush, int k, int w, Emit &&emit,
+                                  Ctl &&ctl = Ctl()) {
   constexpr int CAP = WT ? WT : CM_MAX_W;
   const int W = WT ? WT : w;
   uint32_t n = 0;
@@ -676,7 +680,10 @@ CM_HD uint32_t cm_minimizers_core(const uint8_t *seq, uint32_t begin, uint32_t e
     if (c < 4) {
       fw = ((fw << 2) | c) & mask;
       rv = (rv >> 2) | (((uint64_t)(3 ^ c)) << shift);
-      if (fw == rv) continue;
+      if (fw == rv) {
+        if (ctl(pos, 1)) { flush = false; break; }
+        continue;
+      }
       const uint64_t h0 = cm_hash64(fw, mask), h1 = cm_hash64(rv, mask);
       const uint32_t strand = h0 < h1 ? 0u : 1u;
       ++unamb;
@@ -714,6 +721,7 @@ CM_HD uint32_t cm_minimizers_core(const uint8_t *seq, uint32_t begin, uint32_t e
           if (min_h == wh[j] && min_p != wp[j]) CM_EMIT(wh[j], wp[j]);
       }
     }
+    if (ctl(pos, c < 4 ? 2 : 0)) { flush = false; break; }
   }
   if (flush && min_h != ~0ull) CM_EMIT(min_h, min_p);
 #undef CM_EMIT
@@ -1056,18 +1064,69 @@ CM_HD void cm_s1_fill(const CmDev &d, uint32_t r, const uint8_t *seq) {
 
 // ---------------------------------------------------------------------------------------
 // Reference minimizers for index construction (Index::Construct, index.cc:19-23), one
-// chunk of `chunk` positions per item.  The state machine is cm_minimizers_core;
-// it is started `warm` positions early (>= 2w+k, so ring buffer, running minimum and the
-// unambiguous-length thresholds have converged to the sequential pass's state before the
-// first owned position) and run w+2 positions past the chunk; an emission is kept only
-// when the emitted k-mer's end position lies in [start, start+chunk).  Emitted hit =
+// chunk of `chunk` positions per item.  The state machine is cm_minimizers_core, started
+// in front of the chunk and run past its end; an emission is kept only when the emitted
+// k-mer's end position lies in [start, start+chunk).  Emitted hit =
 // ((rid<<32 | pos) << 1) | strand (minimizer_generator.cc:58-60).  Pass oh = nullptr to count.
+//
+// What the sequential pass carries into a position is (a) the last k unambiguous bases,
+// (b) the unambiguous length, of which only min(., w + k) is ever looked at, and (c) the
+// entries pushed by the last w positions that ADVANCED the window -- the running minimum
+// is the newest smallest of those.  A k-mer equal to its own reverse complement does not
+// advance it (minimizer_generator.cc:42-45) and does not count towards (b).
+//   odd k: no k-mer is its own reverse complement, every position advances.  The run
+//     starts `warm` positions early (>= 2w + k: k bases for (a), w + k more for (b), the
+//     last w of which give (c)) and ends 2w + 2 positions past the chunk, by when every
+//     owned entry has left the window and been emitted or dropped.
+//   even k: a run such as (AT)n freezes the whole state for as long as it lasts, so both
+//     distances are counted in what the sequential pass counts.  The run ends after
+//     2w + 2 window advances past the chunk (or at the sequence end).  In front,
+//     CmChunkCtl follows the warm-up and accepts it if at the first owned position (a),
+//     (b) and (c) are known to be the sequential pass's; if not, the warm-up is doubled,
+//     down to position 0 where the fresh state IS the sequential one.  A failed attempt
+//     has emitted nothing: it ends in front of the first owned position.
 // ---------------------------------------------------------------------------------------
+struct CmChunkCtl {
+  uint32_t s, e;   // owned positions
+  int k, w;
+  bool exact;      // the run began at position 0
+  int v, q, good, past;
+  bool synced, failed;
+  CM_HD CmChunkCtl(uint32_t s_, uint32_t e_, int k_, int w_, bool exact_)
+      : s(s_), e(e_), k(k_), w(w_), exact(exact_), v(0), q(0), good(0), past(0), synced(false), failed(false) {}
+  CM_HD bool operator()(uint32_t pos, int kind) {
+    if (pos >= e) {
+      past += kind != 1;
+      return past >= 2 * w + 2;
+    }
+    if (exact || pos >= s) return false;
+    // v: unambiguous bases seen, up to k -- from the k-th on the k-mer, and with it the palindrome test, is the sequential
+    //    pass's (after an ambiguous base the k-mer still holds the bases in front of it: they decide the test);
+    // q: k-mers counted towards the unambiguous length since then, a lower bound of both passes' lengths;
+    // synced: the two lengths are equal, or both at least w + k;
+    // good: entries pushed in a row that are the sequential pass's, with none of its pushes missing in between.
+    if (kind == 0) {
+      q = 0;
+      if (v >= k - 1) synced = true;   // both lengths are 0 now and every later test is exact
+      if (good < w) ++good;            // an ambiguous base pushes the same empty entry in both passes
+    } else {
+      if (v < k) ++v;
+      if (v < k) {
+        good = 0;                      // the other pass may have taken the other branch here
+      } else if (kind == 2) {
+        if (q < w + k) ++q;
+        if (synced || q >= k) { if (good < w) ++good; } else good = 0;
+        if (q >= w + k) synced = true;
+      }
+    }
+    if (pos + 1 == s && !(synced && good >= w)) { failed = true; return true; }
+    return false;
+  }
+};
+
 CM_HD uint32_t cm_ref_chunk_minimizers(const uint8_t *seq, uint32_t len, uint32_t rid, uint32_t s, uint32_t chunk,
                                        uint32_t warm, int k, int w, uint64_t *oh, uint64_t *ot) {
   const uint32_t e = s + chunk < len ? s + chunk : len;  // owned positions [s,e)
-  const uint32_t begin = s > warm ? s - warm : 0;
-  const uint32_t end = e + 2 * (uint32_t)w + 2 < len ? e + 2 * (uint32_t)w + 2 : len;
   auto own = [&](uint32_t n, uint64_t h, uint32_t p) {
     const uint32_t pp = p >> 1;
     if (pp < s || pp >= e) return false;
@@ -1076,7 +1135,28 @@ CM_HD uint32_t cm_ref_chunk_minimizers(const uint8_t *seq, uint32_t len, uint32_
   };
   // final flush (minimizer_generator.cc:136-138): performed by every chunk whose run reaches
   // the end of the sequence; the ownership test keeps exactly one copy
-  return w == 7 ? cm_minimizers_core<7>(seq, begin, end, end == len, k, w, own) : cm_minimizers_core<0>(seq, begin, end, end == len, k, w, own);
+  if (k & 1) {
+    const uint32_t begin = s > warm ? s - warm : 0;
+    const uint32_t end = e + 2 * (uint32_t)w + 2 < len ? e + 2 * (uint32_t)w + 2 : len;
+    return w == 7 ? cm_minimizers_core<7>(seq, begin, end, end == len, k, w, own) : cm_minimizers_core<0>(seq, begin, end, end == len, k, w, own);
+  }
+  for (uint32_t wm = warm ? warm : 1;;) {
+    const uint32_t begin = s > wm ? s - wm : 0;
+    CmChunkCtl ctl(s, e, k, w, begin == 0);
+    const uint32_t n = w == 7 ? cm_minimizers_core<7>(seq, begin, len, true, k, w, own, ctl) : cm_minimizers_core<0>(seq, begin, len, true, k, w, own, ctl);
+    if (!ctl.failed) return n;
+    wm = wm > s / 2 ? s : 2 * wm;
+  }
+}
+
+// khash sizing (host side of the index builder): kh_put grows the table while
+// n_occupied >= upper_bound = (uint32)(nb*0.77+0.5) before an insertion (khash.h:310-318);
+// the final n_buckets is the smallest power of two >= 4 whose upper bound exceeds
+// n_keys - 1.  0: the table would need more than 2^31 buckets.
+inline uint32_t sy_buckets_for(uint64_t n_keys) {
+  uint64_t nb = 4;
+  while (n_keys > 0 && (uint64_t)((double)nb * 0.77 + 0.5) <= n_keys - 1) nb <<= 1;
+  return nb > 0x80000000ull ? 0 : (uint32_t)nb;
 }
 
 

@@ -3,7 +3,8 @@
 // Stands in for Index::Construct (index.cc:12-89) when a GRCh38-sized index is needed on a
 // box that only has the GPU: collect the reference's minimizers (same state machine as
 // MinimizerGenerator::GenerateMinimizers, run per chunk with a warm-up so that every
-// emission is identical to a sequential pass), sort by (hash, hit) (index.cc:26), derive
+// emission is identical to a sequential pass: cm_ref_chunk_minimizers, cm_stages.h, has the
+// rule and what even k needs beyond it), sort by (hash, hit) (index.cc:26), derive
 // singleton / multi-occurrence entries and the occurrence table (index.cc:41-78), and insert
 // the keys into an open-addressing table with khash's hash, triangular probing and sizing
 // rule (khash.h:232-245, 310-318).  Lookup results are identical to an index built by
@@ -23,7 +24,7 @@
 
 #define SY_BLOCK 256
 #define SY_CHUNK 2048u   // reference positions per thread
-#define SY_WARM 96u      // warm-up positions in front of a chunk (>= 2w + k)
+#define SY_WARM 96u      // warm-up positions in front of a chunk (>= 2w + k); even k: the first attempt, doubled while it does not suffice
 
 CM_HD uint64_t sy_mix(uint64_t x) {  // splitmix64 finalizer: counter-based RNG
   x += 0x9E3779B97F4A7C15ull;
@@ -201,15 +202,7 @@ __global__ __launch_bounds__(SY_BLOCK) void k_sy_fill_empty(uint64_t *bkt, uint6
   if (i < n_words) bkt[i] = (i & 1) ? 0ull : CM_EMPTY_KEY;
 }
 
-// khash sizing: kh_put grows the table while n_occupied >= upper_bound = (uint32)(nb*0.77+0.5)
-// before an insertion (khash.h:310-318); the final n_buckets is the smallest power of two
-// >= 4 whose upper bound exceeds n_keys - 1.
-static uint32_t sy_buckets_for(uint64_t n_keys) {
-  uint64_t nb = 4;
-  while (n_keys > 0 && (uint64_t)((double)nb * 0.77 + 0.5) <= n_keys - 1) nb <<= 1;
-  return nb > 0x80000000ull ? 0 : (uint32_t)nb;
-}
-
+// (khash sizing: sy_buckets_for, cm_stages.h)
 static int sy_build_index(cmgpu_ctx *c) {
   hipStream_t s = c->stream;
   const int k = c->p.k, w = c->p.w;

@@ -77,6 +77,19 @@ int cmgpu_probe_bench(cmgpu_ctx *ctx, const uint64_t *hashes, uint64_t n, int re
 int cmgpu_probe_bench_variant(cmgpu_ctx *ctx, uint64_t n, int repeat, int lookups_per_lane, int pair_prefetch,
                               double *avg_ms, uint64_t *probe_steps, uint64_t *hits);
 
+/* The same kernel once, with its answer per hash (tests/test_gpu_index_build.py compares it with kh_get key by key): n hashes
+ * from host memory (a minimizer's hash, i.e. the table key >> 1) go through k_probe<lookups_per_lane, pair_prefetch>
+ * (lookups_per_lane 1 / 2 / 4 / 8, pair_prefetch 0 / 1) over the file-layout table (file_table != 0) or the table the pipeline
+ * probes (file_table == 0: the re-hashed one of "probe_table_shift" when resident).  kind_out[i] is one of the three values
+ * below and value_out[i] the bucket's value (0 for a miss); *probe_steps / *hits are the launch's totals (buckets visited as
+ * kh_get counts them, hashes found).  Both output arrays hold `capacity` >= n entries: the device arrays are filled with 0xEE
+ * bytes over all of them before the launch and all of them come back, so entries past n show whether the kernel kept to n. */
+#define CMGPU_PROBE_MISS 0       /* kh_get returns kh_end: an empty bucket ended the walk, or it came round */
+#define CMGPU_PROBE_SINGLETON 1  /* the key's low bit is set: the value is the one hit (index_utils.h:56-58) */
+#define CMGPU_PROBE_MULTI 2      /* the value is (offset into the occurrence table) << 32 | count (index_utils.h:28-31) */
+int cmgpu_debug_probe(cmgpu_ctx *ctx, const uint64_t *hashes, uint64_t n, int lookups_per_lane, int pair_prefetch, int file_table,
+                      uint64_t capacity, uint8_t *kind_out, uint64_t *value_out, uint64_t *probe_steps, uint64_t *hits);
+
 /* HBM random-gather microbenchmark on the resident table: n independent 16-byte loads at
  * pseudo-random buckets, average kernel time over `repeat` launches (HIP events). */
 int cmgpu_gather_bench(cmgpu_ctx *ctx, uint64_t n, int repeat, double *avg_ms);

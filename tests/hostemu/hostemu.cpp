@@ -590,6 +590,9 @@ extern "C" long hostemu_ref_minimizers(const cmgpu_ref_view *ref, int k, int w, 
   return n;
 }
 
+// the builder's table-sizing rule; compared by tests with a replay of khash's put / resize rule
+extern "C" uint32_t hostemu_buckets_for(uint64_t n_keys) { return sy_buckets_for(n_keys); }
+
 // one read through the w = 7 minimizer front end (variant 1) or the state machine alone (variant 0)
 extern "C" int hostemu_minimizers_w7(const uint8_t *seq, uint32_t len, int k, int variant, uint64_t *out_hash, uint32_t *out_ps, uint32_t cap) {
   auto put = [&](uint32_t n, uint64_t h, uint32_t p) { if (n < cap) { out_hash[n] = h; out_ps[n] = p; } };

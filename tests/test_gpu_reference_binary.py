@@ -110,24 +110,93 @@ def test_output_equals_reference_binary(run, data, tmp_path):
     assert ds.md5(out_gpu) == ds.md5(out_ref)
 
 
-@pytest.mark.parametrize("k,w", [(21, 11), (15, 5), (27, 7)])
+def _spliced_genome(fa, k, w, out):
+    """the data set's genome with the edge reference (tests/index_refs.py) written over it, sequence by sequence, each piece at a
+    multiple of the index builder's chunk so that its runs lie to the chunk seams as they do there"""
+    import index_refs
+    seqs, name, parts = [], None, []
+    with open(fa, "rb") as f:
+        for ln in f:
+            if ln[:1] == b">":
+                if name is not None:
+                    seqs.append((name, bytearray(b"".join(parts))))
+                name, parts = ln[1:].rstrip(b"\n"), []
+            else:
+                parts.append(ln.rstrip(b"\n"))
+    seqs.append((name, bytearray(b"".join(parts))))
+    edge = index_refs.edge_reference(k, w)
+    for i, (_, piece) in enumerate(edge):
+        _, s = seqs[i % len(seqs)]
+        at = index_refs.CHUNK * (40 + 8 * i)
+        assert at + len(piece) + index_refs.CHUNK < len(s)
+        s[at:at + len(piece)] = piece
+    index_refs.write_fasta(out, [(n, bytes(s)) for n, s in seqs])
+    return out
+
+
+@pytest.mark.parametrize("k,w", [(21, 11), (15, 5), (27, 7), (16, 7)])
 def test_other_kmer_and_window_sizes(k, w, data, tmp_path):
-    """non-default index geometry: ring-buffer minimizers (w != 7), two-pass kernels (k > 26), index
-    built by either program and read by the other"""
+    """non-default index geometry: ring-buffer minimizers (w != 7), two-pass kernels (k > 26), even k (k-mers equal to their own
+    reverse complement do not advance the minimizer window; the genome then carries the edge reference's palindromic and N runs
+    at the builder's chunk seams); index built by either program and read by the other"""
     pre, _ = data("short")
+    fa = pre + ".fa" if k % 2 else _spliced_genome(pre + ".fa", k, w, str(tmp_path / "spliced.fa"))
     idx_ref, idx_gpu = str(tmp_path / "ref.idx"), str(tmp_path / "gpu.idx")
-    subprocess.run([REF, "-i", "-k", str(k), "-w", str(w), "-r", pre + ".fa", "-o", idx_ref], check=True, stderr=subprocess.PIPE)
-    subprocess.run([CLI, "-i", "-k", str(k), "-w", str(w), "-r", pre + ".fa", "-o", idx_gpu], check=True, stderr=subprocess.PIPE)
+    subprocess.run([REF, "-i", "-k", str(k), "-w", str(w), "-r", fa, "-o", idx_ref], check=True, stderr=subprocess.PIPE)
+    subprocess.run([CLI, "-i", "-k", str(k), "-w", str(w), "-r", fa, "-o", idx_gpu], check=True, stderr=subprocess.PIPE)
     reads = ["-1", pre + "_1.fq", "-2", pre + "_2.fq"]
     outs = {}
     for prog, tag in ((REF, "ref"), (CLI, "gpu")):
         for idx, itag in ((idx_ref, "refidx"), (idx_gpu, "gpuidx")):
             out = str(tmp_path / ("%s_%s.bed" % (tag, itag)))
-            cmd = [prog, "--preset", "atac", "-q", "0", "-x", idx, "-r", pre + ".fa"] + reads + ["-o", out] + (["-t", "32"] if prog == REF else [])
+            cmd = [prog, "--preset", "atac", "-q", "0", "-x", idx, "-r", fa] + reads + ["-o", out] + (["-t", "32"] if prog == REF else [])
             r = subprocess.run(cmd, stderr=subprocess.PIPE)
             assert r.returncode == 0, r.stderr.decode()[-2000:]
             outs[(tag, itag)] = ds.md5(out)
     assert len(set(outs.values())) == 1, outs
+    assert os.path.getsize(out) > 100000
+
+
+@pytest.mark.parametrize("k,w", [(16, 7), (22, 10)])
+def test_reference_index_file_equals_oracle_for_even_k(k, w, tmp_path):
+    """the oracle's treatment of k-mers that are their own reverse complement against the program it transcribes: the reference
+    binary's -i file of the edge reference equals the oracle's index on every byte the reference defines (header, flags, occupied
+    buckets, occurrence table; empty buckets hold stale heap bytes in the reference's file)"""
+    import ctypes as C
+    import numpy as np
+    import index_refs
+    import oracle_lib as ol
+    if not os.path.exists(REF):
+        pytest.skip("built reference binary not present")
+    O = ol.lib()
+    fa = index_refs.write_fasta(str(tmp_path / "edge.fa"), index_refs.edge_reference(k, w))
+    path = str(tmp_path / "ref.idx")
+    r = subprocess.run([REF, "-i", "-k", str(k), "-w", str(w), "-r", fa, "-o", path], stderr=subprocess.PIPE)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    ref, own, ld = ol.OraRef(), ol.OraIndex(), ol.OraIndex()
+    assert O.ora_ref_load(fa.encode(), C.byref(ref)) == 0
+    assert O.ora_index_build(C.byref(ref), k, w, C.byref(own)) == 0
+    assert O.ora_index_load(path.encode(), C.byref(ld)) == 0
+    for f in ("k", "w", "n_keys", "n_buckets", "size", "n_occupied", "upper_bound", "n_occ"):
+        assert getattr(ld, f) == getattr(own, f), f
+    nb = own.n_buckets
+
+    def arr(p, n):
+        return np.ctypeslib.as_array(p, shape=(n,))
+
+    fl_a, fl_b = arr(ld.flags, max(1, nb >> 4)), arr(own.flags, max(1, nb >> 4))
+    assert np.array_equal(fl_a, fl_b)
+    i = np.arange(nb, dtype=np.uint32)
+    full = ((fl_b[i >> 4] >> ((i & 15) << 1)) & 3) == 0
+    assert int(full.sum()) == own.size > 1000
+    assert np.array_equal(arr(ld.keys, nb)[full], arr(own.keys, nb)[full])
+    assert np.array_equal(arr(ld.vals, nb)[full], arr(own.vals, nb)[full])
+    assert own.n_occ > 0 and np.array_equal(arr(ld.occ, own.n_occ), arr(own.occ, own.n_occ))
+    # the file's size is the header, the three arrays and the occurrence table: nothing else in it
+    assert os.path.getsize(path) == 28 + max(1, nb >> 4) * 4 + nb * 16 + 4 + own.n_occ * 8
+    for x in (own, ld):
+        O.ora_index_free(C.byref(x))
+    O.ora_ref_free(C.byref(ref))
 
 
 def test_multi_batch_q0_multimappers(tmp_path):
