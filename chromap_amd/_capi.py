@@ -115,7 +115,7 @@ SYMBOLS = ("cmgpu_default_params", "cmgpu_apply_preset", "cmgpu_create", "cmgpu_
            "cmgpu_warm_up", "cmgpu_fastq_set_format", "cmgpu_fastq_scan", "cmgpu_fastq_scan_bgzf", "cmgpu_fastq_take", "cmgpu_fastq_commit", "cmgpu_barcode_abundance_resident",
            "cmgpu_fastq_keep_names", "cmgpu_names_clear", "cmgpu_names_info", "cmgpu_download_names", "cmgpu_store_format_pairs_resident",
            "cmgpu_fastq_set_layout", "cmgpu_fastq_scan_info", "cmgpu_fastq_keep_reads", "cmgpu_reads_clear", "cmgpu_reads_info", "cmgpu_download_reads", "cmgpu_sam_store_append_resident",
-           "cmgpu_sam_store_clear", "cmgpu_sam_store_info", "cmgpu_store_format_sam", "cmgpu_write_sam_header",
+           "cmgpu_sam_store_clear", "cmgpu_sam_store_info", "cmgpu_store_format_sam", "cmgpu_write_sam_header", "cmgpu_store_format_bam", "cmgpu_write_bam_header",
            "cmgpu_summary_enable", "cmgpu_summary_clear", "cmgpu_summary_info", "cmgpu_summary_download", "cmgpu_write_summary", "cmgpu_host_summary_begin", "cmgpu_host_summary_end",
            "cmgpu_load_index_file", "cmgpu_free_host_index", "cmgpu_load_reference_fasta", "cmgpu_free_host_ref",
            "cmgpu_create_synthetic_repeats", "cmgpu_create_synthetic_profile", "cmgpu_generate_resident_batch_indels", "cmgpu_generate_resident_batch_hic", "cmgpu_probe_bench_variant", "cmgpu_gather_sweep", "cmgpu_set_option", "cmgpu_get_option", "cmgpu_swap_resident_batch",
@@ -313,6 +313,8 @@ def declare(L):
     sig("cmgpu_sam_store_info", C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint64)])
     sig("cmgpu_store_format_sam", C.c_int, [C.c_void_p, P(C.c_char_p), C.c_void_p, C.c_uint32, P(Params), C.c_uint32, P(C.c_uint64), P(C.c_uint64)])
     sig("cmgpu_write_sam_header", C.c_int, [P(C.c_char_p), C.c_void_p, C.c_uint32, C.c_char_p])
+    sig("cmgpu_store_format_bam", C.c_int, [C.c_void_p, P(C.c_char_p), C.c_void_p, C.c_uint32, P(Params), C.c_uint32, P(C.c_uint64), P(C.c_uint64)])
+    sig("cmgpu_write_bam_header", C.c_int, [P(C.c_char_p), C.c_void_p, C.c_uint32, C.c_char_p])
     sig("cmgpu_summary_enable", C.c_int, [C.c_void_p, C.c_int])
     sig("cmgpu_summary_clear", C.c_int, [C.c_void_p])
     sig("cmgpu_summary_info", C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint64)])

@@ -181,7 +181,7 @@ static void apply_chr_orders(Run &r) {
 // Pairs output (--preset hic, --pairs) goes through the device ingest like BED: stream 0 keeps the read names in HBM and the final
 // step renders the text from them (cmgpu_store_format_pairs_resident).  --SAM does too: the streams of read 1 and read 2 keep whole
 // reads (names, bases, qualities) in HBM, every batch's alignment records join the SAM record store, and the final step sorts,
-// de-duplicates and renders the lines there (cmgpu_store_format_sam).  --barcode-translate with --SAM stays on the host parser and
+// de-duplicates and renders the lines there (cmgpu_store_format_sam; --BAM: BAM records, cmgpu_store_format_bam).  --barcode-translate with --SAM stays on the host parser and
 // writer: its CB value needs the table.  --gpus N > 1 with pairs or SAM output is refused by validate().  --host-ingest forces the
 // kseq-style parser (the fallback the CMGPU_EFORMAT message names).
 static void configure_contexts(Run &r) {
@@ -677,8 +677,13 @@ static void write_tbi(Run &r, cmgpu_ctx *cx, uint64_t base) {
 static int64_t write_sam_device(Run &r) {
   cmgpu_ctx *ctx = r.ctx();
   uint64_t nl = 0, nbytes = 0;
-  ck(ctx, cmgpu_store_format_sam(ctx, r.out_names.data(), r.out_lengths.data(), r.ref.n_sequences, &r.a.p, r.barcoded ? r.bc_len : 0, &nl, &nbytes));
-  write_header(r, [&](const char *path) { return cmgpu_write_sam_header(r.out_names.data(), r.out_lengths.data(), r.ref.n_sequences, path); });
+  if (r.a.out_bam) {  // --BAM: the same selection, the records and the header in BAM's binary form; both leave as BGZF blocks (parse(): output_bgzf)
+    ck(ctx, cmgpu_store_format_bam(ctx, r.out_names.data(), r.out_lengths.data(), r.ref.n_sequences, &r.a.p, r.barcoded ? r.bc_len : 0, &nl, &nbytes));
+    write_header(r, [&](const char *path) { return cmgpu_write_bam_header(r.out_names.data(), r.out_lengths.data(), r.ref.n_sequences, path); });
+  } else {
+    ck(ctx, cmgpu_store_format_sam(ctx, r.out_names.data(), r.out_lengths.data(), r.ref.n_sequences, &r.a.p, r.barcoded ? r.bc_len : 0, &nl, &nbytes));
+    write_header(r, [&](const char *path) { return cmgpu_write_sam_header(r.out_names.data(), r.out_lengths.data(), r.ref.n_sequences, path); });
+  }
   write_section(r, ctx);
   bgzf_finish(r);
   return (int64_t)nl;
@@ -857,7 +862,10 @@ int main(int argc, char **argv) {
   if (r.device_ingest)
     fprintf(stderr, "Mapped all reads in %.2fs (file read + inflate %.2fs, H2D + device FASTQ parse %.2fs, mapping %.2fs, post-processing + write %.2fs).\n",
             now_s() - r.t_begin, r.t_read, r.t_parse, r.t_map, r.t_post);
-  if (a.output_bgzf)
+  if (a.out_bam)
+    fprintf(stderr, "Compressed %llu bytes of BAM header and records into %llu bytes of BGZF on the device in %.3fs.\n", (unsigned long long)r.bgzf_text_bytes,
+            (unsigned long long)r.bgzf_bytes, r.t_compress);
+  else if (a.output_bgzf)
     fprintf(stderr, "Compressed %llu bytes of text into %llu bytes of BGZF on the device in %.3fs.\n", (unsigned long long)r.bgzf_text_bytes,
             (unsigned long long)r.bgzf_bytes, r.t_compress);
   for (cmgpu_ctx *cx : r.ctxs) cmgpu_destroy(cx);

@@ -60,6 +60,7 @@ struct Args {
   int k = 17, w = 7, device = 0, gpus = 1;
   bool force_exchange = false;
   bool output_bgzf = false;  // --output-bgzf: the output file is BGZF blocks, compressed on the device
+  bool out_bam = false;      // --BAM: SAM's record route (out_sam), the selected records written as a BAM file (always BGZF)
   bool output_tbi = false;   // --output-tbi: <output>.tbi, the tabix index of the BGZF output, built on the device
   uint32_t batch_pairs = 4000000;  // multiple of the reference's 500000-pair read batch
 };
@@ -132,9 +133,10 @@ static Args parse(int argc, char **argv) {
     else if (o == "--allocate-multi-mappings") a.p.allocate_multi_mappings = 1;
     else if (o == "--multi-mapping-allocation-distance") a.p.multi_mapping_allocation_distance = atoi(need("--multi-mapping-allocation-distance"));
     else if (o == "--multi-mapping-allocation-seed") a.p.multi_mapping_allocation_seed = atoi(need("--multi-mapping-allocation-seed"));
-    else if (o == "--BED") { a.out_bed = true; a.out_pairs = false; a.out_sam = false; }
-    else if (o == "--SAM") { a.out_sam = true; a.out_bed = false; a.out_pairs = false; }
-    else if (o == "--TagAlign") { a.out_tagalign = true; a.out_bed = true; a.out_sam = false; a.out_pairs = false; }
+    else if (o == "--BED") { a.out_bed = true; a.out_pairs = false; a.out_sam = false; a.out_bam = false; }
+    else if (o == "--SAM") { a.out_sam = true; a.out_bam = false; a.out_bed = false; a.out_pairs = false; }
+    else if (o == "--BAM") { a.out_sam = true; a.out_bam = true; a.out_bed = false; a.out_pairs = false; }
+    else if (o == "--TagAlign") { a.out_tagalign = true; a.out_bed = true; a.out_sam = false; a.out_bam = false; a.out_pairs = false; }
     else if (o == "--pairs") { a.out_pairs = true; a.out_bed = false; }
     else if (o == "-t" || o == "--num-threads") need("-t");  // host threads are irrelevant here
     else if (o == "--skip-barcode-check") a.skip_bc_check = true;
@@ -193,7 +195,7 @@ static Args parse(int argc, char **argv) {
     else if (o == "-h" || o == "--help") {
       printf("Usage: chromap-amd -i -r ref.fa -o index | chromap-amd [--preset atac|chip|hic] -x index -r ref.fa -1 r1.fq[.gz] [-2 r2.fq[.gz]]\n"
              "       [-b barcode.fq --barcode-whitelist wl.txt] -o out [-e -s -f -l -q --min-read-length --trim-adapters\n"
-             "       --remove-pcr-duplicates --Tn5-shift --low-mem --BED|--TagAlign|--pairs|--SAM --bc-error-threshold ...]\n"
+             "       --remove-pcr-duplicates --Tn5-shift --low-mem --BED|--TagAlign|--pairs|--SAM|--BAM --bc-error-threshold ...]\n"
              "       [--summary FILE [--turn-off-num-uniq-cache-slots] [--frip-est-params a;b;c;d;e]]\n"
              "  --allocate-multi-mappings  BED / TagAlign without --low-mem and without a preset: every read whose mappings have MAPQ < 4 is given to\n"
              "                  one of them, drawn by the uniquely mapped fragments around each; reads with none around are dropped\n"
@@ -203,6 +205,8 @@ static Args parse(int argc, char **argv) {
              "                  with -2 as well the output is --pairs (--preset hic)\n"
              "  --barcode-translate FILE  lines to<TAB or ,>from (gzip or plain): BED column 4 and the SAM CB:Z: value are written as the\n"
              "                  table's names; BED is translated on the device, --SAM on the host\n"
+             "  --BAM           the records of --SAM as a BAM file (@SQ header, NM / MD / CB tags), encoded and BGZF-compressed on the device; one\n"
+             "                  GPU, device ingest, no index (.bai) is written.  Not with --host-ingest, --barcode-translate, -n > 1, --output-tbi\n"
              "  --output-bgzf   the output file as BGZF blocks (bgzip's format, readable by tabix / pairix / samtools), compressed on the\n"
              "                  device; nothing is inferred from the output file's name.  Not where the host renders the text:\n"
              "                  --host-ingest --SAM, --SAM --barcode-translate\n"
@@ -227,7 +231,9 @@ static Args parse(int argc, char **argv) {
   if (a.p.max_num_best_mappings > 8192) die("-n above 8192 is outside this build (a 500000-pair batch then needs more than 2^32 record slots)");
   // (the reference counts MAPPED per mapping there and prints total - mapped as an unsigned number that wraps: nothing to reproduce)
   if (!a.summary_path.empty() && a.p.max_num_best_mappings > 1) die("--summary with -n > 1 is outside this build");
+  if (a.out_bam) a.output_bgzf = true;  // (a BAM file is a BGZF stream: --output-bgzf beside --BAM changes nothing)
   if (a.out_sam) {
+    if (a.out_bam && a.p.max_num_best_mappings > 1) die("--BAM with -n > 1 is outside this build");
     if (a.p.max_num_best_mappings > 1) die("--SAM with -n > 1 is outside this build");
     a.p.output_format = CMGPU_FORMAT_SAM;
   }
@@ -257,6 +263,16 @@ static void validate(Args &a) {
   if (barcoded && a.whitelist.empty() && a.p.remove_pcr_duplicates && a.p.low_memory_mode && !a.cell_level_dedup)
     die("bulk-level duplicate removal ranks barcodes by whitelist abundance: give --barcode-whitelist or --remove-pcr-duplicates-at-cell-level");
   a.p.dedup_at_bulk_level = barcoded && !a.cell_level_dedup ? 1 : 0;  // remove_pcr_duplicates_at_bulk_level defaults to true (mapping_parameters.h:49)
+  // BAM records are encoded from one context's stores in HBM and leave through the BGZF writer
+  if (a.out_bam) {
+    if (a.host_ingest) die("--BAM with --host-ingest is outside this build (the host renders that output, as SAM text; convert it with samtools view -b)");
+    if (!a.translate_path.empty())
+      die("--BAM with --barcode-translate is outside this build (the command line's route for it is the host writer, which renders SAM text)");
+    if (a.output_tbi) die("--output-tbi with --BAM is outside this build (BAM takes a .bai index, which is not built)");
+    if (a.gpus > 1 || a.force_exchange) die("--BAM with --gpus > 1 or --force-exchange is outside this build (the records are encoded by one context from its own stores)");
+    if (a.p.allocate_multi_mappings && !a.p.low_memory_mode)
+      die("--allocate-multi-mappings with --BAM is outside this build (the SAM and BAM writers have no allocation stage)");
+  }
   if ((a.gpus > 1 || a.force_exchange) && (a.out_pairs || a.out_sam || a.host_ingest))
     die("--gpus > 1 needs BED / TagAlign output and device-side FASTQ ingest (pairs and SAM text is rendered by one context from its own stores)");
   // the compressor reads the text store in HBM; the host SAM writers render into a file

@@ -230,6 +230,7 @@ struct cmgpu_ctx {
   bool tabix_have = false;
   uint64_t text_gen = 0, bgzf_text_gen = 0;  // text_gen: counts the texts published to the text store; bgzf_text_gen: the one that was compressed
   uint64_t store_n = 0, store_cap = 0, text_bytes = 0, text_lines = 0;
+  bool text_bam = false;  // the text store holds BAM alignment records (cmgpu_store_format_bam), not lines: text_lines counts records
   uint64_t alloc_multi = 0, alloc_kept = 0, alloc_without_overlap = 0;  // the last cmgpu_store_format's allocation (cmgpu_store_allocation_info)
   double alloc_seconds = 0, alloc_draw_seconds = 0;                     // the stage's time, and its draw's on the host (cmgpu_get_option alloc_us, alloc_draw_us)
   bool store_has_bc = false;

@@ -9,6 +9,8 @@
 //           read_id); a length kernel (duplicate rule, filter, line length), a 64-bit scan, and the format kernel: a GROUP of lanes
 //           per line -- one lane writes the short numeric fields, the group copies name, SEQ, QUAL and MD from the read store
 //           (cm_ingest.hip) with word-wide stores where the destination is aligned
+//   BAM:    cmgpu_store_format_bam runs the same passes and the same length kernel; a selected record's length is that of its BAM
+//           alignment record and the format kernel writes that record (cm_bam.h) where k_sp_format writes the line
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <cstring>
@@ -19,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "cm_bam.h"
 #include "cm_ctx.h"
 #include "cm_kernels.h"
 #include "cm_summary.h"
@@ -208,11 +211,14 @@ __device__ __forceinline__ uint32_t sp_seq_len(const SpRec &r, const uint32_t *_
   *cig_text = r.n_cigar ? ct : 1u;
   return ql < r.trim_len ? ql : r.trim_len;
 }
+// BAM: the length is that of the BAM alignment record (cm_bam.h), and a printed record whose read name does not fit l_read_name counts
+template <bool BAM>
 __global__ __launch_bounds__(SP_BLOCK) void k_sp_len(const uint8_t *__restrict__ rec, const uint64_t *__restrict__ bc, const uint8_t *__restrict__ var,
                                                        const uint64_t *__restrict__ var_offs, const uint32_t *__restrict__ idx, uint32_t n, SpCfg cfg,
                                                        SpReads rs, const uint32_t *__restrict__ name_off, uint64_t *__restrict__ line_len,
                                                        unsigned long long *__restrict__ counts, CmSmDev sm) {
-  // counts[0]: records that belong to no read of the read store; counts[1]: lines whose barcode the translation table does not have
+  // counts[0]: records that belong to no read of the read store; counts[1]: lines whose barcode the translation table does not have;
+  // counts[2]: BAM records whose read name has more than CM_BAM_NAME_MAX bytes
   const uint32_t j = blockIdx.x * SP_BLOCK + threadIdx.x;
   if (j >= n) return;
   const uint32_t i = idx[j];
@@ -269,6 +275,11 @@ __global__ __launch_bounds__(SP_BLOCK) void k_sp_len(const uint8_t *__restrict__
   uint32_t cig_text;
   const uint32_t sl = sp_seq_len(r, reinterpret_cast<const uint32_t *>(var + var_offs[i]), &cig_text);
   const uint32_t nm_len = (uint32_t)(rs.name_offs[mate][q + 1] - rs.name_offs[mate][q]);
+  if (BAM) {
+    if (nm_len > CM_BAM_NAME_MAX) { atomicAdd(counts + 2, 1ull); line_len[j] = 0; return; }
+    line_len[j] = cm_bam_record_size(r, reinterpret_cast<const uint32_t *>(var + var_offs[i]), nm_len, cfg.bc_len != 0, cb_len);
+    return;
+  }
   const uint32_t rnext = r.mrid < 0 || (uint32_t)r.mrid == r.rid ? 1u : name_off[r.mrid + 1] - name_off[r.mrid];
   const uint32_t tl = r.tlen < 0 ? 1u + cm_digits10((uint32_t)(-(int64_t)r.tlen)) : cm_digits10((uint32_t)r.tlen);
   line_len[j] = (uint64_t)nm_len + 1 + cm_digits10(r.flag) + 1 + (name_off[r.rid + 1] - name_off[r.rid]) + 1 + cm_digits10(r.pos + 1) + 1 + cm_digits10(r.mapq) + 1 +
@@ -399,9 +410,52 @@ __global__ __launch_bounds__(SP_BLOCK) void k_sp_format(const uint8_t *__restric
   }
 }
 
-extern "C" int cmgpu_store_format_sam(cmgpu_ctx *c, const char *const *ref_names, const uint32_t *ref_lengths, uint32_t n_sequences, const cmgpu_params *p,
-                                      uint32_t barcode_length, uint64_t *n_lines, uint64_t *n_bytes) {
-  (void)ref_lengths;  // (the @SQ lines are the caller's: cmgpu_write_sam_header)
+// The same G lanes per selected record, which becomes a BAM alignment record (cm_bam.h: cm_bam_encode) at its offset: lane 0 writes the
+// fixed 36 bytes and the tags' heads, the group name, CIGAR, SEQ, QUAL, MD and the barcode.  A translated CB:Z value is copied here, as in
+// k_sp_format.
+template <int G_>
+struct SpLanes {
+  static constexpr int G = G_;
+  uint32_t t;
+};
+template <int G>
+__global__ __launch_bounds__(SP_BLOCK) void k_bam_format(const uint8_t *__restrict__ rec, const uint64_t *__restrict__ bc, const uint8_t *__restrict__ var,
+                                                           const uint64_t *__restrict__ var_offs, const uint32_t *__restrict__ idx, uint32_t n, SpCfg cfg,
+                                                           SpReads rs, const uint64_t *__restrict__ rec_len, const uint64_t *__restrict__ rec_off,
+                                                           uint8_t *__restrict__ out) {
+  const uint64_t jj = ((uint64_t)blockIdx.x * SP_BLOCK + threadIdx.x) / G;
+  const uint32_t j = (uint32_t)jj;
+  if (jj >= n || rec_len[j] == 0) return;
+  SpLanes<G> g;
+  g.t = threadIdx.x % G;
+  const uint32_t i = idx[j];
+  const SpRec r = sp_load(rec, i);
+  const uint32_t mate = r.valid - 1u;
+  const uint64_t q = (uint64_t)(r.read_id - cfg.base);
+  const uint32_t *cg = reinterpret_cast<const uint32_t *>(var + var_offs[i]);
+  const uint8_t *md = reinterpret_cast<const uint8_t *>(cg + r.n_cigar);
+  const uint64_t no = rs.name_offs[mate][q], ro = rs.offs[mate][q];
+  const uint32_t nm_len = (uint32_t)(rs.name_offs[mate][q + 1] - no);
+  const bool has_cb = cfg.bc_len != 0, plain = cfg.bt.tab == nullptr;
+  const uint64_t key = has_cb ? bc[i] : 0;
+  uint32_t cb_len = cfg.bc_len;
+  if (has_cb && !plain) (void)cm_bt_length(cfg.bt, key, cfg.bc_len, &cb_len);  // (k_sp_len selected the record: every segment is in the table)
+  uint8_t *d = cm_bam_encode(g, out + rec_off[j], r, cg, md, rs.names[mate] + no, nm_len, rs.bases[mate] + ro, rs.quals[mate] + ro, has_cb, cb_len, plain, key);
+  if (has_cb && !plain) {  // the `to` strings by the group, the dashes between them by lane 0
+    const uint32_t nseg = cfg.bc_len / cfg.bt.from_len;
+    for (uint32_t sg = 0; sg < nseg; ++sg) {
+      if (sg) { if (g.t == 0) *d = '-'; ++d; }
+      const uint64_t v = cm_bt_find(cfg.bt, cm_bt_seed(cfg.bt, key, nseg, sg));
+      if (v == CM_BT_EMPTY) continue;
+      cm_bam_spread(g, d, (uint32_t)v, CmBamBytes{cfg.bt.blob + (v >> 32)});
+      d += (uint32_t)v;
+    }
+  }
+}
+
+// both writers: the sort, the selection (k_sp_len) and the checks are one; bam: the selected records' lengths and the format kernel are BAM's
+static int sp_format_store(cmgpu_ctx *c, const char *const *ref_names, uint32_t n_sequences, const cmgpu_params *p, uint32_t barcode_length, bool bam,
+                           uint64_t *n_lines, uint64_t *n_bytes) {
   if (!c || !ref_names || !p || !n_lines || !n_bytes) return CMGPU_EINVAL;
   if (p->allocate_multi_mappings && !p->low_memory_mode) { cm_set_error(c, "allocate_multi_mappings: SAM records have no allocation stage"); return CMGPU_EINVAL; }
   CM_HIPCHECK(c, cm_enter(c));
@@ -441,31 +495,58 @@ extern "C" int cmgpu_store_format_sam(cmgpu_ctx *c, const char *const *ref_names
     rs.names[m] = (const uint8_t *)r.names.p; rs.bases[m] = (const uint8_t *)r.bases.p; rs.quals[m] = (const uint8_t *)r.quals.p;
     rs.name_offs[m] = (const uint64_t *)r.name_offs.p; rs.offs[m] = (const uint64_t *)r.offs.p;
   }
-  // the job's spare count words: records that belong to no read of the read store, and lines whose barcode the translation table lacks (k_sp_len)
+  // the job's spare count words: records that belong to no read of the read store, lines whose barcode the translation table lacks, and
+  // BAM records whose read name is too long (k_sp_len)
   if ((rc = job.zero_counts())) return rc;
   CmSmDev sm;  // --summary: the length kernel credits every run to its barcode (the keys are in the table since their reads were counted)
   if ((rc = cm_summary_dev(c, 0, 0, !st.has_bc, &sm))) return rc;
-  hipLaunchKernelGGL(k_sp_len, g, b, 0, s, rec, bc, (const uint8_t *)st.var.p, (const uint64_t *)st.var_offs.p, (const uint32_t *)job.idx(), n, cfg, rs,
-                     job.seq_off(), (uint64_t *)job.llen.p, job.extra_word(), sm);
-  uint64_t total = 0, lines = 0, foreign = 0, misses = 0;
-  if ((rc = job.scan_lines(&total, &lines, &foreign, &misses))) return rc;
+#define SP_LEN(BAM)                                                                                                                                 \
+  hipLaunchKernelGGL(k_sp_len<BAM>, g, b, 0, s, rec, bc, (const uint8_t *)st.var.p, (const uint64_t *)st.var_offs.p, (const uint32_t *)job.idx(), n, cfg, rs, \
+                     job.seq_off(), (uint64_t *)job.llen.p, job.extra_word(), sm)
+  if (bam) SP_LEN(true); else SP_LEN(false);
+#undef SP_LEN
+  uint64_t total = 0, lines = 0, foreign = 0, misses = 0, long_names = 0;
+  if ((rc = job.scan_lines(&total, &lines, &foreign, &misses, &long_names))) return rc;
   if (foreign) {
     cm_set_error(c, std::to_string((unsigned long long)foreign) + " SAM records belong to no read of the read store (reads " + std::to_string(c->rd_base) + " .. " +
                         std::to_string((unsigned long long)c->rd_base + c->rd_n) + ") or to a mate sequence the reference does not have: the record store and the read store are not of one run");
     return CMGPU_EINVAL;
   }
   if (misses) { cm_set_error(c, CM_BT_MISS_MESSAGE); return CMGPU_EFORMAT; }  // (no text: text_bytes is 0 since the call began)
+  if (long_names) {
+    cm_set_error(c, std::to_string((unsigned long long)long_names) + " records have a read name of more than " + std::to_string(CM_BAM_NAME_MAX) +
+                        " bytes, the longest a BAM record's l_read_name holds: no BAM records are written");
+    return CMGPU_EFORMAT;
+  }
   // (the sort's buffers go before the text comes: a realistic run's text is several GB)
   job.release_sort();
-  if ((rc = job.alloc_text(total, "SAM text: " + std::to_string((unsigned long long)total) + " bytes"))) return rc;
+  if ((rc = job.alloc_text(total, std::string(bam ? "BAM records: " : "SAM text: ") + std::to_string((unsigned long long)total) + " bytes"))) return rc;
   const int G = c->opt.sam_group;
   const dim3 gf((unsigned)(((uint64_t)n * G + SP_BLOCK - 1) / SP_BLOCK));
 #define SP_LAUNCH(W)                                                                                                                             \
   hipLaunchKernelGGL(k_sp_format<W>, gf, b, 0, s, rec, bc, (const uint8_t *)st.var.p, (const uint64_t *)st.var_offs.p, (const uint32_t *)job.idx(), n, cfg, rs, \
                      (const uint8_t *)job.names.p, job.seq_off(), (const uint64_t *)job.llen.p, (const uint64_t *)job.loff.p, (uint8_t *)c->text.p)
-  if (G == 16) SP_LAUNCH(16); else if (G == 64) SP_LAUNCH(64); else SP_LAUNCH(8);
+#define BAM_LAUNCH(W)                                                                                                                            \
+  hipLaunchKernelGGL(k_bam_format<W>, gf, b, 0, s, rec, bc, (const uint8_t *)st.var.p, (const uint64_t *)st.var_offs.p, (const uint32_t *)job.idx(), n, cfg, rs, \
+                     (const uint64_t *)job.llen.p, (const uint64_t *)job.loff.p, (uint8_t *)c->text.p)
+  if (bam) { if (G == 16) BAM_LAUNCH(16); else if (G == 64) BAM_LAUNCH(64); else BAM_LAUNCH(8); }
+  else if (G == 16) SP_LAUNCH(16); else if (G == 64) SP_LAUNCH(64); else SP_LAUNCH(8);
+#undef BAM_LAUNCH
 #undef SP_LAUNCH
-  return job.publish(total, lines, n_lines, n_bytes);
+  if ((rc = job.publish(total, lines, n_lines, n_bytes))) return rc;
+  c->text_bam = bam;
+  return CMGPU_OK;
+}
+extern "C" int cmgpu_store_format_sam(cmgpu_ctx *c, const char *const *ref_names, const uint32_t *ref_lengths, uint32_t n_sequences, const cmgpu_params *p,
+                                      uint32_t barcode_length, uint64_t *n_lines, uint64_t *n_bytes) {
+  (void)ref_lengths;  // (the @SQ lines are the caller's: cmgpu_write_sam_header)
+  return sp_format_store(c, ref_names, n_sequences, p, barcode_length, false, n_lines, n_bytes);
+}
+// the same store, sort and selection; the text store then holds BAM alignment records back to back (the header: cmgpu_write_bam_header)
+extern "C" int cmgpu_store_format_bam(cmgpu_ctx *c, const char *const *ref_names, const uint32_t *ref_lengths, uint32_t n_sequences, const cmgpu_params *p,
+                                      uint32_t barcode_length, uint64_t *n_records, uint64_t *n_bytes) {
+  (void)ref_lengths;  // (l_ref is the header's)
+  return sp_format_store(c, ref_names, n_sequences, p, barcode_length, true, n_records, n_bytes);
 }
 
 // the @SQ lines (mapping_writer.cc:312-322: OutputHeader of MappingWriter<SAMMapping>); the text follows with cmgpu_store_write_text(path, append = 1)
@@ -475,6 +556,30 @@ extern "C" int cmgpu_write_sam_header(const char *const *ref_names, const uint32
   if (!f) return CMGPU_EIO;
   bool ok = true;
   for (uint32_t i = 0; i < n_sequences; ++i) ok = fprintf(f, "@SQ\tSN:%s\tLN:%u\n", ref_names[i], ref_lengths[i]) > 0 && ok;
+  ok = fclose(f) == 0 && ok;
+  return ok ? CMGPU_OK : CMGPU_EIO;
+}
+
+// the BAM header before compression (SAM spec 4.2): magic, l_text and the @SQ lines above, n_ref, and per sequence l_name (NUL included),
+// the name, l_ref.  The records follow as BGZF blocks (cmgpu_store_compress_text + cmgpu_bgzf_write)
+extern "C" int cmgpu_write_bam_header(const char *const *ref_names, const uint32_t *ref_lengths, uint32_t n_sequences, const char *out_path) {
+  if (!ref_names || !ref_lengths || !out_path) return CMGPU_EINVAL;
+  std::string text, refs;
+  auto put32 = [](std::string &to, uint32_t v) { for (int b = 0; b < 4; ++b) to.push_back((char)(v >> (8 * b))); };
+  for (uint32_t i = 0; i < n_sequences; ++i) {
+    text += std::string("@SQ\tSN:") + ref_names[i] + "\tLN:" + std::to_string(ref_lengths[i]) + "\n";
+    put32(refs, (uint32_t)strlen(ref_names[i]) + 1u);
+    refs.append(ref_names[i], strlen(ref_names[i]) + 1);
+    put32(refs, ref_lengths[i]);
+  }
+  std::string head("BAM\1", 4);
+  put32(head, (uint32_t)text.size());
+  head += text;
+  put32(head, n_sequences);
+  head += refs;
+  FILE *f = fopen(out_path, "wb");
+  if (!f) return CMGPU_EIO;
+  bool ok = fwrite(head.data(), 1, head.size(), f) == head.size();
   ok = fclose(f) == 0 && ok;
   return ok ? CMGPU_OK : CMGPU_EIO;
 }

@@ -294,6 +294,10 @@ extern "C" int cmgpu_bgzf_index_tabix(cmgpu_ctx *c, uint64_t base_offset, uint64
         cm_set_error(c, "tabix index: the text store has been rendered anew since it was compressed");
         return CMGPU_EINVAL;
       }
+      if (c->text_bam) {
+        cm_set_error(c, "tabix index: the text store holds BAM records, not BED lines (BAM takes a .bai index, which is not built)");
+        return CMGPU_EFORMAT;
+      }
       text = static_cast<const uint8_t *>(c->text.p);
       break;
     case CM_BZ_SRC_UPLOAD: text = static_cast<const uint8_t *>(c->bgzf_in.p); break;

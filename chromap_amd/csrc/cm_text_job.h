@@ -64,7 +64,7 @@ struct CmTextJob {
   std::vector<uint32_t> noff;
   CmTmpBuf names, name_off;        // the sequence names back to back, their n_sequences + 1 offsets
   CmTmpBuf k0, k1, v0, v1, tmp;    // sort: keys in / out, index in / out, work area (the scan's and the reduction's too)
-  CmTmpBuf llen, loff, count;      // n + 1 line lengths, their offsets; three 64-bit words: lines, and two for the writer
+  CmTmpBuf llen, loff, count;      // n + 1 line lengths, their offsets; four 64-bit words: lines, and three for the writer
   uint64_t *ka = nullptr, *kb = nullptr;
   uint32_t *va = nullptr, *vb = nullptr;
 
@@ -86,15 +86,15 @@ struct CmTextJob {
     while (rid_bits < 32 && (1ull << rid_bits) < (uint64_t)n_sequences + rid_extra) ++rid_bits;
     return CMGPU_OK;
   }
-  // the line arrays and the three count words (a writer that frees the sort's buffers before its selection asks for them only then)
+  // the line arrays and the four count words (a writer that frees the sort's buffers before its selection asks for them only then)
   int alloc_lengths() {
-    return llen.ensure(((size_t)n + 1) * 8) || loff.ensure(((size_t)n + 1) * 8) || count.ensure(24) ? enomem("post-processing") : CMGPU_OK;
+    return llen.ensure(((size_t)n + 1) * 8) || loff.ensure(((size_t)n + 1) * 8) || count.ensure(32) ? enomem("post-processing") : CMGPU_OK;
   }
-  // the second and third count words are the writer's: zero_counts before its kernels count in extra_word()[0] and [1], scan_lines
+  // the second to fourth count words are the writer's: zero_counts before its kernels count in extra_word()[0] .. [2], scan_lines
   // brings the values back
   unsigned long long *extra_word() const { return (unsigned long long *)count.p + 1; }
   int zero_counts() {
-    if (hipMemsetAsync(count.p, 0, 24, s) != hipSuccess) { cm_set_error(c, "memset failed"); return CMGPU_EHIP; }
+    if (hipMemsetAsync(count.p, 0, 32, s) != hipSuccess) { cm_set_error(c, "memset failed"); return CMGPU_EHIP; }
     return CMGPU_OK;
   }
 
@@ -117,8 +117,8 @@ struct CmTextJob {
   }
 
   // line lengths -> offsets, bytes and lines of the text; waits for the stream, after which the count words are released.
-  // word1, word2: receive the second and third count words (extra_word)
-  int scan_lines(uint64_t *total, uint64_t *lines, uint64_t *word1 = nullptr, uint64_t *word2 = nullptr) {
+  // word1 .. word3: receive the second to fourth count words (extra_word)
+  int scan_lines(uint64_t *total, uint64_t *lines, uint64_t *word1 = nullptr, uint64_t *word2 = nullptr, uint64_t *word3 = nullptr) {
     const uint64_t *len = (const uint64_t *)llen.p;
     if (hipMemsetAsync((uint64_t *)llen.p + n, 0, 8, s) != hipSuccess) { cm_set_error(c, "memset failed"); return CMGPU_EHIP; }
     size_t tb2 = 0;
@@ -130,6 +130,7 @@ struct CmTextJob {
     if (e == hipSuccess) e = hipMemcpyAsync(lines, count.p, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && word1) e = hipMemcpyAsync(word1, (uint64_t *)count.p + 1, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && word2) e = hipMemcpyAsync(word2, (uint64_t *)count.p + 2, 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && word3) e = hipMemcpyAsync(word3, (uint64_t *)count.p + 3, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = cm_stream_sync(s);
     count.release();
     if (e != hipSuccess) { cm_set_error(c, std::string("post-processing scan: ") + hipGetErrorString(e)); return CMGPU_EHIP; }
@@ -143,6 +144,7 @@ struct CmTextJob {
     c->text_bytes = total;
     ++c->text_gen;
     c->text_lines = lines;
+    c->text_bam = false;  // (cmgpu_store_format_bam sets it behind this call)
     *n_lines = lines;
     *n_bytes = total;
     return CMGPU_OK;

@@ -620,6 +620,23 @@ class ChromapGPU:
         if self.L.cmgpu_write_sam_header(names, C.cast(self.reference_lengths(), C.c_void_p), len(self.names), path.encode()) != 0:
             raise ChromapError("cannot write %s" % path)
 
+    def store_format_bam(self, params=None, barcode_length=0):
+        """store_format_sam's sort and selection, the selected records as BAM alignment records back to back (uncompressed) in the text
+        store; returns (records, bytes).  store_text() fetches them, store_compress_text() makes them BGZF blocks; the header:
+        write_bam_header()"""
+        p = params if params is not None else self.params
+        names = (C.c_char_p * len(self.names))(*self.names)
+        nr, nb = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.cmgpu_store_format_bam(self.ctx, names, C.cast(self.reference_lengths(), C.c_void_p), len(self.names), C.byref(p),
+                                                  int(barcode_length), C.byref(nr), C.byref(nb)), self.ctx)
+        return int(nr.value), int(nb.value)
+
+    def write_bam_header(self, path):
+        """the uncompressed BAM header (magic, the @SQ lines, the reference list) to a file"""
+        names = (C.c_char_p * len(self.names))(*self.names)
+        if self.L.cmgpu_write_bam_header(names, C.cast(self.reference_lengths(), C.c_void_p), len(self.names), path.encode()) != 0:
+            raise ChromapError("cannot write %s" % path)
+
     def debug_mapq(self, kind, error_threshold, reads, pairs):
         """test hook: the MAPQ stage functions on their own (_capi.debug_mapq)"""
         return _capi.debug_mapq(self.L, self.ctx, kind, error_threshold, reads, pairs)

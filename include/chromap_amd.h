@@ -477,6 +477,24 @@ int cmgpu_store_format_sam(cmgpu_ctx *ctx, const char *const *ref_names, const u
                            const cmgpu_params *params, uint32_t barcode_length, uint64_t *n_lines, uint64_t *n_bytes);
 int cmgpu_write_sam_header(const char *const *ref_names, const uint32_t *ref_lengths, uint32_t n_sequences, const char *out_path);
 
+/* ---- BAM output on the device (cm_bam.h) ------------------------------------------------------
+ * The same SAM record store and read store, the same sort and the same selection (duplicates, MAPQ filter, --summary credit, the
+ * checks for foreign records and translation misses) as cmgpu_store_format_sam; the selected records are rendered as BAM alignment
+ * records (SAM spec 4.2: block_size, the 32 fixed bytes, read name, CIGAR words, 4-bit SEQ, QUAL, the tags NM (C / S / I by value),
+ * MD:Z and -- for barcoded stores -- CB:Z) instead of lines.
+ *   cmgpu_store_format_bam   leaves the records back to back, uncompressed, in the context's text store; *n_records counts them
+ *                            (cmgpu_store_info's text_lines).  cmgpu_store_text / cmgpu_store_write_text fetch the bytes;
+ *                            cmgpu_store_compress_text + cmgpu_bgzf_write make them the body of a BAM file (a record may straddle
+ *                            two blocks: the format allows it).  A selected record whose read name has 255 bytes or more does not
+ *                            fit l_read_name: CMGPU_EFORMAT, no output.  cmgpu_bgzf_index_tabix refuses a store made of BAM records.
+ *                            No .bai / .csi index is built; bin is the spec's reg2bin(pos, pos + reference length of the CIGAR).
+ *   cmgpu_write_bam_header   the uncompressed header, on the host: "BAM\1", l_text and cmgpu_write_sam_header's @SQ lines, n_ref,
+ *                            and per sequence l_name (with the NUL), the name, l_ref.  As BGZF blocks (cmgpu_bgzf_write_host_text)
+ *                            in front of the compressed records and with cmgpu_bgzf_write_eof behind them it completes the file */
+int cmgpu_store_format_bam(cmgpu_ctx *ctx, const char *const *ref_names, const uint32_t *ref_lengths, uint32_t n_sequences,
+                           const cmgpu_params *params, uint32_t barcode_length, uint64_t *n_records, uint64_t *n_bytes);
+int cmgpu_write_bam_header(const char *const *ref_names, const uint32_t *ref_lengths, uint32_t n_sequences, const char *out_path);
+
 /* ---- --barcode-translate on the device (src/barcode_translator.h:42-101) -----------------------
  * A translation table per context, held in HBM: with one set, cmgpu_store_format writes column 4 of CMGPU_TEXT_BED_PE_BC /
  * CMGPU_TEXT_BED_SE_BC, and cmgpu_store_format_sam the CB:Z: value, as the table's names instead of ACGT (TagAlign and pairs

@@ -16,6 +16,9 @@ wall time, output sizes, and the compressed file inflated and compared with the 
 `--output-tbi` (with `--preset atac`, with or without `--barcodes`): the job with `--output-bgzf`, the job with `--output-bgzf --output-tbi`
 (the tabix index built on the device) and -- with `--baseline-cli` -- that build with `--output-bgzf`; the builds and flags take turns,
 `--reps` rounds, whole-process wall time; the outputs must inflate to the same text, and the index's own line is kept.
+`--output-bam` (with `--sam`): the job as plain `--SAM`, as `--SAM --output-bgzf` and as `--BAM` (records encoded and compressed on the
+device), `--reps` runs each, whole-process wall time and file sizes; the first records of the BAM file, decoded by tests/bam_model.py, must be
+the first lines of the SAM file.
 Prints one JSON object; everything is written under --dir (default /tmp/chromap_amd_e2e)."""
 import argparse
 import ctypes as C
@@ -131,6 +134,7 @@ def main():
     ap.add_argument("--summary", action="store_true", help="--preset atac: also time the job with --summary FILE (and --baseline-cli without it)")
     ap.add_argument("--output-bgzf", action="store_true", help="--preset hic / --sam: time the job plain, with --output-bgzf, and plain + tools/bgzf.py of the output")
     ap.add_argument("--output-tbi", action="store_true", help="--preset atac: time --output-bgzf without and with --output-tbi (and --baseline-cli with --output-bgzf), taking turns")
+    ap.add_argument("--output-bam", action="store_true", help="--sam: time the job as --SAM, --SAM --output-bgzf and --BAM")
     ap.add_argument("--skip-host-ingest", action="store_true", help="a long job: leave the host parser's run out")
     args = ap.parse_args()
     os.makedirs(args.dir, exist_ok=True)
@@ -209,6 +213,51 @@ def main():
         best["md5_runs"] = md5s_run
         res[label] = best
 
+    if args.output_bam and args.sam:
+        import zlib
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import bam_model
+
+        def inflated_head(path, want):
+            """the first `want` bytes (or a little more) that the BGZF blocks of `path` hold"""
+            got = b""
+            with open(path, "rb") as f:
+                raw = f.read(want)  # (the blocks are never larger than their text here by more than their 26 bytes each)
+            while raw and len(got) < want:
+                d = zlib.decompressobj(31)
+                piece = d.decompress(raw)
+                if not d.eof:
+                    break
+                got += piece
+                raw = d.unused_data
+            return got
+        run("sam", r1, r2)
+        with open(out, "rb") as f:
+            sam_head = f.read(8 << 20)
+        run("sam_output_bgzf", r1, r2, ["--output-bgzf"])
+        res["sam_output_bgzf"]["head_inflates_to_sam_head"] = sam_head.startswith(inflated_head(out, 2 << 20)[:1 << 20])
+        run("bam", r1, r2, ["--BAM"])
+        # whole records of the first MB of the BAM body, printed as SAM, against the SAM file's first lines (SEQ has only ACGT here)
+        head = inflated_head(out, 2 << 20)
+        l_text, = np.frombuffer(head[4:8], "<u4")
+        at = 8 + int(l_text)
+        n_ref, = np.frombuffer(head[at:at + 4], "<u4")
+        at += 4
+        for _ in range(int(n_ref)):
+            at += 8 + int(np.frombuffer(head[at:at + 4], "<u4")[0])
+        end = at
+        while end + 4 <= len(head) and end + 4 + int(np.frombuffer(head[end:end + 4], "<u4")[0]) <= min(len(head), at + (1 << 20)):
+            end += 4 + int(np.frombuffer(head[end:end + 4], "<u4")[0])
+        text = bam_model.decode(head[:end])
+        res["bam"]["records_decoded"] = text.count(b"\n") - int(n_ref)
+        res["bam"]["head_decodes_to_sam_head"] = res["bam"]["records_decoded"] > 1000 and sam_head.startswith(text)
+        res["output_bam"] = {"sam_bytes": res["sam"]["bed_bytes"], "sam_bgzf_bytes": res["sam_output_bgzf"]["bed_bytes"], "bam_bytes": res["bam"]["bed_bytes"],
+                             "wall_s_sam": res["sam"]["wall_s_runs"], "wall_s_sam_output_bgzf": res["sam_output_bgzf"]["wall_s_runs"],
+                             "wall_s_bam": res["bam"]["wall_s_runs"]}
+        res["config"] = {"preset": args.preset, "sam": True, "pairs": args.pairs, "readlen": args.readlen, "genome": args.genome, "reps": args.reps,
+                         "hardware_threads": os.cpu_count(), "cpu_budget": cpu_budget()}
+        print(json.dumps(res))
+        return
     run("device_ingest", r1, r2)
     if args.output_bgzf and two_routes:
         import gzip
