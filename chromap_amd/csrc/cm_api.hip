@@ -135,6 +135,8 @@ extern "C" int cmgpu_set_option(cmgpu_ctx *c, const char *name, int64_t value) {
     c->opt.pack_once = value ? 1 : 0;
   } else if (n == "s3b_short") {  // 0: lists of at most 16 hits at a lane cap of 16 go through k_s3b_candidates like every other cap's (the A/B of k_s3b_short)
     c->opt.s3b_short = value ? 1 : 0;
+  } else if (n == "s6_planes") {  // 0: S6's start positions count the diagonal's mismatches on bytes for every read (the A/B of cm_hamming_diag_planes)
+    c->opt.s6_planes = value ? 1 : 0;
   } else if (n == "generic_kernels") {  // 1: no per-mode kernel instances (cm_stages.h: CmModeAny everywhere) -- the A/B of the paired-end instances
     c->opt.generic_kernels = value ? 1 : 0;
   } else if (n == "item_limit") {  // forces the sub-batch path (tests): largest dense intermediate the pipeline may allocate
@@ -162,6 +164,7 @@ extern "C" int cmgpu_get_option(const cmgpu_ctx *c, const char *name, int64_t *v
   else if (n == "generic_kernels") *value = c->opt.generic_kernels;
   else if (n == "s3b_short") *value = c->opt.s3b_short;
   else if (n == "pack_once") *value = c->opt.pack_once;
+  else if (n == "s6_planes") *value = c->opt.s6_planes;
   else if (n == "alloc_us") *value = (int64_t)(c->alloc_seconds * 1e6);  // the allocation stage of the last cmgpu_store_format
   else if (n == "alloc_draw_us") *value = (int64_t)(c->alloc_draw_seconds * 1e6);  // measurement: host share of the last allocation (cm_post.hip)
   else if (n.rfind("coop_profile_", 0) == 0) {
@@ -556,7 +559,7 @@ static int ensure_pair_arrays(cmgpu_ctx *c, uint32_t n) {
   ENS(n_pos_hit, n2 * 4) ENS(ncp, n2 * 4) ENS(ncn, n2 * 4) ENS(aug, n2) ENS(res_neg, n2 * 4) ENS(res_pos, n2 * 4)
   ENS(resc_n, n2 * 4) ENS(resc_p, n2 * 4) ENS(m_tot, (n2 + 1) * 4) ENS(m_off, (n2 + 1) * 4) ENS(mcp, n2 * 4) ENS(mcn, n2 * 4)
   ENS(nv, (n2 + 1) * 4) ENS(v_off, (n2 + 1) * 4)
-  ENS(force0, n) ENS(fcp, n2 * 4) ENS(fcn, n2 * 4) ENS(alive, n) ENS(ndp, n2 * 4) ENS(ndn, n2 * 4)
+  ENS(read_plain, n2) ENS(force0, n) ENS(fcp, n2 * 4) ENS(fcn, n2 * 4) ENS(alive, n) ENS(ndp, n2 * 4) ENS(ndn, n2 * 4)
   ENS(min_err, n2 * 4) ENS(second_err, n2 * 4) ENS(n_best, n2 * 4) ENS(n_second, n2 * 4)
   ENS(pe_min, (size_t)n * 4) ENS(pe_second, (size_t)n * 4) ENS(pe_nbest, (size_t)n * 4) ENS(pe_nsecond, (size_t)n * 4)
   ENS(pe_first, (size_t)n * 4) ENS(pe_i1, (size_t)n * 4) ENS(pe_i2, (size_t)n * 4) ENS(pe_choice, (size_t)n * 4 * cm_rec_per_pair(c))
@@ -813,7 +816,7 @@ static void cm_bind_dev(cmgpu_ctx *c, CmDev &d, uint32_t lo, uint32_t hi) {
   PTR(hbuf, uint64_t) PTR(hcnt, uint8_t) PTR(n_pos_hit, uint32_t) PTR(ncp, uint32_t) PTR(ncn, uint32_t)
   PTR(aug, uint8_t) PTR(res_neg, int32_t) PTR(res_pos, int32_t) PTR(resc_n, uint32_t) PTR(resc_p, uint32_t)
   PTR(m_tot, uint32_t) PTR(m_off, uint32_t) PTR(mbuf, uint64_t) PTR(mcnt, uint8_t) PTR(mcp, uint32_t) PTR(mcn, uint32_t)
-  PTR(force0, uint8_t) PTR(fbuf, uint64_t) PTR(fcnt, uint8_t) PTR(fcp, uint32_t) PTR(fcn, uint32_t) PTR(alive, uint8_t)
+  PTR(read_plain, uint8_t) PTR(force0, uint8_t) PTR(fbuf, uint64_t) PTR(fcnt, uint8_t) PTR(fcp, uint32_t) PTR(fcn, uint32_t) PTR(alive, uint8_t)
   PTR(dpos, uint64_t) PTR(derr, int16_t) PTR(dsplit, uint32_t) PTR(nv, uint32_t) PTR(v_off, uint32_t) PTR(v_err, int16_t) PTR(v_end, int16_t) PTR(ndp, uint32_t) PTR(ndn, uint32_t)
   PTR(min_err, int32_t) PTR(second_err, int32_t) PTR(n_best, int32_t) PTR(n_second, int32_t)
   PTR(pe_min, int32_t) PTR(pe_second, int32_t) PTR(pe_nbest, int32_t) PTR(pe_nsecond, int32_t)
@@ -833,6 +836,7 @@ static void cm_bind_dev(cmgpu_ctx *c, CmDev &d, uint32_t lo, uint32_t hi) {
   d.wq_dynamic = ((uint32_t)c->opt.coop >> 16) & 1u;
   d.generic_kernels = c->opt.generic_kernels ? 1u : 0u;
   d.s3b_short = c->opt.s3b_short ? 1u : 0u;
+  if (!c->opt.s6_planes || !d.ref_pl) d.read_plain = nullptr;  // (the front ends then keep no flags and cm_ref_start_end stays on bytes)
   if (c->has_rank) {  // stages from verification on address the reference by rank
     d.rid_rank = (const uint32_t *)c->rid_rank.p;
     d.ref_off = (const uint64_t *)c->ref_off_r.p;
@@ -1614,6 +1618,16 @@ extern "C" int cmgpu_debug_array(cmgpu_ctx *c, const char *name, uint32_t *out, 
     if (c->last_range_lo != 0 || c->last_range_hi != c->n_pairs) { cm_set_error(c, "the batch was mapped in sub-batches"); return CMGPU_EINVAL; }
     if (capacity < n || !c->read_planes.p || c->read_planes.cap < n * 4) { cm_set_error(c, "debug array: buffer too small or array not resident"); return CMGPU_ECAPACITY; }
     CM_HIPCHECK(c, hipMemcpy(out, c->read_planes.p, n * 4, hipMemcpyDeviceToHost));
+    return CMGPU_OK;
+  }
+  if (nm == "read_plain") {  // CmDev::read_plain of the last range, one byte per read on the device: widened to the caller's 32-bit entries
+    const uint64_t n = 2ull * c->n_pairs;
+    if (n_out) *n_out = n;
+    if (c->last_range_lo != 0 || c->last_range_hi != c->n_pairs) { cm_set_error(c, "the batch was mapped in sub-batches"); return CMGPU_EINVAL; }
+    if (capacity < n || !c->read_plain.p || c->read_plain.cap < n) { cm_set_error(c, "debug array: buffer too small or array not resident"); return CMGPU_ECAPACITY; }
+    std::vector<uint8_t> b(n);
+    if (n) CM_HIPCHECK(c, hipMemcpy(b.data(), c->read_plain.p, n, hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < n; ++i) out[i] = b[i];
     return CMGPU_OK;
   }
   struct { const char *n; DevBuf *b; int per_pair; } tab[] = {

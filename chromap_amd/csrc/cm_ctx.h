@@ -155,6 +155,7 @@ struct CmOptions {
   int heavy_last = 0;          // heavy-last processing order: 0 auto, 1 always, -1 never
   int spec = 1;                // candidate arrays sized from the previous batch (cmgpu_ctx::pred_m_ok); 0: every batch waits for its totals
   int pack_once = 1;           // reads of at most 64 bases on the fused front end: one conversion to bit planes serves trim, minimizers and S5 (0: three, and k_pack_reads) -- measurement / tests
+  int s6_planes = 1;           // 0: cm_ref_start_end counts the diagonal's mismatches on bytes for plain reads too (cm_hamming_diag) -- measurement / tests
   int s3b_short = 1;           // 0: the general per-lane hit-list kernel at a lane cap of 16 too (k_s3b_candidates) -- measurement / tests
   int generic_kernels = 0;     // 1: the S4-S6 kernels that carry every mode (CmModeAny) for paired-end batches too -- measurement / tests
   int coop_rb = 0;             // tests: run-table size of the cooperative sorters (0: their own)
@@ -201,7 +202,7 @@ struct cmgpu_ctx {
   // per-read / per-pair arrays (names match CmDev)
   DevBuf rlen, scratch_a, scratch_b /* 2n+1 u32 each, free between batches */, mm_cnt, mm_off, mm_hash, mm_ps, pr_val, pr_kind;
   DevBuf hit_tot, hit_off, round2, rep_cnt, rep_len, hbuf, hcnt, n_pos_hit, ncp, ncn;
-  DevBuf aug, res_neg, res_pos, resc_n, resc_p, m_tot, m_off, mbuf, mcnt, mcp, mcn, force0;
+  DevBuf aug, res_neg, res_pos, resc_n, resc_p, m_tot, m_off, mbuf, mcnt, mcp, mcn, force0, read_plain;
   DevBuf fbuf, fcnt, fcp, fcn, alive, dpos, derr, dsplit, nv, v_off, v_err, v_end, ndp, ndn, min_err, second_err, n_best, n_second;
   DevBuf pe_min, pe_second, pe_nbest, pe_nsecond, pe_first, pe_i1, pe_i2, pe_choice, rec, rec_ok;
   DevBuf scan_tmp, stats, partials;

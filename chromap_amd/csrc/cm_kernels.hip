@@ -70,7 +70,10 @@ __global__ void k_prep_count(CmDev d, uint32_t n_pairs, uint32_t lds_half) {
   const CmStaged s = cm_stage_pairs(d, p0, p1, pair, lds_half);
   if (t < PB && pair < p1) cm_s0_prep_ptr(d, pair, s.m0, s.m1);
   __syncthreads();  // rlen of both mates is read below by other threads of this block
-  if (pair < p1) cm_s1_count(d, 2 * pair + (t < PB ? 0 : 1), t < PB ? s.m0 : s.m1);
+  if (pair < p1) {
+    if (d.read_plain) d.read_plain[2 * pair + (t < PB ? 0 : 1)] = 0;  // (this route has no case information: S6 stays on bytes)
+    cm_s1_count(d, 2 * pair + (t < PB ? 0 : 1), t < PB ? s.m0 : s.m1);
+  }
 }
 
 // S1 fill: same staging, minimizers written directly to their dense positions
@@ -120,6 +123,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(PL ? 6 : 1))) void k_prep_mm(CmDev
       uint64_t plu;
       cm_read_planes64(t < PB ? s.m0 : s.m1, raw, &pl0, &pl1, &pln, &plu);
       xp[t] = pl0; xp[T + t] = pl1; xu[t] = (plu & cm_mask64(raw)) == 0 ? 1u : 0u;
+      if (d.read_plain) d.read_plain[2 * pair + (t < PB ? 0 : 1)] = (uint8_t)xu[t];  // kept for S6 (cm_ref_start_end)
     }
     __syncthreads();
     if (t < PB && pair < p1) {
@@ -143,6 +147,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(PL ? 6 : 1))) void k_prep_mm(CmDev
   uint32_t cnt = 0, len = 0;
   if (valid) {
     len = d.rlen[r];
+    if (!PL && d.read_plain) d.read_plain[r] = 0;  // (no case information on this route: S6 stays on bytes)
     auto put = [&](uint32_t n, uint64_t h, uint32_t p) {
       const uint64_t v = h | ((uint64_t)p << hb);
       if (n < stg) { if (E6) { sh_lo[(size_t)n * T + t] = (uint32_t)v; sh_hi[(size_t)n * T + t] = (uint16_t)(v >> 32); } else sh_e[(size_t)n * T + t] = v; }
@@ -284,6 +289,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_prep_flat(CmDev d, uint32_t pair_l
   const uint32_t at = mate ? off_m1 : off_m0;
   if (valid) {
     len = d.rlen[r];
+    if (d.read_plain) d.read_plain[r] = 0;  // (no case information on this route: S6 stays on bytes)
     const uint32_t m = len >= (uint32_t)k ? len - (uint32_t)k + 1 : 0;
     bool bad = false;
     if (m) {

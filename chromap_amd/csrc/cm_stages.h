@@ -2606,6 +2606,35 @@ CM_HD int cm_hamming_diag(const uint8_t *pat, const uint8_t *read, int Lfull, bo
   }
   return cnt;
 }
+// The same count on BIT PLANES, for a read of at most 64 bases that is made of upper-case A/C/G/T only (CmDev::read_plain) and the
+// whole read as the text (toff = 0, Lfull = L, the trimmed length):
+//   rp: reference plane records (CmDev::ref_pl);  g: index of the window's first base in the reference bytes (pat - d.ref, the
+//   coordinate cm_s5b_verify_at passes);  tp / tw: the read's planes of the wanted orientation (CmDev::read_pl), tw words per plane.
+// Three neighbouring records (one 16-byte load each, as in cm_banded_align_planes) hold bases [g & ~31, (g & ~31) + 96), which covers
+// g .. g + 63 for every g & 31; funnelled by g & 31 they give the window's planes W0, W1, WN, WC as 64-bit words.
+// Why the count is cm_hamming_diag's, which compares raw bytes:
+//   the text's character i is an upper-case base -- on the + strand the read's own byte, on the - strand cm_negchar of a byte of
+//   the read, which for an upper-case base is again an upper-case base -- and orientation 0 / 1 of the read's planes is the code of
+//   exactly that character, base i at bit i (cm_finish_read_planes, cm_pack_read_planes_w), with pn clear below L;
+//   a reference byte equals an upper-case base letter iff it is that letter, that is iff it is a letter of ACGTacgt (pn = 0), not a
+//   lower-case one (pc = 0), and its code is the text's (p0, p1 equal) -- 'a' against 'A' is a mismatch of the byte compare and
+//   has pc set here; N, n and every other byte have pn set;
+//   a zero byte behind a chromosome's end has pn = 1 (cm_pack_planes32: code 4) and mismatches, as 0 against a letter does.
+CM_HD int cm_hamming_diag_planes(const CmPlRec *rp, uint64_t g, const uint32_t *tp, uint32_t tw, int L) {
+  CM_GLOBAL_PL rr = (CM_GLOBAL_PL)rp + (g >> 5);
+  CM_GLOBAL_U32 t0 = (CM_GLOBAL_U32)tp;
+  CM_GLOBAL_U32 t1 = t0 + tw;
+  const uint32_t sh = (uint32_t)g & 31u;
+  const CmPlRec ra = rr[0], rb = rr[1], rc = rr[2];
+  const bool two = L > 32;  // (tw may be 1: then every read of the batch has at most 32 bases)
+  const uint64_t x0 = (uint64_t)t0[0] | ((uint64_t)(two ? t0[1] : 0u) << 32);
+  const uint64_t x1 = (uint64_t)t1[0] | ((uint64_t)(two ? t1[1] : 0u) << 32);
+  const uint64_t W0 = (uint64_t)cm_funnel32(ra.p0, rb.p0, sh) | ((uint64_t)cm_funnel32(rb.p0, rc.p0, sh) << 32);
+  const uint64_t W1 = (uint64_t)cm_funnel32(ra.p1, rb.p1, sh) | ((uint64_t)cm_funnel32(rb.p1, rc.p1, sh) << 32);
+  const uint64_t WN = (uint64_t)cm_funnel32(ra.pn, rb.pn, sh) | ((uint64_t)cm_funnel32(rb.pn, rc.pn, sh) << 32);
+  const uint64_t WC = (uint64_t)cm_funnel32(ra.pc, rb.pc, sh) | ((uint64_t)cm_funnel32(rb.pc, rc.pc, sh) << 32);
+  return (int)__builtin_popcountll(((W0 ^ x0) | (W1 ^ x1) | WN | WC) & cm_mask64((uint32_t)L));
+}
 
 // BandedTraceback's bit-vector pass (alignment.cc:672-718) with both strings streamed backwards; its leading Hamming
 // count is cm_hamming_diag (the caller below)
@@ -3122,13 +3151,30 @@ struct CmSpan { uint32_t rid, ref_start, ref_end; };
 // GetRefStartEndPositionForReadFromMapping, non-SAM non-split (mapping_generator.h:657-717,
 // 762-793, 855-916).  The reference reads up to e bytes past the end of a chromosome when
 // ref_pos + e >= length (:703-708); HBM holds zero padding there (kseq's NUL, then zeros).
-CM_HD CmSpan cm_ref_start_end(const CmDev &d, uint64_t dpos, int nerr, int strand, const uint8_t *read, int L) {
+// r: the read's index.  BandedTraceback's leading Hamming count (cm_banded_traceback) is taken on bit planes when the read is
+// plain (CmDev::read_plain: upper-case A/C/G/T only, at most 64 bases, packed by the front end) -- cm_hamming_diag_planes, the same
+// number from three 16-byte loads and a popcount instead of a SWAR pass over the bytes of both strings; every other read, and the
+// traceback proper when the count is not the edit distance, stay on bytes.  cmgpu_set_option "s6_planes" 0 (d.read_plain is then
+// nullptr): bytes throughout.
+CM_HD CmSpan cm_ref_start_end(const CmDev &d, uint32_t r, uint64_t dpos, int nerr, int strand, const uint8_t *read, int L) {
   const int e = d.p.e;
   const uint32_t rid = (uint32_t)(dpos >> 32), ref_pos = (uint32_t)dpos;
   const uint32_t rl = d.ref_len[rid];
   uint32_t vw = ref_pos + 1 > (uint32_t)(L + e) ? ref_pos + 1 - (uint32_t)L - (uint32_t)e : 0;
   if (ref_pos + (uint32_t)e >= rl) vw = rl - (uint32_t)e - (uint32_t)L;
-  const int start = cm_banded_traceback(e, nerr, d.ref + d.ref_off[rid] + vw, read, L, strand == 1, 0, L);
+  const uint8_t *pattern = d.ref + d.ref_off[rid] + vw;
+  const uint64_t g = d.ref_off[rid] + vw + (uint32_t)e;  // the diagonal's first base
+  const bool neg = strand == 1;
+  int start = e;
+  if (nerr != 0) {  // cm_banded_traceback(e, nerr, pattern, read, L, neg, 0, L) with the count from either form
+    int diag;
+    if (d.read_plain && d.read_pl && L <= 64 && d.read_plain[r] != 0 && (g >> 5) + 3 <= d.ref_pl_words)  // (read_plain: only with d.ref_pl)
+      diag = cm_hamming_diag_planes(d.ref_pl, g, cm_read_pl_of(d, r) + (neg ? 3 * (size_t)d.read_pl_w : 0), d.read_pl_w, L);
+    else diag = cm_hamming_diag(pattern + e, read, L, neg, 0, L);
+    if (diag != nerr)
+      start = neg ? cm_banded_traceback_stream<true>(e, nerr, pattern, read, L, 0, L)
+                  : cm_banded_traceback_stream<false>(e, nerr, pattern, read, L, 0, L);
+  }
   CmSpan s;
   s.rid = rid;
   s.ref_start = vw + (uint32_t)start;
@@ -3498,8 +3544,8 @@ CM_HD void cm_emit_record(const CmDev &d, uint32_t pair, const CmPe &pe, uint32_
     a = cm_ref_start_end_sam(d, pair, r1, dp1, s1, cm_read_ptr(d, r1), (int)len1, &sa1);
     b = cm_ref_start_end_sam(d, pair, r2, dp2, s2, cm_read_ptr(d, r2), (int)len2, &sa2);
   } else {
-    a = cm_ref_start_end(d, dp1, e1, s1, cm_read_ptr(d, r1), (int)len1);
-    b = cm_ref_start_end(d, dp2, e2, s2, cm_read_ptr(d, r2), (int)len2);
+    a = cm_ref_start_end(d, r1, dp1, e1, s1, cm_read_ptr(d, r1), (int)len1);
+    b = cm_ref_start_end(d, r2, dp2, e2, s2, cm_read_ptr(d, r2), (int)len2);
   }
   const uint16_t al1 = (uint16_t)(a.ref_end - a.ref_start + 1), al2 = (uint16_t)(b.ref_end - b.ref_start + 1);
   const int force_mapq = d.force0[pair] ? 0 : -1;
@@ -3784,7 +3830,7 @@ CM_HD void cm_emit_single_record(const CmDev &d, uint32_t pair, uint32_t choice,
         CmSamAln sa;
         CmSpan sp;
         if constexpr (SAM) sp = cm_ref_start_end_sam(d, pair, pair, dp[mi], strand, cm_read_ptr(d, r), (int)L, &sa);
-        else sp = cm_ref_start_end(d, dp[mi], de[mi], strand, cm_read_ptr(d, r), (int)L);
+        else sp = cm_ref_start_end(d, r, dp[mi], de[mi], strand, cm_read_ptr(d, r), (int)L);
         const uint16_t al = (uint16_t)(sp.ref_end - sp.ref_start + 1);
         const uint8_t mapq = cm_mapq_single(d, de[mi], al, (int)L, d.p.e, d.second_err[r], d.n_best[r], d.n_second[r], d.rep_len[r]);
         uint8_t *o = d.rec + slot * 24;

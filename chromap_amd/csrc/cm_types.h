@@ -139,6 +139,12 @@ struct CmDev {
   //      read_pl + r * cm_read_pl_stride(read_pl_w) + (o * 3 + q) * read_pl_w, read_pl_w words of 32 bases each.  nullptr: not packed
   uint32_t *read_pl;
   uint32_t read_pl_w;
+  // read r of the range is "plain": every byte of the RAW read (before trimming) is an upper-case A, C, G or T.  Written for every
+  // read by the front-end kernel that handles it: k_prep_mm's planes instance writes what it computes for the trim, every other
+  // front end writes 0.  For a plain read of at most 64 bases the planes say everything the bytes say, letter case included
+  // (cm_hamming_diag_planes): cm_ref_start_end counts mismatches on planes for such reads.  nullptr: not kept -- the reference has no
+  // planes, or cmgpu_set_option "s6_planes" 0 -- and S6 stays on bytes
+  uint8_t *read_plain;  // [2n]
   CmParams p;
   CmMapqTables mq;
   // ---- batch

@@ -119,7 +119,9 @@ int cmgpu_gather_sweep(cmgpu_ctx *ctx, uint64_t n, int repeat, int loads_per_lan
  * instead of the short-list instance k_s3b_short; tests/test_gpu_s3b_short.py compares the two),
  * "pack_once" 1/0 (batches whose longest read has at most 64 bases, on the fused trim + minimizer kernel: 1 converts every read to
  * bit planes once, in that kernel, for the trim, the minimizer pass and the verification's planes; 0 converts the bytes in each of
- * the three, the last in a kernel of its own, k_pack_reads; tests/test_gpu_pack_once.py compares the two).
+ * the three, the last in a kernel of its own, k_pack_reads; tests/test_gpu_pack_once.py compares the two),
+ * "s6_planes" 1/0 (1: the pairing stage's start positions count the mismatches in front of the traceback on bit planes for reads of
+ * at most 64 bases made of upper-case A/C/G/T only; 0: on bytes for every read; tests/test_gpu_s6_planes.py compares the two).
  * Every setting gives the same records (tests/test_gpu_parity.py runs the fuzz data under each; "s3b_short" 1 and 0:
  * tests/test_gpu_s3b_short.py, on its own data and on one fuzz configuration). */
 int cmgpu_set_option(cmgpu_ctx *ctx, const char *name, int64_t value);
@@ -158,7 +160,9 @@ int cmgpu_reference_lengths(cmgpu_ctx *ctx, uint32_t *lengths, uint32_t capacity
  * long-list class l (the CmList ids of cm_types.h), the words above are the lists' work cursors.  A read-only copy.
  * "read_pl": the reads' bit planes as the verification saw them, for a batch mapped in one piece: S = (6 W + 3) & ~3 words per read,
  * W = (longest read + 31) / 32; read r's forward p0 / p1 / pn (W words each), then the reverse complement's, at r * S.  Defined
- * for reads with rlen > 0; *n_out = 2 n S. */
+ * for reads with rlen > 0; *n_out = 2 n S.
+ * "read_plain": per read (2 n entries), for a batch mapped in one piece with "s6_planes" on: 1 when every byte of the raw read is an
+ * upper-case A, C, G or T and the front end's planes instance handled the batch, else 0 (one byte per read on the device). */
 int cmgpu_debug_array(cmgpu_ctx *ctx, const char *name, uint32_t *out, uint64_t capacity, uint64_t *n_out);
 
 /* ---- the MAPQ functions on their own (tests/test_gpu_mapq.py) ----
