@@ -672,20 +672,34 @@ static void write_tbi(Run &r, cmgpu_ctx *cx, uint64_t base) {
   ck(cx, cmgpu_tabix_write(cx, path.c_str()));
   fprintf(stderr, "Built the tabix index on the device and wrote %s (%llu bytes before compression) in %.3fs.\n", path.c_str(), (unsigned long long)n, now_s() - t0);
 }
+// --output-bai: the BAM index of the records cx compressed last, whose blocks stand at `base` in the output file.  The BAM file is
+// complete by now and stays: records the indexer refuses end the run with the indexer's words, and without an index file
+static void write_bai(Run &r, cmgpu_ctx *cx, uint64_t base) {
+  const std::string path = r.a.out_path + ".bai";
+  const double t0 = now_s();
+  uint64_t n = 0;
+  const int rc = cmgpu_bgzf_index_bai(cx, base, r.ref.n_sequences, nullptr, 0, &n);
+  if (rc != CMGPU_OK) { remove(path.c_str()); ck(cx, rc); }
+  ck(cx, cmgpu_bai_write(cx, path.c_str()));
+  fprintf(stderr, "Built the BAM index on the device and wrote %s (%llu bytes) in %.3fs.\n", path.c_str(), (unsigned long long)n, now_s() - t0);
+}
 // ---- the writers: each returns the number of lines written (negative: the file could not be written)
 // sort + duplicate removal + MAPQ filter + SAM lines on the device, from the reads and records in HBM
 static int64_t write_sam_device(Run &r) {
   cmgpu_ctx *ctx = r.ctx();
   uint64_t nl = 0, nbytes = 0;
   if (r.a.out_bam) {  // --BAM: the same selection, the records and the header in BAM's binary form; both leave as BGZF blocks (parse(): output_bgzf)
+    if (r.a.output_bai) ck(ctx, cmgpu_bam_keep_starts(ctx, 1));
     ck(ctx, cmgpu_store_format_bam(ctx, r.out_names.data(), r.out_lengths.data(), r.ref.n_sequences, &r.a.p, r.barcoded ? r.bc_len : 0, &nl, &nbytes));
     write_header(r, [&](const char *path) { return cmgpu_write_bam_header(r.out_names.data(), r.out_lengths.data(), r.ref.n_sequences, path); });
   } else {
     ck(ctx, cmgpu_store_format_sam(ctx, r.out_names.data(), r.out_lengths.data(), r.ref.n_sequences, &r.a.p, r.barcoded ? r.bc_len : 0, &nl, &nbytes));
     write_header(r, [&](const char *path) { return cmgpu_write_sam_header(r.out_names.data(), r.out_lengths.data(), r.ref.n_sequences, path); });
   }
+  const uint64_t bai_base = r.bgzf_bytes;  // (the header's blocks)
   write_section(r, ctx);
   bgzf_finish(r);
+  if (r.a.output_bai) write_bai(r, ctx, bai_base);
   return (int64_t)nl;
 }
 // the host writers: sort, duplicate removal and text from the records and reads collected by map_host_ingest

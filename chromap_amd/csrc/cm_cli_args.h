@@ -62,6 +62,7 @@ struct Args {
   bool output_bgzf = false;  // --output-bgzf: the output file is BGZF blocks, compressed on the device
   bool out_bam = false;      // --BAM: SAM's record route (out_sam), the selected records written as a BAM file (always BGZF)
   bool output_tbi = false;   // --output-tbi: <output>.tbi, the tabix index of the BGZF output, built on the device
+  bool output_bai = false;   // --output-bai: <output>.bai, the BAM index of --BAM output, built on the device
   uint32_t batch_pairs = 4000000;  // multiple of the reference's 500000-pair read batch
 };
 
@@ -188,6 +189,7 @@ static Args parse(int argc, char **argv) {
     else if (o == "--force-exchange") a.force_exchange = true;      // the multi-GPU code path with one GPU
     else if (o == "--output-bgzf") a.output_bgzf = true;
     else if (o == "--output-tbi") a.output_tbi = true;
+    else if (o == "--output-bai") a.output_bai = true;
     else if (o == "--host-ingest") a.host_ingest = true;   // kseq-style host parser (the fallback for text the device ingest refuses)
     else if (o == "--ingest-chunk-mb") { a.chunk_bytes = (size_t)atol(need("--ingest-chunk-mb")) << 20; a.chunk_given = true; }
     else if (o == "--batch-pairs") a.batch_pairs = (uint32_t)atol(need("--batch-pairs"));
@@ -206,12 +208,14 @@ static Args parse(int argc, char **argv) {
              "  --barcode-translate FILE  lines to<TAB or ,>from (gzip or plain): BED column 4 and the SAM CB:Z: value are written as the\n"
              "                  table's names; BED is translated on the device, --SAM on the host\n"
              "  --BAM           the records of --SAM as a BAM file (@SQ header, NM / MD / CB tags), encoded and BGZF-compressed on the device; one\n"
-             "                  GPU, device ingest, no index (.bai) is written.  Not with --host-ingest, --barcode-translate, -n > 1, --output-tbi\n"
+             "                  GPU, device ingest; its index: --output-bai.  Not with --host-ingest, --barcode-translate, -n > 1, --output-tbi\n"
              "  --output-bgzf   the output file as BGZF blocks (bgzip's format, readable by tabix / pairix / samtools), compressed on the\n"
              "                  device; nothing is inferred from the output file's name.  Not where the host renders the text:\n"
              "                  --host-ingest --SAM, --SAM --barcode-translate\n"
              "  --output-tbi    with --output-bgzf and BED or single-end --TagAlign output on one GPU: the tabix index of the output file\n"
              "                  (what `tabix -p bed` would make of it), built on the device and written to <output>.tbi\n"
+             "  --output-bai    with --BAM: the BAM index of the output file (what `samtools index` would make of it, bins not folded), built\n"
+             "                  on the device and written to <output>.bai\n"
              "  --summary FILE  per-barcode CSV (one row for bulk data): barcode,total,duplicate,unmapped,lowmapq counted on the device;\n"
              "                  cachehit, fric, estfrip and numcacheslots are written as 0 (the minimizer cache is not modelled)\n");
       exit(0);
@@ -263,12 +267,13 @@ static void validate(Args &a) {
   if (barcoded && a.whitelist.empty() && a.p.remove_pcr_duplicates && a.p.low_memory_mode && !a.cell_level_dedup)
     die("bulk-level duplicate removal ranks barcodes by whitelist abundance: give --barcode-whitelist or --remove-pcr-duplicates-at-cell-level");
   a.p.dedup_at_bulk_level = barcoded && !a.cell_level_dedup ? 1 : 0;  // remove_pcr_duplicates_at_bulk_level defaults to true (mapping_parameters.h:49)
+  if (a.output_bai && !a.out_bam) die("--output-bai needs --BAM (the index is that of a BAM file's records)");
   // BAM records are encoded from one context's stores in HBM and leave through the BGZF writer
   if (a.out_bam) {
     if (a.host_ingest) die("--BAM with --host-ingest is outside this build (the host renders that output, as SAM text; convert it with samtools view -b)");
     if (!a.translate_path.empty())
       die("--BAM with --barcode-translate is outside this build (the command line's route for it is the host writer, which renders SAM text)");
-    if (a.output_tbi) die("--output-tbi with --BAM is outside this build (BAM takes a .bai index, which is not built)");
+    if (a.output_tbi) die("--output-tbi with --BAM is outside this build (BAM takes a .bai index: --output-bai)");
     if (a.gpus > 1 || a.force_exchange) die("--BAM with --gpus > 1 or --force-exchange is outside this build (the records are encoded by one context from its own stores)");
     if (a.p.allocate_multi_mappings && !a.p.low_memory_mode)
       die("--allocate-multi-mappings with --BAM is outside this build (the SAM and BAM writers have no allocation stage)");
@@ -282,7 +287,7 @@ static void validate(Args &a) {
   // the index is made of one context's sorted BED text and its blocks
   if (a.output_tbi) {
     if (!a.output_bgzf) die("--output-tbi needs --output-bgzf (the index is that of the BGZF blocks)");
-    if (a.out_sam) die("--output-tbi with --SAM is outside this build (a tabix index of SAM text; BAM and its index are not written)");
+    if (a.out_sam) die("--output-tbi with --SAM is outside this build (a tabix index of SAM text; --BAM --output-bai writes BAM and its index)");
     if (a.out_pairs) die("--output-tbi with pairs output is outside this build (pairs text takes a .px2 index, which is not built)");
     if (a.out_tagalign && paired) die("--output-tbi with paired-end --TagAlign is outside this build (two lines per pair: the text is not sorted by start)");
     if (a.gpus > 1 || a.force_exchange) die("--output-tbi with --gpus > 1 or --force-exchange is outside this build (the output has one section per GPU)");

@@ -229,6 +229,13 @@ struct cmgpu_ctx {
   const uint8_t *bgzf_src_ptr = nullptr;
   std::vector<uint8_t> tabix;  // the last index's payload (cmgpu_bgzf_index_tabix)
   bool tabix_have = false;
+  // for the BAM index (cm_bai.h, cm_tabix.hip): with bam_keep, cmgpu_store_format_bam leaves the offsets of the records it wrote, and
+  // the text's size behind them, in bam_starts -- bam_starts_n + 1 64-bit words that belong to text bam_starts_gen of bam_starts_bytes bytes
+  DevBuf bam_starts;
+  bool bam_keep = false, bam_starts_have = false;
+  uint64_t bam_starts_n = 0, bam_starts_gen = 0, bam_starts_bytes = 0;
+  std::vector<uint8_t> bai;  // the last index's payload (cmgpu_bgzf_index_bai)
+  bool bai_have = false;
   uint64_t text_gen = 0, bgzf_text_gen = 0;  // text_gen: counts the texts published to the text store; bgzf_text_gen: the one that was compressed
   uint64_t store_n = 0, store_cap = 0, text_bytes = 0, text_lines = 0;
   bool text_bam = false;  // the text store holds BAM alignment records (cmgpu_store_format_bam), not lines: text_lines counts records
@@ -327,12 +334,15 @@ struct cmgpu_ctx {
             &hit_off, &round2, &rep_cnt, &rep_len, &hbuf, &hcnt, &n_pos_hit, &ncp, &ncn, &aug, &res_neg, &res_pos,
             &resc_n, &resc_p, &m_tot, &m_off, &mbuf, &mcnt, &mcp, &mcn, &force0, &fbuf, &fcnt, &fcp, &fcn, &alive,
             &dpos, &derr, &dsplit, &nv, &v_off, &v_err, &v_end, &ndp, &ndn, &min_err, &second_err, &n_best, &n_second, &pe_min, &pe_second, &pe_nbest,
-            &pe_nsecond, &pe_first, &pe_i1, &pe_i2, &pe_choice, &rec, &rec_ok, &scan_tmp, &stats, &partials, &wl, &pow10_tab, &bcb, &bcq, &bco, &bc_key, &bc_ok, &wl_num, &bt_tab, &bt_blob, &store, &store_bc, &text, &bgzf, &bgzf_slots, &bgzf_tok, &bgzf_sizes, &bgzf_in, &bgzf_coff, &sam_rec, &sam_cigar, &sam_md, &sam_z, &part_cnt, &mm_cursor, &mm_marks, &rid_rank, &ref_off_r, &ref_len_r, &pairs_rank,
+            &pe_nsecond, &pe_first, &pe_i1, &pe_i2, &pe_choice, &rec, &rec_ok, &scan_tmp, &stats, &partials, &wl, &pow10_tab, &bcb, &bcq, &bco, &bc_key, &bc_ok, &wl_num, &bt_tab, &bt_blob, &store, &store_bc, &text, &bgzf, &bgzf_slots, &bgzf_tok, &bgzf_sizes, &bgzf_in, &bgzf_coff, &bam_starts, &sam_rec, &sam_cigar, &sam_md, &sam_z, &part_cnt, &mm_cursor, &mm_marks, &rid_rank, &ref_off_r, &ref_len_r, &pairs_rank,
             &ex.owner, &ex.send, &ex.counts, &ex.stage, &rec_dense, &rec_dense_b, &maxlen_dev, &bkt_fast, &ref_planes, &read_planes, &mm_stage, &coop_prof, &rs_pool, &rs_pool_off, &goff, &coop_slab, &hv_cnt, &hv_list, &perm_reads, &perm_pairs, &hv_tmp, &srt_cnt, &srt_list, &rs_list, &rs_cnt};
   }
 };
 
 void cm_set_error(cmgpu_ctx *ctx, const std::string &msg);
+// cm_tabix.hip, for cmgpu_store_format_bam with bam_keep: the starts of the n_rec records among the n candidates that have a length
+// (llen[i] != 0: loff[i]) become the context's bam_starts, `total` behind them
+int cm_bai_keep_starts(cmgpu_ctx *c, const uint64_t *llen, const uint64_t *loff, uint32_t n, uint64_t n_rec, uint64_t total);
 
 // a HIP call of a function that returns a CMGPU_* code: on failure the call's text and HIP's message become the context's error
 #define CM_HIPCHECK(ctx, call)                                                               \

@@ -727,6 +727,7 @@ extern "C" int cmgpu_store_clear(cmgpu_ctx *c) {
   c->store_pairs_rec = false;
   c->text_bytes = 0;
   c->text_lines = 0;
+  c->bam_starts_have = false;
   return CMGPU_OK;
 }
 

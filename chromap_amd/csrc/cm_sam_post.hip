@@ -466,8 +466,9 @@ static int sp_format_store(cmgpu_ctx *c, const char *const *ref_names, uint32_t 
   *n_bytes = 0;
   c->text_bytes = 0;
   c->text_lines = 0;
+  c->bam_starts_have = false;  // (kept starts are those of one rendering: cmgpu_bam_keep_starts)
   const uint32_t n = (uint32_t)st.n;
-  if (n == 0) return CMGPU_OK;
+  if (n == 0) return bam && c->bam_keep ? cm_bai_keep_starts(c, nullptr, nullptr, 0, 0, 0) : CMGPU_OK;
   if (c->rd_n == 0 || (st.paired && !c->rd_paired)) { cm_set_error(c, "the read store is empty: SAM text needs the reads of the run (cmgpu_fastq_keep_reads)"); return CMGPU_EINVAL; }
   CmTextJob job;
   int rc;
@@ -535,6 +536,7 @@ static int sp_format_store(cmgpu_ctx *c, const char *const *ref_names, uint32_t 
 #undef SP_LAUNCH
   if ((rc = job.publish(total, lines, n_lines, n_bytes))) return rc;
   c->text_bam = bam;
+  if (bam && c->bam_keep) return cm_bai_keep_starts(c, (const uint64_t *)job.llen.p, (const uint64_t *)job.loff.p, n, lines, total);
   return CMGPU_OK;
 }
 extern "C" int cmgpu_store_format_sam(cmgpu_ctx *c, const char *const *ref_names, const uint32_t *ref_lengths, uint32_t n_sequences, const cmgpu_params *p,

@@ -6,6 +6,10 @@
 // raw chunk), 16 bytes per 4 KiB of text (the tiles' newline counts and their scan), 44 bytes per raw chunk (key and number twice
 // for the sort, two virtual offsets, the merge flag), 24 per merged chunk, 8 per 16 kb window of every reference, 40 per reference
 // and its name, and rocprim's work areas.
+// The BAM index of a compressed chain of BAM records (cm_bai.h) is built here too: its keys come from the records' fields, and from
+// the raw chunks on it is the same index -- the same kernels, scans and sort.  Its temporary memory: 16 bytes per record (begin, end,
+// reference, raw chunk; the starts are kept by cmgpu_store_format_bam or uploaded: 8 more), 40 per reference, and the chunks' and
+// windows' as above.
 #include <stdio.h>
 #include <string.h>
 
@@ -13,6 +17,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "cm_bai.h"
 #include "cm_ctx.h"
 #include "cm_tabix.h"
 #include "cm_text_job.h"
@@ -106,14 +111,52 @@ __global__ __launch_bounds__(TX_LANES) void k_tbx_chunk_emit(const uint64_t *__r
   if (j < n) cm_tbx_chunk_emit(key, perm, cbeg, cend, midx, n, j, out);
 }
 
+// ---- the BAM index's per-record kernels (cm_bai.h): one lane per record
+__global__ __launch_bounds__(TX_LANES) void k_bai_parse(CmBaiArrays d) {
+  const uint64_t i = (uint64_t)blockIdx.x * TX_LANES + threadIdx.x;
+  if (i < d.n_rec) cm_bai_rec_parse<TxAtomics>(d, i);
+}
+// (no lane leaves early: the wave's lanes meet to raise their reference's n_intv and counts with one atomic each where they all have
+// the same reference)
+__global__ __launch_bounds__(TX_LANES) void k_bai_flags(CmBaiArrays d) {
+  const uint64_t i = (uint64_t)blockIdx.x * TX_LANES + threadIdx.x;
+  uint32_t t = ~0u, want = 0, unm = 0;
+  if (i < d.n_rec) want = cm_bai_rec_flags_core(d, i, &t, &unm);
+  const uint32_t t0 = __shfl(t, 0, 64);
+  if (__all(t == t0)) {
+    const uint32_t n_unm = (uint32_t)__popcll(__ballot(t != ~0u && unm)), n_all = (uint32_t)__popcll(__ballot(t != ~0u));
+#pragma unroll
+    for (int dlt = 32; dlt > 0; dlt >>= 1) { const uint32_t x = __shfl_xor(want, dlt, 64); want = x > want ? x : want; }
+    if ((threadIdx.x & 63u) == 0 && t != ~0u) {
+      atomicMax(&d.ref[t].n_intv, want);
+      if (n_all - n_unm) atomicAdd(&d.ref[t].n_mapped, (unsigned long long)(n_all - n_unm));
+      if (n_unm) atomicAdd(&d.ref[t].n_unmapped, (unsigned long long)n_unm);
+    }
+  } else if (t != ~0u) {
+    atomicMax(&d.ref[t].n_intv, want);
+    atomicAdd(unm ? &d.ref[t].n_unmapped : &d.ref[t].n_mapped, 1ull);
+  }
+}
+__global__ __launch_bounds__(TX_LANES) void k_bai_emit(CmBaiArrays d) {
+  const uint64_t i = (uint64_t)blockIdx.x * TX_LANES + threadIdx.x;
+  if (i < d.n_rec) cm_bai_rec_emit<TxAtomics>(d, i);
+}
+// out[rank of i among the selected] = loff[i] for the records with a length: the starts of the records the BAM writer wrote
+__global__ __launch_bounds__(TX_LANES) void k_bai_keep(const uint64_t *__restrict__ llen, const uint64_t *__restrict__ loff, const uint64_t *__restrict__ rank, uint64_t n,
+                                                    uint64_t n_out, uint64_t *__restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * TX_LANES + threadIdx.x;
+  if (i < n && llen[i] && rank[i] < n_out) out[rank[i]] = loff[i];
+}
+
 namespace {
 struct TxJob {
   cmgpu_ctx *c;
   hipStream_t s;
+  const char *name = "tabix index";  // the messages' first words
   CmTmpBuf tmp;  // rocprim's work area
   ~TxJob() { (void)hipStreamSynchronize(s); }
-  int enomem() { cm_set_error(c, "out of device memory (tabix index)"); return CMGPU_ENOMEM; }
-  int fail(const char *what, hipError_t e) { cm_set_error(c, std::string("tabix index, ") + what + ": " + hipGetErrorString(e)); return CMGPU_EHIP; }
+  int enomem() { cm_set_error(c, std::string("out of device memory (") + name + ")"); return CMGPU_ENOMEM; }
+  int fail(const char *what, hipError_t e) { cm_set_error(c, std::string(name) + ", " + what + ": " + hipGetErrorString(e)); return CMGPU_EHIP; }
   // flags -> 1 + (number of the run each entry lies in), in place
   int scan_flags(uint32_t *v, uint64_t n) {
     size_t tb = 0;
@@ -145,13 +188,47 @@ static inline uint32_t tx_blocks(uint64_t n) { return (uint32_t)((n + TX_LANES -
     if (e_ != hipSuccess) return (job).fail(what, e_);             \
   } while (0)
 
+// ---- 3. (both indexes) the n_raw raw chunks by (reference, bin), file order kept; neighbours joined; the merged chunks to the host
+static int tx_merge_chunks(TxJob &job, uint64_t *ckey, uint32_t *cval, const uint64_t *cbeg, const uint64_t *cend, uint32_t n_raw, uint64_t n_ref,
+                           std::vector<CmTbxChunk> &h_ch) {
+  hipStream_t s = job.s;
+  CmTmpBuf skey, perm, mflag, merged;
+  struct Wait { hipStream_t s; ~Wait() { (void)hipStreamSynchronize(s); } } wait{s};  // (behind the buffers, as TxJob behind its caller's)
+  h_ch.clear();
+  if (n_raw == 0) return CMGPU_OK;
+  if (skey.ensure((size_t)n_raw * 8) || perm.ensure((size_t)n_raw * 4) || mflag.ensure((size_t)n_raw * 4)) return job.enomem();
+  unsigned bits = 16;
+  while (bits < 48 && (1ull << (bits - 16)) < n_ref) ++bits;
+  {
+    size_t tb = 0;
+    TX_CHECK(job, "sort", rocprim::radix_sort_pairs(nullptr, tb, ckey, (uint64_t *)skey.p, cval, (uint32_t *)perm.p, (size_t)n_raw, 0, bits, s));
+    if (job.tmp.ensure(tb + 256)) return job.enomem();
+    TX_CHECK(job, "sort", rocprim::radix_sort_pairs(job.tmp.p, tb, ckey, (uint64_t *)skey.p, cval, (uint32_t *)perm.p, (size_t)n_raw, 0, bits, s));
+  }
+  hipLaunchKernelGGL(k_tbx_chunk_flags, dim3(tx_blocks(n_raw)), dim3(TX_LANES), 0, s, (const uint64_t *)skey.p, (const uint32_t *)perm.p, cbeg, cend, (uint64_t)n_raw,
+                     (uint32_t *)mflag.p);
+  TX_CHECK(job, "merge", hipGetLastError());
+  { const int rc = job.scan_flags((uint32_t *)mflag.p, n_raw); if (rc) return rc; }
+  uint32_t n_merged = 0;
+  TX_CHECK(job, "merge", hipMemcpyAsync(&n_merged, (uint32_t *)mflag.p + (n_raw - 1), 4, hipMemcpyDeviceToHost, s));
+  TX_CHECK(job, "merge", cm_stream_sync(s));
+  h_ch.resize(n_merged);
+  if (merged.ensure((size_t)n_merged * sizeof(CmTbxChunk))) return job.enomem();
+  hipLaunchKernelGGL(k_tbx_chunk_emit, dim3(tx_blocks(n_raw)), dim3(TX_LANES), 0, s, (const uint64_t *)skey.p, (const uint32_t *)perm.p, cbeg, cend,
+                     (const uint32_t *)mflag.p, (uint64_t)n_raw, (CmTbxChunk *)merged.p);
+  TX_CHECK(job, "merge", hipGetLastError());
+  TX_CHECK(job, "merge", hipMemcpyAsync(h_ch.data(), merged.p, (size_t)n_merged * sizeof(CmTbxChunk), hipMemcpyDeviceToHost, s));
+  TX_CHECK(job, "merge", cm_stream_sync(s));
+  return CMGPU_OK;
+}
+
 static int tx_index(cmgpu_ctx *c, const uint8_t *text, uint64_t n, uint64_t base, std::vector<uint8_t> &payload) {
   if (n == 0) {
     cm_tbx_serialize(nullptr, 0, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, payload);
     return CMGPU_OK;
   }
   hipStream_t s = c->stream;
-  CmTmpBuf tcnt, toff, lstart, beg, end, tid, cidx, err, ref, name_off, names, lin_off, lin, ckey, skey, cval, perm, cbeg, cend, mflag, merged;
+  CmTmpBuf tcnt, toff, lstart, beg, end, tid, cidx, err, ref, name_off, names, lin_off, lin, ckey, cval, cbeg, cend;
   TxJob job;  // (declared behind the buffers: on every return it waits for the stream before they go)
   job.c = c;
   job.s = s;
@@ -226,8 +303,7 @@ static int tx_index(cmgpu_ctx *c, const uint8_t *text, uint64_t n, uint64_t base
   }
   const uint64_t n_win = h_lin_off[n_ref], name_bytes = h_name_off[n_ref];
   if (name_off.ensure(((size_t)n_ref + 1) * 8) || names.ensure(name_bytes + 16) || lin_off.ensure(((size_t)n_ref + 1) * 8) || lin.ensure(n_win * 8 + 16) ||
-      ckey.ensure((size_t)n_raw * 8) || skey.ensure((size_t)n_raw * 8) || cval.ensure((size_t)n_raw * 4) || perm.ensure((size_t)n_raw * 4) ||
-      cbeg.ensure((size_t)n_raw * 8) || cend.ensure((size_t)n_raw * 8) || mflag.ensure((size_t)n_raw * 4)) return job.enomem();
+      ckey.ensure((size_t)n_raw * 8) || cval.ensure((size_t)n_raw * 4) || cbeg.ensure((size_t)n_raw * 8) || cend.ensure((size_t)n_raw * 8)) return job.enomem();
   TX_CHECK(job, "upload", hipMemcpyAsync(name_off.p, h_name_off.data(), h_name_off.size() * 8, hipMemcpyHostToDevice, s));
   TX_CHECK(job, "upload", hipMemcpyAsync(lin_off.p, h_lin_off.data(), h_lin_off.size() * 8, hipMemcpyHostToDevice, s));
   TX_CHECK(job, "memset", hipMemsetAsync(lin.p, 0xff, n_win * 8, s));
@@ -242,26 +318,11 @@ static int tx_index(cmgpu_ctx *c, const uint8_t *text, uint64_t n, uint64_t base
   hipLaunchKernelGGL(k_tbx_emit, dim3(tx_blocks(n_lines)), dim3(TX_LANES), 0, s, d);
   TX_CHECK(job, "raw chunks", hipGetLastError());
   { const int rc = job.back_fill(d.lin, n_win); if (rc) return rc; }
-  // ---- 3. raw chunks by (reference, bin), file order kept; neighbours joined
-  unsigned bits = 16;
-  while (bits < 48 && (1ull << (bits - 16)) < n_ref) ++bits;
-  {
-    size_t tb = 0;
-    TX_CHECK(job, "sort", rocprim::radix_sort_pairs(nullptr, tb, d.ckey, (uint64_t *)skey.p, d.cval, (uint32_t *)perm.p, (size_t)n_raw, 0, bits, s));
-    if (job.tmp.ensure(tb + 256)) return job.enomem();
-    TX_CHECK(job, "sort", rocprim::radix_sort_pairs(job.tmp.p, tb, d.ckey, (uint64_t *)skey.p, d.cval, (uint32_t *)perm.p, (size_t)n_raw, 0, bits, s));
-  }
-  hipLaunchKernelGGL(k_tbx_chunk_flags, dim3(tx_blocks(n_raw)), dim3(TX_LANES), 0, s, (const uint64_t *)skey.p, (const uint32_t *)perm.p, (const uint64_t *)cbeg.p,
-                     (const uint64_t *)cend.p, (uint64_t)n_raw, (uint32_t *)mflag.p);
-  TX_CHECK(job, "merge", hipGetLastError());
-  { const int rc = job.scan_flags((uint32_t *)mflag.p, n_raw); if (rc) return rc; }
-  uint32_t n_merged = 0;
   std::vector<uint8_t> h_names(name_bytes + 1);
   std::vector<uint64_t> h_lin(n_win + 1);
-  TX_CHECK(job, "merge", hipMemcpyAsync(&n_merged, (uint32_t *)mflag.p + (n_raw - 1), 4, hipMemcpyDeviceToHost, s));
-  TX_CHECK(job, "merge", hipMemcpyAsync(h_names.data(), names.p, name_bytes, hipMemcpyDeviceToHost, s));
-  TX_CHECK(job, "merge", hipMemcpyAsync(h_lin.data(), lin.p, n_win * 8, hipMemcpyDeviceToHost, s));
-  TX_CHECK(job, "merge", cm_stream_sync(s));
+  TX_CHECK(job, "names", hipMemcpyAsync(h_names.data(), names.p, name_bytes, hipMemcpyDeviceToHost, s));
+  TX_CHECK(job, "names", hipMemcpyAsync(h_lin.data(), lin.p, n_win * 8, hipMemcpyDeviceToHost, s));
+  TX_CHECK(job, "names", cm_stream_sync(s));
   // a name twice: its second run's first line is the offender (host: as many steps as there are references)
   {
     std::unordered_set<std::string> seen;
@@ -269,15 +330,116 @@ static int tx_index(cmgpu_ctx *c, const uint8_t *text, uint64_t n, uint64_t base
       if (!seen.emplace((const char *)h_names.data() + h_name_off[r], (size_t)h_ref[r].name_len).second)
         return job.format_error((unsigned long long)h_ref[r].first_line << 3 | CM_TBX_E_RECUR);
   }
-  std::vector<CmTbxChunk> h_ch(n_merged);
-  if (merged.ensure((size_t)n_merged * sizeof(CmTbxChunk))) return job.enomem();
-  hipLaunchKernelGGL(k_tbx_chunk_emit, dim3(tx_blocks(n_raw)), dim3(TX_LANES), 0, s, (const uint64_t *)skey.p, (const uint32_t *)perm.p, (const uint64_t *)cbeg.p,
-                     (const uint64_t *)cend.p, (const uint32_t *)mflag.p, (uint64_t)n_raw, (CmTbxChunk *)merged.p);
-  TX_CHECK(job, "merge", hipGetLastError());
-  TX_CHECK(job, "merge", hipMemcpyAsync(h_ch.data(), merged.p, (size_t)n_merged * sizeof(CmTbxChunk), hipMemcpyDeviceToHost, s));
-  TX_CHECK(job, "merge", cm_stream_sync(s));
+  // ---- 3. raw chunks by (reference, bin), file order kept; neighbours joined
+  std::vector<CmTbxChunk> h_ch;
+  { const int rc = tx_merge_chunks(job, d.ckey, d.cval, d.cbeg, d.cend, n_raw, n_ref, h_ch); if (rc) return rc; }
   // ---- 4. the payload
-  cm_tbx_serialize(h_ref.data(), n_ref, n_lines, h_names.data(), h_name_off.data(), h_ch.data(), n_merged, h_lin.data(), h_lin_off.data(), payload);
+  cm_tbx_serialize(h_ref.data(), n_ref, n_lines, h_names.data(), h_name_off.data(), h_ch.data(), h_ch.size(), h_lin.data(), h_lin_off.data(), payload);
+  return CMGPU_OK;
+}
+
+// The BAM index of the n bytes of records at p, record i at starts[i] (device memory, n_rec + 1 entries)
+static int bai_index(cmgpu_ctx *c, const uint8_t *p, uint64_t n, uint64_t base, uint32_t n_ref, const uint64_t *starts, uint64_t n_rec, std::vector<uint8_t> &payload) {
+  hipStream_t s = c->stream;
+  CmTmpBuf beg, end, tid, cidx, err, ref, lin_off, lin, ckey, cval, cbeg, cend;
+  TxJob job;  // (declared behind the buffers: on every return it waits for the stream before they go)
+  job.c = c;
+  job.s = s;
+  job.name = "BAM index";
+  std::vector<CmBaiRef> h_ref(n_ref);
+  std::vector<uint64_t> h_lin_off((size_t)n_ref + 1, 0), h_lin(1);
+  std::vector<CmTbxChunk> h_ch;
+  if (n_rec == 0) {
+    if (n) { cm_set_error(c, "BAM index: " + std::to_string((unsigned long long)n) + " bytes and no record"); return CMGPU_EINVAL; }
+    cm_bai_serialize(h_ref.data(), n_ref, nullptr, 0, h_lin.data(), h_lin_off.data(), payload);
+    return CMGPU_OK;
+  }
+  if (n_rec > CM_BAI_MAX_RECORDS) { cm_set_error(c, "BAM index: more than 2^32 - 2 records"); return CMGPU_EINVAL; }
+  CmBaiArrays d = {};
+  d.t.p = p;
+  d.t.n = n;
+  d.t.n_blocks = c->bgzf_blocks;
+  d.t.coff = (const uint64_t *)c->bgzf_coff.p;
+  d.t.base = base;
+  d.n_rec = n_rec;
+  d.starts = starts;
+  d.n_ref = n_ref;
+  if (beg.ensure(n_rec * 4) || end.ensure(n_rec * 4) || tid.ensure(n_rec * 4) || cidx.ensure(n_rec * 4) || err.ensure(8) ||
+      ref.ensure((size_t)n_ref * sizeof(CmBaiRef) + 16)) return job.enomem();
+  d.beg = (uint32_t *)beg.p;
+  d.end = (uint32_t *)end.p;
+  d.tid = (uint32_t *)tid.p;
+  d.cidx = (uint32_t *)cidx.p;
+  d.err = (unsigned long long *)err.p;
+  d.ref = (CmBaiRef *)ref.p;
+  // ---- 1. per record: fields and checks
+  TX_CHECK(job, "memset", hipMemsetAsync(err.p, 0xff, 8, s));
+  TX_CHECK(job, "memset", hipMemsetAsync(ref.p, 0, (size_t)n_ref * sizeof(CmBaiRef), s));
+  hipLaunchKernelGGL(k_bai_parse, dim3(tx_blocks(n_rec)), dim3(TX_LANES), 0, s, d);
+  TX_CHECK(job, "records", hipGetLastError());
+  unsigned long long word = CM_TBX_NO_ERROR;
+  TX_CHECK(job, "records", hipMemcpyAsync(&word, d.err, 8, hipMemcpyDeviceToHost, s));
+  TX_CHECK(job, "records", cm_stream_sync(s));
+  if (word != CM_TBX_NO_ERROR) {
+    cm_set_error(c, "BAM index: record " + std::to_string((word >> 3) + 1) + " " + cm_bai_cause((uint32_t)(word & 7u)));
+    return CMGPU_EFORMAT;
+  }
+  // ---- 2. references, raw chunks' heads
+  hipLaunchKernelGGL(k_bai_flags, dim3(tx_blocks(n_rec)), dim3(TX_LANES), 0, s, d);
+  TX_CHECK(job, "references", hipGetLastError());
+  { const int rc = job.scan_flags(d.cidx, n_rec); if (rc) return rc; }
+  uint32_t n_raw = 0;
+  TX_CHECK(job, "references", hipMemcpyAsync(&n_raw, d.cidx + (n_rec - 1), 4, hipMemcpyDeviceToHost, s));
+  TX_CHECK(job, "references", hipMemcpyAsync(h_ref.data(), ref.p, (size_t)n_ref * sizeof(CmBaiRef), hipMemcpyDeviceToHost, s));
+  TX_CHECK(job, "references", cm_stream_sync(s));
+  for (uint32_t r = 0; r < n_ref; ++r) h_lin_off[r + 1] = h_lin_off[r] + h_ref[r].n_intv;
+  const uint64_t n_win = h_lin_off[n_ref];
+  if (lin_off.ensure(((size_t)n_ref + 1) * 8) || lin.ensure(n_win * 8 + 16) || ckey.ensure((size_t)n_raw * 8) || cval.ensure((size_t)n_raw * 4) ||
+      cbeg.ensure((size_t)n_raw * 8) || cend.ensure((size_t)n_raw * 8)) return job.enomem();
+  TX_CHECK(job, "upload", hipMemcpyAsync(lin_off.p, h_lin_off.data(), h_lin_off.size() * 8, hipMemcpyHostToDevice, s));
+  TX_CHECK(job, "memset", hipMemsetAsync(lin.p, 0xff, n_win * 8, s));
+  d.lin_off = (const uint64_t *)lin_off.p;
+  d.lin = (unsigned long long *)lin.p;
+  d.ckey = (uint64_t *)ckey.p;
+  d.cbeg = (uint64_t *)cbeg.p;
+  d.cend = (uint64_t *)cend.p;
+  d.cval = (uint32_t *)cval.p;
+  hipLaunchKernelGGL(k_bai_emit, dim3(tx_blocks(n_rec)), dim3(TX_LANES), 0, s, d);
+  TX_CHECK(job, "raw chunks", hipGetLastError());
+  { const int rc = job.back_fill(d.lin, n_win); if (rc) return rc; }
+  h_lin.resize(n_win + 1);
+  TX_CHECK(job, "windows", hipMemcpyAsync(h_lin.data(), lin.p, n_win * 8, hipMemcpyDeviceToHost, s));
+  // ---- 3. raw chunks by (reference, bin), file order kept; neighbours joined
+  { const int rc = tx_merge_chunks(job, d.ckey, d.cval, d.cbeg, d.cend, n_raw, n_ref, h_ch); if (rc) return rc; }
+  // ---- 4. the payload
+  cm_bai_serialize(h_ref.data(), n_ref, h_ch.data(), h_ch.size(), h_lin.data(), h_lin_off.data(), payload);
+  return CMGPU_OK;
+}
+// cmgpu_store_format_bam, behind publish: the offsets of the records it wrote -- loff where llen != 0 -- and `total` behind them
+int cm_bai_keep_starts(cmgpu_ctx *c, const uint64_t *llen, const uint64_t *loff, uint32_t n, uint64_t n_rec, uint64_t total) {
+  hipStream_t s = c->stream;
+  c->bam_starts_have = false;
+  CmTmpBuf rank;
+  TxJob job;
+  job.c = c;
+  job.s = s;
+  job.name = "BAM record starts";
+  if (c->bam_starts.ensure((n_rec + 1) * 8) || (n && rank.ensure((size_t)n * 8))) return job.enomem();
+  if (n) {
+    auto lines_in = rocprim::make_transform_iterator(llen, CmLinesOp());
+    size_t tb = 0;
+    (void)rocprim::exclusive_scan(nullptr, tb, lines_in, (uint64_t *)rank.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
+    if (job.tmp.ensure(tb + 256)) return job.enomem();
+    TX_CHECK(job, "scan", rocprim::exclusive_scan(job.tmp.p, tb, lines_in, (uint64_t *)rank.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s));
+    hipLaunchKernelGGL(k_bai_keep, dim3(tx_blocks(n)), dim3(TX_LANES), 0, s, llen, loff, (const uint64_t *)rank.p, (uint64_t)n, n_rec, (uint64_t *)c->bam_starts.p);
+    TX_CHECK(job, "compaction", hipGetLastError());
+  }
+  TX_CHECK(job, "upload", hipMemcpyAsync((uint64_t *)c->bam_starts.p + n_rec, &total, 8, hipMemcpyHostToDevice, s));
+  TX_CHECK(job, "compaction", cm_stream_sync(s));
+  c->bam_starts_have = true;
+  c->bam_starts_n = n_rec;
+  c->bam_starts_gen = c->text_gen;
+  c->bam_starts_bytes = total;
   return CMGPU_OK;
 }
 
@@ -295,7 +457,7 @@ extern "C" int cmgpu_bgzf_index_tabix(cmgpu_ctx *c, uint64_t base_offset, uint64
         return CMGPU_EINVAL;
       }
       if (c->text_bam) {
-        cm_set_error(c, "tabix index: the text store holds BAM records, not BED lines (BAM takes a .bai index, which is not built)");
+        cm_set_error(c, "tabix index: the text store holds BAM records, not BED lines (BAM takes a .bai index: cmgpu_bgzf_index_bai)");
         return CMGPU_EFORMAT;
       }
       text = static_cast<const uint8_t *>(c->text.p);
@@ -326,6 +488,86 @@ extern "C" int cmgpu_tabix_write(cmgpu_ctx *c, const char *path) {
   if (!c || !path) return CMGPU_EINVAL;
   if (!c->tabix_have) { cm_set_error(c, "no tabix index (cmgpu_bgzf_index_tabix comes first)"); return CMGPU_EINVAL; }
   if (cmgpu_bgzf_write_host_text(path, c->tabix.data(), c->tabix.size(), 0) != CMGPU_OK || cmgpu_bgzf_write_eof(path) != CMGPU_OK) {
+    remove(path);
+    cm_set_error(c, std::string("cannot write ") + path);
+    return CMGPU_EIO;
+  }
+  return CMGPU_OK;
+}
+
+// ---- the BAM index
+extern "C" int cmgpu_bam_keep_starts(cmgpu_ctx *c, int on) {
+  if (!c) return CMGPU_EINVAL;
+  c->bam_keep = on != 0;
+  if (!on) c->bam_starts_have = false;
+  return CMGPU_OK;
+}
+extern "C" int cmgpu_bgzf_index_bai(cmgpu_ctx *c, uint64_t base_offset, uint32_t n_ref, const uint64_t *starts, uint64_t n_records, uint64_t *n_bytes) {
+  if (!c) return CMGPU_EINVAL;
+  CM_HIPCHECK(c, cm_enter(c));
+  c->bai.clear();
+  c->bai_have = false;
+  if (n_bytes) *n_bytes = 0;
+  const uint8_t *p = nullptr;
+  switch (c->bgzf_src) {
+    case CM_BZ_SRC_STORE:
+      if (c->bgzf_text_gen != c->text_gen || c->bgzf_text_bytes != c->text_bytes) {
+        cm_set_error(c, "BAM index: the text store has been rendered anew since it was compressed");
+        return CMGPU_EINVAL;
+      }
+      p = static_cast<const uint8_t *>(c->text.p);
+      break;
+    case CM_BZ_SRC_UPLOAD: p = static_cast<const uint8_t *>(c->bgzf_in.p); break;
+    case CM_BZ_SRC_DEVICE: p = c->bgzf_src_ptr; break;
+    default:
+      cm_set_error(c, "BAM index: no compressed store to index (cmgpu_bgzf_compress or cmgpu_store_compress_text comes first)");
+      return CMGPU_EINVAL;
+  }
+  if (base_offset >> 47) { cm_set_error(c, "BAM index: base offset beyond 2^47"); return CMGPU_EINVAL; }
+  const uint64_t n = c->bgzf_text_bytes;
+  CmTmpBuf up;
+  const uint64_t *d_starts = nullptr;
+  if (!starts) {  // the starts cmgpu_store_format_bam kept: they belong to the rendering that was compressed
+    if (c->bgzf_src != CM_BZ_SRC_STORE || !c->bam_starts_have || c->bam_starts_gen != c->text_gen || c->bam_starts_bytes != c->text_bytes) {
+      cm_set_error(c, c->bgzf_src == CM_BZ_SRC_STORE && !c->text_bam && c->text_bytes
+                          ? "BAM index: the text store does not hold BAM records (cmgpu_store_format_bam renders them)"
+                          : "BAM index: no record starts were kept for the compressed store (cmgpu_bam_keep_starts comes before cmgpu_store_format_bam)");
+      return CMGPU_EINVAL;
+    }
+    d_starts = (const uint64_t *)c->bam_starts.p;
+    n_records = c->bam_starts_n;
+  } else {
+    if (n_records > CM_BAI_MAX_RECORDS) { cm_set_error(c, "BAM index: more than 2^32 - 2 records"); return CMGPU_EINVAL; }
+    if (up.ensure((n_records + 1) * 8)) { cm_set_error(c, "out of device memory (BAM index)"); return CMGPU_ENOMEM; }
+    CM_HIPCHECK(c, hipMemcpyAsync(up.p, starts, (n_records + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    CM_HIPCHECK(c, cm_stream_sync(c->stream));
+    d_starts = (const uint64_t *)up.p;
+  }
+  std::vector<uint8_t> payload;
+  const int rc = bai_index(c, p, n, base_offset, n_ref, d_starts, n_records, payload);
+  if (rc != CMGPU_OK) return rc;
+  c->bai.swap(payload);
+  c->bai_have = true;
+  if (n_bytes) *n_bytes = c->bai.size();
+  return CMGPU_OK;
+}
+extern "C" int cmgpu_bai_download(cmgpu_ctx *c, void *out, uint64_t capacity) {
+  if (!c || !out) return CMGPU_EINVAL;
+  if (!c->bai_have) { cm_set_error(c, "no BAM index (cmgpu_bgzf_index_bai comes first)"); return CMGPU_EINVAL; }
+  if (capacity < c->bai.size()) { cm_set_error(c, "BAM index buffer too small"); return CMGPU_ECAPACITY; }
+  memcpy(out, c->bai.data(), c->bai.size());
+  return CMGPU_OK;
+}
+extern "C" int cmgpu_bai_write(cmgpu_ctx *c, const char *path) {
+  if (!c || !path) return CMGPU_EINVAL;
+  if (!c->bai_have) { cm_set_error(c, "no BAM index (cmgpu_bgzf_index_bai comes first)"); return CMGPU_EINVAL; }
+  FILE *f = fopen(path, "wb");
+  bool ok = f != nullptr;
+  if (f) {
+    ok = fwrite(c->bai.data(), 1, c->bai.size(), f) == c->bai.size();
+    ok = fclose(f) == 0 && ok;
+  }
+  if (!ok) {
     remove(path);
     cm_set_error(c, std::string("cannot write ") + path);
     return CMGPU_EIO;

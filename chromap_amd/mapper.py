@@ -744,6 +744,34 @@ class ChromapGPU:
         """the last bgzf_tabix payload as a .tbi file: BGZF blocks and the end-of-file block"""
         self._check(self.L.cmgpu_tabix_write(self.ctx, path.encode()), self.ctx)
 
+    # ---- the BAM index of the compressed store, built on the device (include/chromap_amd.h; chromap_amd/csrc/cm_bai.h)
+    def bam_keep_starts(self, on=True):
+        """from now on store_format_bam keeps where every record it writes starts (in HBM), for bgzf_bai() of that rendering"""
+        self._check(self.L.cmgpu_bam_keep_starts(self.ctx, int(bool(on))), self.ctx)
+
+    def bgzf_bai(self, base_offset=0, n_ref=None, starts=None):
+        """the .bai file's bytes for the BAM records of the last bgzf_compress / store_compress_text, whose blocks will stand at file
+        offset `base_offset`.  n_ref: the header's number of references (default: this mapper's).  starts: the offsets of the records
+        and the number of bytes behind them, for records the caller compressed itself; None: those store_format_bam kept
+        (bam_keep_starts).  ChromapError for records that cannot be indexed (the message names the record and the cause)"""
+        n = C.c_uint64(0)
+        n_ref = len(self.names) if n_ref is None else int(n_ref)
+        if starts is None:
+            rc = self.L.cmgpu_bgzf_index_bai(self.ctx, int(base_offset), n_ref, None, 0, C.byref(n))
+        else:
+            st = np.ascontiguousarray(starts, np.uint64)
+            if st.size < 1:
+                raise ValueError("starts: the offsets of the records and the number of bytes behind them")
+            rc = self.L.cmgpu_bgzf_index_bai(self.ctx, int(base_offset), n_ref, st.ctypes.data, st.size - 1, C.byref(n))
+        self._check(rc, self.ctx)
+        buf = C.create_string_buffer(max(1, n.value))
+        self._check(self.L.cmgpu_bai_download(self.ctx, buf, n.value), self.ctx)
+        return buf.raw[:n.value]
+
+    def store_write_bai(self, path):
+        """the last bgzf_bai payload as a .bai file (not compressed)"""
+        self._check(self.L.cmgpu_bai_write(self.ctx, path.encode()), self.ctx)
+
     # ---- --summary: per-barcode TOTAL / DUP / LOWMAPQ / MAPPED counted on the device (include/chromap_amd.h)
     def summary_enable(self, on=True):
         """from now on every map_* call counts its reads per barcode and every store_format* call credits the duplicate runs;

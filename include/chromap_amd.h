@@ -487,7 +487,8 @@ int cmgpu_write_sam_header(const char *const *ref_names, const uint32_t *ref_len
  *                            cmgpu_store_compress_text + cmgpu_bgzf_write make them the body of a BAM file (a record may straddle
  *                            two blocks: the format allows it).  A selected record whose read name has 255 bytes or more does not
  *                            fit l_read_name: CMGPU_EFORMAT, no output.  cmgpu_bgzf_index_tabix refuses a store made of BAM records.
- *                            No .bai / .csi index is built; bin is the spec's reg2bin(pos, pos + reference length of the CIGAR).
+ *                            The .bai index: cmgpu_bgzf_index_bai below (no .csi); bin is the spec's reg2bin(pos, pos + reference
+ *                            length of the CIGAR).
  *   cmgpu_write_bam_header   the uncompressed header, on the host: "BAM\1", l_text and cmgpu_write_sam_header's @SQ lines, n_ref,
  *                            and per sequence l_name (with the NUL), the name, l_ref.  As BGZF blocks (cmgpu_bgzf_write_host_text)
  *                            in front of the compressed records and with cmgpu_bgzf_write_eof behind them it completes the file */
@@ -615,6 +616,31 @@ int cmgpu_bgzf_write_eof(const char *path);
 int cmgpu_bgzf_index_tabix(cmgpu_ctx *ctx, uint64_t base_offset, uint64_t *n_bytes);
 int cmgpu_tabix_download(cmgpu_ctx *ctx, void *out, uint64_t capacity);
 int cmgpu_tabix_write(cmgpu_ctx *ctx, const char *path);
+/* ---- BAM index of the compressed store, built on the device (cm_bai.h, cm_tabix.hip) -----------
+ * The .bai a coordinate-sorted BAM file needs (SAM spec 5.2), made from what is in HBM once the compressor is done: the records it
+ * compressed, where each of them starts, and the blocks' sizes.  The binning scheme, the 16 kb linear index, the chunk rules and the
+ * pseudo-bin 37450 are the tabix index's, and so are the kernels from the raw chunks on; the keys are fields of the binary records
+ * (refID, pos, the CIGAR's reference length, flag bit 4).  The records must be a chain -- each ends where the next one starts -- sorted
+ * by (refID, pos), every refID in 0 .. n_ref - 1 (no unmapped records: n_no_coor is 0), no end beyond 2^29 (the format's limit;
+ * `samtools index -c` builds a .csi for such a file).  Anything else is refused with CMGPU_EFORMAT and a message that names the first
+ * offending record and the cause; the context stays usable.  A reference without records has no bin, no pseudo-bin and no window.
+ * Sparse bins are not folded into their parents as htslib does: the index is valid and differs from `samtools index`'s bytes.
+ *   cmgpu_bam_keep_starts   on != 0: from now on cmgpu_store_format_bam keeps the offsets of the records it writes (8 bytes each, in
+ *                           HBM).  They belong to that rendering: the next cmgpu_store_format* or cmgpu_store_clear drops them.
+ *                           Off by default; a context that never turns it on runs what it ran before
+ *   cmgpu_bgzf_index_bai    indexes the records of the last cmgpu_bgzf_compress / cmgpu_store_compress_text against its blocks, which
+ *                           will stand at base_offset in the file (the bytes written before them: the header's blocks).  n_ref: the
+ *                           header's.  starts == NULL: the kept starts of the text store (CMGPU_EINVAL with a message where none
+ *                           were kept or the store does not hold BAM records); else a host array of n_records + 1 offsets, the last
+ *                           one the number of bytes, for records the caller compressed itself.  The payload (the .bai file's bytes)
+ *                           stays with the context; *n_bytes its size.  CMGPU_EINVAL also: nothing compressed yet, or the text
+ *                           store has been rendered anew since
+ *   cmgpu_bai_download      the payload (capacity >= its size, else CMGPU_ECAPACITY)
+ *   cmgpu_bai_write         the payload as a file (a .bai is not compressed); on failure the file is removed */
+int cmgpu_bam_keep_starts(cmgpu_ctx *ctx, int on);
+int cmgpu_bgzf_index_bai(cmgpu_ctx *ctx, uint64_t base_offset, uint32_t n_ref, const uint64_t *starts, uint64_t n_records, uint64_t *n_bytes);
+int cmgpu_bai_download(cmgpu_ctx *ctx, void *out, uint64_t capacity);
+int cmgpu_bai_write(cmgpu_ctx *ctx, const char *path);
 /* --allocate-multi-mappings (MappingProcessor::AllocateMultiMappings, src/mapping_processor.h:319-440): with
  * params->allocate_multi_mappings and without low_memory_mode, cmgpu_store_format gives every read whose surviving records have
  * MAPQ < 4 to one of them, drawn with probability proportional to the uni-mappings (MAPQ >= 4) within

@@ -19,6 +19,9 @@ wall time, output sizes, and the compressed file inflated and compared with the 
 `--output-bam` (with `--sam`): the job as plain `--SAM`, as `--SAM --output-bgzf` and as `--BAM` (records encoded and compressed on the
 device), `--reps` runs each, whole-process wall time and file sizes; the first records of the BAM file, decoded by tests/bam_model.py, must be
 the first lines of the SAM file.
+`--output-bai` (with `--sam`): the job as `--BAM` and as `--BAM --output-bai` (the BAM index built on the device) and -- with
+`--baseline-cli` -- that build with `--BAM`; the builds and flags take turns, `--reps` rounds, whole-process wall time; the BAM files must
+be the same bytes, and the index's own line is kept.
 Prints one JSON object; everything is written under --dir (default /tmp/chromap_amd_e2e)."""
 import argparse
 import ctypes as C
@@ -118,6 +121,37 @@ def output_tbi_job(args, cli, job, out):
     return res
 
 
+def output_bai_job(args, cli, job, out):
+    """--BAM with the parent's build (--baseline-cli), with this build, and with this build and --output-bai: one run of each per round,
+    the order kept, after one untimed round"""
+    variants = ([("parent_bam", args.baseline_cli, ["--BAM"])] if args.baseline_cli else []) + \
+               [("bam", cli, ["--BAM"]), ("bam_output_bai", cli, ["--BAM", "--output-bai"])]
+    res = {label: {"wall_s": [], "lines": []} for label, _, _ in variants}
+    for rnd in range(args.reps + 1):
+        for label, exe, extra in variants:
+            for f in (out, out + ".bai"):
+                if os.path.exists(f):
+                    os.remove(f)
+            os.sync()
+            t0 = time.time()
+            p = subprocess.run([exe] + job + extra, stderr=subprocess.PIPE, check=True)
+            dt = time.time() - t0
+            if rnd == 0:   # untimed: every build's code objects and the files have been read once
+                res[label]["bam_md5"] = subprocess.check_output(["md5sum", out]).split()[0].decode()
+                res[label]["bam_bytes"] = os.path.getsize(out)
+                res[label]["bai_written"] = os.path.exists(out + ".bai")
+                if "--output-bai" in extra:
+                    res[label]["bai_bytes"] = os.path.getsize(out + ".bai")
+                continue
+            res[label]["wall_s"].append(round(dt, 3))
+            res[label]["lines"].append([ln for ln in p.stderr.decode().splitlines()
+                                        if ln.startswith(("Mapped all reads", "Compressed ", "Built the BAM index", "Number of output mappings"))])
+    res["same_bam"] = len({res[label]["bam_md5"] for label, _, _ in variants}) == 1
+    res["config"] = {"preset": args.preset, "pairs": args.pairs, "readlen": args.readlen, "genome": args.genome, "reps": args.reps,
+                     "hardware_threads": os.cpu_count(), "cpu_budget": cpu_budget()}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--genome", type=int, default=200_000_000)
@@ -135,6 +169,7 @@ def main():
     ap.add_argument("--output-bgzf", action="store_true", help="--preset hic / --sam: time the job plain, with --output-bgzf, and plain + tools/bgzf.py of the output")
     ap.add_argument("--output-tbi", action="store_true", help="--preset atac: time --output-bgzf without and with --output-tbi (and --baseline-cli with --output-bgzf), taking turns")
     ap.add_argument("--output-bam", action="store_true", help="--sam: time the job as --SAM, --SAM --output-bgzf and --BAM")
+    ap.add_argument("--output-bai", action="store_true", help="--sam: time --BAM without and with --output-bai (and --baseline-cli with --BAM), taking turns")
     ap.add_argument("--skip-host-ingest", action="store_true", help="a long job: leave the host parser's run out")
     args = ap.parse_args()
     os.makedirs(args.dir, exist_ok=True)
@@ -178,6 +213,10 @@ def main():
 
     if args.output_tbi:
         print(json.dumps(output_tbi_job(args, cli, ["--preset", args.preset, "-x", idx, "-r", fa, "-1", r1, "-2", r2, "-o", out + ".gz"] + job, out + ".gz")))
+        return
+
+    if args.output_bai and args.sam:
+        print(json.dumps(output_bai_job(args, cli, ["--preset", args.preset, "-x", idx, "-r", fa, "-1", r1, "-2", r2, "-o", out + ".bam"] + job, out + ".bam")))
         return
 
     def run(label, f1, f2, extra=(), reps=args.reps, cli=cli, after=None):
