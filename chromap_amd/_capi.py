@@ -112,6 +112,7 @@ SYMBOLS = ("cmgpu_default_params", "cmgpu_apply_preset", "cmgpu_create", "cmgpu_
            "cmgpu_store_text", "cmgpu_store_write_text", "cmgpu_store_info", "cmgpu_store_allocation_info",
            "cmgpu_bgzf_compress", "cmgpu_store_compress_text", "cmgpu_bgzf_info", "cmgpu_bgzf_download", "cmgpu_bgzf_write", "cmgpu_bgzf_write_host_text", "cmgpu_bgzf_write_eof", "cmgpu_bgzf_index_tabix", "cmgpu_tabix_download", "cmgpu_tabix_write",
            "cmgpu_bam_keep_starts", "cmgpu_bgzf_index_bai", "cmgpu_bai_download", "cmgpu_bai_write",
+           "cmgpu_bgzf_index_csi_bam", "cmgpu_bgzf_index_csi_tabix", "cmgpu_csi_download", "cmgpu_csi_write",
            "cmgpu_sam_layout", "cmgpu_download_sam", "cmgpu_write_sam", "cmgpu_download_barcode_keys", "cmgpu_set_barcode_check", "cmgpu_write_sam_barcoded", "cmgpu_write_sam_barcoded_translated",
            "cmgpu_warm_up", "cmgpu_fastq_set_format", "cmgpu_fastq_scan", "cmgpu_fastq_scan_bgzf", "cmgpu_fastq_take", "cmgpu_fastq_commit", "cmgpu_barcode_abundance_resident",
            "cmgpu_fastq_keep_names", "cmgpu_names_clear", "cmgpu_names_info", "cmgpu_download_names", "cmgpu_store_format_pairs_resident",
@@ -282,6 +283,10 @@ def declare(L):
     sig("cmgpu_bgzf_index_bai", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, P(C.c_uint64)])
     sig("cmgpu_bai_download", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64])
     sig("cmgpu_bai_write", C.c_int, [C.c_void_p, C.c_char_p])
+    sig("cmgpu_bgzf_index_csi_bam", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, P(C.c_uint64)])
+    sig("cmgpu_bgzf_index_csi_tabix", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, P(C.c_uint64)])
+    sig("cmgpu_csi_download", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64])
+    sig("cmgpu_csi_write", C.c_int, [C.c_void_p, C.c_char_p])
     sig("cmgpu_store_allocation_info", C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint64), P(C.c_uint64)])
     sig("cmgpu_sam_layout", C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint32)])
     sig("cmgpu_download_sam", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])

@@ -13,6 +13,9 @@
 //  3. per raw chunk, sorted by (reference, bin) with a stable sort: cm_tabix.h's stage 3.
 //  4. the payload, on the host (cm_bai_serialize): a plain file, not BGZF.
 // Sparse bins are not folded into their parents (htslib's compress_binning): the index is valid, and larger than samtools' own.
+// With CmBaiArrays::csi_depth 1 .. 6 the same stages make a CSI index's keys (cm_tabix.h: depth levels, limit 2^(14 + 3 * depth) and
+// 0xffffffff at depth 6, keys reference << 20 | bin); 0 is the .bai's scheme.  pos + reference length is a 64-bit sum before it is
+// compared with the limit: a record at pos 2^31 - 1 does not wrap.
 #ifndef CM_BAI_H_
 #define CM_BAI_H_
 #include "cm_bam.h"
@@ -23,7 +26,7 @@
 #define CM_BAI_E_MALFORMED 1u  // the record does not end where the next one starts, or is too short for its name and CIGAR
 #define CM_BAI_E_NOREF 2u      // refID is no reference of the header (an unmapped record's -1 among them)
 #define CM_BAI_E_UNSORTED 3u   // a smaller refID than the record before, or the same and a smaller pos
-#define CM_BAI_E_RANGE 4u      // an end beyond 2^29
+#define CM_BAI_E_RANGE 4u      // an end beyond 2^29 (beyond the depth's limit for a CSI)
 
 struct CmBaiRef {  // one reference of the header
   uint64_t vbeg, vend;                     // virtual offsets of its first record's start and its last record's end
@@ -44,6 +47,7 @@ struct CmBaiArrays {
   unsigned long long *lin;  // per window of 16 kb: the smallest virtual offset of a record that overlaps it
   uint64_t *ckey, *cbeg, *cend;  // per raw chunk, in file order
   uint32_t *cval;                // per raw chunk: its own number (the sort carries it)
+  uint32_t csi_depth;            // 0: the .bai's scheme; 1 .. 6: a CSI of that depth
 };
 
 CM_HD uint32_t cm_bai_load16(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
@@ -77,9 +81,10 @@ CM_HD void cm_bai_rec_parse(const CmBaiArrays &d, uint64_t i) {
           const int32_t prid = (int32_t)cm_bam_load32(p + sp + 4), ppos = (int32_t)cm_bam_load32(p + sp + 8);
           if (rid < prid || (rid == prid && pos < ppos)) cause = CM_BAI_E_UNSORTED;
         }
-        if (!cause && (pos < 0 || (uint64_t)pos + (rl ? rl : 1u) > CM_TBX_MAX_END)) cause = CM_BAI_E_RANGE;
+        const uint64_t end64 = (uint64_t)(pos < 0 ? 0 : pos) + (rl ? rl : 1u);
+        if (!cause && (pos < 0 || end64 > cm_csi_max_end(cm_tbx_depth_of(d.csi_depth)))) cause = CM_BAI_E_RANGE;
         if (!cause || cause == CM_BAI_E_UNSORTED) tid = (uint32_t)rid;
-        if (!cause) { beg = (uint32_t)pos; end = (uint32_t)(pos + (rl ? rl : 1u)); }
+        if (!cause) { beg = (uint32_t)pos; end = (uint32_t)end64; }
       }
     }
   }
@@ -96,7 +101,8 @@ CM_HD uint32_t cm_bai_rec_flags_core(const CmBaiArrays &d, uint64_t i, uint32_t 
   const uint32_t t = d.tid[i], beg = d.beg[i], end = d.end[i];
   const bool head = i == 0 || d.tid[i - 1] != t;
   const bool tail = i + 1 == d.n_rec || d.tid[i + 1] != t;
-  d.cidx[i] = head || cm_bam_reg2bin(beg, end) != cm_bam_reg2bin(d.beg[i - 1], d.end[i - 1]) ? 1u : 0u;
+  const uint32_t depth = cm_tbx_depth_of(d.csi_depth);
+  d.cidx[i] = head || cm_csi_reg2bin(beg, end, depth) != cm_csi_reg2bin(d.beg[i - 1], d.end[i - 1], depth) ? 1u : 0u;
   CmBaiRef &r = d.ref[t];
   if (head) r.vbeg = cm_tbx_voff(d.t, d.starts[i]);
   if (tail) r.vend = cm_tbx_voff(d.t, d.starts[i + 1]);
@@ -112,7 +118,7 @@ CM_HD void cm_bai_rec_emit(const CmBaiArrays &d, uint64_t i) {
   const bool head = i == 0 || d.tid[i - 1] != t;
   const uint64_t vs = cm_tbx_voff(d.t, d.starts[i]);
   if (i == 0 || d.cidx[i - 1] != d.cidx[i]) {
-    d.ckey[ci] = (uint64_t)t << 16 | cm_bam_reg2bin(beg, end);
+    d.ckey[ci] = (uint64_t)t << cm_tbx_key_shift_of(d.csi_depth) | cm_csi_reg2bin(beg, end, cm_tbx_depth_of(d.csi_depth));
     d.cbeg[ci] = vs;
     d.cval[ci] = ci;
   }
@@ -166,6 +172,11 @@ static inline const char *cm_bai_cause(uint32_t cause) {
   return cause == CM_BAI_E_MALFORMED ? "is malformed: it does not end where the next one starts, or is shorter than its name and CIGAR"
        : cause == CM_BAI_E_NOREF    ? "has no reference of the header (a refID below 0 or not below n_ref): records without a position are not indexed"
        : cause == CM_BAI_E_UNSORTED ? "lies before the record ahead of it: the records are not sorted by reference and position"
-                                    : "ends beyond 2^29, the limit of the BAI format (samtools index -c builds a .csi index for such a file)";
+                                    : "ends beyond 2^29, the limit of the BAI format (samtools index -c or --output-csi builds a .csi index for such a file)";
+}
+// ... for a CSI of the given depth
+static inline std::string cm_csi_bai_cause(uint32_t cause, uint32_t depth) {
+  if (cause != CM_BAI_E_RANGE) return cm_bai_cause(cause);
+  return "ends beyond " + cm_csi_limit_words(depth) + ", the limit of a CSI index of depth " + std::to_string(depth);
 }
 #endif

@@ -683,13 +683,29 @@ static void write_bai(Run &r, cmgpu_ctx *cx, uint64_t base) {
   ck(cx, cmgpu_bai_write(cx, path.c_str()));
   fprintf(stderr, "Built the BAM index on the device and wrote %s (%llu bytes) in %.3fs.\n", path.c_str(), (unsigned long long)n, now_s() - t0);
 }
+// --output-csi: the CSI index of what cx compressed last -- BAM records (bam) or BED / TagAlign lines -- whose blocks stand at `base`
+// in the output file.  Depth 5 (ends up to 2^29, as the .tbi / .bai) unless a reference is longer: then 6.  The output file is complete by
+// now and stays: what the indexer refuses ends the run with the indexer's words, and without an index file
+static void write_csi(Run &r, cmgpu_ctx *cx, uint64_t base, bool bam) {
+  const std::string path = r.a.out_path + ".csi";
+  const double t0 = now_s();
+  uint32_t depth = 5;
+  for (uint32_t len : r.out_lengths)
+    if (len > (1u << 29)) depth = 6;
+  uint64_t n = 0;
+  const int rc = bam ? cmgpu_bgzf_index_csi_bam(cx, base, r.ref.n_sequences, nullptr, 0, depth, &n) : cmgpu_bgzf_index_csi_tabix(cx, base, depth, &n);
+  if (rc != CMGPU_OK) { remove(path.c_str()); ck(cx, rc); }
+  ck(cx, cmgpu_csi_write(cx, path.c_str()));
+  fprintf(stderr, "Built the CSI index (depth %u) on the device and wrote %s (%llu bytes before compression) in %.3fs.\n", depth, path.c_str(),
+          (unsigned long long)n, now_s() - t0);
+}
 // ---- the writers: each returns the number of lines written (negative: the file could not be written)
 // sort + duplicate removal + MAPQ filter + SAM lines on the device, from the reads and records in HBM
 static int64_t write_sam_device(Run &r) {
   cmgpu_ctx *ctx = r.ctx();
   uint64_t nl = 0, nbytes = 0;
   if (r.a.out_bam) {  // --BAM: the same selection, the records and the header in BAM's binary form; both leave as BGZF blocks (parse(): output_bgzf)
-    if (r.a.output_bai) ck(ctx, cmgpu_bam_keep_starts(ctx, 1));
+    if (r.a.output_bai || r.a.output_csi) ck(ctx, cmgpu_bam_keep_starts(ctx, 1));
     ck(ctx, cmgpu_store_format_bam(ctx, r.out_names.data(), r.out_lengths.data(), r.ref.n_sequences, &r.a.p, r.barcoded ? r.bc_len : 0, &nl, &nbytes));
     write_header(r, [&](const char *path) { return cmgpu_write_bam_header(r.out_names.data(), r.out_lengths.data(), r.ref.n_sequences, path); });
   } else {
@@ -700,6 +716,7 @@ static int64_t write_sam_device(Run &r) {
   write_section(r, ctx);
   bgzf_finish(r);
   if (r.a.output_bai) write_bai(r, ctx, bai_base);
+  if (r.a.output_csi) write_csi(r, ctx, bai_base, true);  // (--BAM: validate())
   return (int64_t)nl;
 }
 // the host writers: sort, duplicate removal and text from the records and reads collected by map_host_ingest
@@ -800,6 +817,7 @@ static int64_t write_bed(Run &r) {
   for (cmgpu_ctx *cx : r.ctxs) write_section(r, cx);  // (emptied at the start)
   bgzf_finish(r);
   if (a.output_tbi) write_tbi(r, r.ctx(), tbi_base);  // (one context: validate())
+  if (a.output_csi) write_csi(r, r.ctx(), tbi_base, false);
   r.t_post = now_s() - t0;
   fprintf(stderr, "Sorted, deduplicated and formatted %llu bytes on the device in %.3fs, wrote them in %.3fs.\n", (unsigned long long)nbytes,
           t1 - t0, now_s() - t1);

@@ -63,6 +63,7 @@ struct Args {
   bool out_bam = false;      // --BAM: SAM's record route (out_sam), the selected records written as a BAM file (always BGZF)
   bool output_tbi = false;   // --output-tbi: <output>.tbi, the tabix index of the BGZF output, built on the device
   bool output_bai = false;   // --output-bai: <output>.bai, the BAM index of --BAM output, built on the device
+  bool output_csi = false;   // --output-csi: <output>.csi, the CSI index of --BAM or BGZF BED / TagAlign output, built on the device
   uint32_t batch_pairs = 4000000;  // multiple of the reference's 500000-pair read batch
 };
 
@@ -190,6 +191,7 @@ static Args parse(int argc, char **argv) {
     else if (o == "--output-bgzf") a.output_bgzf = true;
     else if (o == "--output-tbi") a.output_tbi = true;
     else if (o == "--output-bai") a.output_bai = true;
+    else if (o == "--output-csi") a.output_csi = true;
     else if (o == "--host-ingest") a.host_ingest = true;   // kseq-style host parser (the fallback for text the device ingest refuses)
     else if (o == "--ingest-chunk-mb") { a.chunk_bytes = (size_t)atol(need("--ingest-chunk-mb")) << 20; a.chunk_given = true; }
     else if (o == "--batch-pairs") a.batch_pairs = (uint32_t)atol(need("--batch-pairs"));
@@ -208,7 +210,7 @@ static Args parse(int argc, char **argv) {
              "  --barcode-translate FILE  lines to<TAB or ,>from (gzip or plain): BED column 4 and the SAM CB:Z: value are written as the\n"
              "                  table's names; BED is translated on the device, --SAM on the host\n"
              "  --BAM           the records of --SAM as a BAM file (@SQ header, NM / MD / CB tags), encoded and BGZF-compressed on the device; one\n"
-             "                  GPU, device ingest; its index: --output-bai.  Not with --host-ingest, --barcode-translate, -n > 1, --output-tbi\n"
+             "                  GPU, device ingest; its index: --output-bai, --output-csi.  Not with --host-ingest, --barcode-translate, -n > 1, --output-tbi\n"
              "  --output-bgzf   the output file as BGZF blocks (bgzip's format, readable by tabix / pairix / samtools), compressed on the\n"
              "                  device; nothing is inferred from the output file's name.  Not where the host renders the text:\n"
              "                  --host-ingest --SAM, --SAM --barcode-translate\n"
@@ -216,6 +218,10 @@ static Args parse(int argc, char **argv) {
              "                  (what `tabix -p bed` would make of it), built on the device and written to <output>.tbi\n"
              "  --output-bai    with --BAM: the BAM index of the output file (what `samtools index` would make of it, bins not folded), built\n"
              "                  on the device and written to <output>.bai\n"
+             "  --output-csi    with --BAM, or with --output-bgzf and BED or single-end --TagAlign output on one GPU: the CSI index of the output\n"
+             "                  file (what `samtools index -c` / `tabix -C -p bed` would make of it, bins not folded), built on the device and\n"
+             "                  written to <output>.csi; the one index for a chromosome longer than 2^29 bases (min_shift 14, depth 5, or 6\n"
+             "                  with such a chromosome).  Allowed beside --output-tbi / --output-bai\n"
              "  --summary FILE  per-barcode CSV (one row for bulk data): barcode,total,duplicate,unmapped,lowmapq counted on the device;\n"
              "                  cachehit, fric, estfrip and numcacheslots are written as 0 (the minimizer cache is not modelled)\n");
       exit(0);
@@ -291,6 +297,14 @@ static void validate(Args &a) {
     if (a.out_pairs) die("--output-tbi with pairs output is outside this build (pairs text takes a .px2 index, which is not built)");
     if (a.out_tagalign && paired) die("--output-tbi with paired-end --TagAlign is outside this build (two lines per pair: the text is not sorted by start)");
     if (a.gpus > 1 || a.force_exchange) die("--output-tbi with --gpus > 1 or --force-exchange is outside this build (the output has one section per GPU)");
+  }
+  // ... or of one context's BAM records
+  if (a.output_csi) {
+    if (!a.output_bgzf) die("--output-csi needs --BAM or --output-bgzf (the index is that of the BGZF blocks)");
+    if (a.out_sam && !a.out_bam) die("--output-csi with --SAM is outside this build (a CSI index of SAM text; --BAM --output-csi writes BAM and its index)");
+    if (a.out_pairs) die("--output-csi with pairs output is outside this build (pairs text takes a .px2 index, which is not built)");
+    if (a.out_tagalign && paired) die("--output-csi with paired-end --TagAlign is outside this build (two lines per pair: the text is not sorted by start)");
+    if (a.gpus > 1 || a.force_exchange) die("--output-csi with --gpus > 1 or --force-exchange is outside this build (the output has one section per GPU)");
   }
   // the reference allocates in its in-memory flavour only (chromap.h:1305-1353): with --low-mem or a preset the flag does nothing there and here
   if (a.p.allocate_multi_mappings && !a.p.low_memory_mode) {

@@ -236,6 +236,8 @@ struct cmgpu_ctx {
   uint64_t bam_starts_n = 0, bam_starts_gen = 0, bam_starts_bytes = 0;
   std::vector<uint8_t> bai;  // the last index's payload (cmgpu_bgzf_index_bai)
   bool bai_have = false;
+  std::vector<uint8_t> csi;  // the last CSI index's payload (cmgpu_bgzf_index_csi_bam / _tabix)
+  bool csi_have = false;
   uint64_t text_gen = 0, bgzf_text_gen = 0;  // text_gen: counts the texts published to the text store; bgzf_text_gen: the one that was compressed
   uint64_t store_n = 0, store_cap = 0, text_bytes = 0, text_lines = 0;
   bool text_bam = false;  // the text store holds BAM alignment records (cmgpu_store_format_bam), not lines: text_lines counts records

@@ -12,6 +12,13 @@
 //  3. per raw chunk, sorted by (reference, bin) with a stable sort: it joins the chunk before it when it begins in the block in
 //     which that one ends (cm_tbx_chunk_flag), then the merged chunks (cm_tbx_chunk_emit).
 //  4. the payload, on the host, from arrays as long as the index (cm_tbx_serialize).
+// The CSI index (.csi; SAM spec 5.3, CSIv1) is the same index with the number of levels as a parameter: min_shift stays 14 (the 16 kb
+// windows above), depth is 1 .. 6 and the limit of an end 2^(14 + 3 * depth).  Positions are 32-bit here, so depth 6 accepts ends up
+// to 0xffffffff, not 2^32.  CmTbxArrays::csi_depth (and CmBaiArrays') says which: 0 is the .tbi / .bai scheme -- depth 5, limit
+// 2^29, keys reference << 16 | bin -- and 1 .. 6 the CSI's with keys reference << 20 | bin (depth 6 has bins up to 299 592).  A
+// CSI has no linear index: every bin carries `loffset`, the back-filled window value at the bin's first position
+// (cm_csi_bin_loffset, per merged chunk that is the first of its bin); the windows themselves stay where they were made.
+//  4c. the CSI payload, on the host, for both flavours (cm_csi_serialize): BAM (no aux) and tabix (aux: the tabix header's fields).
 // The functions that write a shared word take the way to do it as a template argument `A` (min64): atomics on the device,
 // plain code on the host.
 #ifndef CM_TABIX_H_
@@ -19,6 +26,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <string>
 #include <vector>
 
 #include "cm_types.h"
@@ -28,12 +36,16 @@
 #define CM_TBX_PIECE 16u     // bytes a lane looks at in one go
 #define CM_TBX_MAX_END (1u << 29)
 #define CM_TBX_PSEUDO_BIN 37450u
+#define CM_TBX_KEY_SHIFT 16u  // the chunk key of the .tbi / .bai: reference << 16 | bin
+#define CM_CSI_KEY_SHIFT 20u  // ... of the .csi
+#define CM_CSI_MIN_SHIFT 14u
+#define CM_CSI_MAX_DEPTH 6u
 #define CM_TBX_MAX_LINES 0xfffffffeull
 // why a text cannot be indexed (the low three bits of the error word)
 #define CM_TBX_E_MALFORMED 1u  // fewer than three columns, an empty name, a column 2 or 3 that is not decimal
 #define CM_TBX_E_RECUR 2u      // a name heads a second run of lines (found on the host, among the names)
 #define CM_TBX_E_UNSORTED 3u   // a start smaller than the line's above, same name
-#define CM_TBX_E_RANGE 4u      // an end beyond 2^29
+#define CM_TBX_E_RANGE 4u      // an end beyond 2^29 (beyond the depth's limit for a CSI)
 #define CM_TBX_NO_ERROR (~0ull)
 
 struct CmTbxText {
@@ -48,7 +60,7 @@ struct CmTbxRef {  // one run of lines with the same column 1
   uint64_t name_at;      // text offset of its name
   uint32_t first_line, name_len, n_intv, pad;
 };
-struct CmTbxChunk { uint64_t key, beg, end; };  // key: reference << 16 | bin
+struct CmTbxChunk { uint64_t key, beg, end; };  // key: reference << 16 | bin (CSI: reference << 20 | bin)
 struct CmTbxArrays {
   CmTbxText t;
   uint64_t n_lines;
@@ -62,6 +74,7 @@ struct CmTbxArrays {
   unsigned long long *lin;  // per window of 16 kb: the smallest virtual offset of a line that overlaps it
   uint64_t *ckey, *cbeg, *cend;  // per raw chunk, in text order
   uint32_t *cval;                // per raw chunk: its own number (the sort carries it)
+  uint32_t csi_depth;            // 0: the .tbi's scheme; 1 .. 6: a CSI of that depth
 };
 
 CM_HD uint64_t cm_tbx_voff(const CmTbxText &t, uint64_t u) {
@@ -77,6 +90,35 @@ CM_HD uint32_t cm_tbx_reg2bin(uint32_t beg, uint32_t end) {
   if (beg >> 23 == end >> 23) return 9u + (beg >> 23);
   if (beg >> 26 == end >> 26) return 1u + (beg >> 26);
   return 0;
+}
+// ---- the CSI's scheme: min_shift 14, `depth` levels below bin 0 (1 .. 6)
+// the specification's reg2bin for [beg, end), end > beg; depth 5 gives cm_tbx_reg2bin
+CM_HD uint32_t cm_csi_reg2bin(uint32_t beg, uint32_t end, uint32_t depth) {
+  uint32_t l = depth, s = CM_CSI_MIN_SHIFT, t = ((1u << (3u * depth)) - 1u) / 7u;
+  for (--end; l > 0; --l, s += 3u, t -= 1u << (3u * l))
+    if (beg >> s == end >> s) return t + (beg >> s);
+  return 0;
+}
+CM_HD uint32_t cm_csi_pseudo_bin(uint32_t depth) { return ((1u << (3u * depth + 3u)) - 1u) / 7u + 1u; }
+// the largest end a record may have: 2^(14 + 3 * depth), and 0xffffffff at depth 6 (32-bit positions)
+CM_HD uint64_t cm_csi_max_end(uint32_t depth) {
+  const uint64_t lim = 1ull << (CM_CSI_MIN_SHIFT + 3u * depth);
+  return lim > 0xffffffffull ? 0xffffffffull : lim;
+}
+// the 16 kb window in which bin `bin` begins: the levels walked from the top, at most `depth` steps
+CM_HD uint64_t cm_csi_bin_window(uint32_t bin, uint32_t depth) {
+  uint32_t l = 0, first = 0;  // first: the first bin of level l
+  while (l < depth && bin >= first + (1u << (3u * l))) { first += 1u << (3u * l); ++l; }
+  return (uint64_t)(bin - first) << (3u * (depth - l));
+}
+// what a zero-initialised struct means: the .tbi / .bai scheme
+CM_HD uint32_t cm_tbx_depth_of(uint32_t csi_depth) { return csi_depth ? csi_depth : 5u; }
+CM_HD uint32_t cm_tbx_key_shift_of(uint32_t csi_depth) { return csi_depth ? CM_CSI_KEY_SHIFT : CM_TBX_KEY_SHIFT; }
+// a bin's loffset (htslib's rule): the back-filled window value at the bin's first position.  The bin exists because a record lies
+// in it, so the window is one of its reference's, and after the back-fill it is not all ones
+CM_HD uint64_t cm_csi_bin_loffset(uint64_t key, uint32_t depth, const unsigned long long *lin, const uint64_t *lin_off) {
+  const uint64_t ref = key >> CM_CSI_KEY_SHIFT;
+  return lin[lin_off[ref] + cm_csi_bin_window((uint32_t)(key & ((1u << CM_CSI_KEY_SHIFT) - 1u)), depth)];
 }
 
 // ---- 1. line starts
@@ -119,20 +161,21 @@ CM_HD void cm_tbx_tile_starts(GT &g, const uint8_t *text, uint64_t n, uint64_t t
 }
 
 // ---- 2. per line
-// decimal digits from p on, at most up to le; a value beyond 2^30 stays there
+// decimal digits from p on, at most up to le; a value beyond 2^33 stays there
 CM_HD uint64_t cm_tbx_number(const uint8_t *text, uint64_t &p, uint64_t le, uint32_t *n_digits) {
   uint64_t v = 0;
   uint32_t nd = 0;
   for (; p < le && text[p] >= '0' && text[p] <= '9'; ++p, ++nd) {
     v = v * 10u + (uint32_t)(text[p] - '0');
-    if (v > (1ull << 30)) v = 1ull << 30;
+    if (v > (1ull << 33)) v = 1ull << 33;
   }
   *n_digits = nd;
   return v;
 }
 // the line [s, e) (e: one past its newline): 0 and [beg, end) -- end made beg + 1 where it is not larger -- and the length of
-// column 1, or the cause it cannot be indexed for, with [0, 1)
-CM_HD uint32_t cm_tbx_columns(const uint8_t *text, uint64_t s, uint64_t e, uint32_t *beg, uint32_t *end, uint32_t *name_len) {
+// column 1, or the cause it cannot be indexed for, with [0, 1).  max_end: the largest end the scheme takes
+CM_HD uint32_t cm_tbx_columns(const uint8_t *text, uint64_t s, uint64_t e, uint32_t *beg, uint32_t *end, uint32_t *name_len,
+                              uint64_t max_end = CM_TBX_MAX_END) {
   const uint64_t le = e - 1;
   uint64_t p = s;
   while (p < le && text[p] != '\t') ++p;
@@ -148,7 +191,7 @@ CM_HD uint32_t cm_tbx_columns(const uint8_t *text, uint64_t s, uint64_t e, uint3
   uint64_t x = cm_tbx_number(text, p, le, &nd);
   if (!nd || (p < le && text[p] != '\t')) return CM_TBX_E_MALFORMED;
   if (x <= b) x = b + 1;
-  if (x > CM_TBX_MAX_END) return CM_TBX_E_RANGE;
+  if (x > max_end) return CM_TBX_E_RANGE;
   *beg = (uint32_t)b;
   *end = (uint32_t)x;
   return 0;
@@ -165,7 +208,7 @@ template <class A>
 CM_HD void cm_tbx_line_parse(const CmTbxArrays &d, uint64_t i) {
   const uint64_t s = d.lstart[i], e = d.lstart[i + 1];
   uint32_t beg, end, name_len;
-  const uint32_t cause = cm_tbx_columns(d.t.p, s, e, &beg, &end, &name_len);
+  const uint32_t cause = cm_tbx_columns(d.t.p, s, e, &beg, &end, &name_len, cm_csi_max_end(cm_tbx_depth_of(d.csi_depth)));
   if (cause) A::min64(d.err, (unsigned long long)i << 3 | cause);
   d.beg[i] = beg;
   d.end[i] = end;
@@ -181,7 +224,8 @@ CM_HD uint32_t cm_tbx_line_flags_core(const CmTbxArrays &d, uint64_t i, uint32_t
   bool chead = head;
   if (!head) {
     if (beg < d.beg[i - 1]) *err_mine = (unsigned long long)i << 3 | CM_TBX_E_UNSORTED;
-    chead = cm_tbx_reg2bin(beg, end) != cm_tbx_reg2bin(d.beg[i - 1], d.end[i - 1]);
+    const uint32_t depth = cm_tbx_depth_of(d.csi_depth);
+    chead = cm_csi_reg2bin(beg, end, depth) != cm_csi_reg2bin(d.beg[i - 1], d.end[i - 1], depth);
   }
   d.cidx[i] = chead ? 1u : 0u;
   CmTbxRef &r = d.ref[t];
@@ -206,7 +250,7 @@ CM_HD void cm_tbx_line_emit(const CmTbxArrays &d, uint64_t i) {
   const bool head = i == 0 || d.tid[i - 1] != d.tid[i];
   const uint64_t vs = cm_tbx_voff(d.t, d.lstart[i]);
   if (i == 0 || d.cidx[i - 1] != d.cidx[i]) {
-    d.ckey[ci] = (uint64_t)t << 16 | cm_tbx_reg2bin(beg, end);
+    d.ckey[ci] = (uint64_t)t << cm_tbx_key_shift_of(d.csi_depth) | cm_csi_reg2bin(beg, end, cm_tbx_depth_of(d.csi_depth));
     d.cbeg[ci] = vs;
     d.cval[ci] = ci;
   }
@@ -274,11 +318,80 @@ static inline void cm_tbx_serialize(const CmTbxRef *ref, uint32_t n_ref, uint64_
   }
   cm_tbx_put(o, 0, 8);
 }
+// ---- 4c. the CSI payload (host), both flavours.  ref: one entry per reference (has == 0: no record, no bin); ch: the merged chunks
+// in (reference, bin, file) order with keys reference << 20 | bin; loff[j]: the loffset of chunk j's bin where j is the bin's first
+// chunk; aux: l_aux bytes (BAM flavour: none)
+struct CmCsiRef {
+  uint64_t vbeg, vend, n_mapped, n_unmapped;
+  uint32_t has, pad;
+};
+static inline void cm_csi_serialize(uint32_t depth, const uint8_t *aux, uint32_t l_aux, const CmCsiRef *ref, uint32_t n_ref, const CmTbxChunk *ch, uint64_t n_ch,
+                                    const uint64_t *loff, std::vector<uint8_t> &o) {
+  o.clear();
+  o.reserve(32 + l_aux + (size_t)n_ref * 56 + n_ch * 32);
+  const uint8_t magic[4] = {'C', 'S', 'I', 1};
+  o.insert(o.end(), magic, magic + 4);
+  cm_tbx_put(o, CM_CSI_MIN_SHIFT, 4);
+  cm_tbx_put(o, depth, 4);
+  cm_tbx_put(o, l_aux, 4);
+  if (l_aux) o.insert(o.end(), aux, aux + l_aux);
+  cm_tbx_put(o, n_ref, 4);
+  const uint64_t bin_mask = (1ull << CM_CSI_KEY_SHIFT) - 1u;
+  uint64_t at = 0;
+  for (uint32_t r = 0; r < n_ref; ++r) {
+    if (!ref[r].has) {  // no record: no bin, not the pseudo-bin either
+      cm_tbx_put(o, 0, 4);
+      continue;
+    }
+    uint64_t to = at;
+    uint32_t n_bin = 1;  // the pseudo-bin
+    for (; to < n_ch && ch[to].key >> CM_CSI_KEY_SHIFT == r; ++to)
+      if (to == at || ch[to].key != ch[to - 1].key) ++n_bin;
+    cm_tbx_put(o, n_bin, 4);
+    while (at < to) {
+      uint64_t e = at + 1;
+      while (e < to && ch[e].key == ch[at].key) ++e;
+      cm_tbx_put(o, ch[at].key & bin_mask, 4);
+      cm_tbx_put(o, loff[at], 8);
+      cm_tbx_put(o, e - at, 4);
+      for (; at < e; ++at) { cm_tbx_put(o, ch[at].beg, 8); cm_tbx_put(o, ch[at].end, 8); }
+    }
+    cm_tbx_put(o, cm_csi_pseudo_bin(depth), 4);
+    cm_tbx_put(o, 0, 8);
+    cm_tbx_put(o, 2, 4);
+    cm_tbx_put(o, ref[r].vbeg, 8);
+    cm_tbx_put(o, ref[r].vend, 8);
+    cm_tbx_put(o, ref[r].n_mapped, 8);
+    cm_tbx_put(o, ref[r].n_unmapped, 8);
+  }
+  cm_tbx_put(o, 0, 8);  // n_no_coor: no record without a position is written
+}
+// the tabix flavour's aux: the tabix header behind its magic and n_ref, with the values cm_tbx_serialize writes
+static inline void cm_csi_tabix_aux(uint32_t n_ref, const uint8_t *names, const uint64_t *name_off, std::vector<uint8_t> &aux) {
+  aux.clear();
+  const uint32_t head[6] = {0x10000u, 1u, 2u, 3u, 35u, 0u};
+  for (uint32_t v : head) cm_tbx_put(aux, v, 4);
+  cm_tbx_put(aux, n_ref ? name_off[n_ref] + n_ref : 0, 4);
+  for (uint32_t r = 0; r < n_ref; ++r) {
+    aux.insert(aux.end(), names + name_off[r], names + name_off[r + 1]);
+    aux.push_back(0);
+  }
+}
+// the words for the limit of a scheme's ends: "2^29" for the .tbi / .bai and a CSI of depth 5
+static inline std::string cm_csi_limit_words(uint32_t csi_depth) {
+  const uint32_t depth = cm_tbx_depth_of(csi_depth);
+  return depth == 6 ? std::string("4294967295 (32-bit positions)") : "2^" + std::to_string(CM_CSI_MIN_SHIFT + 3u * depth);
+}
 // the message for an error word
 static inline const char *cm_tbx_cause(uint32_t cause) {
   return cause == CM_TBX_E_MALFORMED ? "is malformed: three tab-separated columns are needed, the first not empty, the second and third decimal"
        : cause == CM_TBX_E_RECUR    ? "begins a second run of lines for a name that had one already: the text is not sorted by name"
        : cause == CM_TBX_E_UNSORTED ? "starts before the line above it: the text is not sorted by start (paired TagAlign, pairs and SAM text is not)"
-                                    : "ends beyond 2^29, the limit of the tabix format";
+                                    : "ends beyond 2^29, the limit of the tabix format (tabix -C or --output-csi builds a .csi index for such a file)";
+}
+// ... for a CSI of the given depth
+static inline std::string cm_csi_tbx_cause(uint32_t cause, uint32_t depth) {
+  if (cause != CM_TBX_E_RANGE) return cm_tbx_cause(cause);
+  return "ends beyond " + cm_csi_limit_words(depth) + ", the limit of a CSI index of depth " + std::to_string(depth);
 }
 #endif

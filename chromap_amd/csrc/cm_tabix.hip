@@ -10,6 +10,9 @@
 // the raw chunks on it is the same index -- the same kernels, scans and sort.  Its temporary memory: 16 bytes per record (begin, end,
 // reference, raw chunk; the starts are kept by cmgpu_store_format_bam or uploaded: 8 more), 40 per reference, and the chunks' and
 // windows' as above.
+// The CSI index of either store (cm_tabix.h) runs the same kernels with its depth in the arrays and one more over the merged chunks
+// (k_csi_loffset: 8 more bytes per merged chunk); its windows are not copied to the host -- chunks, the bins' loffsets and the
+// references' table are.
 #include <stdio.h>
 #include <string.h>
 
@@ -110,6 +113,15 @@ __global__ __launch_bounds__(TX_LANES) void k_tbx_chunk_emit(const uint64_t *__r
   const uint64_t j = (uint64_t)blockIdx.x * TX_LANES + threadIdx.x;
   if (j < n) cm_tbx_chunk_emit(key, perm, cbeg, cend, midx, n, j, out);
 }
+// the CSI's loffset of every bin, at the merged chunk that is the first of its (reference, bin): the back-filled window in which the
+// bin begins.  (The other chunks' words are not read.)
+__global__ __launch_bounds__(TX_LANES) void k_csi_loffset(const CmTbxChunk *__restrict__ ch, uint64_t n, uint32_t depth, const unsigned long long *__restrict__ lin,
+                                                       const uint64_t *__restrict__ lin_off, uint64_t *__restrict__ loff) {
+  const uint64_t j = (uint64_t)blockIdx.x * TX_LANES + threadIdx.x;
+  if (j >= n) return;
+  const uint64_t key = ch[j].key;
+  loff[j] = j == 0 || ch[j - 1].key != key ? cm_csi_bin_loffset(key, depth, lin, lin_off) : 0ull;
+}
 
 // ---- the BAM index's per-record kernels (cm_bai.h): one lane per record
 __global__ __launch_bounds__(TX_LANES) void k_bai_parse(CmBaiArrays d) {
@@ -153,6 +165,7 @@ struct TxJob {
   cmgpu_ctx *c;
   hipStream_t s;
   const char *name = "tabix index";  // the messages' first words
+  uint32_t csi_depth = 0;  // 1 .. 6: a CSI of that depth is being built
   CmTmpBuf tmp;  // rocprim's work area
   ~TxJob() { (void)hipStreamSynchronize(s); }
   int enomem() { cm_set_error(c, std::string("out of device memory (") + name + ")"); return CMGPU_ENOMEM; }
@@ -175,7 +188,8 @@ struct TxJob {
     return e == hipSuccess ? CMGPU_OK : fail("back-fill", e);
   }
   int format_error(unsigned long long word) {
-    cm_set_error(c, "tabix index: line " + std::to_string((word >> 3) + 1) + " " + cm_tbx_cause((uint32_t)(word & 7u)));
+    cm_set_error(c, "tabix index: line " + std::to_string((word >> 3) + 1) + " " +
+                        (csi_depth ? cm_csi_tbx_cause((uint32_t)(word & 7u), csi_depth) : std::string(cm_tbx_cause((uint32_t)(word & 7u)))));
     return CMGPU_EFORMAT;
   }
 };
@@ -188,17 +202,21 @@ static inline uint32_t tx_blocks(uint64_t n) { return (uint32_t)((n + TX_LANES -
     if (e_ != hipSuccess) return (job).fail(what, e_);             \
   } while (0)
 
-// ---- 3. (both indexes) the n_raw raw chunks by (reference, bin), file order kept; neighbours joined; the merged chunks to the host
+// ---- 3. (all indexes) the n_raw raw chunks by (reference, bin), file order kept; neighbours joined; the merged chunks to the host.
+// With job.csi_depth, and lin / lin_off the back-filled windows on the device: the bins' loffsets too (h_loff, one word per chunk)
 static int tx_merge_chunks(TxJob &job, uint64_t *ckey, uint32_t *cval, const uint64_t *cbeg, const uint64_t *cend, uint32_t n_raw, uint64_t n_ref,
-                           std::vector<CmTbxChunk> &h_ch) {
+                           std::vector<CmTbxChunk> &h_ch, const unsigned long long *lin = nullptr, const uint64_t *lin_off = nullptr,
+                           std::vector<uint64_t> *h_loff = nullptr) {
   hipStream_t s = job.s;
-  CmTmpBuf skey, perm, mflag, merged;
+  CmTmpBuf skey, perm, mflag, merged, loff;
   struct Wait { hipStream_t s; ~Wait() { (void)hipStreamSynchronize(s); } } wait{s};  // (behind the buffers, as TxJob behind its caller's)
   h_ch.clear();
+  if (h_loff) h_loff->clear();
   if (n_raw == 0) return CMGPU_OK;
   if (skey.ensure((size_t)n_raw * 8) || perm.ensure((size_t)n_raw * 4) || mflag.ensure((size_t)n_raw * 4)) return job.enomem();
-  unsigned bits = 16;
-  while (bits < 48 && (1ull << (bits - 16)) < n_ref) ++bits;
+  const unsigned key_shift = cm_tbx_key_shift_of(job.csi_depth);
+  unsigned bits = key_shift;
+  while (bits < 32 + key_shift && (1ull << (bits - key_shift)) < n_ref) ++bits;
   {
     size_t tb = 0;
     TX_CHECK(job, "sort", rocprim::radix_sort_pairs(nullptr, tb, ckey, (uint64_t *)skey.p, cval, (uint32_t *)perm.p, (size_t)n_raw, 0, bits, s));
@@ -218,13 +236,28 @@ static int tx_merge_chunks(TxJob &job, uint64_t *ckey, uint32_t *cval, const uin
                      (const uint32_t *)mflag.p, (uint64_t)n_raw, (CmTbxChunk *)merged.p);
   TX_CHECK(job, "merge", hipGetLastError());
   TX_CHECK(job, "merge", hipMemcpyAsync(h_ch.data(), merged.p, (size_t)n_merged * sizeof(CmTbxChunk), hipMemcpyDeviceToHost, s));
+  if (h_loff) {
+    h_loff->resize(n_merged);
+    if (loff.ensure((size_t)n_merged * 8)) return job.enomem();
+    hipLaunchKernelGGL(k_csi_loffset, dim3(tx_blocks(n_merged)), dim3(TX_LANES), 0, s, (const CmTbxChunk *)merged.p, (uint64_t)n_merged, job.csi_depth, lin, lin_off,
+                       (uint64_t *)loff.p);
+    TX_CHECK(job, "loffset", hipGetLastError());
+    TX_CHECK(job, "loffset", hipMemcpyAsync(h_loff->data(), loff.p, (size_t)n_merged * 8, hipMemcpyDeviceToHost, s));
+  }
   TX_CHECK(job, "merge", cm_stream_sync(s));
   return CMGPU_OK;
 }
 
-static int tx_index(cmgpu_ctx *c, const uint8_t *text, uint64_t n, uint64_t base, std::vector<uint8_t> &payload) {
+// csi_depth 0: the .tbi payload; 1 .. 6: the CSI payload (tabix flavour) of that depth
+static int tx_index(cmgpu_ctx *c, const uint8_t *text, uint64_t n, uint64_t base, uint32_t csi_depth, std::vector<uint8_t> &payload) {
   if (n == 0) {
-    cm_tbx_serialize(nullptr, 0, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, payload);
+    if (csi_depth) {
+      std::vector<uint8_t> aux;
+      cm_csi_tabix_aux(0, nullptr, nullptr, aux);
+      cm_csi_serialize(csi_depth, aux.data(), (uint32_t)aux.size(), nullptr, 0, nullptr, 0, nullptr, payload);
+    } else {
+      cm_tbx_serialize(nullptr, 0, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, payload);
+    }
     return CMGPU_OK;
   }
   hipStream_t s = c->stream;
@@ -232,7 +265,9 @@ static int tx_index(cmgpu_ctx *c, const uint8_t *text, uint64_t n, uint64_t base
   TxJob job;  // (declared behind the buffers: on every return it waits for the stream before they go)
   job.c = c;
   job.s = s;
+  job.csi_depth = csi_depth;
   CmTbxArrays d = {};
+  d.csi_depth = csi_depth;
   d.t.p = text;
   d.t.n = n;
   d.t.n_blocks = c->bgzf_blocks;
@@ -319,9 +354,9 @@ static int tx_index(cmgpu_ctx *c, const uint8_t *text, uint64_t n, uint64_t base
   TX_CHECK(job, "raw chunks", hipGetLastError());
   { const int rc = job.back_fill(d.lin, n_win); if (rc) return rc; }
   std::vector<uint8_t> h_names(name_bytes + 1);
-  std::vector<uint64_t> h_lin(n_win + 1);
+  std::vector<uint64_t> h_lin(csi_depth ? 1 : n_win + 1);  // (a CSI's windows stay on the device)
   TX_CHECK(job, "names", hipMemcpyAsync(h_names.data(), names.p, name_bytes, hipMemcpyDeviceToHost, s));
-  TX_CHECK(job, "names", hipMemcpyAsync(h_lin.data(), lin.p, n_win * 8, hipMemcpyDeviceToHost, s));
+  if (!csi_depth) TX_CHECK(job, "names", hipMemcpyAsync(h_lin.data(), lin.p, n_win * 8, hipMemcpyDeviceToHost, s));
   TX_CHECK(job, "names", cm_stream_sync(s));
   // a name twice: its second run's first line is the offender (host: as many steps as there are references)
   {
@@ -332,30 +367,55 @@ static int tx_index(cmgpu_ctx *c, const uint8_t *text, uint64_t n, uint64_t base
   }
   // ---- 3. raw chunks by (reference, bin), file order kept; neighbours joined
   std::vector<CmTbxChunk> h_ch;
-  { const int rc = tx_merge_chunks(job, d.ckey, d.cval, d.cbeg, d.cend, n_raw, n_ref, h_ch); if (rc) return rc; }
+  std::vector<uint64_t> h_loff;
+  {
+    const int rc = tx_merge_chunks(job, d.ckey, d.cval, d.cbeg, d.cend, n_raw, n_ref, h_ch, d.lin, d.lin_off, csi_depth ? &h_loff : nullptr);
+    if (rc) return rc;
+  }
   // ---- 4. the payload
+  if (csi_depth) {
+    std::vector<uint8_t> aux;
+    cm_csi_tabix_aux(n_ref, h_names.data(), h_name_off.data(), aux);
+    std::vector<CmCsiRef> cref(n_ref);
+    for (uint32_t r = 0; r < n_ref; ++r)
+      cref[r] = CmCsiRef{h_ref[r].vbeg, h_ref[r].vend, (r + 1 < n_ref ? h_ref[r + 1].first_line : n_lines) - h_ref[r].first_line, 0, 1u, 0u};
+    cm_csi_serialize(csi_depth, aux.data(), (uint32_t)aux.size(), cref.data(), n_ref, h_ch.data(), h_ch.size(), h_loff.data(), payload);
+    return CMGPU_OK;
+  }
   cm_tbx_serialize(h_ref.data(), n_ref, n_lines, h_names.data(), h_name_off.data(), h_ch.data(), h_ch.size(), h_lin.data(), h_lin_off.data(), payload);
   return CMGPU_OK;
 }
 
 // The BAM index of the n bytes of records at p, record i at starts[i] (device memory, n_rec + 1 entries)
-static int bai_index(cmgpu_ctx *c, const uint8_t *p, uint64_t n, uint64_t base, uint32_t n_ref, const uint64_t *starts, uint64_t n_rec, std::vector<uint8_t> &payload) {
+// csi_depth 0: the .bai's bytes; 1 .. 6: the CSI payload (BAM flavour) of that depth
+static int bai_index(cmgpu_ctx *c, const uint8_t *p, uint64_t n, uint64_t base, uint32_t n_ref, const uint64_t *starts, uint64_t n_rec, uint32_t csi_depth,
+                     std::vector<uint8_t> &payload) {
   hipStream_t s = c->stream;
   CmTmpBuf beg, end, tid, cidx, err, ref, lin_off, lin, ckey, cval, cbeg, cend;
   TxJob job;  // (declared behind the buffers: on every return it waits for the stream before they go)
   job.c = c;
   job.s = s;
   job.name = "BAM index";
+  job.csi_depth = csi_depth;
   std::vector<CmBaiRef> h_ref(n_ref);
-  std::vector<uint64_t> h_lin_off((size_t)n_ref + 1, 0), h_lin(1);
+  std::vector<uint64_t> h_lin_off((size_t)n_ref + 1, 0), h_lin(1), h_loff;
   std::vector<CmTbxChunk> h_ch;
+  // the payload from the host's arrays
+  auto serialize = [&]() {
+    if (!csi_depth) { cm_bai_serialize(h_ref.data(), n_ref, h_ch.data(), h_ch.size(), h_lin.data(), h_lin_off.data(), payload); return; }
+    std::vector<CmCsiRef> cref(n_ref);
+    for (uint32_t r = 0; r < n_ref; ++r)
+      cref[r] = CmCsiRef{h_ref[r].vbeg, h_ref[r].vend, h_ref[r].n_mapped, h_ref[r].n_unmapped, h_ref[r].n_intv ? 1u : 0u, 0u};
+    cm_csi_serialize(csi_depth, nullptr, 0, cref.data(), n_ref, h_ch.data(), h_ch.size(), h_loff.data(), payload);
+  };
   if (n_rec == 0) {
     if (n) { cm_set_error(c, "BAM index: " + std::to_string((unsigned long long)n) + " bytes and no record"); return CMGPU_EINVAL; }
-    cm_bai_serialize(h_ref.data(), n_ref, nullptr, 0, h_lin.data(), h_lin_off.data(), payload);
+    serialize();
     return CMGPU_OK;
   }
   if (n_rec > CM_BAI_MAX_RECORDS) { cm_set_error(c, "BAM index: more than 2^32 - 2 records"); return CMGPU_EINVAL; }
   CmBaiArrays d = {};
+  d.csi_depth = csi_depth;
   d.t.p = p;
   d.t.n = n;
   d.t.n_blocks = c->bgzf_blocks;
@@ -381,7 +441,8 @@ static int bai_index(cmgpu_ctx *c, const uint8_t *p, uint64_t n, uint64_t base, 
   TX_CHECK(job, "records", hipMemcpyAsync(&word, d.err, 8, hipMemcpyDeviceToHost, s));
   TX_CHECK(job, "records", cm_stream_sync(s));
   if (word != CM_TBX_NO_ERROR) {
-    cm_set_error(c, "BAM index: record " + std::to_string((word >> 3) + 1) + " " + cm_bai_cause((uint32_t)(word & 7u)));
+    cm_set_error(c, "BAM index: record " + std::to_string((word >> 3) + 1) + " " +
+                        (csi_depth ? cm_csi_bai_cause((uint32_t)(word & 7u), csi_depth) : std::string(cm_bai_cause((uint32_t)(word & 7u)))));
     return CMGPU_EFORMAT;
   }
   // ---- 2. references, raw chunks' heads
@@ -407,12 +468,17 @@ static int bai_index(cmgpu_ctx *c, const uint8_t *p, uint64_t n, uint64_t base, 
   hipLaunchKernelGGL(k_bai_emit, dim3(tx_blocks(n_rec)), dim3(TX_LANES), 0, s, d);
   TX_CHECK(job, "raw chunks", hipGetLastError());
   { const int rc = job.back_fill(d.lin, n_win); if (rc) return rc; }
-  h_lin.resize(n_win + 1);
-  TX_CHECK(job, "windows", hipMemcpyAsync(h_lin.data(), lin.p, n_win * 8, hipMemcpyDeviceToHost, s));
+  if (!csi_depth) {  // (a CSI's windows stay on the device)
+    h_lin.resize(n_win + 1);
+    TX_CHECK(job, "windows", hipMemcpyAsync(h_lin.data(), lin.p, n_win * 8, hipMemcpyDeviceToHost, s));
+  }
   // ---- 3. raw chunks by (reference, bin), file order kept; neighbours joined
-  { const int rc = tx_merge_chunks(job, d.ckey, d.cval, d.cbeg, d.cend, n_raw, n_ref, h_ch); if (rc) return rc; }
+  {
+    const int rc = tx_merge_chunks(job, d.ckey, d.cval, d.cbeg, d.cend, n_raw, n_ref, h_ch, d.lin, d.lin_off, csi_depth ? &h_loff : nullptr);
+    if (rc) return rc;
+  }
   // ---- 4. the payload
-  cm_bai_serialize(h_ref.data(), n_ref, h_ch.data(), h_ch.size(), h_lin.data(), h_lin_off.data(), payload);
+  serialize();
   return CMGPU_OK;
 }
 // cmgpu_store_format_bam, behind publish: the offsets of the records it wrote -- loff where llen != 0 -- and `total` behind them
@@ -443,12 +509,8 @@ int cm_bai_keep_starts(cmgpu_ctx *c, const uint64_t *llen, const uint64_t *loff,
   return CMGPU_OK;
 }
 
-extern "C" int cmgpu_bgzf_index_tabix(cmgpu_ctx *c, uint64_t base_offset, uint64_t *n_bytes) {
-  if (!c) return CMGPU_EINVAL;
-  CM_HIPCHECK(c, cm_enter(c));
-  c->tabix.clear();
-  c->tabix_have = false;
-  if (n_bytes) *n_bytes = 0;
+// the text of the compressed store indexed: the .tbi payload (csi_depth 0) or the CSI's, into `payload`
+static int tx_index_store(cmgpu_ctx *c, uint64_t base_offset, uint32_t csi_depth, std::vector<uint8_t> &payload) {
   const uint8_t *text = nullptr;
   switch (c->bgzf_src) {
     case CM_BZ_SRC_STORE:
@@ -469,8 +531,16 @@ extern "C" int cmgpu_bgzf_index_tabix(cmgpu_ctx *c, uint64_t base_offset, uint64
       return CMGPU_EINVAL;
   }
   if (base_offset >> 47) { cm_set_error(c, "tabix index: base offset beyond 2^47"); return CMGPU_EINVAL; }
+  return tx_index(c, text, c->bgzf_text_bytes, base_offset, csi_depth, payload);
+}
+extern "C" int cmgpu_bgzf_index_tabix(cmgpu_ctx *c, uint64_t base_offset, uint64_t *n_bytes) {
+  if (!c) return CMGPU_EINVAL;
+  CM_HIPCHECK(c, cm_enter(c));
+  c->tabix.clear();
+  c->tabix_have = false;
+  if (n_bytes) *n_bytes = 0;
   std::vector<uint8_t> payload;
-  const int rc = tx_index(c, text, c->bgzf_text_bytes, base_offset, payload);
+  const int rc = tx_index_store(c, base_offset, 0, payload);
   if (rc != CMGPU_OK) return rc;
   c->tabix.swap(payload);
   c->tabix_have = true;
@@ -502,12 +572,9 @@ extern "C" int cmgpu_bam_keep_starts(cmgpu_ctx *c, int on) {
   if (!on) c->bam_starts_have = false;
   return CMGPU_OK;
 }
-extern "C" int cmgpu_bgzf_index_bai(cmgpu_ctx *c, uint64_t base_offset, uint32_t n_ref, const uint64_t *starts, uint64_t n_records, uint64_t *n_bytes) {
-  if (!c) return CMGPU_EINVAL;
-  CM_HIPCHECK(c, cm_enter(c));
-  c->bai.clear();
-  c->bai_have = false;
-  if (n_bytes) *n_bytes = 0;
+// the records of the compressed store indexed: the .bai's bytes (csi_depth 0) or the CSI's, into `payload`
+static int bai_index_store(cmgpu_ctx *c, uint64_t base_offset, uint32_t n_ref, const uint64_t *starts, uint64_t n_records, uint32_t csi_depth,
+                           std::vector<uint8_t> &payload) {
   const uint8_t *p = nullptr;
   switch (c->bgzf_src) {
     case CM_BZ_SRC_STORE:
@@ -543,8 +610,16 @@ extern "C" int cmgpu_bgzf_index_bai(cmgpu_ctx *c, uint64_t base_offset, uint32_t
     CM_HIPCHECK(c, cm_stream_sync(c->stream));
     d_starts = (const uint64_t *)up.p;
   }
+  return bai_index(c, p, n, base_offset, n_ref, d_starts, n_records, csi_depth, payload);
+}
+extern "C" int cmgpu_bgzf_index_bai(cmgpu_ctx *c, uint64_t base_offset, uint32_t n_ref, const uint64_t *starts, uint64_t n_records, uint64_t *n_bytes) {
+  if (!c) return CMGPU_EINVAL;
+  CM_HIPCHECK(c, cm_enter(c));
+  c->bai.clear();
+  c->bai_have = false;
+  if (n_bytes) *n_bytes = 0;
   std::vector<uint8_t> payload;
-  const int rc = bai_index(c, p, n, base_offset, n_ref, d_starts, n_records, payload);
+  const int rc = bai_index_store(c, base_offset, n_ref, starts, n_records, 0, payload);
   if (rc != CMGPU_OK) return rc;
   c->bai.swap(payload);
   c->bai_have = true;
@@ -568,6 +643,55 @@ extern "C" int cmgpu_bai_write(cmgpu_ctx *c, const char *path) {
     ok = fclose(f) == 0 && ok;
   }
   if (!ok) {
+    remove(path);
+    cm_set_error(c, std::string("cannot write ") + path);
+    return CMGPU_EIO;
+  }
+  return CMGPU_OK;
+}
+
+// ---- the CSI index: either store's, one payload
+static int csi_begin(cmgpu_ctx *c, uint32_t depth, uint64_t *n_bytes) {
+  c->csi.clear();
+  c->csi_have = false;
+  if (n_bytes) *n_bytes = 0;
+  if (depth < 1 || depth > CM_CSI_MAX_DEPTH) { cm_set_error(c, "CSI index: depth must be 1 .. 6"); return CMGPU_EINVAL; }
+  return CMGPU_OK;
+}
+static int csi_keep(cmgpu_ctx *c, std::vector<uint8_t> &payload, uint64_t *n_bytes) {
+  c->csi.swap(payload);
+  c->csi_have = true;
+  if (n_bytes) *n_bytes = c->csi.size();
+  return CMGPU_OK;
+}
+extern "C" int cmgpu_bgzf_index_csi_bam(cmgpu_ctx *c, uint64_t base_offset, uint32_t n_ref, const uint64_t *starts, uint64_t n_records, uint32_t depth,
+                                        uint64_t *n_bytes) {
+  if (!c) return CMGPU_EINVAL;
+  CM_HIPCHECK(c, cm_enter(c));
+  { const int rc = csi_begin(c, depth, n_bytes); if (rc) return rc; }
+  std::vector<uint8_t> payload;
+  const int rc = bai_index_store(c, base_offset, n_ref, starts, n_records, depth, payload);
+  return rc != CMGPU_OK ? rc : csi_keep(c, payload, n_bytes);
+}
+extern "C" int cmgpu_bgzf_index_csi_tabix(cmgpu_ctx *c, uint64_t base_offset, uint32_t depth, uint64_t *n_bytes) {
+  if (!c) return CMGPU_EINVAL;
+  CM_HIPCHECK(c, cm_enter(c));
+  { const int rc = csi_begin(c, depth, n_bytes); if (rc) return rc; }
+  std::vector<uint8_t> payload;
+  const int rc = tx_index_store(c, base_offset, depth, payload);
+  return rc != CMGPU_OK ? rc : csi_keep(c, payload, n_bytes);
+}
+extern "C" int cmgpu_csi_download(cmgpu_ctx *c, void *out, uint64_t capacity) {
+  if (!c || !out) return CMGPU_EINVAL;
+  if (!c->csi_have) { cm_set_error(c, "no CSI index (cmgpu_bgzf_index_csi_bam or cmgpu_bgzf_index_csi_tabix comes first)"); return CMGPU_EINVAL; }
+  if (capacity < c->csi.size()) { cm_set_error(c, "CSI index buffer too small"); return CMGPU_ECAPACITY; }
+  memcpy(out, c->csi.data(), c->csi.size());
+  return CMGPU_OK;
+}
+extern "C" int cmgpu_csi_write(cmgpu_ctx *c, const char *path) {
+  if (!c || !path) return CMGPU_EINVAL;
+  if (!c->csi_have) { cm_set_error(c, "no CSI index (cmgpu_bgzf_index_csi_bam or cmgpu_bgzf_index_csi_tabix comes first)"); return CMGPU_EINVAL; }
+  if (cmgpu_bgzf_write_host_text(path, c->csi.data(), c->csi.size(), 0) != CMGPU_OK || cmgpu_bgzf_write_eof(path) != CMGPU_OK) {
     remove(path);
     cm_set_error(c, std::string("cannot write ") + path);
     return CMGPU_EIO;

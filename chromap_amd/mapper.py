@@ -772,6 +772,35 @@ class ChromapGPU:
         """the last bgzf_bai payload as a .bai file (not compressed)"""
         self._check(self.L.cmgpu_bai_write(self.ctx, path.encode()), self.ctx)
 
+    # ---- the CSI index of the compressed store, built on the device (include/chromap_amd.h; chromap_amd/csrc/cm_tabix.h)
+    def bgzf_csi(self, base_offset=0, n_ref=None, starts=None, depth=5, kind="bam"):
+        """the .csi payload (before compression) of the last bgzf_compress / store_compress_text, whose blocks will stand at file
+        offset `base_offset`: min_shift 14, `depth` levels (1 .. 6; an end may reach 2^(14 + 3 * depth), 0xffffffff at depth 6).
+        kind "bam": the records bgzf_bai() indexes, with its n_ref and starts; kind "bed": the text bgzf_tabix() indexes, in the
+        flavour `tabix -C -p bed` writes.  ChromapError for what cannot be indexed (the message names the record or line)"""
+        n = C.c_uint64(0)
+        if kind == "bed":
+            rc = self.L.cmgpu_bgzf_index_csi_tabix(self.ctx, int(base_offset), int(depth), C.byref(n))
+        elif kind == "bam":
+            n_ref = len(self.names) if n_ref is None else int(n_ref)
+            if starts is None:
+                rc = self.L.cmgpu_bgzf_index_csi_bam(self.ctx, int(base_offset), n_ref, None, 0, int(depth), C.byref(n))
+            else:
+                st = np.ascontiguousarray(starts, np.uint64)
+                if st.size < 1:
+                    raise ValueError("starts: the offsets of the records and the number of bytes behind them")
+                rc = self.L.cmgpu_bgzf_index_csi_bam(self.ctx, int(base_offset), n_ref, st.ctypes.data, st.size - 1, int(depth), C.byref(n))
+        else:
+            raise ValueError('kind: "bam" or "bed"')
+        self._check(rc, self.ctx)
+        buf = C.create_string_buffer(max(1, n.value))
+        self._check(self.L.cmgpu_csi_download(self.ctx, buf, n.value), self.ctx)
+        return buf.raw[:n.value]
+
+    def store_write_csi(self, path):
+        """the last bgzf_csi payload as a .csi file: BGZF blocks and the end-of-file block"""
+        self._check(self.L.cmgpu_csi_write(self.ctx, path.encode()), self.ctx)
+
     # ---- --summary: per-barcode TOTAL / DUP / LOWMAPQ / MAPPED counted on the device (include/chromap_amd.h)
     def summary_enable(self, on=True):
         """from now on every map_* call counts its reads per barcode and every store_format* call credits the duplicate runs;

@@ -487,7 +487,7 @@ int cmgpu_write_sam_header(const char *const *ref_names, const uint32_t *ref_len
  *                            cmgpu_store_compress_text + cmgpu_bgzf_write make them the body of a BAM file (a record may straddle
  *                            two blocks: the format allows it).  A selected record whose read name has 255 bytes or more does not
  *                            fit l_read_name: CMGPU_EFORMAT, no output.  cmgpu_bgzf_index_tabix refuses a store made of BAM records.
- *                            The .bai index: cmgpu_bgzf_index_bai below (no .csi); bin is the spec's reg2bin(pos, pos + reference
+ *                            The .bai index: cmgpu_bgzf_index_bai below (.csi: cmgpu_bgzf_index_csi_bam); bin is the spec's reg2bin(pos, pos + reference
  *                            length of the CIGAR).
  *   cmgpu_write_bam_header   the uncompressed header, on the host: "BAM\1", l_text and cmgpu_write_sam_header's @SQ lines, n_ref,
  *                            and per sequence l_name (with the NUL), the name, l_ref.  As BGZF blocks (cmgpu_bgzf_write_host_text)
@@ -641,6 +641,23 @@ int cmgpu_bam_keep_starts(cmgpu_ctx *ctx, int on);
 int cmgpu_bgzf_index_bai(cmgpu_ctx *ctx, uint64_t base_offset, uint32_t n_ref, const uint64_t *starts, uint64_t n_records, uint64_t *n_bytes);
 int cmgpu_bai_download(cmgpu_ctx *ctx, void *out, uint64_t capacity);
 int cmgpu_bai_write(cmgpu_ctx *ctx, const char *path);
+/* ---- CSI index of the compressed store, built on the device (cm_tabix.h, cm_bai.h, cm_tabix.hip) --
+ * The .csi (SAM spec 5.3, CSIv1) of the same stores: the .tbi's and the .bai's stages with the number of levels as a parameter.
+ * min_shift is 14; depth is 1 .. 6 (else CMGPU_EINVAL) and an end may reach 2^(14 + 3 * depth) -- 2^29 at depth 5, as the .tbi and
+ * .bai; positions are 32-bit, so depth 6 takes ends up to 0xffffffff, not 2^32.  There is no linear index: every bin carries
+ * loffset, the back-filled 16 kb window value at the bin's first position (htslib's rule), computed on the device; the pseudo-bin
+ * ((1 << (3 * depth + 3)) - 1) / 7 + 1 has loffset 0.  Bins are not folded.  What is refused, and with which words, is what the .tbi
+ * / .bai calls refuse; the RANGE message names the limit of the depth in use.
+ *   cmgpu_bgzf_index_csi_bam    the BAM flavour (l_aux = 0) of the records cmgpu_bgzf_index_bai would index; the same arguments
+ *                               (starts == NULL: the kept starts) and depth
+ *   cmgpu_bgzf_index_csi_tabix  the tabix flavour (what `tabix -C -p bed` writes: aux holds the tabix header's format, columns, meta,
+ *                               skip and names) of the text cmgpu_bgzf_index_tabix would index
+ *   cmgpu_csi_download          the last payload of either (capacity >= its size, else CMGPU_ECAPACITY); CMGPU_EINVAL: none built
+ *   cmgpu_csi_write             the payload as a BGZF file, as cmgpu_tabix_write writes a .tbi; CMGPU_EINVAL: none built */
+int cmgpu_bgzf_index_csi_bam(cmgpu_ctx *ctx, uint64_t base_offset, uint32_t n_ref, const uint64_t *starts, uint64_t n_records, uint32_t depth, uint64_t *n_bytes);
+int cmgpu_bgzf_index_csi_tabix(cmgpu_ctx *ctx, uint64_t base_offset, uint32_t depth, uint64_t *n_bytes);
+int cmgpu_csi_download(cmgpu_ctx *ctx, void *out, uint64_t capacity);
+int cmgpu_csi_write(cmgpu_ctx *ctx, const char *path);
 /* --allocate-multi-mappings (MappingProcessor::AllocateMultiMappings, src/mapping_processor.h:319-440): with
  * params->allocate_multi_mappings and without low_memory_mode, cmgpu_store_format gives every read whose surviving records have
  * MAPQ < 4 to one of them, drawn with probability proportional to the uni-mappings (MAPQ >= 4) within

@@ -21,7 +21,8 @@ device), `--reps` runs each, whole-process wall time and file sizes; the first r
 the first lines of the SAM file.
 `--output-bai` (with `--sam`): the job as `--BAM` and as `--BAM --output-bai` (the BAM index built on the device) and -- with
 `--baseline-cli` -- that build with `--BAM`; the builds and flags take turns, `--reps` rounds, whole-process wall time; the BAM files must
-be the same bytes, and the index's own line is kept.
+be the same bytes, and the index's own line is kept.  With `--output-csi` as well: a further run per round as `--BAM --output-csi` (the
+CSI index built on the device), its own line and the `.csi` file's size kept beside the `.bai`'s.
 Prints one JSON object; everything is written under --dir (default /tmp/chromap_amd_e2e)."""
 import argparse
 import ctypes as C
@@ -125,11 +126,12 @@ def output_bai_job(args, cli, job, out):
     """--BAM with the parent's build (--baseline-cli), with this build, and with this build and --output-bai: one run of each per round,
     the order kept, after one untimed round"""
     variants = ([("parent_bam", args.baseline_cli, ["--BAM"])] if args.baseline_cli else []) + \
-               [("bam", cli, ["--BAM"]), ("bam_output_bai", cli, ["--BAM", "--output-bai"])]
+               [("bam", cli, ["--BAM"]), ("bam_output_bai", cli, ["--BAM", "--output-bai"])] + \
+               ([("bam_output_csi", cli, ["--BAM", "--output-csi"])] if args.output_csi else [])   # (--output-csi: the .csi beside the .bai, same session and build)
     res = {label: {"wall_s": [], "lines": []} for label, _, _ in variants}
     for rnd in range(args.reps + 1):
         for label, exe, extra in variants:
-            for f in (out, out + ".bai"):
+            for f in (out, out + ".bai", out + ".csi"):
                 if os.path.exists(f):
                     os.remove(f)
             os.sync()
@@ -137,6 +139,8 @@ def output_bai_job(args, cli, job, out):
             p = subprocess.run([exe] + job + extra, stderr=subprocess.PIPE, check=True)
             dt = time.time() - t0
             if rnd == 0:   # untimed: every build's code objects and the files have been read once
+                if "--output-csi" in extra:
+                    res[label]["csi_bytes"] = os.path.getsize(out + ".csi")
                 res[label]["bam_md5"] = subprocess.check_output(["md5sum", out]).split()[0].decode()
                 res[label]["bam_bytes"] = os.path.getsize(out)
                 res[label]["bai_written"] = os.path.exists(out + ".bai")
@@ -145,7 +149,7 @@ def output_bai_job(args, cli, job, out):
                 continue
             res[label]["wall_s"].append(round(dt, 3))
             res[label]["lines"].append([ln for ln in p.stderr.decode().splitlines()
-                                        if ln.startswith(("Mapped all reads", "Compressed ", "Built the BAM index", "Number of output mappings"))])
+                                        if ln.startswith(("Mapped all reads", "Compressed ", "Built the BAM index", "Built the CSI index", "Number of output mappings"))])
     res["same_bam"] = len({res[label]["bam_md5"] for label, _, _ in variants}) == 1
     res["config"] = {"preset": args.preset, "pairs": args.pairs, "readlen": args.readlen, "genome": args.genome, "reps": args.reps,
                      "hardware_threads": os.cpu_count(), "cpu_budget": cpu_budget()}
@@ -170,6 +174,7 @@ def main():
     ap.add_argument("--output-tbi", action="store_true", help="--preset atac: time --output-bgzf without and with --output-tbi (and --baseline-cli with --output-bgzf), taking turns")
     ap.add_argument("--output-bam", action="store_true", help="--sam: time the job as --SAM, --SAM --output-bgzf and --BAM")
     ap.add_argument("--output-bai", action="store_true", help="--sam: time --BAM without and with --output-bai (and --baseline-cli with --BAM), taking turns")
+    ap.add_argument("--output-csi", action="store_true", help="--sam --output-bai: a fourth run per round with --BAM --output-csi")
     ap.add_argument("--skip-host-ingest", action="store_true", help="a long job: leave the host parser's run out")
     args = ap.parse_args()
     os.makedirs(args.dir, exist_ok=True)
